@@ -17,8 +17,8 @@ multi-GPU group (include/rayzen_hip.h: rz_group_*), enqueued on each member's re
 The JSON says which ran (`config.parallelism`), how many ranks RCCL saw (`rccl_ranks`) and what the reduce cost
 (`reduce_ms`: HIP events around it on the root's stream).  Default N > 1 workload: every rank renders 64*N spp of its own
 pixels (per-GPU work constant: "weak"); `--spp-total T` fixes the frame at T spp instead ("strong"; `--spp-total 256` at
-N = 8 is BASELINE configs[2], the C3 line).  Every N > 1 line ALSO carries `configs2`: three extra steps of the 256-spp frame
-of BASELINE configs[2] on the same N GPUs (strong scaling of that frame; at N = 8 it IS configs[2]).
+N = 8 is BASELINE configs[2], the C3 line).  Every N > 1 `--full` line ALSO carries `configs2`: three extra steps of the 256-spp
+frame of BASELINE configs[2] on the same N GPUs (strong scaling of that frame; at N = 8 it IS configs[2]).
 A run cannot die on the exchange step: a group whose RCCL communicator cannot be made, or whose first exchange fails in the
 warm-up, is rebuilt in the same process (never re-executed) on the next transport down -- rccl gather -> rccl reduce -> plain
 device copies between the members' GPUs (one-process mode) / torch.distributed.reduce (launcher mode) -- and the line says
@@ -26,10 +26,18 @@ which ran and why (`transport`, `transport_fallback`).
 Scene buffers are resident in HBM before the timed region; nothing is skipped inside it.
 
 Rank 0 prints ONE JSON line.  `value` = total camera paths (pixels x spp) / wall time of the K timed steps (max over
-ranks).  `roofline` prices the render kernel against what bounds it -- the SIMDs' instruction issue rate (measured:
-profiles/r02_valu_issue, profiles/r02_issue_sensitivity) -- with the HBM view (algorithmic bytes, counter traffic)
-kept beside it.  `cpu_baseline` = the oracle (a CPU port of the same path) timed on a bounded sample of the same
-frame, which doubles as a full-size parity check of those pixels.
+ranks); `ms_per_step` = that wall time / K.  A plain run does only that: set up, warm up, time the K steps, print.
+`--dump-outputs DIR` then also writes what the last timed step computed -- the (H, W, 4) float32 accumulation frame
+that rz_read_accum hands a caller -- as DIR/accum.npy (a fixed, seeded sample of its rows, DIR/accum_rows.npy with
+their indices in DIR/accum_row_index.npy, where the frame exceeds 64 MB); same arguments, same inputs, same file.
+`--full` adds everything else, each of which costs launches, reads or CPU time of its own:
+  * `roofline` prices the render kernel against what bounds it -- the SIMDs' instruction issue rate (measured:
+    profiles/r02_valu_issue, profiles/r02_issue_sensitivity) -- with the HBM view (algorithmic bytes, counter traffic)
+    kept beside it, and `work` the exact unit tallies of an instrumented launch (rz_render_counted, untimed);
+  * `cpu_baseline` = the oracle (a CPU port of the same path) timed on a bounded sample of the same frame, which
+    doubles as a full-size parity check of those pixels (`parity`; at N > 1 the parity leg alone);
+  * `frame_check` (every pixel received its samples), `library` (the loaded library was built from this tree) and,
+    at N > 1, `configs2`.
 """
 import argparse
 import json
@@ -113,16 +121,40 @@ def parse(argv=None):
     ap.add_argument("--transport", choices=["reduce", "gather"], default="reduce",
                     help="the group's exchange step: reduce = ONE ncclReduce(SUM) of the accumulation buffers (north_star; default), "
                          "gather = each rank's own tiles sent straight to the root (ncclSend / ncclRecv; 1 / N of the bytes)")
-    ap.add_argument("--no-configs2", action="store_true", help="skip the extra BASELINE configs[2] (256 spp) leg of an N > 1 run")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline: roofline and work model, CPU baseline and "
+                         "parity with the oracle, frame check, library provenance, and at N > 1 the configs[2] leg")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed step's accumulation frame to DIR/accum.npy (float32)")
+    ap.add_argument("--no-configs2", action="store_true", help="skip the extra BASELINE configs[2] (256 spp) leg of an N > 1 --full run")
     ap.add_argument("--loopback", action="store_true",
                     help="REHEARSAL of `--gpus N` as one plain process on a box with fewer GPUs: the N members of the group share "
                          "device 0 and device copies stand in for the links (RZ_GROUP_LOOPBACK); everything else -- the dealing of "
                          "tiles, packing, the root's scatter, the timing -- is the code an N-GPU run executes.  Not a scaling number.")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the CPU baseline / parity leg of a --full run")
     ap.add_argument("--cpu-threads", type=int, default=0, help="oracle threads (default: min(16, usable cores) = the box's CPU share)")
-    ap.add_argument("--cpu-bands", type=int, default=36, help="oracle sample: this many 8-row bands of the frame")
-    ap.add_argument("--cpu-full-frame", action="store_true", help="also time the oracle on the WHOLE frame (about 6 s on 16 threads)")
+    ap.add_argument("--cpu-bands", type=int, default=36, help="oracle sample (--full): this many 8-row bands of the frame")
+    ap.add_argument("--cpu-full-frame", action="store_true", help="with --full: also time the oracle on the WHOLE frame (about 6 s on 16 threads)")
     return ap.parse_args(argv)
+
+
+DUMP_MAX_BYTES = 64_000_000
+
+
+def dump_outputs(directory, frame):
+    """The last timed step's accumulation frame as float32 .npy: whole when it fits in DUMP_MAX_BYTES, else the rows of a
+    fixed, seeded sample (sorted) with their indices beside them."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    frame = np.ascontiguousarray(frame, dtype=np.float32)
+    if frame.nbytes <= DUMP_MAX_BYTES:
+        np.save(os.path.join(directory, "accum.npy"), frame)
+        return
+    row_bytes = frame.nbytes // frame.shape[0]
+    keep = max(1, (DUMP_MAX_BYTES - 8 * frame.shape[0]) // row_bytes)
+    rows = np.sort(np.random.default_rng(0).choice(frame.shape[0], size=keep, replace=False))
+    np.save(os.path.join(directory, "accum_rows.npy"), frame[rows])
+    np.save(os.path.join(directory, "accum_row_index.npy"), rows.astype(np.float64))
 
 
 def launch_mode(gpus, environ):
@@ -372,13 +404,14 @@ def main(argv=None):
             transport_fallback.append(tp)
     group, r, members = st["group"], st["r"], st["members"]
 
-    # untimed instrumented launches: exact algorithmic unit counts of this process's launches (all members of a local group)
-    counters = None
-    for m in members:
-        cm = m.render_counted()
-        counters = cm if counters is None else {k: counters[k] + cm[k] for k in cm}
-    alg_bytes = algorithmic_bytes(counters)
-    fence()
+    # --full: untimed instrumented launches: exact algorithmic unit counts of this process's launches (all members of a local group)
+    counters = alg_bytes = None
+    if a.full:
+        for m in members:
+            cm = m.render_counted()
+            counters = cm if counters is None else {k: counters[k] + cm[k] for k in cm}
+        alg_bytes = algorithmic_bytes(counters)
+        fence()
 
     for _ in range(a.warmup):
         step()
@@ -411,18 +444,20 @@ def main(argv=None):
 
     # the frame of the LAST timed step, before anything else is rendered
     final = None
-    if rank == 0:
+    if rank == 0 and (a.full or a.dump_outputs):
         if group is not None:
             final = group.read_frame()
         elif mode == "ranks":
             final = st["frame"].cpu().numpy()
         else:
             final = r.read_accum()
+    if rank == 0 and a.dump_outputs:
+        dump_outputs(a.dump_outputs, final)
 
     # N > 1: BASELINE configs[2] beside the headline -- the 256-spp frame on these N GPUs (strong scaling of THAT frame; at
     # N = 8 it is configs[2] literally).  Three steps behind one warm-up step, same fences, same max over ranks.
     configs2 = None
-    if world > 1 and not a.no_configs2 and not (a.spp_total == 256):
+    if world > 1 and a.full and not a.no_configs2 and not (a.spp_total == 256):
         fp2 = frame_params(sc.camera, W, H, len(sc.lights), bounces, 256, 0, rank, world)
         (group.set_frame if group is not None else r.set_frame)(fp2)
         step()
@@ -507,7 +542,7 @@ def main(argv=None):
         red = out.get("reduce_ms")
         out["step_split_ms"] = {"slowest_kernel": round(slow_k, 3), "reduce": red, "step": out["ms_per_step"],
                                 "other": round(out["ms_per_step"] - slow_k - (red or 0.0), 3)}
-    if rank == 0:
+    if rank == 0 and a.full:
         # size-independent check of the sharding + reduce: every pixel of the final frame received exactly
         # spp_total samples (a pixel rendered twice or not at all by the tile deal would show here)
         out["frame_check"] = {"every_pixel_has_spp_total_samples": bool((final[..., 3] == float(spp_total)).all()),
@@ -582,7 +617,7 @@ def main(argv=None):
             wm["floor_over_executed"] = round(wm["lane_slots"] / max(roof["executed_live_lane_valu"], 1), 4)
             wm["floor_violated"] = bool(wm["lane_slots"] > roof["executed_live_lane_valu"])
         out["roofline"] = roof
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if rank == 0 and world == 1 and a.full and not a.no_cpu_baseline:
         from oracle import rzo
         from helpers import oracle_frame, oracle_scene, sync_oracle_flavour
         out["math_flavour"] = sync_oracle_flavour()      # the oracle evaluates sin / cos / acos as the loaded library does (rz_math_flavour())
@@ -624,7 +659,7 @@ def main(argv=None):
             out["cpu_baseline"]["full_frame"] = {"value": round(W * H * a.spp / tf / 1e6, 4), "seconds": round(tf, 2),
                                                  "bit_identical_to_gpu": bool((full.view(np.uint32) == gpu.view(np.uint32)).all())}
         out["parity"] = {"linf_vs_oracle_on_sample": err, "bit_identical_pixels": same, "pixels_compared": tot}
-    if rank == 0 and world > 1 and not a.no_cpu_baseline:
+    if rank == 0 and world > 1 and a.full and not a.no_cpu_baseline:
         # N > 1: no CPU baseline (that is the N = 1 line's), but the PARITY leg stays -- a few bands of the frame the group has
         # landed on rank 0, against the oracle at the frame's full sample count: tiles that arrived in the wrong place would
         # pass frame_check (every pixel has the same sample count) and fail here

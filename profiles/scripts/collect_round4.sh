@@ -7,7 +7,7 @@
 set -x
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 O=gpurun_out/prof_r04; mkdir -p $O
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_c2 -o run -- python3 bench.py --no-cpu-baseline --steps 5 --warmup 1 > $O/kt_c2.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_c2 -o run -- python3 bench.py --full --no-cpu-baseline --steps 5 --warmup 1 > $O/kt_c2.log 2>&1
 python3 profiles/scripts/pmc_collect.py $O/pmc_c2.json "rz_render_samples" --workload 1920,1080,64,4,76 -- python3 profiles/scripts/one_frame.py c2 > $O/pmc_c2.log 2>&1
 for c in c4 c5full c2g glassbunny c2close ref c3; do
   rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_$c -o run -- python3 profiles/scripts/one_frame.py $c > $O/kt_$c.log 2>&1

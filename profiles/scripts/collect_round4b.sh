@@ -4,7 +4,7 @@
 set -x
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 O=gpurun_out/prof_r04; mkdir -p $O
-python3 bench.py --steps 10 --warmup 3 --cpu-full-frame > $O/bench_c2.json 2> $O/bench_c2.err
+python3 bench.py --full --steps 10 --warmup 3 --cpu-full-frame > $O/bench_c2.json 2> $O/bench_c2.err
 # RayZen's own scene at 1080p / 64 spp (added late in the round: its trace and counters are taken here, and copied to where
 # bench_configs.py looks for them on this box; install_profiles4.py does the same at home)
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_ref64 -o run -- python3 profiles/scripts/one_frame.py ref64 > $O/kt_ref64.log 2>&1

@@ -15,10 +15,10 @@ one() {
 }
 case "$1" in
 1)
-  rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_bench -o run -- python3 bench.py --no-cpu-baseline --steps 5 --warmup 1 > $O/kt_bench.log 2>&1
+  rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_bench -o run -- python3 bench.py --full --no-cpu-baseline --steps 5 --warmup 1 > $O/kt_bench.log 2>&1
   one c2 --workload 1920,1080,64,4,76
   mkdir -p profiles/r05_c2_kernel && cp $O/pmc_c2.json profiles/r05_c2_kernel/pmc_rz_render_samples.json
-  python3 bench.py --steps 20 --warmup 5 --cpu-full-frame > $O/bench_c2.json 2> $O/bench_c2.err
+  python3 bench.py --full --steps 20 --warmup 5 --cpu-full-frame > $O/bench_c2.json 2> $O/bench_c2.err
   python3 profiles/scripts/rank_share.py 1 2 4 8 > $O/rank_share.log 2>&1
   ;;
 2) for c in c2close c3 c4 ref ref16; do one $c; done ;;

@@ -11,4 +11,4 @@ for i in 1 2 3; do
 done
 # ... and the N > 1 bench path rehearsed on the one GPU with the final tree (all members on device 0: not a scaling number)
 unset RAYZEN_HIP_SO
-timeout -k 10 300 python bench.py --gpus 2 --loopback --steps 3 --warmup 1 > $O/bench_n2_loopback.json 2> $O/bench_n2_loopback.err; echo "n2 loopback rc=$?"; tail -c 700 $O/bench_n2_loopback.json
+timeout -k 10 300 python bench.py --full --gpus 2 --loopback --steps 3 --warmup 1 > $O/bench_n2_loopback.json 2> $O/bench_n2_loopback.err; echo "n2 loopback rc=$?"; tail -c 700 $O/bench_n2_loopback.json

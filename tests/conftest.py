@@ -7,8 +7,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-REFERENCE = "/root/reference/RayZen"          # present in the build container only, never on the GPU box
-
 
 def pytest_configure(config):
     config.addinivalue_line("markers", "gpu: needs a real MI355X (run with -m gpu on the GPU box)")
@@ -34,10 +32,3 @@ def _built():
     from helpers import sync_oracle_flavour
     sync_oracle_flavour()
     yield
-
-
-@pytest.fixture(scope="session")
-def reference_dir():
-    if not os.path.isdir(REFERENCE):
-        pytest.skip("reference checkout not present (GPU box)")
-    return REFERENCE

@@ -9,6 +9,9 @@ import pytest
 from oracle import rzo
 from rayzen_amd import scene as S
 
+# RayZen's own meshes/cube.obj and meshes/monkey.obj, stored as fixtures
+MESHES = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "meshes")
+
 
 def _soup(n, seed, scale=1.0, dup=False):
     rng = np.random.default_rng(seed)
@@ -76,9 +79,9 @@ def test_cube_matches_the_reference_run_recorded_by_the_survey():
     assert len(nodes) == 9 and (nodes["count"] > 0).sum() == 5 and depth == 5   # "depth 4" counted in edges
 
 
-def test_monkey_matches_the_reference_run_recorded_by_the_survey(reference_dir):
+def test_monkey_matches_the_reference_run_recorded_by_the_survey():
     """monkey.obj (968 tris) -> 625 nodes, 313 leaves, depth 11, 3.09 tris/leaf."""
-    path = os.path.join(reference_dir, "meshes", "monkey.obj")
+    path = os.path.join(MESHES, "monkey.obj")
     tris = S.load_obj(path, 1)
     assert len(tris) == 968
     assert tris.tobytes() == rzo.load_obj(path, 1).tobytes()
@@ -90,8 +93,8 @@ def test_monkey_matches_the_reference_run_recorded_by_the_survey(reference_dir):
     assert nodes.tobytes() == n2.tobytes() and idx.tobytes() == i2.tobytes()
 
 
-def test_synthetic_cube_is_the_reference_asset(reference_dir):
-    assert S.make_cube(3).tobytes() == S.load_obj(os.path.join(reference_dir, "meshes", "cube.obj"), 3).tobytes()
+def test_synthetic_cube_is_the_reference_asset():
+    assert S.make_cube(3).tobytes() == S.load_obj(os.path.join(MESHES, "cube.obj"), 3).tobytes()
 
 
 def test_empty_mesh_gives_an_empty_leaf_root_with_inverted_bounds():

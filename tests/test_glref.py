@@ -234,7 +234,7 @@ def test_full_size_frames_against_the_live_shader(config):
     arguments -- are those of the full-size frames, which the small fixtures do not reach."""
     glref = _glref(same_llvmpipe=True)
     if config.startswith("rayzen"):
-        sc = S.reference_scene(include_empty=False, monkey_obj="/root/reference/RayZen/meshes/monkey.obj")
+        sc = S.reference_scene(include_empty=False, monkey_obj=os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "meshes", "monkey.obj"))
         r = dict(W=800, H=600, budget=5, spp=1)
     else:
         sc, W, H, _, b = S.named_config("c2")

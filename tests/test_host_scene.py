@@ -294,10 +294,10 @@ def test_disk_cache_invalidation_and_the_reference_s_stale_data_quirks(tmp_path)
         assert healed.arrays[b].tobytes() == want.arrays[b].tobytes(), b
 
 
-def test_obj_mesh_replaces_the_stand_in_and_is_fitted_in_object_space(reference_dir):
+def test_obj_mesh_replaces_the_stand_in_and_is_fitted_in_object_space():
     """a real OBJ dropped into assets/ is rendered instead of the procedural mesh.  Its vertices (not its
     transform) are scaled: the shader's |a| < 1e-4 cull works in object space (FS:396)."""
-    path = os.path.join(reference_dir, "meshes", "monkey.obj")
+    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "meshes", "monkey.obj")   # RayZen's meshes/monkey.obj
     sc = S.bunny_scene(obj_path=path, radius=2.8)
     tris = sc.arrays[S.BIND_TRIANGLES]
     assert len(tris) == 12 + 968                                        # floor cube + Suzanne
