@@ -100,7 +100,7 @@ typedef enum rz_status {
     RZ_ERR_BAD_SCENE      = -6,  /* uploaded arrays are inconsistent */
     RZ_ERR_BUFFER_SIZE    = -7,  /* caller buffer too small */
     RZ_ERR_NO_MEMORY      = -8,  /* a host allocation failed inside the library (std::bad_alloc never crosses the ABI) */
-    RZ_ERR_INTERNAL       = -9   /* a render kernel reached one of its "cannot happen" bounds: pixels may be missing (rz_sync reports it) */
+    RZ_ERR_INTERNAL       = -9   /* a render kernel (or a ray query) reached one of its "cannot happen" bounds: pixels may be missing (rz_sync reports it) */
 } rz_status;
 
 /* Per-frame parameters = the uniforms of sendSceneDataToShader
@@ -391,6 +391,47 @@ typedef struct rz_launch_plan {
 } rz_launch_plan;
 int rz_debug_last_plan(rz_ctx* ctx, rz_launch_plan* out);
 
+/* ------------------------------------------------------------------------ */
+/* Batched ray queries on the uploaded scene (new: the reference has none).  */
+/* ------------------------------------------------------------------------ */
+/* The closest hit of FS:457-503 (traverseTLAS) and the transparency-aware visibility walk of FS:507-528 (shadowVisibility), for
+ * rays of the caller's choosing, by the very traversal a frame uses: a hit is what a camera or shadow ray of the frame would
+ * see.  The direction need not be unit.  t is the WORLD distance length(worldHit - origin) (FS:485); a triangle is accepted as
+ * the shader accepts it (local t > 1e-4, |a| >= 1e-4: FS:391-416), and an instance whose BLAS is empty or invalid is never hit.
+ * rz_ray.max_dist is read by rz_shadow_rays only (FS:517's maxDist; 1e30f for a directional light); rz_trace_rays ignores it.
+ * A miss: t = 1e30f (the shader's initial tHit), material = instance = triangle = prim = -1, point and normal zero.
+ *   instance  index into binding 9 (rz_bvh_instance)
+ *   prim      index into binding 0 (rz_triangle) of the triangle hit
+ *   triangle  prim - instances[instance].globalTriOffset: the mesh-local id rz_present_params.selected_tri names
+ * Pointers are DEVICE memory (16-byte aligned) by default: the call is enqueued on the context's stream (rz_set_stream) and
+ * returns at once; results are valid after rz_sync or the caller's own synchronisation of that stream.  With RZ_RAYS_HOST they
+ * are host memory: the call stages them through buffers of the context and returns when the results are written, having read
+ * the backstop word itself (RZ_ERR_INTERNAL if a walk was cut short).  A query sees the scene as of the last rz_upload /
+ * rz_update / rz_update_transforms issued before it; it needs no rz_set_frame and touches no render state (accumulation,
+ * currentIor, pools).  n == 0: RZ_OK, nothing launched.  RZ_ERR_INVALID_ARG: null context, null pointer with n > 0, a device
+ * pointer not 16-byte aligned, n > INT32_MAX, unknown flags; RZ_ERR_NOT_READY: no scene uploaded.
+ * (Additive: no existing struct changed, so RZ_ABI_VERSION stays 5.) */
+typedef struct rz_ray {
+    float    origin[3];
+    float    max_dist;
+    float    dir[3];
+    uint32_t reserved;
+} rz_ray;                       /* 32 B */
+typedef struct rz_hit {
+    float   t;
+    float   point[3];           /* world-space hit point */
+    float   normal[3];          /* world-space geometric normal, unit (FS:489-491) */
+    int32_t material, instance, triangle, prim, reserved;
+} rz_hit;                       /* 48 B */
+typedef struct rz_visibility {
+    float   visibility;         /* the product of the transparencies passed (1 when nothing was met, 0 when blocked) */
+    int32_t lit;                /* 1: shadowVisibility returned true */
+} rz_visibility;                /* 8 B */
+#define RZ_RAYS_HOST        1u  /* pointers are host memory: staged through context buffers, returns when results are written */
+#define RZ_RAYS_INCOHERENT  2u  /* walk lane by lane (trace_spread): a scheduling hint, identical results */
+int rz_trace_rays(rz_ctx* ctx, const rz_ray* rays, rz_hit* hits, size_t n, unsigned flags);
+int rz_shadow_rays(rz_ctx* ctx, const rz_ray* rays, rz_visibility* out, size_t n, unsigned flags);
+
 /* Number of HIP devices visible to the process (0 without a GPU). */
 int rz_device_count(void);
 
@@ -412,7 +453,8 @@ int rz_math_flavour(void);
 const char* rz_source_hash(void);
 /* sizeof() of the ABI structs as compiled into the library, for layout
  * checks from other languages: which = 0 triangle, 1 node, 2 instance,
- * 3 material, 4 light, 5 frame_params, 6 counters. */
+ * 3 material, 4 light, 5 frame_params, 6 counters, 7 ray, 8 hit,
+ * 9 visibility. */
 size_t rz_sizeof(int which);
 
 #ifdef __cplusplus

@@ -21,6 +21,7 @@ HIP_SYMBOLS = (
     "rz_group_last_error", "rz_group_size", "rz_group_local_count", "rz_group_rank", "rz_group_ctx", "rz_group_upload",
     "rz_group_update", "rz_group_set_frame", "rz_group_render", "rz_group_reduce", "rz_group_sync", "rz_group_read_frame",
     "rz_group_frame_device_ptr", "rz_group_last_reduce_ms", "rz_group_transport", "rz_group_set_transport", "rz_abi_version", "rz_debug_poke_backstop", "rz_math_flavour",
+    "rz_trace_rays", "rz_shadow_rays",
 )
 ABI_VERSION = 5         # RZ_ABI_VERSION of the include/rayzen_hip.h this file mirrors
 # the symbols include/rayzen_host.h declares
@@ -72,6 +73,25 @@ class LaunchPlan(C.Structure):
     _fields_ = [("groups", C.c_int64), ("grid", C.c_int64), ("per_claim", C.c_int32), ("claim_units", C.c_int32),
                 ("batches_per_pixel", C.c_int32), ("pixels_per_wave", C.c_int32), ("lds_stack_entries", C.c_int32),
                 ("overflow_entries", C.c_int32), ("transparent", C.c_int32), ("scratch_mib", C.c_int32)]
+
+
+class Ray(C.Structure):
+    """rz_ray of include/rayzen_hip.h (32 B)."""
+    _fields_ = [("origin", C.c_float * 3), ("max_dist", C.c_float), ("dir", C.c_float * 3), ("reserved", C.c_uint32)]
+
+
+class Hit(C.Structure):
+    """rz_hit of include/rayzen_hip.h (48 B)."""
+    _fields_ = [("t", C.c_float), ("point", C.c_float * 3), ("normal", C.c_float * 3), ("material", C.c_int32),
+                ("instance", C.c_int32), ("triangle", C.c_int32), ("prim", C.c_int32), ("reserved", C.c_int32)]
+
+
+class Visibility(C.Structure):
+    """rz_visibility of include/rayzen_hip.h (8 B)."""
+    _fields_ = [("visibility", C.c_float), ("lit", C.c_int32)]
+
+
+RAYS_HOST, RAYS_INCOHERENT = 1, 2       # RZ_RAYS_HOST, RZ_RAYS_INCOHERENT
 
 
 class Counters(C.Structure):
@@ -146,7 +166,8 @@ def hip():
         for name, res, args in (("rz_group_last_reduce_ms", i, [vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
                                 ("rz_group_transport", C.c_char_p, [vp]),
                                 ("rz_group_set_transport", i, [vp, C.c_char_p]),
-                                ("rz_abi_version", i, []), ("rz_debug_poke_backstop", i, [vp, C.c_uint]), ("rz_math_flavour", i, [])):
+                                ("rz_abi_version", i, []), ("rz_debug_poke_backstop", i, [vp, C.c_uint]), ("rz_math_flavour", i, []),
+                                ("rz_trace_rays", i, [vp, vp, vp, sz, C.c_uint]), ("rz_shadow_rays", i, [vp, vp, vp, sz, C.c_uint])):
             try:
                 fn = getattr(L, name)
                 fn.restype, fn.argtypes = res, args

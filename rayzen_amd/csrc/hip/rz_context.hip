@@ -131,6 +131,10 @@ struct rz_ctx {
     bool geomOnDevice = false, geomHostFresh = false;
     size_t devNodes = 0, devIdx = 0;
     std::map<int, rz_bvh_node> devRoots;    // node offset of a mesh -> its root node
+    // ray queries (rz_trace_rays / rz_shadow_rays, rz_rays.hip): their own BLAS overflow columns, the staging buffers of
+    // RZ_RAYS_HOST calls and the globalTriOffset of every instance (re-uploaded after the instances change)
+    DevBuf dRayOvf, dRayIn, dRayOut, dRayInstOff;
+    bool rayInstOffStale = true;
 };
 
 namespace {
@@ -541,6 +545,7 @@ int finalize_body(rz_ctx* c) {
             }
         }
         c->maxBlasDepth = 1;
+        c->rayInstOffStale = true;
         for (size_t i = 0; i < nInst; ++i) {
             const BlasView& V = c->views.at(std::make_tuple(inst[i].blasNodeOffset, inst[i].blasTriOffset, inst[i].globalTriOffset));
             DevInstance& D = dev[i];
@@ -655,6 +660,10 @@ int finalize(rz_ctx* c) {
 #define RZ_CLAIM_STRIDE_PAD 0      // extra dwords between the scratch regions of neighbouring resident waves
 #endif
 
+long long tlas_index_count(const rz_ctx* c) {
+    return c->deviceOwnsTlas ? (long long)c->tlasHostCounts[1] : (long long)hostCount<int32_t>(c, RZ_BIND_TLAS_INDICES);
+}
+
 // One lane per sample: independent samples when no triangle is transparent, speculated currentIor otherwise
 // (rz_kernels.hip).  The one-lane-per-pixel kernel remains as RZ_FLAG_MEGAKERNEL (the literal, sequential form).
 bool use_samples(const rz_ctx* c) { return (c->flags & RZ_FLAG_MEGAKERNEL) == 0; }
@@ -669,36 +678,64 @@ int ensure_group_counter(rz_ctx* c) {
     return RZ_OK;
 }
 
+// The BLAS stack of a launch of one-wave workgroups (K.blasStackCap entries per lane needed).  LDS budget: the stack's LDS
+// window is cut to what keeps `wavesPerCu` waves on a CU beside `fixedLds` bytes of other LDS per wave; deeper entries go to
+// global overflow columns in `ovf`, which are indexed by resident workgroup and therefore only exist for persistent launches
+// (`residentWaves` > 0: the grid).  Sets K.blasStackCap (the window, when one is cut), K.blasOvfCap and K.blasOvf.
+int size_blas_stack(rz_ctx* c, KParams& K, size_t fixedLds, int wavesPerCu, long long residentWaves, DevBuf& ovf) {
+    const int need = K.blasStackCap;
+    const size_t budget = (size_t)160 * 1024 / wavesPerCu;
+    int window = budget > fixedLds ? (int)((budget - fixedLds) / 512) : 0;
+    if (const char* e = std::getenv("RZ_BLAS_STACK_WINDOW")) window = std::atoi(e);        // test aid: force a small window
+    window = std::max(window, 2);
+    K.blasOvfCap = 0; K.blasOvf = nullptr;
+    if (residentWaves > 0 && need > window) {
+        K.blasStackCap = window;
+        K.blasOvfCap = need - window;
+        const int rc = ensure(c, ovf, (size_t)residentWaves * K.blasOvfCap * 64 * sizeof(uint2));
+        if (rc != RZ_OK) return rc;
+        K.blasOvf = static_cast<uint2*>(ovf.p);
+    }
+    return RZ_OK;
+}
+
+// What every kernel that walks the scene reads of it (render_samples / render_pixels, rz_rays.hip).
+void scene_kparams(const rz_ctx* c, KParams& K) {
+    K.pairs = static_cast<const DevPair*>(c->dPairs.p);
+    K.tris = static_cast<const DevTri*>(c->dTris.p);
+    K.triN = static_cast<const DevTriN*>(c->dTriN.p);
+    K.instances = static_cast<const DevInstance*>(c->dInst.p);
+    K.tlasDfs = static_cast<const TlasDfs*>(c->dTlasDfs.p);
+    K.tlasIndices = static_cast<const int32_t*>(c->dTlasIdx.p);
+    K.materials = static_cast<const DevMaterial*>(c->dMat.p);
+    K.lights = static_cast<const DevLight*>(c->dLight.p);
+    K.nTlasDfs = c->nTlasDfs;
+    K.nMaterials = (int)hostCount<rz_material>(c, RZ_BIND_MATERIALS);
+    K.blasStackCap = std::max(1, c->maxBlasDepth - 1);
+    // a pop followed by two pushes never holds more entries than the tree has levels (FS:460: stack[64])
+    K.tlasStackCap = 0;         // the TLAS walk keeps no stack (rz_trace.h: trace_closest)
+    K.traceRoundCap = (int)std::min<long long>(0x7fffffff, tlas_index_count(c) + (long long)c->nTlasDfs + 64);
+    K.regularBoxes = c->irregularBoxes ? 0 : 1;
+}
+
 int render_samples(rz_ctx* c, KParams K, bool counted, int evSlot) {
     K.nSlots = K.nLocalTiles * 64;
     int rc = ensure_group_counter(c);
     if (rc != RZ_OK) return rc;
     K.groupCounter = static_cast<unsigned*>(c->dGroupCtr.p);
-    // LDS budget: the BLAS stack's LDS window is cut to what keeps the target number of waves on a CU (16 for the
-    // opaque variant = its VGPR limit, and for the transparent one too: 5.4 KB of versions leave it a 9-entry window --
-    // measured 40.2 -> 34.3 ms on the glass+mirror scene against 12 waves with the whole stack in LDS); deeper entries go to global overflow columns,
-    // which are indexed by resident workgroup and therefore only exist for persistent launches.
+    // (16 waves per CU for the opaque variant = its VGPR limit, and for the transparent one too: 5.4 KB of versions leave it a
+    // 9-entry window -- measured 40.2 -> 34.3 ms on the glass+mirror scene against 12 waves with the whole stack in LDS)
     const SamplesPlan plan = plan_render_samples(K.spp, K.nSlots, c->sceneHasTransparency);
-    const int need = K.blasStackCap;
 #ifndef RZ_GLASS_WAVES_PER_CU
 #define RZ_GLASS_WAVES_PER_CU 16
 #endif
 #ifndef RZ_OPAQUE_WAVES_PER_CU
 #define RZ_OPAQUE_WAVES_PER_CU 16
 #endif
-    const size_t budget = (size_t)160 * 1024 / (c->sceneHasTransparency ? RZ_GLASS_WAVES_PER_CU : RZ_OPAQUE_WAVES_PER_CU);
-    const size_t fixed = samples_lds_extra(c->sceneHasTransparency, plan.compact) + (size_t)K.tlasStackCap * 256;
-    int window = budget > fixed ? (int)((budget - fixed) / 512) : 0;
-    if (const char* e = std::getenv("RZ_BLAS_STACK_WINDOW")) window = std::atoi(e);        // test aid: force a small window
-    window = std::max(window, 2);
-    K.blasOvfCap = 0; K.blasOvf = nullptr;
-    if (plan.perClaim > 0 && need > window) {
-        K.blasStackCap = window;
-        K.blasOvfCap = need - window;
-        rc = ensure(c, c->dBlasOvf, (size_t)plan.grid * K.blasOvfCap * 64 * sizeof(uint2));
-        if (rc != RZ_OK) return rc;
-        K.blasOvf = static_cast<uint2*>(c->dBlasOvf.p);
-    }
+    rc = size_blas_stack(c, K, samples_lds_extra(c->sceneHasTransparency, plan.compact) + (size_t)K.tlasStackCap * 256,
+                         c->sceneHasTransparency ? RZ_GLASS_WAVES_PER_CU : RZ_OPAQUE_WAVES_PER_CU,
+                         plan.perClaim > 0 ? plan.grid : 0, c->dBlasOvf);
+    if (rc != RZ_OK) return rc;
     // Compacting launches: every resident wave's scratch (rz_kernels.hip: WAIT SLOTS, pool_process) --
     //   * its pool of parked paths: room for the chunk it collects before it traces them + the most one more claim can park;
     //   * its claim scratch (the addends of the claim it is running, 1.5 KB per unit) and behind it its wait slots, one waiting
@@ -796,19 +833,10 @@ int do_render(rz_ctx* c, bool counted, rz_counters* out) {
         accum = static_cast<float4*>(c->ownAccum.p);
     }
     KParams K{};
-    K.pairs = static_cast<const DevPair*>(c->dPairs.p);
-    K.tris = static_cast<const DevTri*>(c->dTris.p);
-    K.triN = static_cast<const DevTriN*>(c->dTriN.p);
-    K.instances = static_cast<const DevInstance*>(c->dInst.p);
-    K.tlasDfs = static_cast<const TlasDfs*>(c->dTlasDfs.p);
-    K.tlasIndices = static_cast<const int32_t*>(c->dTlasIdx.p);
-    K.materials = static_cast<const DevMaterial*>(c->dMat.p);
-    K.lights = static_cast<const DevLight*>(c->dLight.p);
+    scene_kparams(c, K);
     K.accum = accum;
     K.ior = static_cast<float*>(c->dIor.p);
-    K.nTlasDfs = c->nTlasDfs;
     K.nLights = std::max(0, std::min<int>(f.num_lights, (int)hostCount<rz_light>(c, RZ_BIND_LIGHTS)));
-    K.nMaterials = (int)hostCount<rz_material>(c, RZ_BIND_MATERIALS);
     K.width = f.width; K.height = f.height;
     K.tilesX = (f.width + RZ_TILE_W - 1) / RZ_TILE_W;
     K.tilesY = (f.height + RZ_TILE_H - 1) / RZ_TILE_H;
@@ -817,23 +845,18 @@ int do_render(rz_ctx* c, bool counted, rz_counters* out) {
     K.nLocalTiles = (nTiles - f.tile_rank + f.tile_nranks - 1) / f.tile_nranks;
     K.maxBounces = f.bounce_budget > 0 ? f.bounce_budget : 5;      // FS:673
     K.spp = f.spp; K.sampleBase = f.sample_base;
-    K.blasStackCap = std::max(1, c->maxBlasDepth - 1);
-    // a pop followed by two pushes never holds more entries than the tree has levels (FS:460: stack[64])
-    K.tlasStackCap = 0;         // the TLAS walk keeps no stack (rz_trace.h: trace_closest)
     std::memcpy(K.invView, f.inv_view, 64);
     std::memcpy(K.invProj, f.inv_proj, 64);
     std::memcpy(K.camPos, f.cam_pos, 12);
     std::memcpy(K.hemi0, c->hemi0, 12);
     {
-        const long long nIdx = c->deviceOwnsTlas ? (long long)c->tlasHostCounts[1] : (long long)hostCount<int32_t>(c, RZ_BIND_TLAS_INDICES);
-        K.traceRoundCap = (int)std::min<long long>(0x7fffffff, nIdx + (long long)c->nTlasDfs + 64);
+        const long long nIdx = tlas_index_count(c);
         // Spread rays are traced lane by lane when they have several instances to spread over: with two (C2: floor + mesh) the
         // wave-cursor walk's scalar fetches and octant tests are worth more than walking both instances at once.
         // RZ_SPREAD_MIN_INSTANCES overrides the threshold (0 = never; A/B aid).
         long long minInst = RZ_SPREAD_MIN_INSTANCES;
         if (const char* e = std::getenv("RZ_SPREAD_MIN_INSTANCES")) minInst = std::atoll(e);
         K.spreadTrace = (minInst > 0 && nIdx >= minInst) ? 1 : 0;
-        K.regularBoxes = c->irregularBoxes ? 0 : 1;
     }
     const size_t perWave = (size_t)K.blasStackCap * 512 + (size_t)K.tlasStackCap * 256 + 4864;
     if (perWave * 4 > 160 * 1024)   // sized for the largest (4-wave) workgroup
@@ -928,6 +951,9 @@ size_t rz_sizeof(int which) {
         case 4: return sizeof(rz_light);
         case 5: return sizeof(rz_frame_params);
         case 6: return sizeof(rz_counters);
+        case 7: return sizeof(rz_ray);
+        case 8: return sizeof(rz_hit);
+        case 9: return sizeof(rz_visibility);
         default: return 0;
     }
 }
@@ -967,8 +993,8 @@ void rz_destroy(rz_ctx* c) {
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     for (DevBuf* b : {&c->dPairs, &c->dTris, &c->dInst, &c->dTlasNodes, &c->dTlasIdx, &c->dMat, &c->dLight,
-                      &c->dCounters, &c->dResolve, &c->dGroupCtr, &c->dBlasOvf, &c->ownAccum, &c->dIor, &c->dXforms, &c->dInstRef, &c->dTlasScratch, &c->dProjBoxes, &c->dBuildWs, &c->dTlasDfs, &c->dTriN, &c->dRawNodes, &c->dRawIdx, &c->dRawTris, &c->dRelayoutWs, &c->dClaimScratch, &c->dWavePools, &c->dWaitMeta, &c->dSnap
-                      })
+                      &c->dCounters, &c->dResolve, &c->dGroupCtr, &c->dBlasOvf, &c->ownAccum, &c->dIor, &c->dXforms, &c->dInstRef, &c->dTlasScratch, &c->dProjBoxes, &c->dBuildWs, &c->dTlasDfs, &c->dTriN, &c->dRawNodes, &c->dRawIdx, &c->dRawTris, &c->dRelayoutWs, &c->dClaimScratch, &c->dWavePools, &c->dWaitMeta, &c->dSnap,
+                      &c->dRayOvf, &c->dRayIn, &c->dRayOut, &c->dRayInstOff})
         b->release();
     if (c->tlasHostCounts) (void)hipHostFree(c->tlasHostCounts);
     if (c->relayoutPinned) (void)hipHostFree(c->relayoutPinned);
@@ -1282,8 +1308,9 @@ int rz_sync(rz_ctx* c) {
             RZ_HIP(c, hipMemcpy(&bits, w, sizeof bits, hipMemcpyDeviceToHost));
             if (bits != 0u) {
                 RZ_HIP(c, hipMemset(w, 0, sizeof bits));
-                return fail(c, RZ_ERR_INTERNAL, "a render kernel reached a backstop (bits 0x%x:%s%s%s): pixels of the last frame(s) may be missing",
-                            bits, (bits & 1u) ? " claim without wait slots" : "", (bits & 2u) ? " pool did not drain" : "", (bits & 4u) ? " currentIor chains did not resolve" : "");
+                return fail(c, RZ_ERR_INTERNAL, "a render kernel reached a backstop (bits 0x%x:%s%s%s%s): pixels of the last frame(s) may be missing",
+                            bits, (bits & 1u) ? " claim without wait slots" : "", (bits & 2u) ? " pool did not drain" : "", (bits & 4u) ? " currentIor chains did not resolve" : "",
+                            (bits & RZ_BACKSTOP_RAYS) ? " a ray query's walk was cut short" : "");
             }
         }
         return RZ_OK;
@@ -1428,6 +1455,74 @@ static int present_impl(rz_ctx* c, const rz_present_params* pp, uint8_t* rgba8, 
     return RZ_OK;
 }
 
+// rz_trace_rays / rz_shadow_rays (rz_rays.hip).  The queries read the device scene as the last upload / update / transform
+// update left it (finalize), and nothing of the frame: no rz_set_frame needed, no render state touched.
+static int rays_impl(rz_ctx* c, const rz_ray* rays, void* out, size_t n, unsigned flags, bool shadow) {
+    const char* what = shadow ? "rz_shadow_rays" : "rz_trace_rays";
+    if (!c) return fail(nullptr, RZ_ERR_INVALID_ARG, "%s: null context", what);
+    if (flags & ~(RZ_RAYS_HOST | RZ_RAYS_INCOHERENT)) return fail(c, RZ_ERR_INVALID_ARG, "%s: unknown flags 0x%x", what, flags);
+    if (n > (size_t)std::numeric_limits<int32_t>::max()) return fail(c, RZ_ERR_INVALID_ARG, "%s: %zu rays, at most %d per call", what, n, std::numeric_limits<int32_t>::max());
+    if (n && (!rays || !out)) return fail(c, RZ_ERR_INVALID_ARG, "%s: null %s", what, rays ? "output" : "rays");
+    const bool host = (flags & RZ_RAYS_HOST) != 0;
+    if (!host && ((reinterpret_cast<uintptr_t>(rays) | reinterpret_cast<uintptr_t>(out)) & 15u))
+        return fail(c, RZ_ERR_INVALID_ARG, "%s: device pointers must be 16-byte aligned", what);
+    for (int b : {RZ_BIND_TRIANGLES, RZ_BIND_MATERIALS, RZ_BIND_LIGHTS, RZ_BIND_TLAS_NODES, RZ_BIND_TLAS_INDICES,
+                  RZ_BIND_BLAS_NODES, RZ_BIND_BLAS_INDICES, RZ_BIND_INSTANCES})
+        if (!c->present[b]) return fail(c, RZ_ERR_NOT_READY, "%s: no scene (binding %d has not been uploaded)", what, b);
+    if (n == 0) return RZ_OK;
+    int rc = finalize(c);
+    if (rc != RZ_OK) return rc;
+    KParams K{};
+    scene_kparams(c, K);
+    rc = ensure_group_counter(c);           // (only its backstop word: the claim counter is the render's)
+    if (rc != RZ_OK) return rc;
+    if (!shadow && c->rayInstOffStale) {
+        const rz_bvh_instance* inst = hostArr<rz_bvh_instance>(c, RZ_BIND_INSTANCES);
+        const size_t nInst = hostCount<rz_bvh_instance>(c, RZ_BIND_INSTANCES);
+        alloc_point(c);
+        std::vector<int32_t> off(nInst);
+        for (size_t i = 0; i < nInst; ++i) off[i] = inst[i].globalTriOffset;     // (rz_update_transforms keeps the offsets)
+        rc = upload_vec(c, c->dRayInstOff, off.data(), nInst * sizeof(int32_t));
+        if (rc != RZ_OK) return rc;
+        RZ_HIP(c, hipStreamSynchronize(c->stream));     // the staging vector dies at scope exit
+        c->rayInstOffStale = false;
+    }
+    RaysLaunch R{};
+    R.n = (int)n;
+    R.grid = rays_grid((long long)n);
+    R.shadow = shadow;
+    R.spread = (flags & RZ_RAYS_INCOHERENT) != 0;
+    R.instTriOff = static_cast<const int32_t*>(c->dRayInstOff.p);
+    R.errWord = static_cast<unsigned*>(c->dGroupCtr.p) + RZ_ERRWORD;
+    rc = size_blas_stack(c, K, 0, RZ_RAYS_WAVES_PER_CU, R.grid, c->dRayOvf);
+    if (rc != RZ_OK) return rc;
+    const size_t inBytes = n * sizeof(rz_ray), outBytes = n * (shadow ? sizeof(rz_visibility) : sizeof(rz_hit));
+    R.rays = rays;
+    R.out = out;
+    if (host) {
+        rc = ensure(c, c->dRayIn, inBytes);
+        if (rc != RZ_OK) return rc;
+        rc = ensure(c, c->dRayOut, outBytes);
+        if (rc != RZ_OK) return rc;
+        RZ_HIP(c, hipMemcpyAsync(c->dRayIn.p, rays, inBytes, hipMemcpyHostToDevice, c->stream));
+        R.rays = c->dRayIn.p;
+        R.out = c->dRayOut.p;
+    }
+    launch_rays(K, R, c->stream);
+    RZ_HIP(c, hipGetLastError());
+    if (!host) return RZ_OK;
+    RZ_HIP(c, hipMemcpyAsync(out, c->dRayOut.p, outBytes, hipMemcpyDeviceToHost, c->stream));
+    RZ_HIP(c, hipStreamSynchronize(c->stream));
+    unsigned bits = 0;
+    unsigned* w = static_cast<unsigned*>(c->dGroupCtr.p) + RZ_ERRWORD;
+    RZ_HIP(c, hipMemcpy(&bits, w, sizeof bits, hipMemcpyDeviceToHost));
+    if (bits != 0u) {
+        RZ_HIP(c, hipMemset(w, 0, sizeof bits));
+        return fail(c, RZ_ERR_INTERNAL, "%s: a kernel reached a backstop (bits 0x%x): results may be wrong", what, bits);
+    }
+    return RZ_OK;
+}
+
 int rz_last_render_ms(rz_ctx* c, float* ms, int* launches) {
     if (!c) return fail(nullptr, RZ_ERR_INVALID_ARG, "null context");
     if (!c->timed) return fail(c, RZ_ERR_NOT_READY, "nothing rendered yet");
@@ -1496,6 +1591,13 @@ int rz_clear_accum(rz_ctx* c) {
 
 int rz_build_geometry(rz_ctx* c, const rz_triangle* triangles, size_t n_triangles, rz_mesh_build* meshes, size_t n_meshes) {
     return guarded(c, "rz_build_geometry", [&] { return build_geometry_impl(c, triangles, n_triangles, meshes, n_meshes); });
+}
+
+int rz_trace_rays(rz_ctx* c, const rz_ray* rays, rz_hit* hits, size_t n, unsigned flags) {
+    return guarded(c, "rz_trace_rays", [&] { return rays_impl(c, rays, hits, n, flags, false); });
+}
+int rz_shadow_rays(rz_ctx* c, const rz_ray* rays, rz_visibility* out, size_t n, unsigned flags) {
+    return guarded(c, "rz_shadow_rays", [&] { return rays_impl(c, rays, out, n, flags, true); });
 }
 
 int rz_debug_read_layout(rz_ctx* c, int which, void* out, size_t bytes, size_t* needed) {

@@ -24,6 +24,20 @@ void dump_wave_log(int nWaves);
 void dump_gstats();
 #endif
 
+// ---- rz_rays.hip
+constexpr int RZ_RAYS_WAVES_PER_CU = 16;         // resident waves per CU of a ray-query launch (one wave per workgroup)
+struct RaysLaunch {
+    const void* rays;           // device: n x rz_ray
+    void* out;                  // device: n x rz_hit (trace) or n x rz_visibility (shadow)
+    int n;
+    long long grid;             // rays_grid(n)
+    bool shadow, spread;        // which query; the lane-by-lane walk (trace_spread) instead of the wave-cursor one
+    const int32_t* instTriOff;  // trace: globalTriOffset of every instance
+    unsigned* errWord;          // the context's backstop word
+};
+long long rays_grid(long long n);
+void launch_rays(const KParams& K, const RaysLaunch& R, hipStream_t stream);
+
 // ---- rz_tlas_device.hip
 void launch_tlas_refit(const TlasWork& W, hipStream_t s);
 

@@ -1,0 +1,161 @@
+// rz_rays.hip -- batched ray queries on the device scene (include/rayzen_hip.h: rz_trace_rays, rz_shadow_rays).
+//
+// The render path is the only other user of the scene the context keeps on the device; these kernels ask it the two
+// questions a caller outside the frame asks:
+//   * rz_trace_rays_kernel: the closest hit of FS:457-503, one lane per ray, by the render's own query (rz_trace.h:
+//     trace_closest, or trace_spread -- a scheduling choice, same bytes), plus the triangle that won (TraceExtra);
+//   * rz_shadow_rays_kernel: the transparency-aware visibility walk of FS:507-528, one lane per ray, up to 32 queries a ray.
+// Both run on a persistent grid of one-wave workgroups: each wave takes 64 consecutive rays per step of a grid-stride loop,
+// reads a ray with two 16-B loads per lane and writes its result with three 16-B stores (a hit) or one 8-B store (a
+// visibility).  The BLAS stack is an LDS window plus per-resident-wave overflow columns, sized by the render's rule
+// (rz_context.hip: size_blas_stack).  Nothing of the render state -- accumulation, currentIor, pools, the claim counter -- is
+// touched; a walk that stops at its backstop sets RZ_BACKSTOP_RAYS in the context's backstop word, as the render kernels do.
+#include <algorithm>
+
+#include "rz_internal.h"
+#include "rz_trace.h"
+
+namespace rz {
+
+// One wave per workgroup; 4 waves per SIMD = 16 per CU, the occupancy the LDS budget of size_blas_stack is cut for.
+#ifndef RZ_RAYS_MIN_WAVES
+#define RZ_RAYS_MIN_WAVES 4
+#endif
+
+__device__ __forceinline__ void rays_backstop(unsigned* errWord, bool cut) {
+    const unsigned long long m = rz_ballot(cut);
+    if (m != 0ull && (threadIdx.x & 63) == (unsigned)__builtin_ctzll(m)) atomicOr(errWord, RZ_BACKSTOP_RAYS);
+}
+
+template <bool OVF, bool SPREAD>
+__device__ __forceinline__ bool ray_query(const KParams& K, v3 o, v3 d, HitRec& h, const BlasStackT<OVF>& bstk, TraceExtra& x) {
+    Tally c = {};
+    return SPREAD ? trace_spread<false, OVF, true>(K, o, d, h, bstk, c, &x) : trace_closest<false, OVF, true>(K, o, d, h, bstk, c, &x);
+}
+
+template <bool OVF>
+__device__ __forceinline__ BlasStackT<OVF> rays_stack(const KParams& K, unsigned char* lds_raw) {
+    const int lane = threadIdx.x & 63;
+    return BlasStackT<OVF>{reinterpret_cast<uint2*>(lds_raw) + lane,
+                           OVF ? K.blasOvf + ((size_t)blockIdx.x * K.blasOvfCap) * 64 + lane : nullptr, K.blasStackCap};
+}
+
+// rays: n x rz_ray (2 float4: origin, max_dist | dir, reserved); hits: n x rz_hit (3 float4: t, point | normal, material |
+// instance, triangle, prim, reserved); instTriOff: globalTriOffset of every instance (rz_bvh_instance)
+template <bool OVF, bool SPREAD>
+__global__ __launch_bounds__(64, RZ_RAYS_MIN_WAVES) void rz_trace_rays_kernel(const KParams K, const float4* __restrict__ rays,
+                                                                               float4* __restrict__ hits, const int n,
+                                                                               const int32_t* __restrict__ instTriOff, unsigned* errWord) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
+    const BlasStackT<OVF> bstk = rays_stack<OVF>(K, lds_raw);
+    const int lane = threadIdx.x & 63;
+    bool cut = false;
+    for (long long base = (long long)blockIdx.x * 64; base < n; base += (long long)gridDim.x * 64) {
+        const long long i = base + lane;
+        if (i < n) {
+            const float4 a = rays[2 * i], b = rays[2 * i + 1];
+            HitRec h;
+            TraceExtra x;
+            const bool found = ray_query<OVF, SPREAD>(K, mk3(a.x, a.y, a.z), mk3(b.x, b.y, b.z), h, bstk, x);
+            cut = cut || x.cut;
+            // a miss: the shader's initial tHit (FS:459), ids -1, point and normal zero
+            float4 r0 = make_float4(1e30f, 0.0f, 0.0f, 0.0f);
+            float4 r1 = make_float4(0.0f, 0.0f, 0.0f, __int_as_float(-1));
+            float4 r2 = make_float4(__int_as_float(-1), __int_as_float(-1), __int_as_float(-1), 0.0f);
+            if (found) {
+                const int prim = K.tris[x.tri].src;         // the winner's index in binding 0
+                r0 = make_float4(h.t, h.p.x, h.p.y, h.p.z);
+                r1 = make_float4(h.n.x, h.n.y, h.n.z, __int_as_float(h.mat));
+                r2 = make_float4(__int_as_float(h.inst), __int_as_float(prim - instTriOff[h.inst]), __int_as_float(prim), 0.0f);
+            }
+            hits[3 * i] = r0;
+            hits[3 * i + 1] = r1;
+            hits[3 * i + 2] = r2;
+        }
+    }
+    rays_backstop(errWord, cut);
+}
+
+// FS:507-528 per ray: origin, max_dist | dir.  out: n x rz_visibility (visibility, lit).  A lane whose walk has ended stays
+// out of the wave's further queries (the wave-uniform loop with a predicated body of the render's single trace call site).
+template <bool OVF, bool SPREAD>
+__global__ __launch_bounds__(64, RZ_RAYS_MIN_WAVES) void rz_shadow_rays_kernel(const KParams K, const float4* __restrict__ rays,
+                                                                                float2* __restrict__ out, const int n, unsigned* errWord) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
+    const BlasStackT<OVF> bstk = rays_stack<OVF>(K, lds_raw);
+    const int lane = threadIdx.x & 63;
+    bool cut = false;
+    for (long long base = (long long)blockIdx.x * 64; base < n; base += (long long)gridDim.x * 64) {
+        const long long i = base + lane;
+        bool run = i < n;
+        v3 o = mk3(0.0f, 0.0f, 0.0f), d = o;
+        float maxDist = 0.0f;
+        if (run) {
+            const float4 a = rays[2 * i], b = rays[2 * i + 1];
+            o = mk3(a.x, a.y, a.z);
+            maxDist = a.w;
+            d = mk3(b.x, b.y, b.z);
+        }
+        float vis = 1.0f, traveled = 0.0f;
+        int iter = 0;
+        bool lit = false;
+        bool anyRun = rz_ballot(run) != 0ull;
+        while (anyRun) {
+            if (run) {
+                HitRec h;
+                TraceExtra x;
+                const bool found = ray_query<OVF, SPREAD>(K, o, d, h, bstk, x);
+                cut = cut || x.cut;
+                bool done = false;
+                if (!found) { done = true; lit = true; }                        // FS:514
+                else if (h.t < 0.001f) { o = o + d * 0.001f; }                  // FS:515
+                else {
+                    traveled += h.t;                                            // FS:516-517
+                    if (traveled >= maxDist) { done = true; lit = true; }
+                    else {
+                        const float tr = K.materials[h.mat].transparency;       // FS:518-525
+                        if (tr > 0.0f) { vis *= tr; o = h.p + d * 0.001f; }
+                        else { vis = 0.0f; done = true; lit = false; }
+                    }
+                }
+                if (!done) {
+                    iter += 1;
+                    if (!(iter < 32 && vis > 0.05f)) { done = true; lit = vis > 0.05f; }    // FS:511, 527
+                }
+                run = !done;
+            }
+            anyRun = rz_ballot(run) != 0ull;
+        }
+        if (i < n) out[i] = make_float2(vis, __int_as_float(lit ? 1 : 0));
+    }
+    rays_backstop(errWord, cut);
+}
+
+long long rays_grid(long long n) {
+    static int nCU = 0;
+    if (nCU == 0) {
+        int dev = 0; hipDeviceProp_t prop;
+        nCU = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
+                  ? prop.multiProcessorCount : 256;
+    }
+    return std::min<long long>((n + 63) / 64, (long long)nCU * RZ_RAYS_WAVES_PER_CU);
+}
+
+void launch_rays(const KParams& K, const RaysLaunch& R, hipStream_t stream) {
+    const dim3 g((unsigned)R.grid), b(64);
+    const size_t lds = (size_t)K.blasStackCap * 64 * sizeof(uint2);
+    const bool ovf = K.blasOvfCap > 0;
+    const float4* rays = static_cast<const float4*>(R.rays);
+#define RZ_LAUNCH_RAYS(O, S)                                                                                                        \
+    do {                                                                                                                            \
+        if (R.shadow) hipLaunchKernelGGL((rz_shadow_rays_kernel<O, S>), g, b, lds, stream, K, rays, static_cast<float2*>(R.out),  \
+                                         R.n, R.errWord);                                                                           \
+        else hipLaunchKernelGGL((rz_trace_rays_kernel<O, S>), g, b, lds, stream, K, rays, static_cast<float4*>(R.out), R.n,        \
+                                R.instTriOff, R.errWord);                                                                           \
+    } while (0)
+    if (ovf) { if (R.spread) RZ_LAUNCH_RAYS(true, true); else RZ_LAUNCH_RAYS(true, false); }
+    else { if (R.spread) RZ_LAUNCH_RAYS(false, true); else RZ_LAUNCH_RAYS(false, false); }
+#undef RZ_LAUNCH_RAYS
+}
+
+}  // namespace rz

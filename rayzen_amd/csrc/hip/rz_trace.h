@@ -132,6 +132,11 @@ struct HitRec {
     int inst;
 };
 
+// What a ray query (rz_rays.hip) takes from a closest-hit query beyond HitRec: the winning triangle (its leaf-order DevTri
+// index, -1 on a miss) and whether the walk stopped at its backstop instead of at its end.  Only asked for with EXTRA = true:
+// the render kernels' instantiations (EXTRA = false) never compute it.
+struct TraceExtra { int tri; bool cut; };
+
 // Number of lanes for which p holds, compared on the scalar unit (written with __popcll the compiler widened the count
 // to 64 bits and compared it with a VECTOR instruction, v_cmp_gt_u64 on an SGPR pair, plus two mask operations).
 __device__ __forceinline__ int mask_count(unsigned long long m) {
@@ -682,8 +687,9 @@ __device__ __forceinline__ int traverse_blas_mi(const KParams& K, int inst, v3 l
 // (The shader's stack[64] has no overflow guard; the oracle skips a push that would not fit.  The number of entries
 //  below a node when it is popped is a property of the tree -- one per ancestor whose right subtree holds it -- so
 //  the layout marks such nodes as never expanding: count 0.)
-template <bool COUNT, bool OVF>
-__device__ __forceinline__ bool trace_closest(const KParams& K, v3 o, v3 d, HitRec& h, const BlasStackT<OVF>& bstk, Tally& c) {
+template <bool COUNT, bool OVF, bool EXTRA = false>
+__device__ __forceinline__ bool trace_closest(const KParams& K, v3 o, v3 d, HitRec& h, const BlasStackT<OVF>& bstk, Tally& c,
+                                              TraceExtra* x = nullptr) {
     float tHit = 1e30f;
     int bestTri = -1, bestInst = -1;
     v3 bestP = mk3(0.0f, 0.0f, 0.0f);
@@ -694,7 +700,8 @@ __device__ __forceinline__ bool trace_closest(const KParams& K, v3 o, v3 d, HitR
     // (pos strictly grows -- a skip position lies behind its node, by construction on the host and on the device -- so the
     //  list is walked in at most nDfs steps; `step` is the backstop against a list that says otherwise: a wave that never
     //  leaves this loop takes the device with it)
-    for (int pos = 0, step = 0; pos < nDfs && step < nDfs; ++step) {
+    int pos = 0;
+    for (int step = 0; pos < nDfs && step < nDfs; ++step) {
         const f32x16 q = sload16(K.tlasDfs + pos);
         const bool at = idx == pos;
         RZ_SITE(c, 4);
@@ -747,6 +754,7 @@ __device__ __forceinline__ bool trace_closest(const KParams& K, v3 o, v3 d, HitR
             pos = skip;
         }
     }
+    if constexpr (EXTRA) { x->tri = bestTri; x->cut = pos < nDfs; }
     if (bestTri < 0) return false;
     // the winner's normal and material (FS:411-412, 489-491): the triangle's own normal comes precomputed (DevTriN)
     const float4 nm = *reinterpret_cast<const float4*>(K.triN + bestTri);
@@ -771,8 +779,9 @@ __device__ __forceinline__ bool trace_closest(const KParams& K, v3 o, v3 d, HitR
 // (traverse_blas_mi); then they go on behind their leaves.  Per lane the pops, the culls against its own tHit, the instance
 // entries and their order are exactly trace_closest's: same result, same tallies; which of the two runs is a scheduling
 // decision of the caller (wave-uniform) that cannot change a bit of the image.
-template <bool COUNT, bool OVF>
-__device__ __forceinline__ bool trace_spread(const KParams& K, v3 o, v3 d, HitRec& h, const BlasStackT<OVF>& bstk, Tally& c) {
+template <bool COUNT, bool OVF, bool EXTRA = false>
+__device__ __forceinline__ bool trace_spread(const KParams& K, v3 o, v3 d, HitRec& h, const BlasStackT<OVF>& bstk, Tally& c,
+                                             TraceExtra* x = nullptr) {
     float tHit = 1e30f;
     int bestTri = -1, bestInst = -1;
     v3 bestP = mk3(0.0f, 0.0f, 0.0f);
@@ -829,6 +838,7 @@ __device__ __forceinline__ bool trace_spread(const KParams& K, v3 o, v3 d, HitRe
             if (pnext < pend) { pinst = K.tlasIndices[pnext]; ++pnext; } else pinst = -1;
         }
     } while (again && ++round < K.traceRoundCap);
+    if constexpr (EXTRA) { x->tri = bestTri; x->cut = again; }
     if (bestTri < 0) return false;
     const float4 nm = *reinterpret_cast<const float4*>(K.triN + bestTri);
     const v3 ln = mk3(nm.x, nm.y, nm.z);

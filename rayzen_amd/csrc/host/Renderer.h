@@ -6,12 +6,15 @@
 //   updateDynamicBVHAndSSBOs(scene)    <- main.cpp:1123-1208 (TLAS rebuild + glBufferSubData)
 //   sendSceneDataToShader(scene, ...)  <- main.cpp:1356-1392 (uniforms)
 //   draw() / finish()                  <- main.cpp:637 glDrawArrays / :1347 glFinish
+//   pick(mouseX, mouseY, scene)        <- main.cpp:501-552 (brute-force picking loop), one ray query instead
 // Unlike the reference's per-frame path, updateDynamicBVHAndSSBOs re-uploads
 // only what changed (instances + TLAS, a few KB), not all geometry.
 #pragma once
 #include <cstring>
 #include <map>
+#include <optional>
 #include <stdexcept>
+#include <utility>
 #include <string>
 #include <vector>
 
@@ -144,6 +147,42 @@ public:
         std::vector<uint8_t> out((size_t)width_ * height_ * 4);
         check(rz_resolve_rgba8(ctx_, out.data(), out.size()), "rz_resolve_rgba8");
         return out;
+    }
+    // Batched ray queries on the uploaded scene (rz_trace_rays / rz_shadow_rays), host memory: return when the results are written.
+    std::vector<rz_hit> traceRays(const std::vector<rz_ray>& rays, bool incoherent = false) {
+        std::vector<rz_hit> hits(rays.size());
+        check(rz_trace_rays(ctx_, rays.data(), hits.data(), rays.size(), RZ_RAYS_HOST | (incoherent ? RZ_RAYS_INCOHERENT : 0u)), "rz_trace_rays");
+        return hits;
+    }
+    std::vector<rz_visibility> shadowRays(const std::vector<rz_ray>& rays, bool incoherent = false) {
+        std::vector<rz_visibility> out(rays.size());
+        check(rz_shadow_rays(ctx_, rays.data(), out.data(), rays.size(), RZ_RAYS_HOST | (incoherent ? RZ_RAYS_INCOHERENT : 0u)), "rz_shadow_rays");
+        return out;
+    }
+    // The picking ray of main.cpp:505-513 (cursor -> NDC -> inverse projection -> eye direction -> inverse view), for a
+    // screen of width x height pixels.
+    static rz_ray pickRay(double mouseX, double mouseY, int width, int height, const Camera& camera) {
+        const float ndcX = 2.0f * float(mouseX) / float(width) - 1.0f;
+        const float ndcY = 1.0f - 2.0f * float(mouseY) / float(height);
+        vec4 rayEye = inverse(camera.projectionMatrix) * vec4{ndcX, ndcY, -1.0f, 1.0f};
+        rayEye = vec4{rayEye.x, rayEye.y, -1.0f, 0.0f};
+        const vec4 w = inverse(camera.viewMatrix) * rayEye;
+        const vec3 dir = normalize(vec3{w.x, w.y, w.z});
+        rz_ray r{};
+        r.origin[0] = camera.position.x; r.origin[1] = camera.position.y; r.origin[2] = camera.position.z;
+        r.max_dist = 1e30f;
+        r.dir[0] = dir.x; r.dir[1] = dir.y; r.dir[2] = dir.z;
+        return r;
+    }
+    // main.cpp:501-552 as one closest-hit query: (instance, mesh-local triangle) under the cursor -- the values
+    // rz_present_params.selected_blas / selected_tri take -- or nothing on a miss (the reference then keeps its previous
+    // selection: main.cpp:548).  The screen is the frame of the last sendSceneDataToShader.  World distances decide, not the
+    // reference's object-local t; |a| < 1e-4 rejects as in the shader; empty BLAS are never hit ("Picking").
+    std::optional<std::pair<int, int>> pick(double mouseX, double mouseY, const Scene& scene) {
+        const std::vector<rz_ray> ray{pickRay(mouseX, mouseY, width_, height_, scene.camera)};
+        const rz_hit h = traceRays(ray)[0];
+        if (h.instance < 0) return std::nullopt;
+        return std::make_pair(h.instance, h.triangle);
     }
     float lastRenderMs() { float ms = 0; int n = 0; check(rz_last_render_ms(ctx_, &ms, &n), "rz_last_render_ms"); return ms; }
     rz_ctx* context() { return ctx_; }

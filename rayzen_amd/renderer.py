@@ -34,6 +34,46 @@ def frame_params(camera, width, height, num_lights, bounce_budget, spp, sample_b
     return p
 
 
+RAY_DTYPE = np.dtype([("origin", "<f4", 3), ("max_dist", "<f4"), ("dir", "<f4", 3), ("reserved", "<u4")])   # rz_ray
+HIT_DTYPE = np.dtype([("t", "<f4"), ("point", "<f4", 3), ("normal", "<f4", 3), ("material", "<i4"), ("instance", "<i4"),
+                      ("triangle", "<i4"), ("prim", "<i4"), ("reserved", "<i4")])                                # rz_hit
+VISIBILITY_DTYPE = np.dtype([("visibility", "<f4"), ("lit", "<i4")])                                         # rz_visibility
+
+
+def make_rays(origins, dirs, max_dist=1e30):
+    """An rz_ray array from (n, 3) origins and directions (float32) and a scalar or (n,) max_dist."""
+    o = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
+    d = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
+    if o.shape != d.shape:
+        raise ValueError(f"origins {o.shape} and dirs {d.shape} differ")
+    rays = np.zeros(o.shape[0], RAY_DTYPE)
+    rays["origin"], rays["dir"] = o, d
+    rays["max_dist"] = np.broadcast_to(np.asarray(max_dist, np.float32), (o.shape[0],))
+    return rays
+
+
+def _glm_mul(m, v):
+    """GLM 0.9.9's mat4 * vec4 in float32: (m0 x + m1 y) + (m2 z + m3 w), m column-major (16 floats)."""
+    c = np.asarray(m, np.float32).reshape(4, 4)
+    x, y, z, w = (np.float32(a) for a in v)
+    return (c[0] * x + c[1] * y) + (c[2] * z + c[3] * w)
+
+
+def pick_ray(mouse_x, mouse_y, screen_w, screen_h, camera):
+    """RayZen's picking ray (main.cpp:505-513), step by step in float32: the cursor in NDC, the clip-space point
+    (ndcX, ndcY, -1, 1) through the inverse projection, made a direction (x, y, -1, 0) in eye space, through the inverse view
+    and normalised (glm::normalize: v * (1 / sqrt(dot(v, v)))).  Returns (origin, dir), each (3,) float32; origin is the camera
+    position.  Host-only, no GPU."""
+    f32 = np.float32
+    ndc_x = f32(2.0) * f32(mouse_x) / f32(screen_w) - f32(1.0)
+    ndc_y = f32(1.0) - f32(2.0) * f32(mouse_y) / f32(screen_h)
+    ray_eye = _glm_mul(camera.inv_proj, (ndc_x, ndc_y, f32(-1.0), f32(1.0)))
+    v = _glm_mul(camera.inv_view, (ray_eye[0], ray_eye[1], f32(-1.0), f32(0.0)))[:3]
+    dot = (v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]
+    direction = (v * (f32(1.0) / np.sqrt(dot))).astype(np.float32)
+    return np.asarray(camera.position, np.float32).copy(), direction
+
+
 class Renderer:
     def __init__(self, device=0, flags=0):
         self._L = _lib.hip()
@@ -236,6 +276,51 @@ class Renderer:
 
     def accum_device_ptr(self):
         return self._L.rz_accum_device_ptr(self._c)
+
+    # -- ray queries (rz_trace_rays / rz_shadow_rays) ---------------------------
+    def trace_rays(self, origins, dirs, incoherent=False):
+        """Closest hits of (n, 3) float32 rays on the uploaded scene (host memory; returns when done).  Returns a dict of numpy
+        arrays: t, point, normal, material, instance, triangle, prim (a miss: t = 1e30, ids -1, point / normal zero)."""
+        rays = make_rays(origins, dirs)
+        hits = np.zeros(rays.shape[0], HIT_DTYPE)
+        flags = _lib.RAYS_HOST | (_lib.RAYS_INCOHERENT if incoherent else 0)
+        self._check(self._L.rz_trace_rays(self._c, rays.ctypes.data if rays.size else None, hits.ctypes.data if hits.size else None,
+                                          rays.shape[0], flags), "rz_trace_rays")
+        return {k: hits[k].copy() for k in ("t", "point", "normal", "material", "instance", "triangle", "prim")}
+
+    def trace_rays_device(self, rays_ptr, hits_ptr, n, incoherent=False):
+        """rz_trace_rays on device memory (rz_ray[n] in, rz_hit[n] out, 16-B aligned): enqueued on the context's stream,
+        asynchronous -- the hits are valid after sync() or the caller's own synchronisation of that stream."""
+        self._check(self._L.rz_trace_rays(self._c, C.c_void_p(rays_ptr), C.c_void_p(hits_ptr), int(n),
+                                          _lib.RAYS_INCOHERENT if incoherent else 0), "rz_trace_rays")
+
+    def shadow_rays(self, origins, dirs, max_dist, incoherent=False):
+        """FS:507-528 for (n, 3) float32 rays with a scalar or (n,) max_dist (host memory).  Returns (lit bool (n,),
+        visibility float32 (n,))."""
+        rays = make_rays(origins, dirs, max_dist)
+        out = np.zeros(rays.shape[0], VISIBILITY_DTYPE)
+        flags = _lib.RAYS_HOST | (_lib.RAYS_INCOHERENT if incoherent else 0)
+        self._check(self._L.rz_shadow_rays(self._c, rays.ctypes.data if rays.size else None, out.ctypes.data if out.size else None,
+                                           rays.shape[0], flags), "rz_shadow_rays")
+        return out["lit"] != 0, out["visibility"].copy()
+
+    def shadow_rays_device(self, rays_ptr, out_ptr, n, incoherent=False):
+        """rz_shadow_rays on device memory (rz_ray[n] in, rz_visibility[n] out, 16-B aligned); asynchronous."""
+        self._check(self._L.rz_shadow_rays(self._c, C.c_void_p(rays_ptr), C.c_void_p(out_ptr), int(n),
+                                           _lib.RAYS_INCOHERENT if incoherent else 0), "rz_shadow_rays")
+
+    def pick(self, mouse_x, mouse_y, screen_w, screen_h, camera):
+        """What RayZen's BLAS debug mode picks under the cursor (main.cpp:501-552), by one closest-hit query of the picking
+        ray (pick_ray) on the uploaded scene.  Returns (instance, triangle) -- exactly what present(show_bvh=True, bvh_mode=1,
+        selected_blas=instance, selected_tri=triangle) takes -- or None on a miss.  The reference KEEPS its previous selection
+        when nothing is hit (main.cpp:548); a caller that wants that behaviour keeps its own on None.
+        Unlike the reference's brute-force loop it compares world distances (as the shader does), rejects at |a| < 1e-4 (the
+        shader's bound, not 1e-6) and never hits an empty or invalid BLAS: it picks what the frame shows."""
+        o, d = pick_ray(mouse_x, mouse_y, screen_w, screen_h, camera)
+        h = self.trace_rays(o[None], d[None])
+        if h["instance"][0] < 0:
+            return None
+        return int(h["instance"][0]), int(h["triangle"][0])
 
     # -- convenience -----------------------------------------------------------
     def render_scene(self, scene, width, height, spp, bounce_budget, num_lights=None, tile_rank=0, tile_nranks=1,
