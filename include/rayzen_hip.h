@@ -432,6 +432,40 @@ typedef struct rz_visibility {
 int rz_trace_rays(rz_ctx* ctx, const rz_ray* rays, rz_hit* hits, size_t n, unsigned flags);
 int rz_shadow_rays(rz_ctx* ctx, const rz_ray* rays, rz_visibility* out, size_t n, unsigned flags);
 
+/* ------------------------------------------------------------------------ */
+/* Editor preview (main.cpp:1210-1322, shaders/editor_{vertex,fragment}.glsl) */
+/* ------------------------------------------------------------------------ */
+/* RayZen's editor mode (F1) -- flat-shaded geometry, GGX direct lighting from every light, an ambient term, no shadows -- as a
+ * ray cast instead of a raster pass: per pixel, the closest hit of the ray through the pixel centre (the render's camera ray
+ * with no jitter, from cam_pos), clipped as the rasteriser clips (the world hit through view then proj: visible iff
+ * -w <= z_clip <= w; beyond the far plane the pixel is background; a surface in front of the near plane is skipped and the
+ * query restarts where the ray crosses the near plane, at most 4 times), shaded by editor_fragment.glsl:58-112 with the hit's
+ * world normal (normalize(mat3(transpose(inverseTransform)) * faceNormal): uNormalMatrix * faceNormal of main.cpp:1299-1301 up
+ * to rounding).  No culling: a back face gets NdotV = 0 (diffuse only).  Where nothing visible is hit: the clear colour.
+ * From `frame` the call reads width, height, inv_view, inv_proj, view, proj, cam_pos and num_lights (the loop runs over
+ * min(num_lights, lights uploaded)); it needs no rz_set_frame and leaves the frame rz_set_frame set, the accumulation,
+ * currentIor and rz_debug_last_plan as they were.  Outputs (each optional: NULL is not written), row 0 = the bottom row:
+ *   rgba8   width*height*4 B: rint(clamp(colour, 0, 1) * 255), alpha 255 (rz_present's quantisation)
+ *   rgb32f  width*height*3 floats: the colour before quantisation
+ *   hits    width*height rz_hit: a visible hit exactly as rz_trace_rays returns it for the pixel's ray, except that t counts
+ *           from the camera after a near-plane restart; a background pixel gets the miss record (t = 1e30f, ids -1)
+ * Pointers are DEVICE memory by default (hits 16-byte aligned, the others 4-byte): the call is enqueued on the context's stream
+ * and sees the scene as of the last rz_upload / rz_update / rz_update_transforms issued before it.  With RZ_EDITOR_HOST they
+ * are host memory: staged through a buffer of the context, the call returns when they are written and reports a walk cut
+ * short at its backstop as rz_trace_rays does (RZ_ERR_INTERNAL).  RZ_ERR_INVALID_ARG: null context or frame, width or
+ * height <= 0, more than INT32_MAX pixels, a misaligned device pointer, unknown flags; RZ_ERR_BUFFER_SIZE: a non-NULL output
+ * smaller than the above; RZ_ERR_NOT_READY: no scene uploaded, or no materials.
+ * (Additive: RZ_ABI_VERSION stays 5.) */
+typedef struct rz_editor_params {      /* NULL = RayZen's values */
+    float ambient[3];  float pad0;      /* uAmbientColor, main.cpp:1269: 0.03 */
+    float clear[4];                     /* glClearColor, main.cpp:260: 0.05 0.05 0.07 1 */
+} rz_editor_params;                     /* 32 B; rz_sizeof(10) */
+#define RZ_EDITOR_HOST       1u  /* outputs are host memory: staged, returns when written */
+#define RZ_EDITOR_INCOHERENT 2u  /* trace_spread: scheduling hint, identical results */
+int rz_render_editor(rz_ctx* ctx, const rz_frame_params* frame, const rz_editor_params* params,
+                     uint8_t* rgba8, size_t rgba8_bytes, float* rgb32f, size_t rgb32f_bytes,
+                     rz_hit* hits, size_t hits_bytes, unsigned flags);
+
 /* Number of HIP devices visible to the process (0 without a GPU). */
 int rz_device_count(void);
 
@@ -454,7 +488,7 @@ const char* rz_source_hash(void);
 /* sizeof() of the ABI structs as compiled into the library, for layout
  * checks from other languages: which = 0 triangle, 1 node, 2 instance,
  * 3 material, 4 light, 5 frame_params, 6 counters, 7 ray, 8 hit,
- * 9 visibility. */
+ * 9 visibility, 10 editor_params. */
 size_t rz_sizeof(int which);
 
 #ifdef __cplusplus

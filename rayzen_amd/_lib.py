@@ -21,7 +21,7 @@ HIP_SYMBOLS = (
     "rz_group_last_error", "rz_group_size", "rz_group_local_count", "rz_group_rank", "rz_group_ctx", "rz_group_upload",
     "rz_group_update", "rz_group_set_frame", "rz_group_render", "rz_group_reduce", "rz_group_sync", "rz_group_read_frame",
     "rz_group_frame_device_ptr", "rz_group_last_reduce_ms", "rz_group_transport", "rz_group_set_transport", "rz_abi_version", "rz_debug_poke_backstop", "rz_math_flavour",
-    "rz_trace_rays", "rz_shadow_rays",
+    "rz_trace_rays", "rz_shadow_rays", "rz_render_editor",
 )
 ABI_VERSION = 5         # RZ_ABI_VERSION of the include/rayzen_hip.h this file mirrors
 # the symbols include/rayzen_host.h declares
@@ -92,6 +92,14 @@ class Visibility(C.Structure):
 
 
 RAYS_HOST, RAYS_INCOHERENT = 1, 2       # RZ_RAYS_HOST, RZ_RAYS_INCOHERENT
+
+
+class EditorParams(C.Structure):
+    """rz_editor_params of include/rayzen_hip.h (32 B)."""
+    _fields_ = [("ambient", C.c_float * 3), ("pad0", C.c_float), ("clear", C.c_float * 4)]
+
+
+EDITOR_HOST, EDITOR_INCOHERENT = 1, 2   # RZ_EDITOR_HOST, RZ_EDITOR_INCOHERENT
 
 
 class Counters(C.Structure):
@@ -167,7 +175,8 @@ def hip():
                                 ("rz_group_transport", C.c_char_p, [vp]),
                                 ("rz_group_set_transport", i, [vp, C.c_char_p]),
                                 ("rz_abi_version", i, []), ("rz_debug_poke_backstop", i, [vp, C.c_uint]), ("rz_math_flavour", i, []),
-                                ("rz_trace_rays", i, [vp, vp, vp, sz, C.c_uint]), ("rz_shadow_rays", i, [vp, vp, vp, sz, C.c_uint])):
+                                ("rz_trace_rays", i, [vp, vp, vp, sz, C.c_uint]), ("rz_shadow_rays", i, [vp, vp, vp, sz, C.c_uint]),
+                                ("rz_render_editor", i, [vp, C.POINTER(FrameParams), vp, vp, sz, vp, sz, vp, sz, C.c_uint])):
             try:
                 fn = getattr(L, name)
                 fn.restype, fn.argtypes = res, args

@@ -38,6 +38,24 @@ struct RaysLaunch {
 long long rays_grid(long long n);
 void launch_rays(const KParams& K, const RaysLaunch& R, hipStream_t stream);
 
+// ---- rz_editor.hip
+struct EditorLaunch {
+    float view[16], proj[16];   // rz_frame_params.view / proj (the clip test of a hit)
+    float ambient[3];           // rz_editor_params.ambient
+    float clear[4];             // rz_editor_params.clear
+    long long units;            // 64-pixel units of the frame: 64-pixel runs of a row (rows = 1), or 8 x 8 tiles
+    int unitsX;                 // units per row of units
+    int rows;                   // 1: a wave covers 64 pixels of one row (the default); 0: an 8 x 8 tile (RZ_EDITOR_TILES=1, an A/B aid)
+    long long grid;             // rays_grid(width * height)
+    bool spread;                // the lane-by-lane walk (trace_spread)
+    uchar4* rgba8;              // device outputs, each optional (nullptr: not written); row 0 = bottom
+    float* rgb32f;              // width x height x 3
+    float4* hits;               // width x height rz_hit (3 float4)
+    const int32_t* instTriOff;  // globalTriOffset of every instance (as RaysLaunch)
+    unsigned* errWord;          // the context's backstop word
+};
+void launch_editor(const KParams& K, const EditorLaunch& E, hipStream_t stream);
+
 // ---- rz_tlas_device.hip
 void launch_tlas_refit(const TlasWork& W, hipStream_t s);
 

@@ -57,6 +57,15 @@ struct Path {
     int gflag;          // pooled paths of a transparent scene (GMODE 2): 1 = P.ior is the value the sequential shader would hand this sample (it may scatter at glass)
 };
 
+// FS:206-212: the camera ray direction through the (jittered) screen point (ux, uy) in [0, 1]^2.
+__device__ __forceinline__ v3 camera_dir(const float* __restrict__ invProj, const float* __restrict__ invView, const float ux, const float uy) {
+    const float cx = ux * 2.0f - 1.0f, cy = uy * 2.0f - 1.0f;
+    const float* ip = invProj;
+    const float ex = ((ip[0] * cx + ip[4] * cy) + ip[8] * -1.0f) + ip[12] * 1.0f;
+    const float ey = ((ip[1] * cx + ip[5] * cy) + ip[9] * -1.0f) + ip[13] * 1.0f;
+    const v3 world = xform_dir(invView, mk3(ex, ey, -1.0f));
+    return normalize(world);
+}
 // FS:204-212 + FS:688-692: the sample's seed and its camera ray direction from (uv, fragCoord.x + y, sample index).
 struct CameraRay { v2 seed; v3 d; };
 __device__ __forceinline__ CameraRay camera_ray(const float* __restrict__ invProj, const float* __restrict__ invView, const v2 uv, const float fragSum, const int samp) {
@@ -66,14 +75,13 @@ __device__ __forceinline__ CameraRay camera_ray(const float* __restrict__ invPro
     r.seed.y = uv.y * sf;
     v2 s1; s1.x = r.seed.x + 1.0f; s1.y = r.seed.y + 1.0f;
     const float jx = rand_(r.seed) * 0.00002f, jy = rand_(s1) * 0.00002f;
-    const float ux = uv.x + jx, uy = uv.y + jy;
-    const float cx = ux * 2.0f - 1.0f, cy = uy * 2.0f - 1.0f;
-    const float* ip = invProj;
-    const float ex = ((ip[0] * cx + ip[4] * cy) + ip[8] * -1.0f) + ip[12] * 1.0f;
-    const float ey = ((ip[1] * cx + ip[5] * cy) + ip[9] * -1.0f) + ip[13] * 1.0f;
-    const v3 world = xform_dir(invView, mk3(ex, ey, -1.0f));
-    r.d = normalize(world);
+    r.d = camera_dir(invProj, invView, uv.x + jx, uv.y + jy);
     return r;
+}
+// The ray through the centre of a pixel (the editor preview, rz_editor.hip): camera_ray with a jitter of zero.  uv.x + 0.0f
+// is uv.x for the positive uv of a pixel centre, so the direction is bit for bit the one camera_ray computes for jx = jy = 0.
+__device__ __forceinline__ v3 camera_ray_centre(const float* __restrict__ invProj, const float* __restrict__ invView, const v2 uv) {
+    return camera_dir(invProj, invView, uv.x, uv.y);
 }
 template <bool COUNT>
 __device__ __forceinline__ void begin_sample(const KParams& K, Path& P, Tally& c) {

@@ -7,9 +7,11 @@
 //   sendSceneDataToShader(scene, ...)  <- main.cpp:1356-1392 (uniforms)
 //   draw() / finish()                  <- main.cpp:637 glDrawArrays / :1347 glFinish
 //   pick(mouseX, mouseY, scene)        <- main.cpp:501-552 (brute-force picking loop), one ray query instead
+//   renderEditor(scene, width, height) <- main.cpp:1210-1322 (renderRasterized + the editor shaders), a ray cast instead
 // Unlike the reference's per-frame path, updateDynamicBVHAndSSBOs re-uploads
 // only what changed (instances + TLAS, a few KB), not all geometry.
 #pragma once
+#include <algorithm>
 #include <cstring>
 #include <map>
 #include <optional>
@@ -183,6 +185,23 @@ public:
         const rz_hit h = traceRays(ray)[0];
         if (h.instance < 0) return std::nullopt;
         return std::make_pair(h.instance, h.triangle);
+    }
+    // Editor mode (F1): renderRasterized (main.cpp:1281-1310) as one rz_render_editor call on the uploaded scene, with the
+    // uniforms of sendRasterSceneData (main.cpp:1266-1275): the camera's view, projection and position, numLights =
+    // scene.lights.size(), ambient 0.03, clear colour (0.05, 0.05, 0.07, 1).  Returns width x height RGBA8, row 0 = the bottom
+    // row (as resolveRGBA8); host memory, returns when written.  Needs no sendSceneDataToShader and leaves its frame alone.
+    std::vector<uint8_t> renderEditor(const Scene& scene, int width, int height, bool incoherent = false) {
+        rz_frame_params p{};
+        p.width = width; p.height = height;
+        mat4 iv = inverse(scene.camera.viewMatrix), ip = inverse(scene.camera.projectionMatrix);
+        std::memcpy(p.inv_view, iv.m, 64); std::memcpy(p.inv_proj, ip.m, 64);
+        std::memcpy(p.view, scene.camera.viewMatrix.m, 64); std::memcpy(p.proj, scene.camera.projectionMatrix.m, 64);
+        p.cam_pos[0] = scene.camera.position.x; p.cam_pos[1] = scene.camera.position.y; p.cam_pos[2] = scene.camera.position.z;
+        p.num_lights = (int)scene.lights.size();
+        std::vector<uint8_t> out((size_t)std::max(width, 0) * (size_t)std::max(height, 0) * 4);    // (a bad size: rz_render_editor says so)
+        check(rz_render_editor(ctx_, &p, nullptr, out.data(), out.size(), nullptr, 0, nullptr, 0,
+                               RZ_EDITOR_HOST | (incoherent ? RZ_EDITOR_INCOHERENT : 0u)), "rz_render_editor");
+        return out;
     }
     float lastRenderMs() { float ms = 0; int n = 0; check(rz_last_render_ms(ctx_, &ms, &n), "rz_last_render_ms"); return ms; }
     rz_ctx* context() { return ctx_; }

@@ -74,6 +74,29 @@ def pick_ray(mouse_x, mouse_y, screen_w, screen_h, camera):
     return np.asarray(camera.position, np.float32).copy(), direction
 
 
+def editor_rays(camera, width, height):
+    """The rays rz_render_editor casts (rz_path.h: camera_ray_centre), one per pixel centre, step by step in float32: uv =
+    (px + 0.5) / width, (py + 0.5) / height; (u * 2 - 1, v * 2 - 1, -1, 1) through the inverse projection, made a direction
+    (x, y, -1, 0) through the inverse view and normalised as v / sqrt(dot(v, v)).  Returns (height * width,) rz_ray records in
+    pixel order (row 0 = the bottom row) with origin = the camera position and max_dist = 1e30.  Host-only, no GPU."""
+    f32 = np.float32
+    px = np.arange(width, dtype=f32)
+    py = np.arange(height, dtype=f32)
+    ux = ((px + f32(0.5)) / f32(width))[None, :]
+    uy = ((py + f32(0.5)) / f32(height))[:, None]
+    cx = ux * f32(2.0) - f32(1.0)
+    cy = uy * f32(2.0) - f32(1.0)
+    ip = np.asarray(camera.inv_proj, f32)
+    iv = np.asarray(camera.inv_view, f32)
+    ex = ((ip[0] * cx + ip[4] * cy) + ip[8] * f32(-1.0)) + ip[12] * f32(1.0)
+    ey = ((ip[1] * cx + ip[5] * cy) + ip[9] * f32(-1.0)) + ip[13] * f32(1.0)
+    w = [(iv[r] * ex + iv[4 + r] * ey) + iv[8 + r] * f32(-1.0) for r in range(3)]
+    dot = (w[0] * w[0] + w[1] * w[1]) + w[2] * w[2]
+    s = np.sqrt(dot)
+    d = np.stack([c / s for c in w], -1).astype(f32).reshape(-1, 3)
+    return make_rays(np.broadcast_to(np.asarray(camera.position, f32), d.shape), d)
+
+
 class Renderer:
     def __init__(self, device=0, flags=0):
         self._L = _lib.hip()
@@ -321,6 +344,46 @@ class Renderer:
         if h["instance"][0] < 0:
             return None
         return int(h["instance"][0]), int(h["triangle"][0])
+
+    # -- editor preview (rz_render_editor) ---------------------------------------
+    @staticmethod
+    def _editor_args(camera, width, height, num_lights, ambient, clear):
+        # num_lights=None: every light uploaded (the call loops over min(num_lights, lights uploaded))
+        fp = frame_params(camera, width, height, 0x7fffffff if num_lights is None else num_lights, 0, 1)
+        if ambient is None and clear is None:
+            return fp, None
+        ep = _lib.EditorParams()
+        ep.ambient[:] = [0.03] * 3 if ambient is None else [float(a) for a in ambient]
+        ep.clear[:] = [0.05, 0.05, 0.07, 1.0] if clear is None else [float(a) for a in clear]
+        return fp, C.byref(ep)
+
+    def render_editor(self, camera, width, height, num_lights=None, ambient=None, clear=None, rgb32f=False, hits=False,
+                      incoherent=False):
+        """RayZen's editor preview (main.cpp:1210-1322) of the uploaded scene, by a ray cast (host memory; returns when done).
+        Returns (rgba8 uint8 (H, W, 4), rgb float32 (H, W, 3) or None, hits HIT_DTYPE (H, W) or None); row 0 = bottom row.
+        ambient (3) and clear (4) default to RayZen's 0.03 and (0.05, 0.05, 0.07, 1)."""
+        fp, ep = self._editor_args(camera, width, height, num_lights, ambient, clear)
+        out8 = np.empty((height, width, 4), np.uint8)
+        rgb = np.empty((height, width, 3), np.float32) if rgb32f else None
+        hh = np.empty((height, width), HIT_DTYPE) if hits else None
+        flags = _lib.EDITOR_HOST | (_lib.EDITOR_INCOHERENT if incoherent else 0)
+        self._check(self._L.rz_render_editor(self._c, C.byref(fp), ep, out8.ctypes.data, out8.nbytes,
+                                             None if rgb is None else rgb.ctypes.data, 0 if rgb is None else rgb.nbytes,
+                                             None if hh is None else hh.ctypes.data, 0 if hh is None else hh.nbytes, flags),
+                    "rz_render_editor")
+        return out8, rgb, hh
+
+    def render_editor_device(self, camera, width, height, rgba8_ptr=None, rgb32f_ptr=None, hits_ptr=None, num_lights=None,
+                             ambient=None, clear=None, incoherent=False):
+        """rz_render_editor into device memory (each output optional; hits 16-B aligned, the others 4-B): enqueued on the
+        context's stream, asynchronous -- the outputs are valid after sync() or the caller's own synchronisation of that
+        stream.  Sizes: rgba8 W*H*4 B, rgb32f W*H*12 B, hits W*H*48 B."""
+        fp, ep = self._editor_args(camera, width, height, num_lights, ambient, clear)
+        n = int(width) * int(height)
+        self._check(self._L.rz_render_editor(self._c, C.byref(fp), ep, C.c_void_p(rgba8_ptr), n * 4 if rgba8_ptr else 0,
+                                             C.c_void_p(rgb32f_ptr), n * 12 if rgb32f_ptr else 0, C.c_void_p(hits_ptr),
+                                             n * 48 if hits_ptr else 0, _lib.EDITOR_INCOHERENT if incoherent else 0),
+                    "rz_render_editor")
 
     # -- convenience -----------------------------------------------------------
     def render_scene(self, scene, width, height, spp, bounce_budget, num_lights=None, tile_rank=0, tile_nranks=1,
