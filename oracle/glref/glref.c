@@ -81,26 +81,8 @@ typedef struct {
     float fps, view[16], proj[16], invView[16], invProj[16], camPos[3];
 } blob_header;
 
-int main(int argc, char** argv) {
-    if (argc < 3) DIE("usage: glref <scene.blob> <out.f32> [shader_dir]");
-    const char* shader_dir = argc > 3 ? argv[3] : "/root/reference/RayZen/shaders";
-    const char* driver = getenv("GLREF_DRIVER") ? getenv("GLREF_DRIVER") : "/usr/lib/x86_64-linux-gnu/dri/swrast_dri.so";
-
-    /* ---- the scene ---- */
-    FILE* bf = fopen(argv[1], "rb");
-    if (!bf) DIE("cannot open %s", argv[1]);
-    blob_header H;
-    if (fread(&H, sizeof H, 1, bf) != 1 || memcmp(H.magic, "RZGL", 4) != 0 || H.version != 2) DIE("bad blob header");
-    void* bufs[10];
-    uint64_t bytes[10];
-    for (int b = 0; b < 10; ++b) {
-        if (fread(&bytes[b], 8, 1, bf) != 1) DIE("short blob");
-        bufs[b] = malloc(bytes[b] ? bytes[b] : 1);
-        if (bytes[b] && fread(bufs[b], 1, bytes[b], bf) != bytes[b]) DIE("short blob (binding %d)", b);
-    }
-    fclose(bf);
-
-    /* ---- Mesa's software driver, loaded the way libGLX_mesa loads it ---- */
+/* ---- Mesa's software driver, loaded the way libGLX_mesa loads it; a 4.3 core context made current ---- */
+static void make_current(const char* driver) {
     void* drv = dlopen(driver, RTLD_NOW | RTLD_GLOBAL);
     if (!drv) DIE("dlopen %s: %s", driver, dlerror());
     const __DRIextension** (*get_ext)(void) = (const __DRIextension** (*)(void))dlsym(drv, __DRI_DRIVER_GET_EXTENSIONS "_swrast");
@@ -123,11 +105,326 @@ int main(int argc, char** argv) {
     __DRIdrawable* draw = swrast->createNewDrawable(screen, configs[0], NULL);
     if (!draw) DIE("createNewDrawable failed");
     if (!core->bindContext(ctx, draw, draw)) DIE("bindContext failed");
-
+    
     void* glapi = dlopen("libglapi.so.0", RTLD_NOW | RTLD_GLOBAL);
     if (!glapi) DIE("dlopen libglapi.so.0: %s", dlerror());
     get_proc = (void* (*)(const char*))dlsym(glapi, "_glapi_get_proc_address");
     if (!get_proc) DIE("no _glapi_get_proc_address");
+}
+
+/* ---- editor mode (blob magic "RZED"): RayZen's raster pass, buildRasterMeshes / sendRasterSceneData / renderRasterized
+ * (main.cpp:1210-1297), with editor_vertex.glsl + editor_fragment.glsl read from shader_dir.
+ *
+ *   scene.blob (little endian), written by oracle/glref/glref.py: render_editor:
+ *     char magic[4] = "RZED"; int32 version = 1;
+ *     int32 width, height, numLights, nMeshes, nObjects;
+ *     float view[16], proj[16], camPos[3], ambient[3], clear[4];
+ *     uint64 bytes; materials (binding 1);  uint64 bytes; lights (binding 2)
+ *     nMeshes x { int32 nVertices; nVertices x RasterVertex {float position[3], normal[3]; int32 materialIndex} }
+ *     nObjects x { int32 mesh (-1: no mesh, skipped); float model[16]; float normalMatrix[9] }   -- gameObjects order
+ *   out (row 0 = the bottom row): W*H x float[4] FragColor from an RGBA32F attachment; W*H x uint8[4] FragColor from an RGBA8
+ *     attachment (the window's format); then the ID pass: W*H x int32[4] (object, gl_PrimitiveID, materialIndex, 1; -1 where
+ *     nothing was drawn), W*H x float[4] (worldPos, gl_FragCoord.z), W*H x float[4] (the interpolated normal, 0);
+ *     then W*H x uint32 the depth buffer (glReadPixels GL_UNSIGNED_INT).
+ *   Each pass has its own framebuffer with a 24-bit depth renderbuffer (GLFW's default window depth), GL_LESS, cleared to
+ *   1.0; no culling, no blending, no multisampling.  The ID pass runs the fragment shader named by GLREF_FRAGMENT (the
+ *   harness's own oracle/glref/editor_ids.glsl) behind RayZen's editor_vertex.glsl; the harness fails unless all three
+ *   passes leave bitwise-equal depth buffers, i.e. rasterised the same fragments. */
+typedef struct {
+    char magic[4];
+    int32_t version, width, height, numLights, nMeshes, nObjects;
+    float view[16], proj[16], camPos[3], ambient[3], clear[4];
+} editor_header;
+
+static void* read_sized(FILE* f, uint64_t* n) {
+    if (fread(n, 8, 1, f) != 1) DIE("short blob");
+    void* p = malloc(*n ? *n : 1);
+    if (*n && fread(p, 1, *n, f) != *n) DIE("short blob");
+    return p;
+}
+
+/* The ID pass's fragment shader (GLREF_FRAGMENT) holds the token GLREF_FRAGMENT_INPUTS once; it is replaced by the input
+ * block that RayZen's editor_fragment.glsl declares -- from `in VS_OUT` through the block's closing `;`, which must occur
+ * exactly once there -- so that the two fragment shaders read the same interface and no copy of it is kept here. */
+static char* splice_inputs(const char* ids, const char* frag, const char* path) {
+    const char* tok = "GLREF_FRAGMENT_INPUTS";
+    const char* at = strstr(ids, tok);
+    if (!at || strstr(at + 1, tok)) DIE("%s: expected exactly one %s", path, tok);
+    const char* b = strstr(frag, "in VS_OUT");
+    if (!b || strstr(b + 1, "in VS_OUT")) DIE("editor_fragment.glsl: expected exactly one input block `in VS_OUT`");
+    const char* close = strchr(b, '}');
+    const char* e = close ? strchr(close, ';') : NULL;
+    if (!e) DIE("editor_fragment.glsl: the input block does not end");
+    const size_t head = (size_t)(at - ids), block = (size_t)(e + 1 - b);
+    char* out = malloc(strlen(ids) - strlen(tok) + block + 1);
+    memcpy(out, ids, head);
+    memcpy(out + head, b, block);
+    strcpy(out + head + block, at + strlen(tok));
+    return out;
+}
+
+static int editor_main(FILE* bf, const char* out_path, const char* shader_dir, const char* driver) {
+    rewind(bf);
+    editor_header H;
+    if (fread(&H, sizeof H, 1, bf) != 1 || H.version != 1 || H.width <= 0 || H.height <= 0 || H.nMeshes < 0 || H.nObjects < 0)
+        DIE("bad editor blob header");
+    uint64_t matBytes, lightBytes;
+    void* mats = read_sized(bf, &matBytes);
+    void* lights = read_sized(bf, &lightBytes);
+    int32_t* nVerts = calloc((size_t)H.nMeshes + 1, sizeof(int32_t));
+    void** verts = calloc((size_t)H.nMeshes + 1, sizeof(void*));
+    for (int m = 0; m < H.nMeshes; ++m) {
+        if (fread(&nVerts[m], 4, 1, bf) != 1 || nVerts[m] < 0 || nVerts[m] % 3) DIE("bad mesh %d", m);
+        verts[m] = malloc((size_t)nVerts[m] * 28 + 1);
+        if (nVerts[m] && fread(verts[m], 28, (size_t)nVerts[m], bf) != (size_t)nVerts[m]) DIE("short blob (mesh %d)", m);
+    }
+    int32_t* objMesh = calloc((size_t)H.nObjects + 1, sizeof(int32_t));
+    float* objModel = calloc((size_t)H.nObjects * 16 + 1, sizeof(float));
+    float* objNormal = calloc((size_t)H.nObjects * 9 + 1, sizeof(float));
+    for (int o = 0; o < H.nObjects; ++o) {
+        if (fread(&objMesh[o], 4, 1, bf) != 1 || fread(objModel + 16 * o, 64, 1, bf) != 1 || fread(objNormal + 9 * o, 36, 1, bf) != 1)
+            DIE("short blob (object %d)", o);
+        if (objMesh[o] >= H.nMeshes) DIE("object %d: no mesh %d", o, objMesh[o]);
+    }
+    fclose(bf);
+
+    make_current(driver);
+    GLFN(PFNGLGETSTRINGPROC, glGetString);
+    GLFN(PFNGLGETERRORPROC, glGetError);
+    fprintf(stderr, "glref: %s | %s | GLSL %s\n", (const char*)glGetString(GL_RENDERER), (const char*)glGetString(GL_VERSION),
+            (const char*)glGetString(GL_SHADING_LANGUAGE_VERSION));
+    GLFN(PFNGLCREATESHADERPROC, glCreateShader);
+    GLFN(PFNGLSHADERSOURCEPROC, glShaderSource);
+    GLFN(PFNGLCOMPILESHADERPROC, glCompileShader);
+    GLFN(PFNGLGETSHADERIVPROC, glGetShaderiv);
+    GLFN(PFNGLGETSHADERINFOLOGPROC, glGetShaderInfoLog);
+    GLFN(PFNGLCREATEPROGRAMPROC, glCreateProgram);
+    GLFN(PFNGLATTACHSHADERPROC, glAttachShader);
+    GLFN(PFNGLLINKPROGRAMPROC, glLinkProgram);
+    GLFN(PFNGLGETPROGRAMIVPROC, glGetProgramiv);
+    GLFN(PFNGLGETPROGRAMINFOLOGPROC, glGetProgramInfoLog);
+    GLFN(PFNGLUSEPROGRAMPROC, glUseProgram);
+    GLFN(PFNGLGETUNIFORMLOCATIONPROC, glGetUniformLocation);
+    GLFN(PFNGLUNIFORM1IPROC, glUniform1i);
+    GLFN(PFNGLUNIFORM3FVPROC, glUniform3fv);
+    GLFN(PFNGLUNIFORMMATRIX3FVPROC, glUniformMatrix3fv);
+    GLFN(PFNGLUNIFORMMATRIX4FVPROC, glUniformMatrix4fv);
+    GLFN(PFNGLGENBUFFERSPROC, glGenBuffers);
+    GLFN(PFNGLBINDBUFFERPROC, glBindBuffer);
+    GLFN(PFNGLBUFFERDATAPROC, glBufferData);
+    GLFN(PFNGLBINDBUFFERBASEPROC, glBindBufferBase);
+    GLFN(PFNGLGENVERTEXARRAYSPROC, glGenVertexArrays);
+    GLFN(PFNGLBINDVERTEXARRAYPROC, glBindVertexArray);
+    GLFN(PFNGLVERTEXATTRIBPOINTERPROC, glVertexAttribPointer);
+    GLFN(PFNGLVERTEXATTRIBIPOINTERPROC, glVertexAttribIPointer);
+    GLFN(PFNGLENABLEVERTEXATTRIBARRAYPROC, glEnableVertexAttribArray);
+    GLFN(PFNGLGENFRAMEBUFFERSPROC, glGenFramebuffers);
+    GLFN(PFNGLBINDFRAMEBUFFERPROC, glBindFramebuffer);
+    GLFN(PFNGLFRAMEBUFFERTEXTURE2DPROC, glFramebufferTexture2D);
+    GLFN(PFNGLFRAMEBUFFERRENDERBUFFERPROC, glFramebufferRenderbuffer);
+    GLFN(PFNGLGENRENDERBUFFERSPROC, glGenRenderbuffers);
+    GLFN(PFNGLBINDRENDERBUFFERPROC, glBindRenderbuffer);
+    GLFN(PFNGLRENDERBUFFERSTORAGEPROC, glRenderbufferStorage);
+    GLFN(PFNGLCHECKFRAMEBUFFERSTATUSPROC, glCheckFramebufferStatus);
+    GLFN(PFNGLGENTEXTURESPROC, glGenTextures);
+    GLFN(PFNGLBINDTEXTUREPROC, glBindTexture);
+    GLFN(PFNGLTEXIMAGE2DPROC, glTexImage2D);
+    GLFN(PFNGLDRAWBUFFERSPROC, glDrawBuffers);
+    GLFN(PFNGLVIEWPORTPROC, glViewport);
+    GLFN(PFNGLCLEARCOLORPROC, glClearColor);
+    GLFN(PFNGLCLEARDEPTHPROC, glClearDepth);
+    GLFN(PFNGLCLEARPROC, glClear);
+    GLFN(PFNGLCLEARBUFFERIVPROC, glClearBufferiv);
+    GLFN(PFNGLCLEARBUFFERFVPROC, glClearBufferfv);
+    GLFN(PFNGLDRAWARRAYSPROC, glDrawArrays);
+    GLFN(PFNGLFINISHPROC, glFinish);
+    GLFN(PFNGLREADPIXELSPROC, glReadPixels);
+    GLFN(PFNGLREADBUFFERPROC, glReadBuffer);
+    GLFN(PFNGLENABLEPROC, glEnable);
+    GLFN(PFNGLDISABLEPROC, glDisable);
+    GLFN(PFNGLDEPTHFUNCPROC, glDepthFunc);
+    GLFN(PFNGLDEPTHMASKPROC, glDepthMask);
+    GLFN(PFNGLCLAMPCOLORPROC, glClampColor);
+
+    /* two programs: RayZen's (editor_vertex + editor_fragment) and the ID pass (editor_vertex + GLREF_FRAGMENT) */
+    const char* idFrag = getenv("GLREF_FRAGMENT");
+    if (!idFrag) DIE("editor mode needs GLREF_FRAGMENT (the ID pass's fragment shader)");
+    GLuint progs[2];
+    char path[4096];
+    snprintf(path, sizeof path, "%s/editor_fragment.glsl", shader_dir);
+    const char* editorFrag = read_text(path);
+    for (int p = 0; p < 2; ++p) {
+        progs[p] = glCreateProgram();
+        for (int i = 0; i < 2; ++i) {
+            if (i == 0) snprintf(path, sizeof path, "%s/editor_vertex.glsl", shader_dir);
+            else if (p == 0) snprintf(path, sizeof path, "%s/editor_fragment.glsl", shader_dir);
+            else snprintf(path, sizeof path, "%s", idFrag);
+            const char* src = p == 0 && i == 1 ? editorFrag : read_text(path);
+            if (p == 1 && i == 1) src = splice_inputs(src, editorFrag, path);
+            GLuint sh = glCreateShader(i == 0 ? GL_VERTEX_SHADER : GL_FRAGMENT_SHADER);
+            glShaderSource(sh, 1, &src, NULL);
+            glCompileShader(sh);
+            GLint ok = 0;
+            glGetShaderiv(sh, GL_COMPILE_STATUS, &ok);
+            if (!ok) { char log[8192]; glGetShaderInfoLog(sh, sizeof log, NULL, log); DIE("%s does not compile:\n%s", path, log); }
+            glAttachShader(progs[p], sh);
+        }
+        glLinkProgram(progs[p]);
+        GLint ok = 0;
+        glGetProgramiv(progs[p], GL_LINK_STATUS, &ok);
+        if (!ok) { char log[8192]; glGetProgramInfoLog(progs[p], sizeof log, NULL, log); DIE("link failed:\n%s", log); }
+    }
+
+    /* SSBOs 1 and 2 (main.cpp:1281-1282) */
+    const void* ssbo[2] = {mats, lights};
+    const uint64_t ssboBytes[2] = {matBytes, lightBytes};
+    for (int b = 0; b < 2; ++b) {
+        if (!ssboBytes[b]) continue;
+        GLuint id;
+        glGenBuffers(1, &id);
+        glBindBuffer(GL_SHADER_STORAGE_BUFFER, id);
+        glBufferData(GL_SHADER_STORAGE_BUFFER, (GLsizeiptr)ssboBytes[b], ssbo[b], GL_STATIC_DRAW);
+        glBindBufferBase(GL_SHADER_STORAGE_BUFFER, (GLuint)(b + 1), id);
+    }
+
+    /* buildRasterMeshes (main.cpp:1210-1256): one VAO / VBO per non-empty mesh, the RasterVertex layout */
+    GLuint* vao = calloc((size_t)H.nMeshes + 1, sizeof(GLuint));
+    for (int m = 0; m < H.nMeshes; ++m) {
+        if (!nVerts[m]) continue;
+        GLuint vbo;
+        glGenVertexArrays(1, &vao[m]);
+        glGenBuffers(1, &vbo);
+        glBindVertexArray(vao[m]);
+        glBindBuffer(GL_ARRAY_BUFFER, vbo);
+        glBufferData(GL_ARRAY_BUFFER, (GLsizeiptr)nVerts[m] * 28, verts[m], GL_STATIC_DRAW);
+        glEnableVertexAttribArray(0);
+        glVertexAttribPointer(0, 3, GL_FLOAT, GL_FALSE, 28, (void*)0);
+        glEnableVertexAttribArray(1);
+        glVertexAttribPointer(1, 3, GL_FLOAT, GL_FALSE, 28, (void*)12);
+        glEnableVertexAttribArray(2);
+        glVertexAttribIPointer(2, 1, GL_INT, 28, (void*)24);
+        glBindVertexArray(0);
+        glBindBuffer(GL_ARRAY_BUFFER, 0);
+    }
+
+    /* three framebuffers: colour RGBA32F, colour RGBA8, ID pass (RGBA32I + 2 x RGBA32F); each with a 24-bit depth buffer */
+    const int W = H.width, Ht = H.height;
+    const size_t n = (size_t)W * Ht;
+    const GLenum fmts[3][3] = {{GL_RGBA32F, 0, 0}, {GL_RGBA8, 0, 0}, {GL_RGBA32I, GL_RGBA32F, GL_RGBA32F}};
+    const GLenum bufs[3] = {GL_COLOR_ATTACHMENT0, GL_COLOR_ATTACHMENT1, GL_COLOR_ATTACHMENT2};
+    GLuint fbo[3];
+    uint32_t* depth[3];
+    FILE* of = fopen(out_path, "wb");
+    if (!of) DIE("cannot write %s", out_path);
+    glViewport(0, 0, W, Ht);
+    glClampColor(GL_CLAMP_READ_COLOR, GL_FALSE);
+    glDisable(GL_CULL_FACE);
+    glDisable(GL_BLEND);
+    glDisable(GL_MULTISAMPLE);
+    for (int pass = 0; pass < 3; ++pass) {
+        glGenFramebuffers(1, &fbo[pass]);
+        glBindFramebuffer(GL_FRAMEBUFFER, fbo[pass]);
+        const int nAtt = pass == 2 ? 3 : 1;
+        for (int a = 0; a < nAtt; ++a) {
+            GLuint tex;
+            glGenTextures(1, &tex);
+            glBindTexture(GL_TEXTURE_2D, tex);
+            const GLenum f = fmts[pass][a];
+            glTexImage2D(GL_TEXTURE_2D, 0, f, W, Ht, 0, f == GL_RGBA32I ? GL_RGBA_INTEGER : GL_RGBA,
+                         f == GL_RGBA32I ? GL_INT : f == GL_RGBA8 ? GL_UNSIGNED_BYTE : GL_FLOAT, NULL);
+            glFramebufferTexture2D(GL_FRAMEBUFFER, bufs[a], GL_TEXTURE_2D, tex, 0);
+        }
+        GLuint rb;
+        glGenRenderbuffers(1, &rb);
+        glBindRenderbuffer(GL_RENDERBUFFER, rb);
+        glRenderbufferStorage(GL_RENDERBUFFER, GL_DEPTH_COMPONENT24, W, Ht);
+        glFramebufferRenderbuffer(GL_FRAMEBUFFER, GL_DEPTH_ATTACHMENT, GL_RENDERBUFFER, rb);
+        glDrawBuffers(nAtt, bufs);
+        if (glCheckFramebufferStatus(GL_FRAMEBUFFER) != GL_FRAMEBUFFER_COMPLETE) DIE("framebuffer %d incomplete", pass);
+
+        /* renderRasterized (main.cpp:1259-1297) */
+        glEnable(GL_DEPTH_TEST);
+        glDepthFunc(GL_LESS);
+        glDepthMask(GL_TRUE);
+        glClearDepth(1.0);
+        if (pass < 2) {
+            glClearColor(H.clear[0], H.clear[1], H.clear[2], H.clear[3]);
+            glClear(GL_COLOR_BUFFER_BIT | GL_DEPTH_BUFFER_BIT);
+        } else {
+            const GLint none[4] = {-1, -1, -1, -1};
+            const GLfloat zero[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+            glClearBufferiv(GL_COLOR, 0, none);
+            glClearBufferfv(GL_COLOR, 1, zero);
+            glClearBufferfv(GL_COLOR, 2, zero);
+            glClear(GL_DEPTH_BUFFER_BIT);
+        }
+        const GLuint prog = progs[pass == 2];
+        glUseProgram(prog);
+        glUniformMatrix4fv(glGetUniformLocation(prog, "uView"), 1, GL_FALSE, H.view);
+        glUniformMatrix4fv(glGetUniformLocation(prog, "uProj"), 1, GL_FALSE, H.proj);
+        glUniform3fv(glGetUniformLocation(prog, "uCameraPos"), 1, H.camPos);
+        glUniform1i(glGetUniformLocation(prog, "numLights"), H.numLights);
+        glUniform3fv(glGetUniformLocation(prog, "uAmbientColor"), 1, H.ambient);
+        const GLint modelLoc = glGetUniformLocation(prog, "uModel"), normalLoc = glGetUniformLocation(prog, "uNormalMatrix");
+        const GLint objLoc = glGetUniformLocation(prog, "uObjectIndex");
+        for (int o = 0; o < H.nObjects; ++o) {
+            const int m = objMesh[o];
+            if (m < 0 || !nVerts[m]) continue;
+            glUniformMatrix4fv(modelLoc, 1, GL_FALSE, objModel + 16 * o);
+            glUniformMatrix3fv(normalLoc, 1, GL_FALSE, objNormal + 9 * o);
+            if (objLoc >= 0) glUniform1i(objLoc, o);
+            glBindVertexArray(vao[m]);
+            glDrawArrays(GL_TRIANGLES, 0, nVerts[m]);
+        }
+        glBindVertexArray(0);
+        glUseProgram(0);
+        glFinish();
+
+        for (int a = 0; a < nAtt; ++a) {
+            const GLenum f = fmts[pass][a];
+            const size_t px = f == GL_RGBA8 ? 4 : 16;
+            void* buf = malloc(n * px);
+            glReadBuffer(bufs[a]);
+            glReadPixels(0, 0, W, Ht, f == GL_RGBA32I ? GL_RGBA_INTEGER : GL_RGBA,
+                         f == GL_RGBA32I ? GL_INT : f == GL_RGBA8 ? GL_UNSIGNED_BYTE : GL_FLOAT, buf);
+            if (fwrite(buf, px, n, of) != n) DIE("cannot write %s", out_path);
+            free(buf);
+        }
+        depth[pass] = malloc(n * 4);
+        glReadPixels(0, 0, W, Ht, GL_DEPTH_COMPONENT, GL_UNSIGNED_INT, depth[pass]);
+        const GLenum e = glGetError();
+        if (e != GL_NO_ERROR) DIE("GL error 0x%x in pass %d", e, pass);
+        if (pass > 0 && memcmp(depth[pass], depth[0], n * 4)) DIE("pass %d left another depth buffer than the colour pass", pass);
+    }
+    if (fwrite(depth[0], 4, n, of) != n) DIE("cannot write %s", out_path);
+    fclose(of);
+    return 0;
+}
+
+int main(int argc, char** argv) {
+    if (argc < 3) DIE("usage: glref <scene.blob> <out.f32> [shader_dir]");
+    const char* shader_dir = argc > 3 ? argv[3] : "/root/reference/RayZen/shaders";
+    const char* driver = getenv("GLREF_DRIVER") ? getenv("GLREF_DRIVER") : "/usr/lib/x86_64-linux-gnu/dri/swrast_dri.so";
+
+    /* ---- the scene ---- */
+    FILE* bf = fopen(argv[1], "rb");
+    if (!bf) DIE("cannot open %s", argv[1]);
+    char magic[4];
+    if (fread(magic, 4, 1, bf) != 1) DIE("short blob");
+    if (!memcmp(magic, "RZED", 4)) return editor_main(bf, argv[2], shader_dir, driver);
+    rewind(bf);
+    blob_header H;
+    if (fread(&H, sizeof H, 1, bf) != 1 || memcmp(H.magic, "RZGL", 4) != 0 || H.version != 2) DIE("bad blob header");
+    void* bufs[10];
+    uint64_t bytes[10];
+    for (int b = 0; b < 10; ++b) {
+        if (fread(&bytes[b], 8, 1, bf) != 1) DIE("short blob");
+        bufs[b] = malloc(bytes[b] ? bytes[b] : 1);
+        if (bytes[b] && fread(bufs[b], 1, bytes[b], bf) != bytes[b]) DIE("short blob (binding %d)", b);
+    }
+    fclose(bf);
+
+    make_current(driver);
 
     GLFN(PFNGLGETSTRINGPROC, glGetString);
     GLFN(PFNGLGETERRORPROC, glGetError);

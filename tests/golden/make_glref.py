@@ -17,6 +17,16 @@ budgets 1-2, and 3-8 with up to 8 samples), and a table of llvmpipe's own sin / 
 
 `spp` > 1 renders set FS:676's constant `int numSamples = 1; // increase for better quality` to spp in the text the
 harness loads -- the only edit it can make, and the one the product's `spp` stands for.  They are labelled (spp field).
+
+glref_editor_*.npz: RayZen's editor frame (F1: editor_vertex.glsl + editor_fragment.glsl rasterised with a depth test,
+main.cpp:1210-1297; the harness's editor mode) -- the colour as float32 rgb and as RGBA8, and an ID pass over the same
+fragments: object index, gl_PrimitiveID and the 24-bit window depth per pixel.  Scenes: the Cornell box, RayZen's own (real
+monkey.obj, 4:3), the coverage scene of tests/test_editor_gpu.py at numLights 0, 4 and 9, a rotated and non-uniformly scaled
+blob, and a camera close above a floor and beside a wall that both cross the near plane, the floor also the far plane.  They
+pin rz_render_editor through tests/editor_glref.py.
+
+    python tests/golden/make_glref.py editor                (the editor fixtures alone)
+    python tests/golden/make_glref.py editor_cornell ...    (these editor fixtures alone; `cornell` names the path tracer's)
 """
 import json
 import os
@@ -82,12 +92,90 @@ def math_table():
     return x, y
 
 
+def editor_scenes():
+    """name -> (make scene, [dict(W, H, num_lights)]).  Moderate triangle counts: triangles much smaller than a pixel would make
+    the edge class of tests/editor_glref.py the rule instead of the exception."""
+    from rayzen_amd import scene as S
+    from test_editor_gpu import _coverage_lights, _coverage_scene
+
+    def skewed():
+        sc = S.Scene(camera=S.Camera(position=(0.0, 1.2, 5.0), target=(0.0, -0.15, -1.0), aspect=4 / 3))
+        floor = sc.add_mesh(S.make_quad((-5, -1.2, 5), (5, -1.2, 5), (5, -1.2, -5), (-5, -1.2, -5), 4))
+        sc.add_object(floor)
+        for k, (mat, axis, angle, sc3, at) in enumerate([(0, (1, 1, 0), 0.7, (1.6, 0.6, 1.0), (-1.3, 0.1, 0.0)),
+                                                         (2, (0, 1, 1), -0.9, (0.5, 1.4, 0.8), (1.3, 0.2, -0.3))]):
+            blob = sc.add_mesh(S.make_blob(10, 1.0, mat, seed=3 + k))
+            m = S.translate(S.identity(), at)
+            m = S.rotate(m, angle, axis)
+            sc.add_object(blob, S.scale(m, sc3))
+        return sc.build()
+
+    def clip():
+        sc = S.Scene(camera=S.Camera(position=(0.0, 0.04, 0.0), target=(0.25, -0.22, -1.0), aspect=4 / 3, near=0.1, far=100.0))
+        floor = sc.add_mesh(S.make_quad((-60, 0, 4), (60, 0, 4), (60, 0, -20), (-60, 0, -20), 4))      # 0.04 below the eye
+        ramp = sc.add_mesh(S.make_quad((-60, 0, -20), (60, 0, -20), (60, 30, -240), (-60, 30, -240), 1))  # on beyond far = 100
+        wall = sc.add_mesh(S.make_quad((0.07, 0, 3), (0.07, 0, -5), (0.07, 2, -5), (0.07, 2, 3), 1))      # 0.07 beside the eye
+        sc.add_object(floor)
+        sc.add_object(ramp)
+        sc.add_object(wall)
+        blob = sc.add_mesh(S.make_blob(8, 0.6, 0, seed=2))
+        sc.add_object(blob, S.translate(S.identity(), (1.2, 0.6, -3.0)))
+        return sc.build()
+
+    return {
+        "cornell": (S.cornell_scene, [dict(W=192, H=192, num_lights=None)]),
+        "rayzen_main": (lambda: S.reference_scene(include_empty=False, monkey_obj=MONKEY), [dict(W=256, H=192, num_lights=None)]),
+        "coverage": (lambda: _coverage_scene(_coverage_lights()), [dict(W=256, H=192, num_lights=n) for n in (0, 4, 9)]),
+        "skewed": (skewed, [dict(W=256, H=192, num_lights=None)]),
+        "clip": (clip, [dict(W=256, H=192, num_lights=None)]),
+    }
+
+
+EDITOR_OUTPUTS = ("rgb", "rgba8", "object", "prim", "depth")
+
+
+def editor_fixture(name):
+    """The arrays of glref_editor_<name>.npz, rendered now."""
+    from rayzen_amd import scene as S
+    from oracle.glref import glref
+    make, renders = editor_scenes()[name]
+    sc = make()
+    cam = sc.camera
+    data = {f"b{b}": np.frombuffer(np.ascontiguousarray(sc.arrays[b]).tobytes(), np.uint8) for b in S.BINDING_DTYPES}
+    data.update(cam_view=cam.view, cam_proj=cam.proj, cam_inv_view=cam.inv_view, cam_inv_proj=cam.inv_proj,
+                cam_pos=np.asarray(cam.position, np.float32))
+    renders = [dict(r, num_lights=len(sc.lights) if r["num_lights"] is None else r["num_lights"]) for r in renders]
+    info = ""
+    for k, r in enumerate(renders):
+        out = glref.render_editor_scene(sc, r["W"], r["H"], r["num_lights"])
+        info = out["gl"]
+        for key in EDITOR_OUTPUTS:
+            data[f"{key}{k}"] = out[key]
+    data["renders"] = np.array(json.dumps(renders))
+    data["gl"] = np.array(info)
+    return data
+
+
+def main_editor(only):
+    total = 0
+    for name in editor_scenes():
+        if only and f"editor_{name}" not in only and "editor" not in only:
+            continue
+        data = editor_fixture(name)
+        path = os.path.join(HERE, f"glref_editor_{name}.npz")
+        np.savez_compressed(path, **data)
+        total += os.path.getsize(path)
+        print("editor", name, json.loads(str(data["renders"])), os.path.getsize(path), "bytes")
+    return total
+
+
 def main():
     from rayzen_amd import scene as S
     from oracle.glref import glref
     assert glref.available(), "needs /root/reference and Mesa's swrast_dri.so (the build container)"
-    total = 0
-    only = set(sys.argv[1:])             # make_glref.py [scene ...]: regenerate these fixtures alone
+    only = set(sys.argv[1:])             # make_glref.py [scene ...]: regenerate these fixtures alone ("editor": all editor ones,
+                                         # "editor_<name>": one of them)
+    total = main_editor(only)
     for name, make, renders in scenes():
         if only and name not in only:
             continue

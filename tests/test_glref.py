@@ -40,7 +40,8 @@ from helpers import oracle_scene, oracle_frame
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLDEN = os.path.join(HERE, "golden")
 FIXTURES = sorted(f[len("glref_"):-len(".npz")] for f in os.listdir(GOLDEN)
-                  if f.startswith("glref_") and f.endswith(".npz") and f != "glref_math_table.npz")
+                  if f.startswith("glref_") and f.endswith(".npz") and f != "glref_math_table.npz"
+                  and not f.startswith("glref_editor_"))          # (the editor's raster frames: tests/test_glref_editor.py)
 OVERLAY_KEYS = ("fps", "show_lights", "show_bvh", "bvh_mode", "selected_blas", "selected_tri")
 
 
