@@ -214,6 +214,50 @@ typedef struct rz_mesh_build {
 } rz_mesh_build;
 int rz_build_geometry(rz_ctx* ctx, const rz_triangle* triangles, size_t n_triangles, rz_mesh_build* meshes, size_t n_meshes);
 
+/* Deforming meshes: a BLAS REFIT on the device.  (No counterpart in the reference: RayZen re-uploads the triangle array
+ * every frame, main.cpp:1196-1201, but builds each BLAS once, main.cpp:1125-1136, so moved vertices are culled by stale
+ * boxes there -- and here too after rz_update on binding 0 alone.)
+ *
+ * Replaces elements [first_triangle, first_triangle + n_triangles) of binding 0 with `triangles` (all 64 bytes of each,
+ * materialIndex included), then refits every mesh whose triangle range intersects that interval -- the whole mesh, not
+ * only the touched leaves.  A mesh is a distinct (blasNodeOffset, blasTriOffset, globalTriOffset) among the uploaded
+ * instances; its triangle range is [globalTriOffset, globalTriOffset + the slots its leaves name).  n_triangles == 0
+ * (`triangles` may be NULL): every mesh is refitted from binding 0 as it stands -- what makes a preceding rz_update on
+ * binding 0 correct.
+ *
+ * THE RESULT, for each refitted mesh, in binding 7 (leftFirst and count of every node and all of binding 8 unchanged):
+ *   - a leaf's box is computeBounds (RayZen/src/BVH.cpp:11-19) over its own slots: start at (+FLT_MAX, -FLT_MAX), slots in
+ *     order, bmin = glm::min(bmin, glm::min(v0, glm::min(v1, v2))), bmax likewise with glm::max, where
+ *     glm::min(a, b) = (b < a) ? b : a and glm::max(a, b) = (a < b) ? b : a;
+ *   - an internal node's box is glm::min(left.min, right.min), glm::max(left.max, right.max);
+ *   - a leaf with count == 0 (the root of an empty mesh) is left as it is.
+ * This fixes every bit, signs of zero and NaN planes included; BVH::refit / rzh_refit_blas (librayzen_host.so) state the
+ * same on the host and the device result is held to their bytes.  A refit of an unmodified mesh reproduces the builder's
+ * nodes.
+ *
+ * Everything derived follows on the device, in place, without the re-layout and without a sort: the device copies of
+ * the triangles and nodes, the leaf-ordered triangles and their normals, the child boxes of the traversal's node pairs,
+ * the root box of every instance of the mesh, and -- with the transforms currently in force -- the world boxes and the
+ * TLAS (the kernel of rz_update_transforms).  "A transparent material is in use" and "an irregular child box exists" come
+ * out as a fresh upload would derive them.  Afterwards the context is indistinguishable from a fresh one that was given
+ * the new binding 0 and the refitted binding 7 with everything else equal: rz_read_binding (host mirrors are fetched on
+ * demand) and rz_debug_read_layout return the same bytes, and frames, ray queries, the editor preview, the denoiser's
+ * guide and rz_present's wireframe are bit-identical.  No render state is touched (accumulation, currentIor, the frame,
+ * pools, rz_debug_last_plan).  The geometry may have come from rz_upload or from rz_build_geometry; a context made with
+ * RZ_FLAG_HOST_RELAYOUT patches its host copies and lets the host re-layout run (same bytes).
+ *
+ * `triangles` is DEVICE memory by default (16-byte aligned); the work is enqueued on the context's stream, ordered with
+ * renders and queries on it, and the call synchronises that stream where rz_update_transforms does (the root boxes and
+ * the TLAS depth come back).  With RZ_REFIT_HOST it is host memory and the pointer is not retained.
+ *
+ * RZ_ERR_INVALID_ARG: null context, NULL `triangles` with n_triangles > 0, a misaligned device pointer, unknown flags.
+ * RZ_ERR_OUT_OF_RANGE: the interval reaches past the end of binding 0.  RZ_ERR_NOT_READY: a binding is missing.  These
+ * launch nothing and leave the context as it was.  RZ_ERR_BAD_SCENE: where a fresh upload of the result would say so (a
+ * materialIndex outside the materials: found on the device, so the triangles are in place by then, and every later
+ * call reports the same until binding 0 or the materials are corrected).  RZ_ERR_NO_MEMORY as everywhere. */
+#define RZ_REFIT_HOST 1u   /* `triangles` is host memory: staged through a context buffer */
+int rz_refit_geometry(rz_ctx* ctx, const rz_triangle* triangles, size_t first_triangle, size_t n_triangles, unsigned flags);
+
 /* Copy a binding's current content back to the host in RayZen's own layout (after rz_update_transforms: the
  * instances / TLAS nodes / TLAS indices the device built).  out == NULL: only *needed is set. */
 int rz_read_binding(rz_ctx* ctx, rz_binding binding, void* out, size_t bytes, size_t* needed);

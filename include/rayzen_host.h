@@ -24,6 +24,12 @@ int rzh_load_obj(const char* path, int materialIndex, rz_triangle* out, int cap)
  * longest root-to-leaf path in nodes. */
 int rzh_build_blas(const rz_triangle* tris, int n, rz_bvh_node* nodes_out, int32_t* idx_out, int* depth_out);
 
+/* BVH::refit (no counterpart in the reference): the boxes of an existing BLAS recomputed bottom-up from moved
+ * triangles; every leftFirst, count and the index array stay.  tris: the mesh's n triangles in their original order;
+ * nodes_inout: its n_nodes nodes (child indices relative to the array); idx: its n indices.  The definition of every
+ * byte is rz_refit_geometry's in rayzen_hip.h.  0, or -1 on a null / inconsistent argument (nothing is written). */
+int rzh_refit_blas(const rz_triangle* tris, int n, rz_bvh_node* nodes_inout, int n_nodes, const int32_t* idx);
+
 /* BVH::buildTLAS (src/BVH.cpp:178-240) over world-space instance boxes
  * (only boundsMin/boundsMax of world_roots are read).  nodes_out capacity
  * 2*n, idx_out capacity n.  Returns the node count. */
@@ -53,6 +59,10 @@ typedef int (*rzh_blas_builder_fn)(void* ctx, const rz_triangle* tris, size_t n,
                                    int32_t* indices_out, size_t* n_nodes, int* depth, float* device_ms);
 int  rzh_scene_set_blas_builder(rzh_scene* s, rzh_blas_builder_fn fn, void* ctx);
 int  rzh_scene_update_dynamic(rzh_scene* s);
+/* The mesh's vertices moved: tris replaces its n triangles (n must be the count it was added with); every stored copy
+ * gets them and a refitted BLAS, then the world boxes and the TLAS are rebuilt with the transforms in force.  The byte
+ * partner of rz_refit_geometry, as rzh_scene_update_dynamic is of rz_update_transforms.  0, or -1 (nothing touched). */
+int  rzh_scene_refit_mesh(rzh_scene* s, int mesh_id, const rz_triangle* tris, int n);
 /* pointer/size of a geometry array (bindings 0, 5, 6, 7, 8, 9); valid until
  * the next build/update/destroy */
 const void* rzh_scene_buffer(const rzh_scene* s, rz_binding b, size_t* bytes);

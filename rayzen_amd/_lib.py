@@ -21,7 +21,7 @@ HIP_SYMBOLS = (
     "rz_group_last_error", "rz_group_size", "rz_group_local_count", "rz_group_rank", "rz_group_ctx", "rz_group_upload",
     "rz_group_update", "rz_group_set_frame", "rz_group_render", "rz_group_reduce", "rz_group_sync", "rz_group_read_frame",
     "rz_group_frame_device_ptr", "rz_group_last_reduce_ms", "rz_group_transport", "rz_group_set_transport", "rz_abi_version", "rz_debug_poke_backstop", "rz_math_flavour",
-    "rz_trace_rays", "rz_shadow_rays", "rz_render_editor", "rz_denoise", "rz_present_denoised",
+    "rz_trace_rays", "rz_shadow_rays", "rz_render_editor", "rz_denoise", "rz_present_denoised", "rz_refit_geometry",
 )
 ABI_VERSION = 5         # RZ_ABI_VERSION of the include/rayzen_hip.h this file mirrors
 # the symbols include/rayzen_host.h declares
@@ -31,7 +31,7 @@ HOST_SYMBOLS = (
     "rzh_scene_build", "rzh_scene_set_blas_builder", "rzh_scene_update_dynamic", "rzh_scene_buffer", "rzh_scene_depths",
     "rzh_scene_save_cache", "rzh_scene_load_cache", "rzh_scene_build_cached",
     "rzh_camera_matrices", "rzh_mat_translate", "rzh_mat_scale", "rzh_mat_rotate", "rzh_mat_inverse",
-    "rzh_make_cube", "rzh_make_blob", "rzh_version",
+    "rzh_make_cube", "rzh_make_blob", "rzh_version", "rzh_refit_blas", "rzh_scene_refit_mesh",
 )
 
 
@@ -109,6 +109,7 @@ class DenoiseParams(C.Structure):
 
 
 DENOISE_HOST = 1                        # RZ_DENOISE_HOST
+REFIT_HOST = 1                          # RZ_REFIT_HOST
 
 
 class Counters(C.Structure):
@@ -187,7 +188,8 @@ def hip():
                                 ("rz_trace_rays", i, [vp, vp, vp, sz, C.c_uint]), ("rz_shadow_rays", i, [vp, vp, vp, sz, C.c_uint]),
                                 ("rz_render_editor", i, [vp, C.POINTER(FrameParams), vp, vp, sz, vp, sz, vp, sz, C.c_uint]),
                                 ("rz_denoise", i, [vp, vp, vp, sz, vp, sz, vp, sz, C.c_uint]),
-                                ("rz_present_denoised", i, [vp, C.POINTER(PresentParams), vp, vp, sz, vp, sz])):
+                                ("rz_present_denoised", i, [vp, C.POINTER(PresentParams), vp, vp, sz, vp, sz]),
+                                ("rz_refit_geometry", i, [vp, vp, sz, sz, C.c_uint])):
             try:
                 fn = getattr(L, name)
                 fn.restype, fn.argtypes = res, args
@@ -212,6 +214,8 @@ def host():
         L.rzh_load_obj.restype, L.rzh_load_obj.argtypes = i, [C.c_char_p, i, vp, i]
         L.rzh_build_blas.restype, L.rzh_build_blas.argtypes = i, [vp, i, vp, vp, C.POINTER(i)]
         L.rzh_build_tlas.restype, L.rzh_build_tlas.argtypes = i, [vp, i, vp, vp, C.POINTER(i)]
+        L.rzh_refit_blas.restype, L.rzh_refit_blas.argtypes = i, [vp, i, vp, i, vp]
+        L.rzh_scene_refit_mesh.restype, L.rzh_scene_refit_mesh.argtypes = i, [vp, i, vp, i]
         L.rzh_world_bounds.restype, L.rzh_world_bounds.argtypes = None, [vp, vp, vp, vp]
         L.rzh_scene_create.restype, L.rzh_scene_create.argtypes = vp, []
         L.rzh_scene_destroy.restype, L.rzh_scene_destroy.argtypes = None, [vp]

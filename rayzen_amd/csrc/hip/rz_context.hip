@@ -50,6 +50,16 @@ struct BlasView {
     int depth = 1;
     bool empty = false;
     bool mayGlass = true;       // a triangle of the view may use a transparent material (a scheduling hint for the kernels: DevInstance.flags bit 1)
+    bool irregular = false;     // device re-layout: one of its child boxes has min > max or a NaN plane
+    int nPairs = 0, nSlots = 0; // what the view occupies behind pairBase / triBase
+};
+
+// What rz_refit_geometry needs of a laid-out view beyond the arrays (refit_topology): the breadth-first ranks of its
+// internal nodes, level by level.  Derived once per layout, kept until the views are laid out again.
+struct RefitView {
+    std::tuple<int, int, int> key;
+    int rankBase = 0;               // where its rankToNode entries start in dRefitRank
+    std::vector<int> levelStart;    // ranks of tree level d: [levelStart[d], levelStart[d + 1]); empty: the root is a leaf
 };
 
 constexpr int kNumBindings = 10;
@@ -139,6 +149,14 @@ struct rz_ctx {
     // the denoiser (rz_denoise / rz_present_denoised, rz_denoise.hip): the guide (2 float4 per pixel), the two float4 buffers
     // its passes ping-pong between, and the (colour, 1) buffer rz_present_denoised presents
     DevBuf dDnGuide, dDnPing, dDnPong, dDnOut;
+    // rz_refit_geometry (rz_refit.hip)
+    bool trisHostStale = false;         // binding 0 on the device (dRawTris) is newer than the host copy: fetched on demand (sync_tris_host)
+    unsigned long long layoutGen = 0;   // counts the times the views / instances were laid out
+    unsigned long long refitGen = ~0ull; // the layout the refit topology below was derived from
+    std::vector<RefitView> refitViews;  // in the order of `views`
+    DevBuf dRefitRank, dRefitInstView, dRefitViewOff, dRefitFlags, dRefitRoots;
+    unsigned char* refitPinned = nullptr;   // per view: 4 flag words, then per view: its root node
+    size_t refitPinnedCap = 0;
 };
 
 namespace {
@@ -224,6 +242,7 @@ size_t blasNodeCount(const rz_ctx* c) { return c->geomOnDevice ? c->devNodes : h
 size_t blasIdxCount(const rz_ctx* c) { return c->geomOnDevice ? c->devIdx : hostCount<int32_t>(c, RZ_BIND_BLAS_INDICES); }
 
 int sync_geom_host(rz_ctx* c);
+int sync_tris_host(rz_ctx* c);
 
 // Lay out one BLAS: breadth-first walk from its root, one DevPair per internal
 // node (so the hot top levels are contiguous), triangles gathered to leaf order.
@@ -323,6 +342,8 @@ int build_view(rz_ctx* c, int nodeOff, int triOff, int gTriOff, BlasView& V) {
         c->hTris.push_back(d);
     }
     V.mayGlass = viewGlass;
+    V.nSlots = maxSlot;
+    V.nPairs = (int)c->hPairs.size() - V.pairBase;
     return RZ_OK;
 }
 
@@ -339,6 +360,17 @@ int sync_geom_host(rz_ctx* c) {
     if (c->devNodes) RZ_HIP(c, hipMemcpy(c->host[RZ_BIND_BLAS_NODES].data(), c->dRawNodes.p, c->devNodes * sizeof(rz_bvh_node), hipMemcpyDeviceToHost));
     if (c->devIdx) RZ_HIP(c, hipMemcpy(c->host[RZ_BIND_BLAS_INDICES].data(), c->dRawIdx.p, c->devIdx * sizeof(int32_t), hipMemcpyDeviceToHost));
     c->geomHostFresh = true;
+    return RZ_OK;
+}
+
+// After a device-pointer rz_refit_geometry the triangles exist only in dRawTris: bring them to the host copy before
+// anything reads, patches or re-uploads that (rz_read_binding, rz_update, either re-layout).
+int sync_tris_host(rz_ctx* c) {
+    if (!c->trisHostStale) return RZ_OK;
+    RZ_HIP(c, hipStreamSynchronize(c->stream));
+    const size_t bytes = c->host[RZ_BIND_TRIANGLES].size();
+    if (bytes) RZ_HIP(c, hipMemcpy(c->host[RZ_BIND_TRIANGLES].data(), c->dRawTris.p, bytes, hipMemcpyDeviceToHost));
+    c->trisHostStale = false;
     return RZ_OK;
 }
 
@@ -468,6 +500,8 @@ int device_view(rz_ctx* c, int nodeOff, int triOff, int gTriOff, BlasView& V) {
     if (rc > 0) return 1;
     c->devTransparent |= viewFlags;
     V.mayGlass = (viewFlags & 1u) != 0;
+    V.irregular = (viewFlags & 2u) != 0;
+    V.nPairs = R.nPairs; V.nSlots = R.nSlots;
     V.pairBase = R.pairBase; V.triBase = R.triBase; V.rootEnc = R.rootEnc; V.depth = R.depth; V.empty = R.empty != 0;
     std::memcpy(V.rootMin, R.rootMin, 12); std::memcpy(V.rootMax, R.rootMax, 12);
     c->devPairsUsed += R.nPairs; c->devTrisUsed += R.nSlots;
@@ -481,6 +515,7 @@ int finalize_body(rz_ctx* c) {
         if (!c->present[b]) return fail(c, RZ_ERR_NOT_READY, "binding %d has not been uploaded", b);
 
     // (the per-view "may hold transparent triangles" hints were taken from the materials of the moment the views were laid out)
+    if (c->geomDirty) { int rc = sync_tris_host(c); if (rc != RZ_OK) return rc; }
     if (c->geomDirty) c->matChangedSinceLayout = false;
     else if (c->matDirty && !c->matChangedSinceLayout) { c->matChangedSinceLayout = true; c->instDirty = true; }
     // materials first: the device re-layout checks triangle material indices against them
@@ -504,6 +539,7 @@ int finalize_body(rz_ctx* c) {
         const size_t nInst = hostCount<rz_bvh_instance>(c, RZ_BIND_INSTANCES);
         alloc_point(c);
         std::vector<DevInstance> dev(nInst);
+        ++c->layoutGen;             // (what rz_refit_geometry derived from the last layout is void)
         // Pass 1: lay out every BLAS view the instances name that is not laid out yet -- on the device
         // (rz_relayout.hip), or, if that finds the arrays inconsistent (or is switched off), on the host, which
         // also words the error.
@@ -1000,8 +1036,10 @@ void rz_destroy(rz_ctx* c) {
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     for (DevBuf* b : {&c->dPairs, &c->dTris, &c->dInst, &c->dTlasNodes, &c->dTlasIdx, &c->dMat, &c->dLight,
                       &c->dCounters, &c->dResolve, &c->dGroupCtr, &c->dBlasOvf, &c->ownAccum, &c->dIor, &c->dXforms, &c->dInstRef, &c->dTlasScratch, &c->dProjBoxes, &c->dBuildWs, &c->dTlasDfs, &c->dTriN, &c->dRawNodes, &c->dRawIdx, &c->dRawTris, &c->dRelayoutWs, &c->dClaimScratch, &c->dWavePools, &c->dWaitMeta, &c->dSnap,
-                      &c->dRayOvf, &c->dRayIn, &c->dRayOut, &c->dRayInstOff, &c->dDnGuide, &c->dDnPing, &c->dDnPong, &c->dDnOut})
+                      &c->dRayOvf, &c->dRayIn, &c->dRayOut, &c->dRayInstOff, &c->dDnGuide, &c->dDnPing, &c->dDnPong, &c->dDnOut,
+                      &c->dRefitRank, &c->dRefitInstView, &c->dRefitViewOff, &c->dRefitFlags, &c->dRefitRoots})
         b->release();
+    if (c->refitPinned) (void)hipHostFree(c->refitPinned);
     if (c->tlasHostCounts) (void)hipHostFree(c->tlasHostCounts);
     if (c->relayoutPinned) (void)hipHostFree(c->relayoutPinned);
     for (int i = 0; i < rz_ctx::kRing; ++i) {
@@ -1026,6 +1064,7 @@ static int upload_impl(rz_ctx* c, rz_binding binding, const void* data, size_t b
     }
     alloc_point(c);
     c->host[binding].assign(static_cast<const unsigned char*>(data), static_cast<const unsigned char*>(data) + bytes);
+    if (binding == RZ_BIND_TRIANGLES) c->trisHostStale = false;
     c->present[binding] = true;
     switch (binding) {
         case RZ_BIND_MATERIALS: c->matDirty = true; break;
@@ -1048,6 +1087,7 @@ static int update_impl(rz_ctx* c, rz_binding binding, size_t offset, const void*
         if (rc != RZ_OK) return rc;
         c->geomOnDevice = false;            // the host copies are the truth again
     }
+    if (binding == RZ_BIND_TRIANGLES) { int rc = sync_tris_host(c); if (rc != RZ_OK) return rc; }
     if (offset > c->host[binding].size() || bytes > c->host[binding].size() - offset)
         return fail(c, RZ_ERR_OUT_OF_RANGE, "binding %d: update [%zu,+%zu) past its %zu bytes", (int)binding, offset, bytes, c->host[binding].size());
     if (bytes == 0) return RZ_OK;
@@ -1063,6 +1103,8 @@ static int update_impl(rz_ctx* c, rz_binding binding, size_t offset, const void*
     return RZ_OK;
 }
 
+static int tlas_rebuild(rz_ctx* c, const float* transforms, size_t n);
+
 static int update_transforms_impl(rz_ctx* c, const float* transforms, size_t n) {
     if (!c) return fail(nullptr, RZ_ERR_INVALID_ARG, "null context");
     if (!transforms && n) return fail(c, RZ_ERR_INVALID_ARG, "null transforms");
@@ -1071,6 +1113,13 @@ static int update_transforms_impl(rz_ctx* c, const float* transforms, size_t n) 
     if (rc != RZ_OK) return rc;
     const size_t nInst = hostCount<rz_bvh_instance>(c, RZ_BIND_INSTANCES);
     if (n != nInst) return fail(c, RZ_ERR_INVALID_ARG, "%zu transforms for %zu instances", n, nInst);
+    return tlas_rebuild(c, transforms, n);
+}
+
+// World boxes, TLAS and TlasDfs from the root boxes in DevInstance and n transforms (rz_tlas_refit), then one
+// synchronisation.  transforms == nullptr: the ones dXforms holds already (those of the last rz_update_transforms).
+static int tlas_rebuild(rz_ctx* c, const float* transforms, size_t n) {
+    int rc;
     if (n == 0) return RZ_OK;
     if (n > (size_t)1 << 20) return fail(c, RZ_ERR_INVALID_ARG, "too many instances for the device TLAS builder");
     if (!c->tlasHostCounts) RZ_HIP(c, hipHostMalloc(reinterpret_cast<void**>(&c->tlasHostCounts), 64, hipHostMallocDefault));
@@ -1090,7 +1139,7 @@ static int update_transforms_impl(rz_ctx* c, const float* transforms, size_t n) 
     if (rc != RZ_OK) return rc;
     // the reference-layout records keep their offsets: seed them from the host copy once per host-side change
     RZ_HIP(c, hipMemcpyAsync(c->dInstRef.p, c->host[RZ_BIND_INSTANCES].data(), n * sizeof(rz_bvh_instance), hipMemcpyHostToDevice, c->stream));
-    RZ_HIP(c, hipMemcpyAsync(c->dXforms.p, transforms, n * 64, hipMemcpyHostToDevice, c->stream));
+    if (transforms) RZ_HIP(c, hipMemcpyAsync(c->dXforms.p, transforms, n * 64, hipMemcpyHostToDevice, c->stream));
     TlasWork W{};
     char* sc = static_cast<char*>(c->dTlasScratch.p);
     W.transforms = static_cast<const float*>(c->dXforms.p);
@@ -1115,6 +1164,322 @@ static int update_transforms_impl(rz_ctx* c, const float* transforms, size_t n) 
     c->nTlasDfs = c->tlasHostCounts[0];
     c->tlasDepth = std::max(1, c->tlasHostCounts[2]);
     c->deviceOwnsTlas = true;
+    return RZ_OK;
+}
+
+// ---- rz_refit_geometry --------------------------------------------------------------------------------------------
+
+// The views of the current layout, breadth first: rank of every internal node (== its pair index, rz_relayout.hip) and
+// where each tree level starts; which view every instance uses.  Derived on the host from the node array (fetched once
+// if it lives on the device), uploaded, and kept until the views are laid out again.
+static int refit_topology(rz_ctx* c) {
+    if (c->refitGen == c->layoutGen) return RZ_OK;
+    int rc = sync_geom_host(c);
+    if (rc != RZ_OK) return rc;
+    if (c->deviceOwnsTlas) { rc = sync_host_from_device(c); if (rc != RZ_OK) return rc; c->deviceOwnsTlas = true; }
+    const rz_bvh_node* nodes = hostArr<rz_bvh_node>(c, RZ_BIND_BLAS_NODES);
+    const long long nNodes = (long long)hostCount<rz_bvh_node>(c, RZ_BIND_BLAS_NODES);
+    alloc_point(c);
+    std::vector<RefitView> rv;
+    std::vector<int32_t> rank, viewOff;
+    std::map<std::tuple<int, int, int>, int> viewIndex;
+    for (const auto& kv : c->views) {
+        const int nodeOff = std::get<0>(kv.first);
+        RefitView R;
+        R.key = kv.first;
+        R.rankBase = (int)rank.size();
+        if (nodeOff < 0 || nodeOff >= nNodes) return fail(c, RZ_ERR_INTERNAL, "rz_refit_geometry: a laid-out view starts outside the node array");
+        if (nodes[nodeOff].count < 0) {
+            // the host re-layout's queue (build_view): queue[i] is the i-th internal node, and its pair is pair i
+            size_t head = rank.size(), levelEnd = head + 1;
+            rank.push_back(0);
+            R.levelStart.push_back(0);
+            while (head < rank.size()) {
+                if (head == levelEnd) { R.levelStart.push_back((int)(head - (size_t)R.rankBase)); levelEnd = rank.size(); }
+                const int L = nodes[nodeOff + rank[head++]].leftFirst;
+                if (L < 1 || (long long)nodeOff + L + 1 >= nNodes || rank.size() - (size_t)R.rankBase > (size_t)nNodes)
+                    return fail(c, RZ_ERR_INTERNAL, "rz_refit_geometry: a laid-out view is not a tree");
+                for (int k = 0; k < 2; ++k)
+                    if (nodes[nodeOff + L + k].count < 0) { if ((rank.size() & 4095) == 0) alloc_point(c); rank.push_back(L + k); }
+            }
+            R.levelStart.push_back((int)(rank.size() - (size_t)R.rankBase));
+            if ((int)(rank.size() - (size_t)R.rankBase) != kv.second.nPairs)
+                return fail(c, RZ_ERR_INTERNAL, "rz_refit_geometry: a view has %d pairs, its tree %zu internal nodes", kv.second.nPairs, rank.size() - (size_t)R.rankBase);
+        }
+        viewIndex[kv.first] = (int)rv.size();
+        viewOff.push_back(nodeOff);
+        rv.push_back(std::move(R));
+    }
+    const rz_bvh_instance* inst = hostArr<rz_bvh_instance>(c, RZ_BIND_INSTANCES);
+    const size_t nInst = hostCount<rz_bvh_instance>(c, RZ_BIND_INSTANCES);
+    std::vector<int32_t> instView(nInst, -1);
+    for (size_t i = 0; i < nInst; ++i) {
+        auto it = viewIndex.find(std::make_tuple(inst[i].blasNodeOffset, inst[i].blasTriOffset, inst[i].globalTriOffset));
+        if (it != viewIndex.end()) instView[i] = it->second;
+    }
+    // the views' flag words start from what the layout found (a view this call does not refit keeps its own)
+    std::vector<unsigned> flags(4 * rv.size(), 0u);
+    {
+        size_t v = 0;
+        for (const auto& kv : c->views) { flags[4 * v] = (kv.second.mayGlass ? 1u : 0u) | (kv.second.irregular ? 2u : 0u); ++v; }
+    }
+    if ((rc = upload_vec(c, c->dRefitRank, rank.data(), rank.size() * sizeof(int32_t))) != RZ_OK) return rc;
+    if ((rc = upload_vec(c, c->dRefitInstView, instView.data(), instView.size() * sizeof(int32_t))) != RZ_OK) return rc;
+    if ((rc = upload_vec(c, c->dRefitViewOff, viewOff.data(), viewOff.size() * sizeof(int32_t))) != RZ_OK) return rc;
+    if ((rc = upload_vec(c, c->dRefitFlags, flags.data(), flags.size() * sizeof(unsigned))) != RZ_OK) return rc;
+    if ((rc = ensure(c, c->dRefitRoots, std::max<size_t>(rv.size(), 1) * sizeof(rz_bvh_node))) != RZ_OK) return rc;
+    const size_t pinnedNeed = rv.size() * (16 + sizeof(rz_bvh_node)) + 64;
+    if (pinnedNeed > c->refitPinnedCap) {
+        if (c->refitPinned) (void)hipHostFree(c->refitPinned);
+        c->refitPinned = nullptr; c->refitPinnedCap = 0;
+        RZ_HIP(c, hipHostMalloc(reinterpret_cast<void**>(&c->refitPinned), pinnedNeed, hipHostMallocDefault));
+        c->refitPinnedCap = pinnedNeed;
+    }
+    RZ_HIP(c, hipStreamSynchronize(c->stream));     // the staging vectors die at scope exit
+    c->refitViews.swap(rv);
+    c->refitGen = c->layoutGen;
+    return RZ_OK;
+}
+
+// The definition of include/rayzen_hip.h on the host copies of one mesh (the partner of BVH::refit, for node arrays whose
+// children need not be numbered after their parents): breadth first from the root, then the visited nodes in reverse.
+// *nSlots: the slots its leaves name.  false: the arrays are inconsistent (nothing written; the re-layout words the error).
+static bool host_refit_mesh(rz_ctx* c, rz_bvh_node* nodes, long long nNodes, const int32_t* idx, long long nIdx, const rz_triangle* tris,
+                            long long nTris, int nodeOff, int triOff, int gTriOff, bool write, long long* nSlots) {
+    if (nodeOff < 0 || nodeOff >= nNodes || triOff < 0 || triOff > nIdx) return false;
+    alloc_point(c);
+    std::vector<int> order;
+    order.push_back(0);
+    long long maxSlot = 0;
+    for (size_t head = 0; head < order.size(); ++head) {
+        const rz_bvh_node& N = nodes[nodeOff + order[head]];
+        if (N.count >= 0) {
+            if (N.leftFirst < 0 || (long long)triOff + N.leftFirst + N.count > nIdx) return false;
+            for (int s = 0; s < N.count; ++s) {
+                const long long src = (long long)gTriOff + idx[triOff + N.leftFirst + s];
+                if (src < 0 || src >= nTris) return false;
+            }
+            maxSlot = std::max(maxSlot, (long long)N.leftFirst + N.count);
+            continue;
+        }
+        const int L = N.leftFirst;
+        if (L < 1 || (long long)nodeOff + L + 1 >= nNodes || order.size() > (size_t)nNodes) return false;
+        if ((order.size() & 4095) == 0) alloc_point(c);
+        order.push_back(L);
+        order.push_back(L + 1);
+    }
+    if (nSlots) *nSlots = maxSlot;
+    if (!write) return true;
+    const float fmax = std::numeric_limits<float>::max();
+    auto gmin = [](float a, float b) { return (b < a) ? b : a; };      // glm::min
+    auto gmax = [](float a, float b) { return (a < b) ? b : a; };      // glm::max
+    for (size_t k = order.size(); k-- > 0;) {
+        rz_bvh_node& N = nodes[nodeOff + order[k]];
+        if (N.count > 0) {
+            float mn[3] = {fmax, fmax, fmax}, mx[3] = {-fmax, -fmax, -fmax};
+            for (int s = 0; s < N.count; ++s) {
+                const rz_triangle& t = tris[(long long)gTriOff + idx[triOff + N.leftFirst + s]];
+                for (int a = 0; a < 3; ++a) {
+                    mn[a] = gmin(mn[a], gmin(t.v0[a], gmin(t.v1[a], t.v2[a])));
+                    mx[a] = gmax(mx[a], gmax(t.v0[a], gmax(t.v1[a], t.v2[a])));
+                }
+            }
+            std::memcpy(N.boundsMin, mn, 12); std::memcpy(N.boundsMax, mx, 12);
+        } else if (N.count < 0) {
+            const rz_bvh_node& A = nodes[nodeOff + N.leftFirst];
+            const rz_bvh_node& B = nodes[nodeOff + N.leftFirst + 1];
+            for (int a = 0; a < 3; ++a) { N.boundsMin[a] = gmin(A.boundsMin[a], B.boundsMin[a]); N.boundsMax[a] = gmax(A.boundsMax[a], B.boundsMax[a]); }
+        }
+    }
+    return true;
+}
+
+// The transforms in force, for the TLAS step: dXforms if rz_update_transforms wrote the current ones, else the instances'.
+static int refit_tlas_step(rz_ctx* c) {
+    const size_t nInst = hostCount<rz_bvh_instance>(c, RZ_BIND_INSTANCES);
+    if (nInst == 0) return RZ_OK;
+    if (c->deviceOwnsTlas) return tlas_rebuild(c, nullptr, nInst);
+    const rz_bvh_instance* inst = hostArr<rz_bvh_instance>(c, RZ_BIND_INSTANCES);
+    alloc_point(c);
+    std::vector<float> xf(nInst * 16);
+    for (size_t i = 0; i < nInst; ++i) std::memcpy(&xf[i * 16], inst[i].transform, 64);
+    return tlas_rebuild(c, xf.data(), nInst);      // (synchronises before xf dies)
+}
+
+// The host route: patch the host copies, refit there, and let the re-layout run (RZ_FLAG_HOST_RELAYOUT; a layout that
+// fell back to the host; materials changed since the views were laid out).  Same bytes as the device route.
+static int refit_on_host(rz_ctx* c, const rz_triangle* triangles, size_t first, size_t n, bool hostPtr) {
+    int rc = sync_host_from_device(c);
+    if (rc != RZ_OK) return rc;
+    if ((rc = sync_tris_host(c)) != RZ_OK) return rc;
+    if ((rc = sync_geom_host(c)) != RZ_OK) return rc;
+    c->geomOnDevice = false;            // the host copies are the truth again
+    if (n) {
+        unsigned char* dst = c->host[RZ_BIND_TRIANGLES].data() + first * sizeof(rz_triangle);
+        if (hostPtr) std::memcpy(dst, triangles, n * sizeof(rz_triangle));
+        else {
+            RZ_HIP(c, hipStreamSynchronize(c->stream));
+            RZ_HIP(c, hipMemcpy(dst, triangles, n * sizeof(rz_triangle), hipMemcpyDeviceToHost));
+        }
+    }
+    rz_bvh_node* nodes = reinterpret_cast<rz_bvh_node*>(c->host[RZ_BIND_BLAS_NODES].data());
+    const long long nNodes = (long long)hostCount<rz_bvh_node>(c, RZ_BIND_BLAS_NODES), nIdx = (long long)hostCount<int32_t>(c, RZ_BIND_BLAS_INDICES);
+    const long long nTris = (long long)hostCount<rz_triangle>(c, RZ_BIND_TRIANGLES);
+    const rz_bvh_instance* inst = hostArr<rz_bvh_instance>(c, RZ_BIND_INSTANCES);
+    const size_t nInst = hostCount<rz_bvh_instance>(c, RZ_BIND_INSTANCES);
+    std::map<std::tuple<int, int, int>, bool> seen;
+    for (size_t i = 0; i < nInst; ++i) {
+        const auto key = std::make_tuple(inst[i].blasNodeOffset, inst[i].blasTriOffset, inst[i].globalTriOffset);
+        if (seen.count(key)) continue;
+        seen[key] = true;
+        long long slots = 0;
+        if (!host_refit_mesh(c, nodes, nNodes, hostArr<int32_t>(c, RZ_BIND_BLAS_INDICES), nIdx, hostArr<rz_triangle>(c, RZ_BIND_TRIANGLES), nTris,
+                             inst[i].blasNodeOffset, inst[i].blasTriOffset, inst[i].globalTriOffset, false, &slots))
+            continue;
+        const long long lo = inst[i].globalTriOffset, hi = lo + slots;
+        if (n && !((long long)first < hi && lo < (long long)(first + n))) continue;
+        (void)host_refit_mesh(c, nodes, nNodes, hostArr<int32_t>(c, RZ_BIND_BLAS_INDICES), nIdx, hostArr<rz_triangle>(c, RZ_BIND_TRIANGLES), nTris,
+                              inst[i].blasNodeOffset, inst[i].blasTriOffset, inst[i].globalTriOffset, true, nullptr);
+    }
+    c->geomDirty = true;
+    if ((rc = finalize(c)) != RZ_OK) return rc;
+    return refit_tlas_step(c);
+}
+
+static int refit_geometry_impl(rz_ctx* c, const rz_triangle* triangles, size_t first, size_t n, unsigned flags) {
+    const char* what = "rz_refit_geometry";
+    if (!c) return fail(nullptr, RZ_ERR_INVALID_ARG, "%s: null context", what);
+    if (flags & ~RZ_REFIT_HOST) return fail(c, RZ_ERR_INVALID_ARG, "%s: unknown flags 0x%x", what, flags);
+    if (n && !triangles) return fail(c, RZ_ERR_INVALID_ARG, "%s: null triangles", what);
+    const bool hostPtr = (flags & RZ_REFIT_HOST) != 0;
+    if (n && !hostPtr && (reinterpret_cast<uintptr_t>(triangles) & 15u)) return fail(c, RZ_ERR_INVALID_ARG, "%s: the device pointer must be 16-byte aligned", what);
+    for (int b : {RZ_BIND_TRIANGLES, RZ_BIND_BLAS_NODES, RZ_BIND_BLAS_INDICES, RZ_BIND_INSTANCES, RZ_BIND_MATERIALS, RZ_BIND_LIGHTS,
+                  RZ_BIND_TLAS_NODES, RZ_BIND_TLAS_INDICES})
+        if (!c->present[b]) return fail(c, RZ_ERR_NOT_READY, "%s: no scene (binding %d has not been uploaded)", what, b);
+    const size_t nTris = hostCount<rz_triangle>(c, RZ_BIND_TRIANGLES);
+    if (first > nTris || n > nTris - first)
+        return fail(c, RZ_ERR_OUT_OF_RANGE, "%s: triangles [%zu,+%zu) past the %zu of binding 0", what, first, n, nTris);
+    RZ_HIP(c, hipSetDevice(c->device));
+    int rc;
+    bool copied = false;                // binding 0 holds the new triangles already
+    if (c->geomDirty && n) {
+        // a re-layout is pending anyway (the geometry was uploaded or patched since the last launch -- or an earlier refit left a
+        // bad materialIndex behind): the new triangles go into the host copy first, so that it is their layout that is checked
+        if ((rc = sync_tris_host(c)) != RZ_OK) return rc;
+        unsigned char* dst = c->host[RZ_BIND_TRIANGLES].data() + first * sizeof(rz_triangle);
+        if (hostPtr) std::memcpy(dst, triangles, n * sizeof(rz_triangle));
+        else {
+            RZ_HIP(c, hipStreamSynchronize(c->stream));
+            RZ_HIP(c, hipMemcpy(dst, triangles, n * sizeof(rz_triangle), hipMemcpyDeviceToHost));
+        }
+        copied = true;                  // (the re-layout below uploads them with the rest)
+    }
+    rc = finalize(c);                   // the device scene must exist: the refit patches it
+    if (rc != RZ_OK) return rc;
+    if (!c->layoutOnDevice || c->matChangedSinceLayout) return refit_on_host(c, triangles, first, n, hostPtr);
+    if ((rc = refit_topology(c)) != RZ_OK) return rc;
+    // (every host allocation of the call happens before anything is enqueued: a failure leaves the context as it was)
+    const size_t nInst = hostCount<rz_bvh_instance>(c, RZ_BIND_INSTANCES);
+    alloc_point(c);
+    std::vector<float> xf;              // the transforms in force, unless dXforms holds them (rz_update_transforms wrote the current ones)
+    if (!c->deviceOwnsTlas) {
+        const rz_bvh_instance* inst = hostArr<rz_bvh_instance>(c, RZ_BIND_INSTANCES);
+        xf.resize(nInst * 16);
+        for (size_t i = 0; i < nInst; ++i) std::memcpy(&xf[i * 16], inst[i].transform, 64);
+    }
+    std::vector<char> touched(c->refitViews.size(), 0);
+
+    // binding 0 first (every triangle of the interval, whether a mesh names it or not) ...
+    if (n && !copied) {
+        void* dst = static_cast<rz_triangle*>(c->dRawTris.p) + first;
+        if (hostPtr) {
+            RZ_HIP(c, hipMemcpyAsync(dst, triangles, n * sizeof(rz_triangle), hipMemcpyHostToDevice, c->stream));
+            std::memcpy(c->host[RZ_BIND_TRIANGLES].data() + first * sizeof(rz_triangle), triangles, n * sizeof(rz_triangle));
+        } else {
+            RZ_HIP(c, hipMemcpyAsync(dst, triangles, n * sizeof(rz_triangle), hipMemcpyDeviceToDevice, c->stream));
+            c->trisHostStale = true;
+        }
+    }
+    // ... then every view whose triangle range meets the interval
+    const int nViews = (int)c->refitViews.size();
+    const int nMat = (int)hostCount<rz_material>(c, RZ_BIND_MATERIALS);
+    unsigned* dFlags = static_cast<unsigned*>(c->dRefitFlags.p);
+    int nTouched = 0;
+    for (int v = 0; v < nViews; ++v) {
+        const RefitView& R = c->refitViews[(size_t)v];
+        const BlasView& V = c->views.at(R.key);
+        const long long lo = std::get<2>(R.key), hi = lo + V.nSlots;
+        if (n && !((long long)first < hi && lo < (long long)(first + n))) continue;
+        if (V.empty) continue;          // (a count == 0 root is left as it is)
+        touched[(size_t)v] = 1; ++nTouched;
+        RZ_HIP(c, hipMemsetAsync(dFlags + 4 * v, 0, 16, c->stream));
+        RefitViewWork W{};
+        W.nodes = static_cast<rz_bvh_node*>(c->dRawNodes.p) + std::get<0>(R.key);
+        W.idx = static_cast<const int32_t*>(c->dRawIdx.p) + std::get<1>(R.key);
+        W.rawTris = static_cast<const rz_triangle*>(c->dRawTris.p);
+        W.nTris = (long long)nTris;
+        W.gTriOff = std::get<2>(R.key);
+        W.nSlots = V.nSlots;
+        W.tris = static_cast<DevTri*>(c->dTris.p) + V.triBase;
+        W.triN = static_cast<DevTriN*>(c->dTriN.p) + V.triBase;
+        W.pairs = static_cast<DevPair*>(c->dPairs.p) + V.pairBase;
+        W.rankToNode = static_cast<const int32_t*>(c->dRefitRank.p) + R.rankBase;
+        W.levelStart = R.levelStart.data();
+        W.nLevels = R.levelStart.empty() ? 0 : (int)R.levelStart.size() - 1;
+        W.mats = static_cast<const rz_material*>(c->dMat.p);
+        W.nMat = nMat;
+        W.vflags = dFlags + 4 * v;
+        const int e = refit_view_device(W, c->stream);
+        if (e != 0) return fail(c, RZ_ERR_HIP, "%s: %s", what, hipGetErrorString((hipError_t)(-e)));
+    }
+    unsigned* hFlags = reinterpret_cast<unsigned*>(c->refitPinned);
+    rz_bvh_node* hRoots = reinterpret_cast<rz_bvh_node*>(c->refitPinned + (size_t)nViews * 16);
+    if (nTouched) {
+        const int e = refit_roots_device(static_cast<DevInstance*>(c->dInst.p), (int)nInst, static_cast<const int32_t*>(c->dRefitInstView.p),
+                                         static_cast<const int32_t*>(c->dRefitViewOff.p), nViews, static_cast<const rz_bvh_node*>(c->dRawNodes.p),
+                                         dFlags, static_cast<rz_bvh_node*>(c->dRefitRoots.p), c->stream);
+        if (e != 0) return fail(c, RZ_ERR_HIP, "%s: %s", what, hipGetErrorString((hipError_t)(-e)));
+        RZ_HIP(c, hipMemcpyAsync(hFlags, dFlags, (size_t)nViews * 16, hipMemcpyDeviceToHost, c->stream));
+        RZ_HIP(c, hipMemcpyAsync(hRoots, c->dRefitRoots.p, (size_t)nViews * sizeof(rz_bvh_node), hipMemcpyDeviceToHost, c->stream));
+        // the node array on the device is the truth from here on, as after rz_build_geometry (the host copy is fetched on demand)
+        if (!c->geomOnDevice) {
+            c->devNodes = hostCount<rz_bvh_node>(c, RZ_BIND_BLAS_NODES);
+            c->devIdx = hostCount<int32_t>(c, RZ_BIND_BLAS_INDICES);
+            c->devRoots.clear();
+            c->geomOnDevice = true;
+        }
+        c->geomHostFresh = false;
+    }
+    // world boxes and the TLAS with the transforms in force; its synchronisation is this call's (host-pointer copies have left `triangles`)
+    rc = tlas_rebuild(c, c->deviceOwnsTlas ? nullptr : xf.data(), nInst);
+    if (rc != RZ_OK) return rc;
+    if (nInst == 0) RZ_HIP(c, hipStreamSynchronize(c->stream));
+    if (!nTouched) return RZ_OK;
+    unsigned all = 0;
+    int badTri = -1;
+    {
+        int v = 0;
+        for (auto& kv : c->views) {
+            BlasView& V = kv.second;
+            if (touched[(size_t)v]) {
+                V.mayGlass = (hFlags[4 * v] & 1u) != 0;
+                V.irregular = (hFlags[4 * v] & 2u) != 0;
+                if ((hFlags[4 * v] & 4u) && badTri < 0) badTri = (int)hFlags[4 * v + 1];
+                std::memcpy(V.rootMin, hRoots[v].boundsMin, 12);
+                std::memcpy(V.rootMax, hRoots[v].boundsMax, 12);
+            }
+            all |= (V.mayGlass ? 1u : 0u) | (V.irregular ? 2u : 0u);
+            c->devRoots[std::get<0>(kv.first)] = hRoots[v];
+            ++v;
+        }
+    }
+    c->devTransparent = all;
+    c->sceneHasTransparency = (all & 1u) != 0;
+    c->irregularBoxes = (all & 2u) != 0;
+    if (badTri >= 0) {
+        c->geomDirty = true;            // what a fresh upload of these triangles says, now and at every later call
+        return fail(c, RZ_ERR_BAD_SCENE, "%s: triangle %d has a materialIndex outside the %d materials uploaded", what, badTri, nMat);
+    }
     return RZ_OK;
 }
 
@@ -1175,6 +1540,7 @@ static int build_geometry_impl(rz_ctx* c, const rz_triangle* triangles, size_t n
     {   // (the last allocation that can fail: a copy first, then nothing below throws)
         std::vector<unsigned char> tcopy(reinterpret_cast<const unsigned char*>(triangles), reinterpret_cast<const unsigned char*>(triangles) + nTris * sizeof(rz_triangle));
         c->host[RZ_BIND_TRIANGLES].swap(tcopy);
+        c->trisHostStale = false;
     }
     RZ_HIP(c, hipStreamSynchronize(c->stream));        // nothing in flight reads the old arrays
     std::swap(c->dRawNodes, fresh.nodes);               // (the old ones are released with `fresh`)
@@ -1231,6 +1597,7 @@ static int read_binding_impl(rz_ctx* c, rz_binding binding, void* out, size_t by
     if (!c->present[binding]) return fail(c, RZ_ERR_NOT_READY, "binding %d has not been uploaded", (int)binding);
     if (c->deviceOwnsTlas) { int rc = sync_host_from_device(c); if (rc != RZ_OK) return rc; c->deviceOwnsTlas = true; }
     if (c->geomOnDevice && (binding == RZ_BIND_BLAS_NODES || binding == RZ_BIND_BLAS_INDICES)) { int rc = sync_geom_host(c); if (rc != RZ_OK) return rc; }
+    if (binding == RZ_BIND_TRIANGLES) { int rc = sync_tris_host(c); if (rc != RZ_OK) return rc; }
     const size_t have = c->host[binding].size();
     if (needed) *needed = have;
     if (!out) return RZ_OK;
@@ -1850,6 +2217,9 @@ int rz_update(rz_ctx* c, rz_binding binding, size_t offset, const void* data, si
 }
 int rz_update_transforms(rz_ctx* c, const float* transforms, size_t n) {
     return guarded(c, "rz_update_transforms", [&] { return update_transforms_impl(c, transforms, n); });
+}
+int rz_refit_geometry(rz_ctx* c, const rz_triangle* triangles, size_t first_triangle, size_t n_triangles, unsigned flags) {
+    return guarded(c, "rz_refit_geometry", [&] { return refit_geometry_impl(c, triangles, first_triangle, n_triangles, flags); });
 }
 int rz_build_blas(rz_ctx* c, const rz_triangle* tris, size_t n, rz_bvh_node* nodes_out, size_t nodes_cap, int32_t* indices_out, size_t* n_nodes, int* depth, float* device_ms) {
     return guarded(c, "rz_build_blas", [&] { return build_blas_impl(c, tris, n, nodes_out, nodes_cap, indices_out, n_nodes, depth, device_ms); });

@@ -108,6 +108,28 @@ int tri_normals_device(const DevTri* tris, long long n, DevTriN* out, hipStream_
 int relayout_check_materials_device(const DevTri* tris, long long n, const rz_material* mats, int nMat, void* workspace, int* pinned,
                                     unsigned* transparentOut, int* detail, hipStream_t s);
 
+// ---- rz_refit.hip
+struct RefitViewWork {          // one BLAS view to refit; every pointer is the VIEW's part of its array unless it says otherwise
+    rz_bvh_node* nodes;         // dRawNodes + blasNodeOffset
+    const int32_t* idx;         // dRawIdx + blasTriOffset
+    const rz_triangle* rawTris; // the WHOLE triangle array (already patched) and its length
+    long long nTris;
+    int gTriOff;                // globalTriOffset
+    int nSlots;                 // leaf slots of the view
+    DevTri* tris;               // dTris + triBase
+    DevTriN* triN;              // dTriN + triBase
+    DevPair* pairs;             // dPairs + pairBase
+    const int32_t* rankToNode;  // device: pair index (breadth-first rank of an internal node) -> node index in the view
+    const int* levelStart;      // HOST: ranks of tree level d are [levelStart[d], levelStart[d + 1]); nLevels + 1 entries
+    int nLevels;                // 0: the root is a leaf
+    const rz_material* mats;
+    int nMat;
+    unsigned* vflags;           // device, 4 words, zeroed by the caller: [0] bit 0 transparent, bit 1 irregular child box, bit 2 bad material index; [1] one such triangle
+};
+int refit_view_device(const RefitViewWork& W, hipStream_t s);
+int refit_roots_device(DevInstance* inst, int nInst, const int32_t* instView, const int32_t* viewNodeOff, int nViews,
+                       const rz_bvh_node* nodes, const unsigned* vflags, rz_bvh_node* rootsOut, hipStream_t s);
+
 // ---- rz_present.hip
 struct ProjBox;                 // screen-space corners of one box (rz_present.hip)
 struct PresentParams {

@@ -224,6 +224,36 @@ void BVH::buildTLAS(const std::vector<BVHInstance>& meshInstances, const std::ve
     }
 }
 
+// Keeps the topology (every leftFirst, count and the index array) and recomputes only the boxes from `tris`, bottom-up:
+//   * a leaf (count > 0): computeBounds (RayZen/src/BVH.cpp:11-19) over its own slots, in order, from +-FLT_MAX;
+//   * an internal node: glm::min(left.min, right.min), glm::max(left.max, right.max);
+//   * a leaf with count == 0 (the root of an empty mesh) is left as it is.
+// Children are numbered after their parent (buildBLAS appends them), so one pass from the last node to the first sees
+// both children of a node before the node itself.  The device half (rz_refit.hip) is held to these bytes.
+void BVH::refit(const std::vector<Triangle>& tris) { refit(tris.data(), nodes.data(), (int)nodes.size(), triIndices.data()); }
+
+void BVH::refit(const Triangle* tris, BVHNode* nodes, int nNodes, const int* idx) {
+    const float FMAX = std::numeric_limits<float>::max();
+    for (int n = nNodes - 1; n >= 0; --n) {
+        BVHNode& N = nodes[n];
+        if (N.count > 0) {
+            vec3 bmin(FMAX), bmax(-FMAX);
+            for (int s = 0; s < N.count; ++s) {
+                const Triangle& t = tris[idx[N.leftFirst + s]];
+                bmin = vmin(bmin, triMin(t));
+                bmax = vmax(bmax, triMax(t));
+            }
+            N.boundsMin = bmin;
+            N.boundsMax = bmax;
+        } else if (N.count < 0) {
+            const BVHNode& L = nodes[N.leftFirst];
+            const BVHNode& R = nodes[N.leftFirst + 1];
+            N.boundsMin = vmin(L.boundsMin, R.boundsMin);
+            N.boundsMax = vmax(L.boundsMax, R.boundsMax);
+        }
+    }
+}
+
 int BVH::depth() const {
     if (nodes.empty()) return 0;
     int best = 1;

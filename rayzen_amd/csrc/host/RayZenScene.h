@@ -69,6 +69,12 @@ public:
     void buildBLAS(const Triangle* tris, int n);
     // BVH.cpp:178-240.
     void buildTLAS(const std::vector<BVHInstance>& meshInstances, const std::vector<BVHNode>& meshRootNodes);
+    // Refit for a deformed mesh (no counterpart in the reference, which builds each BLAS once): topology and index
+    // array kept, boxes recomputed bottom-up from `tris` (the mesh's triangles in their original order).  The exact
+    // definition is with the implementation (BVH.cpp) and in include/rayzen_hip.h (rz_refit_geometry).
+    void refit(const std::vector<Triangle>& tris);
+    // ... the same on raw arrays: child indices relative to `nodes`, `idx` the mesh's index array, triangle = tris[idx[slot]]
+    static void refit(const Triangle* tris, BVHNode* nodes, int nNodes, const int* idx);
     // Longest root-to-leaf path, in nodes (root alone = 1).  The render
     // library sizes its LDS traversal stacks from this.
     int depth() const;
@@ -168,6 +174,11 @@ struct SceneBuffers {
     // false only when `blasBuilder` is set and fails (nothing is built then; the host builder is NOT used instead).
     bool build(const Scene& scene, bool shareMeshes = false);
     void updateDynamic(const Scene& scene);
+    // A mesh's vertices moved (`mesh.triangles` already holds the new ones, same count): every stored copy of it gets
+    // the new triangles and a refitted BLAS (BVH::refit), the instances' root boxes follow, and the world boxes and
+    // the TLAS are rebuilt with the transforms in force, as updateDynamic does.  false: the mesh is not in the scene
+    // or its triangle count changed (nothing is touched then).  The byte partner of rz_refit_geometry.
+    bool refitMesh(const Scene& scene, const Mesh* mesh);
 
     // Optional replacement for BVH::buildBLAS, e.g. rz_build_blas of include/rayzen_hip.h bound to a context (the
     // device builder, byte-identical output).  Fills `out.nodes` / `out.triIndices`; returns false on failure.

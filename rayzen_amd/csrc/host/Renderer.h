@@ -125,6 +125,15 @@ public:
         for (size_t i = 0; i < scene.gameObjects.size(); ++i) std::memcpy(&xf[i * 16], scene.gameObjects[i].transform.m, 64);
         check(rz_update_transforms(ctx_, xf.data(), scene.gameObjects.size()), "rz_update_transforms");
     }
+    // Deforming meshes (rz_refit_geometry; the reference has no counterpart): `triangles` replace binding 0 from element
+    // firstTriangle on, every mesh they touch is refitted on the device and the TLAS follows with the transforms in force.
+    // refitAll: every mesh from binding 0 as it stands (after an rz_update of binding 0).  The host copies in buffers_
+    // are NOT updated: rz_read_binding returns the refitted arrays.
+    void refitMesh(size_t firstTriangle, const std::vector<Triangle>& triangles) {
+        check(rz_refit_geometry(ctx_, reinterpret_cast<const rz_triangle*>(triangles.data()), firstTriangle, triangles.size(), RZ_REFIT_HOST),
+              "rz_refit_geometry");
+    }
+    void refitAll() { check(rz_refit_geometry(ctx_, nullptr, 0, 0, 0), "rz_refit_geometry"); }
     void sendSceneDataToShader(const Scene& scene, int width, int height, int bounceBudget, int spp = 1,
                                int sampleBase = 0, int tileRank = 0, int tileNRanks = 1) {
         rz_frame_params p{};

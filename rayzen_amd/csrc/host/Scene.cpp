@@ -99,6 +99,43 @@ bool SceneBuffers::build(const Scene& scene, bool shareMeshes) {
     return true;
 }
 
+bool SceneBuffers::refitMesh(const Scene& scene, const Mesh* mesh) {
+    const size_t nObj = std::min(meshInstances.size(), scene.gameObjects.size());
+    const int nTris = (int)mesh->triangles.size();
+    // where the copies of this mesh live: node offset -> (index offset, triangle base, node count)
+    struct Copy { int triOffset, triBase, nNodes; };
+    std::map<int, Copy> copies;
+    std::vector<int> starts;
+    for (const BVHInstance& inst : meshInstances) starts.push_back(inst.blasNodeOffset);
+    starts.push_back((int)allBLASNodes.size());
+    std::sort(starts.begin(), starts.end());
+    for (size_t i = 0; i < nObj; ++i) {
+        if (scene.gameObjects[i].mesh.get() != mesh) continue;
+        const BVHInstance& inst = meshInstances[i];
+        const int end = *std::upper_bound(starts.begin(), starts.end(), inst.blasNodeOffset);
+        if (inst.blasTriOffset < 0 || (size_t)inst.blasTriOffset + (size_t)nTris > allBLASTriIndices.size() || inst.globalTriOffset < 0 ||
+            (size_t)inst.globalTriOffset + (size_t)nTris > allTriangles.size())
+            return false;
+        copies[inst.blasNodeOffset] = {inst.blasTriOffset, inst.globalTriOffset, end - inst.blasNodeOffset};
+    }
+    if (copies.empty()) return false;
+    for (const auto& kv : copies) {
+        const Copy& c = kv.second;
+        std::copy(mesh->triangles.begin(), mesh->triangles.end(), allTriangles.begin() + c.triBase);
+        BVH::refit(allTriangles.data() + c.triBase, allBLASNodes.data() + kv.first, c.nNodes, allBLASTriIndices.data() + c.triOffset);
+    }
+    for (size_t i = 0; i < meshInstances.size(); ++i)
+        if (copies.count(meshInstances[i].blasNodeOffset)) blasRoots[i] = allBLASNodes[(size_t)meshInstances[i].blasNodeOffset];
+    std::vector<BVHNode> worldRootNodes(meshInstances.size());
+    for (size_t i = 0; i < meshInstances.size(); ++i) worldRootNodes[i] = worldRootNode(blasRoots[i], meshInstances[i].transform);
+    BVH tlas;
+    tlas.buildTLAS(meshInstances, worldRootNodes);
+    tlasNodes = tlas.nodes;
+    tlasTriIndices = tlas.triIndices;
+    tlasDepth = tlas.depth();
+    return true;
+}
+
 void SceneBuffers::updateDynamic(const Scene& scene) {
     size_t n = std::min(meshInstances.size(), scene.gameObjects.size());
     std::vector<BVHNode> worldRootNodes(meshInstances.size());

@@ -46,6 +46,20 @@ int rzh_build_blas(const rz_triangle* tris, int n, rz_bvh_node* nodes_out, int32
     return (int)bvh.nodes.size();
 }
 
+int rzh_refit_blas(const rz_triangle* tris, int n, rz_bvh_node* nodes_inout, int n_nodes, const int32_t* idx) {
+    if (n < 0 || n_nodes < 1 || !nodes_inout || (n > 0 && (!tris || !idx))) return -1;
+    BVHNode* nodes = reinterpret_cast<BVHNode*>(nodes_inout);
+    for (int k = 0; k < n_nodes; ++k) {         // nothing outside the arrays is read: a leaf's slots, an internal node's children
+        const BVHNode& N = nodes[k];
+        if (N.count > 0 && (N.leftFirst < 0 || (long long)N.leftFirst + N.count > n)) return -1;
+        if (N.count < 0 && (N.leftFirst <= k || (long long)N.leftFirst + 1 >= n_nodes)) return -1;
+    }
+    for (int s = 0; s < n; ++s)
+        if (idx[s] < 0 || idx[s] >= n) return -1;
+    BVH::refit(reinterpret_cast<const Triangle*>(tris), nodes, n_nodes, idx);
+    return 0;
+}
+
 int rzh_build_tlas(const rz_bvh_node* world_roots, int n, rz_bvh_node* nodes_out, int32_t* idx_out, int* n_idx_out) {
     if (n < 0 || !nodes_out || (n > 0 && (!world_roots || !idx_out))) return -1;
     std::vector<BVHInstance> inst((size_t)n);
@@ -121,6 +135,14 @@ int rzh_scene_update_dynamic(rzh_scene* s) {
     if (!s || !s->built) return -1;
     s->buffers.updateDynamic(s->scene);
     return 0;
+}
+
+int rzh_scene_refit_mesh(rzh_scene* s, int mesh_id, const rz_triangle* tris, int n) {
+    if (!s || !s->built || mesh_id < 0 || mesh_id >= (int)s->meshes.size() || n < 0 || (n > 0 && !tris)) return -1;
+    Mesh& m = *s->meshes[(size_t)mesh_id];
+    if ((size_t)n != m.triangles.size()) return -1;
+    if (n > 0) std::memcpy(static_cast<void*>(m.triangles.data()), tris, (size_t)n * sizeof(Triangle));
+    return s->buffers.refitMesh(s->scene, &m) ? 0 : -1;
 }
 
 const void* rzh_scene_buffer(const rzh_scene* s, rz_binding b, size_t* bytes) {

@@ -141,6 +141,23 @@ class Renderer:
         t = np.ascontiguousarray(transforms, np.float32).reshape(-1, 16)
         self._check(self._L.rz_update_transforms(self._c, t.ctypes.data, t.shape[0]), "rz_update_transforms")
 
+    def refit_geometry(self, triangles=None, first=0):
+        """rz_refit_geometry from host memory: `triangles` (TRIANGLE dtype) replace binding 0 from element `first` on and every
+        mesh they touch is refitted on the device -- boxes recomputed, topology kept, everything derived patched in place,
+        world boxes and TLAS rebuilt with the transforms in force.  triangles=None: refit every mesh from binding 0 as it
+        stands (what makes a preceding update() of binding 0 correct)."""
+        from .scene import TRIANGLE as TRIANGLE_DTYPE
+        if triangles is None:
+            self._check(self._L.rz_refit_geometry(self._c, None, 0, 0, 0), "rz_refit_geometry")
+            return
+        t = np.ascontiguousarray(triangles, TRIANGLE_DTYPE)
+        self._check(self._L.rz_refit_geometry(self._c, t.ctypes.data if t.shape[0] else None, int(first), t.shape[0], _lib.REFIT_HOST),
+                    "rz_refit_geometry")
+
+    def refit_geometry_device(self, ptr, first, n):
+        """rz_refit_geometry on device memory (rz_triangle[n], 16-B aligned), enqueued on the context's stream."""
+        self._check(self._L.rz_refit_geometry(self._c, C.c_void_p(ptr), int(first), int(n), 0), "rz_refit_geometry")
+
     def build_blas(self, triangles):
         """BVH::buildBLAS (BVH.cpp:99-175, SAH) on the device.  triangles: TRIANGLE_DTYPE array.
         Returns (nodes, indices, depth, device_ms); byte-identical to the reference builder's output."""

@@ -124,6 +124,19 @@ def build_blas(tris):
     return nodes[:nn].copy(), idx[:n].copy(), depth.value
 
 
+def refit_blas(tris, nodes, idx):
+    """BVH::refit (librayzen_host.so: rzh_refit_blas): the boxes of `nodes` recomputed bottom-up from the moved `tris` (the
+    mesh's triangles in their original order); topology and `idx` kept.  Returns the refitted copy of `nodes`."""
+    tris = np.ascontiguousarray(tris)
+    assert tris.dtype.itemsize == 64
+    out = np.ascontiguousarray(nodes, BVH_NODE).copy()
+    idx = np.ascontiguousarray(idx, np.int32)
+    n = tris.shape[0]
+    if _lib.host().rzh_refit_blas(_p(tris) if n else None, n, _p(out), out.shape[0], _p(idx) if n else None) != 0:
+        raise RuntimeError("rzh_refit_blas failed (inconsistent arrays)")
+    return out
+
+
 def build_tlas(world_roots):
     r = np.ascontiguousarray(world_roots)
     assert r.dtype.itemsize == 32
@@ -278,6 +291,16 @@ class Scene:
         self._pull(GEOMETRY_BINDINGS)
         self.cache_report = dict(ssbo_loaded=bool(rep[0]), ssbo_invalidated=bool(rep[1]), blas_loaded=rep[2],
                                  blas_built=rep[3], tlas_loaded=bool(rep[4]))
+        return self
+
+    def refit_mesh(self, mesh_id, tris):
+        """A mesh's vertices moved: `tris` replace its triangles (same count), every stored copy is refitted (BVH::refit), and
+        the world boxes and the TLAS are rebuilt with the transforms in force.  The host partner of Renderer.refit_geometry."""
+        tris = np.ascontiguousarray(tris)
+        assert tris.dtype.itemsize == 64
+        if _lib.host().rzh_scene_refit_mesh(self._h, int(mesh_id), _p(tris) if tris.shape[0] else None, tris.shape[0]) != 0:
+            raise RuntimeError("rzh_scene_refit_mesh failed (unknown mesh, or its triangle count changed)")
+        self._pull(GEOMETRY_BINDINGS)
         return self
 
     def update_dynamic(self):
