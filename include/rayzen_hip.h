@@ -564,6 +564,92 @@ int rz_denoise(rz_ctx* ctx, const rz_denoise_params* params, const float* rgba_i
 int rz_present_denoised(rz_ctx* ctx, const rz_present_params* present, const rz_denoise_params* params,
                         uint8_t* rgba8, size_t rgba8_bytes, float* rgb32f, size_t rgb32f_bytes);
 
+/* ------------------------------------------------------------------------ */
+/* Temporal accumulation and a variance-guided filter (new: the reference has none) */
+/* ------------------------------------------------------------------------ */
+/* For the one-sample frame of a camera and instances that move: every call blends the frame into a per-pixel history that is
+ * carried to where the pixel's surface was in the previous call's frame (reprojection, through the instance's previous
+ * transform), and filters the result with rz_denoise's a-trous guided by the luminance variance (SVGF: Schied et al., HPG 2017;
+ * rz_temporal.hip).  Per pixel p = (px, py), row 0 = the bottom row; W, H = the frame's width and height; binary32 throughout,
+ * every expression evaluated as written (no fused multiply-add), sums left to right:
+ *  1 guide, colour   G_p, c_p, alpha_p exactly as rz_denoise's (the same guide kernel); d_p = c_p / max(alpha_p, 1e-3) for a hit
+ *            when demodulate is set, else c_p; l_p = (0.2126 d.r + 0.7152 d.g) + 0.0722 d.b.
+ *  2 reprojection    a 3 x 4 transform applies as ((m0 x + m1 y) + m2 z) + m3 per row (m0..m3 its columns); dot(a, b) =
+ *            (a.x b.x + a.y b.y) + a.z b.z.
+ *            hit on instance i:  o = inverseTransform_i (x_p, 1);  x' = transformPrev_i (o, 1);
+ *              n' = b / sqrt(dot(b, b)), b = mat3(transpose(inversePrev_i)) (mat3(transpose(transform_i)) n_p)
+ *              (mat3(transpose(M)) v: the dot products of M's columns with v).  If transform_i equals transformPrev_i bit for
+ *              bit (the 3 x 4 part), x' = x_p and n' = n_p: the round trip is skipped.  t' = sqrt(dot(x' - cam_prev, x' - cam_prev)).
+ *            miss:  x' = the unit direction of the pixel-centre ray (what the guide's ray was cast along), with w = 0.
+ *            e = ((view_prev[k] x'.x + view_prev[4+k] x'.y) + view_prev[8+k] x'.z) + view_prev[12+k] w, k = 0..3 (w = 1 for a
+ *            hit); clip likewise from proj_prev and e.  No history if clip.w <= 0 (hit or miss alike).
+ *            u = (clip.x / clip.w * 0.5 + 0.5) * W - 0.5, v likewise with clip.y and H; no history unless -1 < u < W and
+ *            -1 < v < H.
+ *            Static shortcut: when view and proj equal the previous call's bit for bit and (for a hit) so does the instance's
+ *            transform, (u, v) = (px, py) exactly -- one tap of weight 1.
+ *  3 taps    x0 = floor(u), y0 = floor(v), fx = u - x0, fy = v - y0; the taps q = (x0, y0), (x0+1, y0), (x0, y0+1),
+ *            (x0+1, y0+1), in this order, with weights (1-fx)(1-fy), fx (1-fy), (1-fx) fy, fx fy.  A tap counts iff its weight
+ *            is > 0, it lies inside the image, the previous guide at q has p's hit-or-miss status and, for a hit: the same
+ *            instance, dot(n', n_q) >= normal_cos, and |dot(n', x_q - x')| <= plane_tol * t' * f_prev, f_prev =
+ *            2 |inv_proj_prev[5]| / H.  S = the sum of the counted weights; history is accepted iff S >= 0.01, and then
+ *            D_h, (m1, m2) = (sum of w * value over the counted taps) / S, and N_h = N_0 + (sum of w * (N_q - N_0)) / S with N_0
+ *            the first counted tap's N (the same mean; taps of one length give that length exactly).
+ *  4 accumulation    N_p = min(N_h + 1, max_history) with history, else 1 (N is carried as a float);  a = max(alpha, 1 / N_p);
+ *            D_p = D_h + a * (d_p - D_h);  am = max(alpha_moments, 1 / N_p);  M1 = m1 + am * (l_p - m1);
+ *            M2 = m2 + am * (l_p * l_p - m2).  Without history D_p = d_p, (M1, M2) = (l_p, l_p * l_p).
+ *  5 variance        N_p >= 4: max(0, M2 - M1 * M1).  Below: max(0, E[l^2] - E[l]^2) * (4 / N_p) over the 7 x 7 window around p
+ *            of the luminance of D (this call's), with weights 1 for p itself and, for q = p + (a, b) inside the image,
+ *            [hit_p == hit_q] W_geom, W_geom = rz_denoise's at step 1 with tap distance max(|a|, |b|) (1 between two misses).
+ *  6 filter  K passes of rz_denoise's a-trous on (D, variance): the same taps, h, W_geom, hit-or-miss rule and border rule; the
+ *            colour weight is exp(-|l_p - l_q| / (sigma_l * sqrt(g_p) + 1e-8)) with l the luminance of the pass's input and
+ *            g_p the input variance under the 3 x 3 kernel (1/4 centre, 1/8 edges, 1/16 corners) at distance 1, renormalised
+ *            over the taps inside the image.  The variance is filtered along: var'_p = sum_q w_pq^2 var_q / (sum_q w_pq)^2.
+ *            After the last pass a hit's colour is multiplied by alpha_p again (demodulate).
+ *            K = 0: the output is D_p alpha_p (demodulate and a hit; else D_p) where history was accepted and c_p itself where
+ *            it was not -- so a call on an empty history returns exactly what rz_denoise returns for K = 0.
+ * The history -- D | N, the moments, the guide (rz_hit records), the frame's view, proj, inv_proj and cam_pos, and every
+ * instance's transform and inverseTransform -- lives in the context: allocated by the first call, sized by the frame, freed by
+ * rz_destroy.  A call commits what it computed as the new history (two sets of buffers swap roles; no frame is copied) unless
+ * RZ_TEMPORAL_KEEP is set, which computes the same outputs and leaves the history as it was.  The history is dropped (the next
+ * call starts every pixel at N = 1) by rz_temporal_reset, by a frame of another width or height, by another instance count, by
+ * rz_upload on binding 0, 7, 8 or 9, and by rz_build_geometry.  It is KEPT across rz_update, rz_update_transforms and
+ * rz_refit_geometry: a deformed mesh reprojects by its instance transform only, and the validity tests of step 3 are what
+ * discard the taps that no longer belong to the pixel's surface.
+ * Outputs of rz_denoise_temporal (each optional), conventions and errors are rz_denoise's: rgb32f, guides, and
+ *   stats    width*height*2 floats: N_p after this call, and the variance of step 5 (what the filter's first pass reads)
+ * Device pointers by default (rgba_in and guides 16-byte aligned, rgb32f and stats 4-byte), enqueued on the context's stream;
+ * RZ_TEMPORAL_HOST: host memory, staged, returns when written and reports a cut walk itself.  rgba_in NULL reads the context's
+ * accumulation.  A call with every output NULL still advances the history.  rz_present_temporal is to this call what
+ * rz_present_denoised is to rz_denoise (on an empty history with K = 0: rz_present's bytes).  No render state is touched.
+ * RZ_ERR_INVALID_ARG additionally: alpha or alpha_moments outside [0, 1] or NaN, max_history < 1, normal_cos outside [-1, 1],
+ * plane_tol or sigma_l not finite and > 0.  Nothing is launched by a call that fails, and the history stays as it was.
+ * Defaults (params NULL): alpha = alpha_moments = 0.2, max_history = 32, normal_cos = 0.9, plane_tol = 2, K = 5, sigma_l = 0.5,
+ * sigma_normal = 128, sigma_plane = 1, demodulate = 1 -- sigma_l chosen by the CPU measurement of tests/test_temporal_abi.py
+ * (the sweep).
+ * (Additive: RZ_ABI_VERSION stays 5.) */
+typedef struct rz_temporal_params {     /* NULL = defaults */
+    float   alpha, alpha_moments;       /* the least weight of the new frame (colour, moments), 0..1 */
+    int32_t max_history;                /* the cap of N, >= 1 */
+    float   normal_cos, plane_tol;      /* tap validity: the least n'.n_q; the plane distance in previous-frame pixel footprints */
+    int32_t iterations;                 /* K, 0..10 */
+    float   sigma_l, sigma_normal, sigma_plane;
+    int32_t demodulate;
+    int32_t reserved[6];                /* must be 0 */
+} rz_temporal_params;                   /* 64 B; rz_sizeof(12) */
+#define RZ_TEMPORAL_HOST 1u             /* pointers are host memory, as RZ_DENOISE_HOST */
+#define RZ_TEMPORAL_KEEP 4u             /* compute the outputs, leave the history as it was */
+int rz_denoise_temporal(rz_ctx* ctx, const rz_temporal_params* params, const float* rgba_in, size_t rgba_in_bytes,
+                        float* rgb32f, size_t rgb32f_bytes, rz_hit* guides, size_t guides_bytes,
+                        float* stats, size_t stats_bytes, unsigned flags);
+int rz_present_temporal(rz_ctx* ctx, const rz_present_params* present, const rz_temporal_params* params,
+                        uint8_t* rgba8, size_t rgba8_bytes, float* rgb32f, size_t rgb32f_bytes);
+int rz_temporal_reset(rz_ctx* ctx);
+/* TEST HOOK: the stored history as raw bytes, in the style of rz_debug_read_layout (out NULL: only *needed is set; an empty
+ * history has 0 bytes of everything).  which = 0: D | N, width*height float4;  1: the moments, width*height float2;  2: the
+ * guide, width*height rz_hit;  3: view[16], proj[16], inv_proj[16], cam_pos[3] of the frame it was made for (51 floats);
+ * 4: per instance 24 floats: inverseTransform then transform, each as columns 0..3, rows 0..2. */
+int rz_debug_read_temporal(rz_ctx* ctx, int which, void* out, size_t bytes, size_t* needed);
+
 /* Number of HIP devices visible to the process (0 without a GPU). */
 int rz_device_count(void);
 
@@ -586,7 +672,7 @@ const char* rz_source_hash(void);
 /* sizeof() of the ABI structs as compiled into the library, for layout
  * checks from other languages: which = 0 triangle, 1 node, 2 instance,
  * 3 material, 4 light, 5 frame_params, 6 counters, 7 ray, 8 hit,
- * 9 visibility, 10 editor_params, 11 denoise_params. */
+ * 9 visibility, 10 editor_params, 11 denoise_params, 12 temporal_params. */
 size_t rz_sizeof(int which);
 
 #ifdef __cplusplus

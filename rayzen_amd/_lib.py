@@ -22,6 +22,7 @@ HIP_SYMBOLS = (
     "rz_group_update", "rz_group_set_frame", "rz_group_render", "rz_group_reduce", "rz_group_sync", "rz_group_read_frame",
     "rz_group_frame_device_ptr", "rz_group_last_reduce_ms", "rz_group_transport", "rz_group_set_transport", "rz_abi_version", "rz_debug_poke_backstop", "rz_math_flavour",
     "rz_trace_rays", "rz_shadow_rays", "rz_render_editor", "rz_denoise", "rz_present_denoised", "rz_refit_geometry",
+    "rz_denoise_temporal", "rz_present_temporal", "rz_temporal_reset", "rz_debug_read_temporal",
 )
 ABI_VERSION = 5         # RZ_ABI_VERSION of the include/rayzen_hip.h this file mirrors
 # the symbols include/rayzen_host.h declares
@@ -109,6 +110,18 @@ class DenoiseParams(C.Structure):
 
 
 DENOISE_HOST = 1                        # RZ_DENOISE_HOST
+
+
+class TemporalParams(C.Structure):
+    """rz_temporal_params of include/rayzen_hip.h (64 B)."""
+    _fields_ = [("alpha", C.c_float), ("alpha_moments", C.c_float), ("max_history", C.c_int32), ("normal_cos", C.c_float),
+                ("plane_tol", C.c_float), ("iterations", C.c_int32), ("sigma_l", C.c_float), ("sigma_normal", C.c_float),
+                ("sigma_plane", C.c_float), ("demodulate", C.c_int32), ("reserved", C.c_int32 * 6)]
+
+
+TEMPORAL_DEFAULTS = dict(alpha=0.2, alpha_moments=0.2, max_history=32, normal_cos=0.9, plane_tol=2.0, iterations=5, sigma_l=0.5,
+                         sigma_normal=128.0, sigma_plane=1.0, demodulate=1)
+TEMPORAL_HOST, TEMPORAL_KEEP = 1, 4     # RZ_TEMPORAL_HOST, RZ_TEMPORAL_KEEP
 REFIT_HOST = 1                          # RZ_REFIT_HOST
 
 
@@ -189,7 +202,11 @@ def hip():
                                 ("rz_render_editor", i, [vp, C.POINTER(FrameParams), vp, vp, sz, vp, sz, vp, sz, C.c_uint]),
                                 ("rz_denoise", i, [vp, vp, vp, sz, vp, sz, vp, sz, C.c_uint]),
                                 ("rz_present_denoised", i, [vp, C.POINTER(PresentParams), vp, vp, sz, vp, sz]),
-                                ("rz_refit_geometry", i, [vp, vp, sz, sz, C.c_uint])):
+                                ("rz_refit_geometry", i, [vp, vp, sz, sz, C.c_uint]),
+                                ("rz_denoise_temporal", i, [vp, vp, vp, sz, vp, sz, vp, sz, vp, sz, C.c_uint]),
+                                ("rz_present_temporal", i, [vp, C.POINTER(PresentParams), vp, vp, sz, vp, sz]),
+                                ("rz_temporal_reset", i, [vp]),
+                                ("rz_debug_read_temporal", i, [vp, i, vp, sz, C.POINTER(sz)])):
             try:
                 fn = getattr(L, name)
                 fn.restype, fn.argtypes = res, args

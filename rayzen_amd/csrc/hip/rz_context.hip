@@ -149,6 +149,15 @@ struct rz_ctx {
     // the denoiser (rz_denoise / rz_present_denoised, rz_denoise.hip): the guide (2 float4 per pixel), the two float4 buffers
     // its passes ping-pong between, and the (colour, 1) buffer rz_present_denoised presents
     DevBuf dDnGuide, dDnPing, dDnPong, dDnOut;
+    // rz_denoise_temporal (rz_temporal.hip): two sets of history buffers (colour | N, moments, guide, instance transforms) that
+    // swap roles at every committing call -- set tmpCur is the stored history, the other one is written -- the per-instance
+    // "transform unchanged" flags, and the frame the history was made for
+    DevBuf dTmpCol[2], dTmpMom[2], dTmpHits[2], dTmpInst[2], dTmpSame;
+    int tmpCur = 0;
+    bool tmpValid = false;
+    int tmpW = 0, tmpH = 0;
+    size_t tmpInst = 0;
+    float tmpView[16] = {}, tmpProj[16] = {}, tmpInvProj[16] = {}, tmpCam[3] = {};
     // rz_refit_geometry (rz_refit.hip)
     bool trisHostStale = false;         // binding 0 on the device (dRawTris) is newer than the host copy: fetched on demand (sync_tris_host)
     unsigned long long layoutGen = 0;   // counts the times the views / instances were laid out
@@ -996,6 +1005,7 @@ size_t rz_sizeof(int which) {
         case 9: return sizeof(rz_visibility);
         case 10: return sizeof(rz_editor_params);
         case 11: return sizeof(rz_denoise_params);
+        case 12: return sizeof(rz_temporal_params);
         default: return 0;
     }
 }
@@ -1037,7 +1047,9 @@ void rz_destroy(rz_ctx* c) {
     for (DevBuf* b : {&c->dPairs, &c->dTris, &c->dInst, &c->dTlasNodes, &c->dTlasIdx, &c->dMat, &c->dLight,
                       &c->dCounters, &c->dResolve, &c->dGroupCtr, &c->dBlasOvf, &c->ownAccum, &c->dIor, &c->dXforms, &c->dInstRef, &c->dTlasScratch, &c->dProjBoxes, &c->dBuildWs, &c->dTlasDfs, &c->dTriN, &c->dRawNodes, &c->dRawIdx, &c->dRawTris, &c->dRelayoutWs, &c->dClaimScratch, &c->dWavePools, &c->dWaitMeta, &c->dSnap,
                       &c->dRayOvf, &c->dRayIn, &c->dRayOut, &c->dRayInstOff, &c->dDnGuide, &c->dDnPing, &c->dDnPong, &c->dDnOut,
-                      &c->dRefitRank, &c->dRefitInstView, &c->dRefitViewOff, &c->dRefitFlags, &c->dRefitRoots})
+                      &c->dRefitRank, &c->dRefitInstView, &c->dRefitViewOff, &c->dRefitFlags, &c->dRefitRoots,
+                      &c->dTmpCol[0], &c->dTmpCol[1], &c->dTmpMom[0], &c->dTmpMom[1], &c->dTmpHits[0], &c->dTmpHits[1],
+                      &c->dTmpInst[0], &c->dTmpInst[1], &c->dTmpSame})
         b->release();
     if (c->refitPinned) (void)hipHostFree(c->refitPinned);
     if (c->tlasHostCounts) (void)hipHostFree(c->tlasHostCounts);
@@ -1065,6 +1077,8 @@ static int upload_impl(rz_ctx* c, rz_binding binding, const void* data, size_t b
     alloc_point(c);
     c->host[binding].assign(static_cast<const unsigned char*>(data), static_cast<const unsigned char*>(data) + bytes);
     if (binding == RZ_BIND_TRIANGLES) c->trisHostStale = false;
+    if (binding == RZ_BIND_TRIANGLES || binding == RZ_BIND_BLAS_NODES || binding == RZ_BIND_BLAS_INDICES || binding == RZ_BIND_INSTANCES)
+        c->tmpValid = false;                // new geometry or instances: rz_denoise_temporal's history describes another scene
     c->present[binding] = true;
     switch (binding) {
         case RZ_BIND_MATERIALS: c->matDirty = true; break;
@@ -1549,6 +1563,7 @@ static int build_geometry_impl(rz_ctx* c, const rz_triangle* triangles, size_t n
     c->host[RZ_BIND_BLAS_INDICES].clear();
     c->present[RZ_BIND_TRIANGLES] = c->present[RZ_BIND_BLAS_NODES] = c->present[RZ_BIND_BLAS_INDICES] = true;
     c->geomOnDevice = true; c->geomHostFresh = false;
+    c->tmpValid = false;                    // (rz_denoise_temporal's history)
     c->devNodes = nodeOff; c->devIdx = idxOff;
     c->devRoots.swap(roots);
     c->geomDirty = true;
@@ -2177,6 +2192,255 @@ static int present_denoised_impl(rz_ctx* c, const rz_present_params* pp, const r
     return denoise_backstop(c, what);
 }
 
+// rz_denoise_temporal / rz_present_temporal (rz_temporal.hip).  They read what rz_denoise reads and touch no render state; the
+// history they keep is the context's own (rz_ctx: dTmp*).
+static const rz_temporal_params kTemporalDefaults = {0.2f, 0.2f, 32, 0.9f, 2.0f, 5, 0.5f, 128.0f, 1.0f, 1, {0, 0, 0, 0, 0, 0}};
+
+static int temporal_check(rz_ctx* c, const char* what, const rz_temporal_params& P) {
+    if (!(P.alpha >= 0.0f && P.alpha <= 1.0f) || !(P.alpha_moments >= 0.0f && P.alpha_moments <= 1.0f))
+        return fail(c, RZ_ERR_INVALID_ARG, "%s: alpha %g, alpha_moments %g outside [0, 1]", what, (double)P.alpha, (double)P.alpha_moments);
+    if (P.max_history < 1) return fail(c, RZ_ERR_INVALID_ARG, "%s: max_history %d < 1", what, P.max_history);
+    if (!(P.normal_cos >= -1.0f && P.normal_cos <= 1.0f)) return fail(c, RZ_ERR_INVALID_ARG, "%s: normal_cos %g outside [-1, 1]", what, (double)P.normal_cos);
+    if (!(P.plane_tol > 0.0f && P.plane_tol < INFINITY) || !(P.sigma_l > 0.0f && P.sigma_l < INFINITY))
+        return fail(c, RZ_ERR_INVALID_ARG, "%s: plane_tol %g, sigma_l %g (finite, > 0)", what, (double)P.plane_tol, (double)P.sigma_l);
+    for (int r : P.reserved)
+        if (r) return fail(c, RZ_ERR_INVALID_ARG, "%s: reserved words must be 0", what);
+    // the rest is rz_denoise's (sigma_color has no counterpart: any valid value)
+    const rz_denoise_params D = {P.iterations, 1.0f, P.sigma_normal, P.sigma_plane, P.demodulate, {0, 0, 0}};
+    return denoise_check(c, what, D);
+}
+
+// Casts the guide, accumulates, filters, and commits the history unless `keep`.  in: RGBA32F sum and count (device); outputs
+// (device, each optional): rgb, out4 ((colour, 1)), hits (rz_hit), stats (N, variance).
+static int temporal_run(rz_ctx* c, const rz_temporal_params& P, const float4* in, float* rgb, float4* out4, float4* hits,
+                        float* stats, bool keep) {
+    const rz_frame_params& f = c->frame;
+    const size_t np = (size_t)f.width * f.height;
+    int rc = finalize(c);
+    if (rc != RZ_OK) return rc;
+    const size_t nInst = hostCount<rz_bvh_instance>(c, RZ_BIND_INSTANCES);
+    const bool havePrev = c->tmpValid && c->tmpW == f.width && c->tmpH == f.height && c->tmpInst == nInst;
+    const int cur = c->tmpCur, nxt = cur ^ 1;
+    rc = ensure(c, c->dTmpCol[nxt], np * 16);
+    if (rc == RZ_OK) rc = ensure(c, c->dTmpMom[nxt], np * 8);
+    if (rc == RZ_OK) rc = ensure(c, c->dTmpHits[nxt], np * sizeof(rz_hit));
+    if (rc == RZ_OK) rc = ensure(c, c->dTmpInst[nxt], nInst * 96);
+    if (rc == RZ_OK) rc = ensure(c, c->dTmpSame, nInst * sizeof(int));
+    if (rc == RZ_OK) rc = ensure(c, c->dDnGuide, np * 32);
+    const bool filter = (rgb || out4) && P.iterations > 0;
+    if (rc == RZ_OK && filter) rc = ensure(c, c->dDnPong, np * 16);
+    if (rc == RZ_OK && filter && P.iterations > 1) rc = ensure(c, c->dDnPing, np * 16);
+    if (rc == RZ_OK) rc = ensure_group_counter(c);          // (only its backstop word)
+    if (rc == RZ_OK) rc = ensure_ray_inst_off(c);
+    if (rc != RZ_OK) return rc;
+    // the guide: rz_denoise's kernel, its rz_hit records straight into the history being written
+    KParams K{};
+    scene_kparams(c, K);
+    K.width = f.width; K.height = f.height;
+    std::memcpy(K.invView, f.inv_view, 64);
+    std::memcpy(K.invProj, f.inv_proj, 64);
+    std::memcpy(K.camPos, f.cam_pos, 12);
+    DenoiseGuideLaunch G{};
+    G.unitsX = (f.width + 63) / 64;
+    G.units = (long long)G.unitsX * f.height;
+    G.grid = rays_grid(G.units * 64);
+    G.guide = static_cast<float4*>(c->dDnGuide.p);
+    G.hits = static_cast<float4*>(c->dTmpHits[nxt].p);
+    G.instTriOff = static_cast<const int32_t*>(c->dRayInstOff.p);
+    G.errWord = static_cast<unsigned*>(c->dGroupCtr.p) + RZ_ERRWORD;
+    rc = size_blas_stack(c, K, 0, RZ_RAYS_WAVES_PER_CU, G.grid, c->dRayOvf);
+    if (rc != RZ_OK) return rc;
+    launch_denoise_guides(K, G, c->stream);
+    RZ_HIP(c, hipGetLastError());
+    if (hits) RZ_HIP(c, hipMemcpyAsync(hits, G.hits, np * sizeof(rz_hit), hipMemcpyDeviceToDevice, c->stream));
+    launch_temporal_instances(K.instances, static_cast<const float*>(c->dTmpInst[cur].p), static_cast<float*>(c->dTmpInst[nxt].p),
+                              static_cast<int*>(c->dTmpSame.p), (int)nInst, havePrev, c->stream);
+    RZ_HIP(c, hipGetLastError());
+    const double fpx = 2.0 * std::fabs((double)f.inv_proj[5]) / (double)f.height;
+    TemporalLaunch T{};
+    T.accum = in;
+    T.hits = G.hits;
+    T.materials = K.materials;
+    T.instances = K.instances;
+    T.colPrev = static_cast<const float4*>(c->dTmpCol[cur].p);
+    T.momPrev = static_cast<const float2*>(c->dTmpMom[cur].p);
+    T.hitsPrev = static_cast<const float4*>(c->dTmpHits[cur].p);
+    T.instPrev = static_cast<const float*>(c->dTmpInst[cur].p);
+    T.instSame = static_cast<const int*>(c->dTmpSame.p);
+    T.colNext = static_cast<float4*>(c->dTmpCol[nxt].p);
+    T.momNext = static_cast<float2*>(c->dTmpMom[nxt].p);
+    T.dst = P.iterations == 0 ? out4 : nullptr;
+    T.rgb = P.iterations == 0 ? rgb : nullptr;
+    T.width = f.width; T.height = f.height;
+    T.nMaterials = K.nMaterials;
+    T.demodulate = P.demodulate;
+    T.havePrev = havePrev ? 1 : 0;
+    T.cameraSame = havePrev && std::memcmp(c->tmpView, f.view, 64) == 0 && std::memcmp(c->tmpProj, f.proj, 64) == 0;
+    T.alpha = P.alpha; T.alphaMoments = P.alpha_moments; T.maxHistory = (float)P.max_history;
+    T.normalCos = P.normal_cos; T.planeTol = P.plane_tol;
+    T.fPrev = 2.0f * std::fabs(c->tmpInvProj[5]) / (float)f.height;
+    std::memcpy(T.viewPrev, c->tmpView, 64);
+    std::memcpy(T.projPrev, c->tmpProj, 64);
+    std::memcpy(T.camPrev, c->tmpCam, 12);
+    std::memcpy(T.invView, f.inv_view, 64);
+    std::memcpy(T.invProj, f.inv_proj, 64);
+    launch_temporal_accumulate(T, c->stream);
+    RZ_HIP(c, hipGetLastError());
+    if (filter || stats) {
+        TemporalVarLaunch V{};
+        V.col = T.colNext;
+        V.mom = T.momNext;
+        V.guide = G.guide;
+        V.dst = filter ? static_cast<float4*>(c->dDnPong.p) : nullptr;
+        V.stats = stats;
+        V.width = f.width; V.height = f.height;
+        V.sigmaNormal = P.sigma_normal;
+        V.planeScale = (float)(1.0 / ((double)P.sigma_plane * fpx));
+        launch_temporal_variance(V, c->stream);
+        RZ_HIP(c, hipGetLastError());
+    }
+    if (filter) {
+        TemporalFilterLaunch F{};
+        F.guide = G.guide;
+        F.materials = K.materials;
+        F.width = f.width; F.height = f.height;
+        F.sigmaL = P.sigma_l;
+        F.sigmaNormal = P.sigma_normal;
+        F.demodulate = P.demodulate;
+        float4* ping = static_cast<float4*>(c->dDnPing.p);
+        float4* pong = static_cast<float4*>(c->dDnPong.p);
+        for (int i = 0; i < P.iterations; ++i) {
+            const bool last = i == P.iterations - 1;
+            F.step = 1 << i;
+            F.planeScale = (float)(1.0 / ((double)P.sigma_plane * fpx * (double)(1 << i)));
+            F.src = (i % 2 == 1) ? ping : pong;         // pass 0 reads what the variance kernel wrote
+            F.dst = last ? out4 : ((i % 2 == 0) ? ping : pong);
+            F.rgb = last ? rgb : nullptr;
+            launch_temporal_pass(F, last, c->stream);
+            RZ_HIP(c, hipGetLastError());
+        }
+    }
+    if (!keep) {            // the set just written becomes the history
+        c->tmpCur = nxt;
+        c->tmpValid = true;
+        c->tmpW = f.width; c->tmpH = f.height; c->tmpInst = nInst;
+        std::memcpy(c->tmpView, f.view, 64);
+        std::memcpy(c->tmpProj, f.proj, 64);
+        std::memcpy(c->tmpInvProj, f.inv_proj, 64);
+        std::memcpy(c->tmpCam, f.cam_pos, 12);
+    }
+    return RZ_OK;
+}
+
+static int temporal_impl(rz_ctx* c, const rz_temporal_params* pp, const float* rgba_in, size_t rgba_in_bytes, float* rgb32f,
+                         size_t rgb32f_bytes, rz_hit* guides, size_t guides_bytes, float* stats, size_t stats_bytes, unsigned flags) {
+    const char* what = "rz_denoise_temporal";
+    if (!c) return fail(nullptr, RZ_ERR_INVALID_ARG, "%s: null context", what);
+    if (flags & ~(RZ_TEMPORAL_HOST | RZ_TEMPORAL_KEEP)) return fail(c, RZ_ERR_INVALID_ARG, "%s: unknown flags 0x%x", what, flags);
+    const rz_temporal_params& P = pp ? *pp : kTemporalDefaults;
+    int rc = temporal_check(c, what, P);
+    if (rc != RZ_OK) return rc;
+    const bool host = (flags & RZ_TEMPORAL_HOST) != 0;
+    if (!host && (((reinterpret_cast<uintptr_t>(rgba_in) | reinterpret_cast<uintptr_t>(guides)) & 15u) ||
+                  ((reinterpret_cast<uintptr_t>(rgb32f) | reinterpret_cast<uintptr_t>(stats)) & 3u)))
+        return fail(c, RZ_ERR_INVALID_ARG, "%s: device pointers must be 16-byte (rgba_in, guides) or 4-byte (rgb32f, stats) aligned", what);
+    const size_t np = (size_t)c->frame.width * c->frame.height;
+    const size_t bIn = np * 16, bRgb = np * 3 * sizeof(float), bHits = np * sizeof(rz_hit), bStats = np * 2 * sizeof(float);
+    if (rgba_in && rgba_in_bytes < bIn) return fail(c, RZ_ERR_BUFFER_SIZE, "%s: rgba_in needs %zu bytes, got %zu", what, bIn, rgba_in_bytes);
+    if (!rgba_in && c->extAccum && c->extAccumBytes < bIn)
+        return fail(c, RZ_ERR_BUFFER_SIZE, "%s: bound accumulation buffer holds %zu bytes, frame needs %zu", what, c->extAccumBytes, bIn);
+    if (rgb32f && rgb32f_bytes < bRgb) return fail(c, RZ_ERR_BUFFER_SIZE, "%s: rgb32f needs %zu bytes, got %zu", what, bRgb, rgb32f_bytes);
+    if (guides && guides_bytes < bHits) return fail(c, RZ_ERR_BUFFER_SIZE, "%s: guides needs %zu bytes, got %zu", what, bHits, guides_bytes);
+    if (stats && stats_bytes < bStats) return fail(c, RZ_ERR_BUFFER_SIZE, "%s: stats needs %zu bytes, got %zu", what, bStats, stats_bytes);
+    RZ_HIP(c, hipSetDevice(c->device));
+    const float4* in = rgba_in ? reinterpret_cast<const float4*>(rgba_in) : static_cast<const float4*>(rz_accum_device_ptr(c));
+    float* dRgb = rgb32f;
+    float* dStats = stats;
+    float4* dHits = reinterpret_cast<float4*>(guides);
+    // host buffers are staged as rz_denoise stages them: the input in dRayIn; hits, rgb32f, then stats in dRayOut
+    const size_t oRgb = guides ? (bHits + 15) & ~size_t(15) : 0;
+    const size_t oStats = oRgb + (rgb32f ? (bRgb + 15) & ~size_t(15) : 0);
+    if (host) {
+        if (rgba_in) {
+            rc = ensure(c, c->dRayIn, bIn);
+            if (rc != RZ_OK) return rc;
+            RZ_HIP(c, hipMemcpyAsync(c->dRayIn.p, rgba_in, bIn, hipMemcpyHostToDevice, c->stream));
+            in = static_cast<const float4*>(c->dRayIn.p);
+        }
+        rc = ensure(c, c->dRayOut, oStats + (stats ? bStats : 0));
+        if (rc != RZ_OK) return rc;
+        char* base = static_cast<char*>(c->dRayOut.p);
+        dHits = guides ? reinterpret_cast<float4*>(base) : nullptr;
+        dRgb = rgb32f ? reinterpret_cast<float*>(base + oRgb) : nullptr;
+        dStats = stats ? reinterpret_cast<float*>(base + oStats) : nullptr;
+    }
+    rc = temporal_run(c, P, in, dRgb, nullptr, dHits, dStats, (flags & RZ_TEMPORAL_KEEP) != 0);
+    if (rc != RZ_OK) return rc;
+    if (!host) return RZ_OK;
+    const char* base = static_cast<const char*>(c->dRayOut.p);
+    if (guides) RZ_HIP(c, hipMemcpyAsync(guides, base, bHits, hipMemcpyDeviceToHost, c->stream));
+    if (rgb32f) RZ_HIP(c, hipMemcpyAsync(rgb32f, base + oRgb, bRgb, hipMemcpyDeviceToHost, c->stream));
+    if (stats) RZ_HIP(c, hipMemcpyAsync(stats, base + oStats, bStats, hipMemcpyDeviceToHost, c->stream));
+    RZ_HIP(c, hipStreamSynchronize(c->stream));
+    return denoise_backstop(c, what);
+}
+
+static int present_temporal_impl(rz_ctx* c, const rz_present_params* pp, const rz_temporal_params* tp, uint8_t* rgba8,
+                                 size_t rgba8_bytes, float* rgb32f, size_t rgb32f_bytes) {
+    const char* what = "rz_present_temporal";
+    if (!c) return fail(nullptr, RZ_ERR_INVALID_ARG, "%s: null context", what);
+    if (!pp) return fail(c, RZ_ERR_INVALID_ARG, "%s: null present params", what);
+    const rz_temporal_params& P = tp ? *tp : kTemporalDefaults;
+    int rc = temporal_check(c, what, P);
+    if (rc != RZ_OK) return rc;
+    const size_t np = (size_t)c->frame.width * c->frame.height;
+    if (c->extAccum && c->extAccumBytes < np * 16)
+        return fail(c, RZ_ERR_BUFFER_SIZE, "%s: bound accumulation buffer holds %zu bytes, frame needs %zu", what, c->extAccumBytes, np * 16);
+    if (rgba8 && rgba8_bytes < np * 4) return fail(c, RZ_ERR_BUFFER_SIZE, "%s: rgba8 buffer needs %zu bytes", what, np * 4);
+    if (rgb32f && rgb32f_bytes < np * 12) return fail(c, RZ_ERR_BUFFER_SIZE, "%s: rgb32f buffer needs %zu bytes", what, np * 12);
+    RZ_HIP(c, hipSetDevice(c->device));
+    rc = ensure(c, c->dDnOut, np * 16);
+    if (rc != RZ_OK) return rc;
+    float4* out4 = static_cast<float4*>(c->dDnOut.p);
+    rc = temporal_run(c, P, static_cast<const float4*>(rz_accum_device_ptr(c)), nullptr, out4, nullptr, nullptr, false);
+    if (rc != RZ_OK) return rc;
+    rc = present_impl(c, pp, rgba8, rgba8_bytes, rgb32f, rgb32f_bytes, out4);
+    if (rc != RZ_OK) return rc;
+    return denoise_backstop(c, what);
+}
+
+static int debug_read_temporal_impl(rz_ctx* c, int which, void* out, size_t bytes, size_t* needed) {
+    if (!c) return fail(nullptr, RZ_ERR_INVALID_ARG, "null context");
+    if (which < 0 || which > 4) return fail(c, RZ_ERR_INVALID_ARG, "which = %d", which);
+    RZ_HIP(c, hipSetDevice(c->device));
+    const size_t np = c->tmpValid ? (size_t)c->tmpW * c->tmpH : 0;
+    const int cur = c->tmpCur;
+    float cam[51];
+    size_t have = 0;
+    const void* src = nullptr;
+    switch (which) {
+        case 0: have = np * 16; src = c->dTmpCol[cur].p; break;
+        case 1: have = np * 8; src = c->dTmpMom[cur].p; break;
+        case 2: have = np * sizeof(rz_hit); src = c->dTmpHits[cur].p; break;
+        case 3: have = c->tmpValid ? sizeof cam : 0; break;
+        default: have = c->tmpValid ? c->tmpInst * 96 : 0; src = c->dTmpInst[cur].p; break;
+    }
+    if (needed) *needed = have;
+    if (!out || have == 0) return RZ_OK;
+    if (bytes < have) return fail(c, RZ_ERR_BUFFER_SIZE, "rz_debug_read_temporal: %zu bytes held, buffer has %zu", have, bytes);
+    if (which == 3) {
+        std::memcpy(cam, c->tmpView, 64);
+        std::memcpy(cam + 16, c->tmpProj, 64);
+        std::memcpy(cam + 32, c->tmpInvProj, 64);
+        std::memcpy(cam + 48, c->tmpCam, 12);
+        std::memcpy(out, cam, sizeof cam);
+        return RZ_OK;
+    }
+    RZ_HIP(c, hipStreamSynchronize(c->stream));
+    RZ_HIP(c, hipMemcpy(out, src, have, hipMemcpyDeviceToHost));
+    return RZ_OK;
+}
+
 int rz_last_render_ms(rz_ctx* c, float* ms, int* launches) {
     if (!c) return fail(nullptr, RZ_ERR_INVALID_ARG, "null context");
     if (!c->timed) return fail(c, RZ_ERR_NOT_READY, "nothing rendered yet");
@@ -2274,6 +2538,26 @@ int rz_present_denoised(rz_ctx* c, const rz_present_params* present, const rz_de
     return guarded(c, "rz_present_denoised", [&] {
         return present_denoised_impl(c, present, params, rgba8, rgba8_bytes, rgb32f, rgb32f_bytes);
     });
+}
+int rz_denoise_temporal(rz_ctx* c, const rz_temporal_params* params, const float* rgba_in, size_t rgba_in_bytes, float* rgb32f,
+                        size_t rgb32f_bytes, rz_hit* guides, size_t guides_bytes, float* stats, size_t stats_bytes, unsigned flags) {
+    return guarded(c, "rz_denoise_temporal", [&] {
+        return temporal_impl(c, params, rgba_in, rgba_in_bytes, rgb32f, rgb32f_bytes, guides, guides_bytes, stats, stats_bytes, flags);
+    });
+}
+int rz_present_temporal(rz_ctx* c, const rz_present_params* present, const rz_temporal_params* params, uint8_t* rgba8,
+                        size_t rgba8_bytes, float* rgb32f, size_t rgb32f_bytes) {
+    return guarded(c, "rz_present_temporal", [&] {
+        return present_temporal_impl(c, present, params, rgba8, rgba8_bytes, rgb32f, rgb32f_bytes);
+    });
+}
+int rz_temporal_reset(rz_ctx* c) {
+    if (!c) return fail(nullptr, RZ_ERR_INVALID_ARG, "rz_temporal_reset: null context");
+    c->tmpValid = false;
+    return RZ_OK;
+}
+int rz_debug_read_temporal(rz_ctx* c, int which, void* out, size_t bytes, size_t* needed) {
+    return guarded(c, "rz_debug_read_temporal", [&] { return debug_read_temporal_impl(c, which, out, bytes, needed); });
 }
 int rz_debug_read_layout(rz_ctx* c, int which, void* out, size_t bytes, size_t* needed) {
     return guarded(c, "rz_debug_read_layout", [&]() -> int {

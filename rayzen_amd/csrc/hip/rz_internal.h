@@ -84,6 +84,59 @@ struct DenoiseLaunch {
 void launch_denoise_pass(const DenoiseLaunch& D, bool first, bool last, hipStream_t stream);
 void launch_denoise_resolve(const DenoiseLaunch& D, hipStream_t stream);
 
+// ---- rz_temporal.hip
+struct TemporalLaunch {         // rz_temporal_accumulate
+    const float4* accum;        // RGBA32F sum and count
+    const float4* hits;         // this frame's guide: width x height rz_hit (3 float4)
+    const DevMaterial* materials;
+    const DevInstance* instances;
+    const float4* colPrev;      // the history: colour | N
+    const float2* momPrev;      // ... the luminance moments
+    const float4* hitsPrev;     // ... the guide
+    const float* instPrev;      // ... per instance inverseTransform[12], transform[12] (DevInstance's packing)
+    const int* instSame;        // per instance: 1 = its transform is the stored one bit for bit
+    float4* colNext;            // the history this call writes
+    float2* momNext;
+    float4* dst;                // K = 0 only: (colour, 1), optional
+    float* rgb;                 // K = 0 only: width x height x 3, optional
+    int width, height;
+    int nMaterials;
+    int demodulate;
+    int havePrev;               // 0: no history, every pixel starts at N = 1
+    int cameraSame;             // view and proj equal the stored ones bit for bit
+    float alpha, alphaMoments, maxHistory, normalCos, planeTol;
+    float fPrev;                // 2 |inv_proj_prev[5]| / height
+    float viewPrev[16], projPrev[16], camPrev[3];
+    float invView[16], invProj[16];     // this frame's (the direction of a miss)
+};
+struct TemporalVarLaunch {      // rz_temporal_variance
+    const float4* col;          // colour | N, as the accumulate kernel left it
+    const float2* mom;
+    const float4* guide;        // DenoiseGuideLaunch::guide
+    float4* dst;                // colour | variance: the filter's input, optional
+    float* stats;               // width x height x 2 (N, variance), optional
+    int width, height;
+    float sigmaNormal;
+    float planeScale;           // 1 / (sigma_plane f)
+};
+struct TemporalFilterLaunch {   // rz_temporal_atrous
+    const float4* src;          // colour | variance
+    const float4* guide;
+    const DevMaterial* materials;
+    float4* dst;                // the pass's output (the last pass: (colour, 1)); may be null on the last pass
+    float* rgb;                 // the last pass: width x height x 3 floats, optional
+    int width, height;
+    int step;                   // s = 2^i
+    float sigmaL;
+    float sigmaNormal;
+    float planeScale;           // 1 / (sigma_plane f s)
+    int demodulate;
+};
+void launch_temporal_instances(const DevInstance* inst, const float* prev, float* next, int* same, int n, bool havePrev, hipStream_t stream);
+void launch_temporal_accumulate(const TemporalLaunch& T, hipStream_t stream);
+void launch_temporal_variance(const TemporalVarLaunch& V, hipStream_t stream);
+void launch_temporal_pass(const TemporalFilterLaunch& F, bool last, hipStream_t stream);
+
 // ---- rz_tlas_device.hip
 void launch_tlas_refit(const TlasWork& W, hipStream_t s);
 

@@ -9,6 +9,8 @@
 //   pick(mouseX, mouseY, scene)        <- main.cpp:501-552 (brute-force picking loop), one ray query instead
 //   renderEditor(scene, width, height) <- main.cpp:1210-1322 (renderRasterized + the editor shaders), a ray cast instead
 //   denoise() / presentDenoised()      <- new: the a-trous denoiser of the 1-spp frame (rz_denoise / rz_present_denoised)
+//   denoiseTemporal() / presentTemporal() / resetTemporal()
+//                                      <- new: temporal accumulation + the variance-guided filter (rz_denoise_temporal)
 // Unlike the reference's per-frame path, updateDynamicBVHAndSSBOs re-uploads
 // only what changed (instances + TLAS, a few KB), not all geometry.
 #pragma once
@@ -226,6 +228,23 @@ public:
         check(rz_present_denoised(ctx_, &present, params, out.data(), out.size(), nullptr, 0), "rz_present_denoised");
         return out;
     }
+    // Temporal accumulation by reprojection plus the variance-guided filter: blends the last frame set into the history the
+    // context keeps and returns the colour (width x height x 3 floats, row 0 = bottom, unclamped).  keep: leave the history
+    // as it was.  Call once per frame, after draw().
+    std::vector<float> denoiseTemporal(const rz_temporal_params* params = nullptr, bool keep = false) {
+        std::vector<float> out((size_t)width_ * (size_t)height_ * 3);
+        check(rz_denoise_temporal(ctx_, params, nullptr, 0, out.data(), out.size() * sizeof(float), nullptr, 0, nullptr, 0,
+                                  RZ_TEMPORAL_HOST | (keep ? RZ_TEMPORAL_KEEP : 0u)), "rz_denoise_temporal");
+        return out;
+    }
+    // rz_present with that colour: RGBA8 (width x height x 4, row 0 = bottom), overlays on top; advances the history.
+    std::vector<uint8_t> presentTemporal(const rz_present_params& present, const rz_temporal_params* params = nullptr) {
+        std::vector<uint8_t> out((size_t)width_ * (size_t)height_ * 4);
+        check(rz_present_temporal(ctx_, &present, params, out.data(), out.size(), nullptr, 0), "rz_present_temporal");
+        return out;
+    }
+    // Drops the history (a cut: the next frame starts every pixel anew).
+    void resetTemporal() { check(rz_temporal_reset(ctx_), "rz_temporal_reset"); }
     float lastRenderMs() { float ms = 0; int n = 0; check(rz_last_render_ms(ctx_, &ms, &n), "rz_last_render_ms"); return ms; }
     rz_ctx* context() { return ctx_; }
     const SceneBuffers& buffers() const { return buffers_; }

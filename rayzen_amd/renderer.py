@@ -456,6 +456,90 @@ class Renderer:
                                                 rgb.nbytes), "rz_present_denoised")
         return rgb, rgba8
 
+    # -- temporal accumulation (rz_denoise_temporal / rz_present_temporal) ---------
+    @staticmethod
+    def _temporal_params(kw):
+        # nothing given: the library's defaults (params NULL)
+        unknown = set(kw) - set(_lib.TEMPORAL_DEFAULTS)
+        if unknown:
+            raise TypeError(f"unknown temporal parameter(s): {sorted(unknown)}")
+        if all(v is None for v in kw.values()):
+            return None
+        p = _lib.TemporalParams()
+        for name, default in _lib.TEMPORAL_DEFAULTS.items():
+            v = kw.get(name)
+            v = default if v is None else v
+            setattr(p, name, int(v) if isinstance(default, int) else float(v))
+        return C.byref(p)
+
+    def denoise_temporal(self, rgba_in=None, guides=False, stats=False, keep=False, **params):
+        """Temporal accumulation by reprojection plus the variance-guided a-trous filter (include/rayzen_hip.h:
+        rz_denoise_temporal) on the accumulation, or on rgba_in ((H, W, 4) float32, sum and count), for the size and camera of the
+        last set_frame (host memory; returns when done).  Every call blends the frame into the history the context keeps; keep=True
+        computes the outputs and leaves the history as it was.  Returns the colour (H, W, 3) float32, then -- where asked -- the
+        guide as (H, W) HIT_DTYPE and the stats (H, W, 2) float32 (history length N, variance); row 0 = bottom row.
+        params: alpha, alpha_moments, max_history, normal_cos, plane_tol, iterations, sigma_l, sigma_normal, sigma_plane,
+        demodulate (those left out take the library's defaults)."""
+        tp = self._temporal_params(params)
+        src = None if rgba_in is None else np.ascontiguousarray(rgba_in, np.float32)
+        rgb = np.empty((self.height, self.width, 3), np.float32)
+        hh = np.empty((self.height, self.width), HIT_DTYPE) if guides else None
+        st = np.empty((self.height, self.width, 2), np.float32) if stats else None
+        flags = _lib.TEMPORAL_HOST | (_lib.TEMPORAL_KEEP if keep else 0)
+        self._check(self._L.rz_denoise_temporal(self._c, tp, None if src is None else src.ctypes.data, 0 if src is None else src.nbytes,
+                                                rgb.ctypes.data, rgb.nbytes, None if hh is None else hh.ctypes.data,
+                                                0 if hh is None else hh.nbytes, None if st is None else st.ctypes.data,
+                                                0 if st is None else st.nbytes, flags), "rz_denoise_temporal")
+        out = (rgb,) + ((hh,) if guides else ()) + ((st,) if stats else ())
+        return out if len(out) > 1 else rgb
+
+    def denoise_temporal_device(self, rgb32f_ptr=None, guides_ptr=None, stats_ptr=None, rgba_in_ptr=None, keep=False, **params):
+        """rz_denoise_temporal on device memory (rgba_in and guides 16-B aligned, rgb32f and stats 4-B; each optional): enqueued
+        on the context's stream, asynchronous.  Sizes: rgba_in W*H*16 B, rgb32f W*H*12 B, guides W*H*48 B, stats W*H*8 B."""
+        tp = self._temporal_params(params)
+        n = self.width * self.height
+        self._check(self._L.rz_denoise_temporal(self._c, tp, C.c_void_p(rgba_in_ptr), n * 16 if rgba_in_ptr else 0,
+                                                C.c_void_p(rgb32f_ptr), n * 12 if rgb32f_ptr else 0, C.c_void_p(guides_ptr),
+                                                n * 48 if guides_ptr else 0, C.c_void_p(stats_ptr), n * 8 if stats_ptr else 0,
+                                                _lib.TEMPORAL_KEEP if keep else 0), "rz_denoise_temporal")
+
+    def present_temporal(self, fps=0.0, show_fps=True, show_lights=False, show_bvh=False, bvh_mode=0, selected_blas=0,
+                         selected_tri=0, **params):
+        """present() with the temporally accumulated, filtered colour in place of the resolve (the history advances): the
+        overlays are drawn on top.  Returns (rgb float32 (H,W,3), rgba8 uint8 (H,W,4))."""
+        p = _lib.PresentParams(float(fps), int(bool(show_fps)), int(bool(show_lights)), int(bool(show_bvh)),
+                               int(bvh_mode), int(selected_blas), int(selected_tri))
+        tp = self._temporal_params(params)
+        rgb = np.empty((self.height, self.width, 3), np.float32)
+        rgba8 = np.empty((self.height, self.width, 4), np.uint8)
+        self._check(self._L.rz_present_temporal(self._c, C.byref(p), tp, rgba8.ctypes.data, rgba8.nbytes, rgb.ctypes.data,
+                                                rgb.nbytes), "rz_present_temporal")
+        return rgb, rgba8
+
+    def temporal_reset(self):
+        """Drops the history: the next temporal call starts every pixel at N = 1."""
+        self._check(self._L.rz_temporal_reset(self._c), "rz_temporal_reset")
+
+    def debug_read_temporal(self, which):
+        """Test hook: the stored history (0: colour | N float32 (H, W, 4); 1: moments (H, W, 2); 2: the guide, HIT_DTYPE (H, W);
+        3: view, proj, inv_proj, cam_pos as 51 floats; 4: per instance inverseTransform and transform, (n, 2, 4, 3) -- columns
+        0..3, rows 0..2).  An empty history: None."""
+        need = C.c_size_t(0)
+        self._check(self._L.rz_debug_read_temporal(self._c, int(which), None, 0, C.byref(need)), "rz_debug_read_temporal")
+        if need.value == 0:
+            return None
+        raw = np.zeros(need.value, np.uint8)
+        self._check(self._L.rz_debug_read_temporal(self._c, int(which), raw.ctypes.data, raw.nbytes, C.byref(need)),
+                    "rz_debug_read_temporal")
+        if which == 2:
+            return raw.view(HIT_DTYPE).reshape(self.height, self.width)
+        f = raw.view(np.float32)
+        if which == 0:
+            return f.reshape(self.height, self.width, 4)
+        if which == 1:
+            return f.reshape(self.height, self.width, 2)
+        return f.reshape(-1, 2, 4, 3) if which == 4 else f
+
     # -- convenience -----------------------------------------------------------
     def render_scene(self, scene, width, height, spp, bounce_budget, num_lights=None, tile_rank=0, tile_nranks=1,
                      chunk=None):
