@@ -229,11 +229,14 @@ int rz_build_geometry(rz_ctx* ctx, const rz_triangle* triangles, size_t n_triang
  *   - a leaf's box is computeBounds (RayZen/src/BVH.cpp:11-19) over its own slots: start at (+FLT_MAX, -FLT_MAX), slots in
  *     order, bmin = glm::min(bmin, glm::min(v0, glm::min(v1, v2))), bmax likewise with glm::max, where
  *     glm::min(a, b) = (b < a) ? b : a and glm::max(a, b) = (a < b) ? b : a;
- *   - an internal node's box is glm::min(left.min, right.min), glm::max(left.max, right.max);
+ *   - an internal node's box is glm::min(left.min, right.min), glm::max(left.max, right.max), except that a bound which
+ *     compares equal to the one the node holds keeps the node's bits.  Only the sign of a zero can differ: BVH::buildBLAS
+ *     folds a node's box over its triangles in the order they had before the node's range was sorted for its children
+ *     (BVH.cpp:112, 131-133), which the children's union cannot reproduce;
  *   - a leaf with count == 0 (the root of an empty mesh) is left as it is.
- * This fixes every bit, signs of zero and NaN planes included; BVH::refit / rzh_refit_blas (librayzen_host.so) state the
+ * This fixes every bit given the nodes in place, signs of zero and NaN planes included; BVH::refit / rzh_refit_blas (librayzen_host.so) state the
  * same on the host and the device result is held to their bytes.  A refit of an unmodified mesh reproduces the builder's
- * nodes.
+ * nodes, RayZen's own included (tests/test_cppref_gpu.py).
  *
  * Everything derived follows on the device, in place, without the re-layout and without a sort: the device copies of
  * the triangles and nodes, the leaf-ordered triangles and their normals, the child boxes of the traversal's node pairs,

@@ -14,9 +14,12 @@
  * budget with math flavour 1 (llvmpipe's three built-ins replayed bit for bit:
  * the default, and the product's), to rounding wherever no random number is
  * drawn with flavour 0 (rounds 1-4's binary64 built-ins).
- * Its HOST half (rz_oracle_bvh.c) stays UNPINNED beyond the node counts the
- * survey recorded: BVH.cpp / Mesh.cpp / main.cpp need GLM (and GLFW / GLEW),
- * neither vendored nor installed, and a stand-in is not allowed.  DESIGN.md 2.
+ * Its HOST half (rz_oracle_bvh.c): the BLAS / TLAS builders and the OBJ reader
+ * are PINNED against RayZen's own BVH.cpp / Mesh.cpp, compiled as they stand
+ * against a stand-in for the GLM operations they use (oracle/cppref,
+ * tests/test_cppref.py, tests/golden/cppref_*.npz).  UNPINNED: GLM's own
+ * arithmetic (the stand-in's) and main.cpp's flatten / glm::inverse, which need
+ * GLFW / GLEW / GLM, neither vendored nor installed.  DESIGN.md 2.
  *
  * Plain C restatement of
  *   RayZen/shaders/fragment_shader.glsl ("FS") :188-212, 380-567, 569-663, 668-773

@@ -20,6 +20,7 @@
 #include "rz_oracle.h"
 
 #include <float.h>
+#include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -288,6 +289,39 @@ void rzo_mat4_inverse(const float m[16], float out[16]) {
 #undef E
 }
 
+/* One `iss >> float` of Mesh.cpp:20 as libstdc++ performs it in the "C" locale: skip white space; gather [+-] digits [. digits]
+ * [e|E [+-] digits] (an exponent letter only after a digit; leading zeros collapse to one) and no other character -- `nan`, `inf`
+ * and hexadecimal are not numbers to it; strtof the run: not wholly consumed -> 0 and fail; +-HUGE_VALF -> +-FLT_MAX and fail;
+ * underflow is no failure.  At the end of the line: fail, nothing stored.  Returns 0 once the stream has failed. */
+static int istream_float(const char** pp, float* value) {
+    const char* p = *pp;
+    while (*p == ' ' || (*p >= '\t' && *p <= '\r')) ++p;
+    if (!*p) { *pp = p; return 0; }
+    char* run = (char*)malloc(strlen(p) + 2);
+    size_t n = 0;
+    int mantissa = 0, point = 0, exponent = 0;
+    if (*p == '+' || *p == '-') run[n++] = *p++;
+    while (*p == '0') { if (!mantissa) { run[n++] = '0'; mantissa = 1; } ++p; }
+    for (;;) {
+        if (*p >= '0' && *p <= '9') { run[n++] = *p++; mantissa = 1; }
+        else if (*p == '.' && !point && !exponent) { run[n++] = *p++; point = 1; }
+        else if ((*p == 'e' || *p == 'E') && !exponent && mantissa) {
+            run[n++] = 'e'; ++p; exponent = 1;
+            if (*p == '+' || *p == '-') run[n++] = *p++;
+        } else break;
+    }
+    run[n] = 0;
+    char* end = NULL;
+    float f = strtof(run, &end);
+    int ok = 1;
+    if (end == run || *end != 0) { f = 0.0f; ok = 0; }
+    else if (f == HUGE_VALF) { f = FLT_MAX; ok = 0; }
+    else if (f == -HUGE_VALF) { f = -FLT_MAX; ok = 0; }
+    free(run);
+    *value = f; *pp = p;
+    return ok;
+}
+
 /* Mesh.cpp:6-50: "v " and "f " lines only; face tokens split at the first '/';
  * 1-based indices; polygons fan-triangulated around the first vertex. */
 int rzo_load_obj(const char* path, int materialIndex, rzo_triangle* out, int cap) {
@@ -300,13 +334,14 @@ int rzo_load_obj(const char* path, int materialIndex, rzo_triangle* out, int cap
     while (getline(&line, &lcap, f) >= 0) {
         if (line[0] == 'v' && line[1] == ' ') {
             float x = 0, y = 0, z = 0;
-            sscanf(line + 2, "%f %f %f", &x, &y, &z);
+            const char* p = line + 2;
+            if (istream_float(&p, &x) && istream_float(&p, &y)) istream_float(&p, &z);
             if (nv == vcap) { vcap *= 2; verts = (float*)realloc(verts, vcap * 3 * sizeof(float)); }
             verts[3 * nv] = x; verts[3 * nv + 1] = y; verts[3 * nv + 2] = z; ++nv;
         } else if (line[0] == 'f' && line[1] == ' ') {
             unsigned int vi[256]; int nvi = 0;
             char* save = NULL;
-            for (char* tok = strtok_r(line + 2, " \t\r\n", &save); tok && nvi < 256; tok = strtok_r(NULL, " \t\r\n", &save)) {
+            for (char* tok = strtok_r(line + 2, " \t\r\n\v\f", &save); tok && nvi < 256; tok = strtok_r(NULL, " \t\r\n\v\f", &save)) {
                 char* slash = strchr(tok, '/');
                 if (slash) *slash = 0;
                 vi[nvi++] = (unsigned int)atoi(tok);

@@ -3,7 +3,8 @@
 TEST INFRASTRUCTURE ONLY: importable from tests/, __graft_entry__.smoke() and
 bench.py's cpu_baseline leg.  The product package (rayzen_amd/) never imports
 this module.  Pinned against RayZen's own shader run on Mesa llvmpipe (oracle/glref, tests/test_glref.py);
-the host half (BVH / OBJ / flatten) is unpinned beyond node counts -- see oracle/rz_oracle.h.
+the BLAS / TLAS builders and the OBJ reader against RayZen's own BVH.cpp / Mesh.cpp (oracle/cppref, tests/test_cppref.py);
+main.cpp's flatten stays unpinned -- see oracle/rz_oracle.h.
 """
 import ctypes as C
 import os

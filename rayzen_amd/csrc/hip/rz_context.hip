@@ -1302,7 +1302,11 @@ static bool host_refit_mesh(rz_ctx* c, rz_bvh_node* nodes, long long nNodes, con
         } else if (N.count < 0) {
             const rz_bvh_node& A = nodes[nodeOff + N.leftFirst];
             const rz_bvh_node& B = nodes[nodeOff + N.leftFirst + 1];
-            for (int a = 0; a < 3; ++a) { N.boundsMin[a] = gmin(A.boundsMin[a], B.boundsMin[a]); N.boundsMax[a] = gmax(A.boundsMax[a], B.boundsMax[a]); }
+            for (int a = 0; a < 3; ++a) {       // a bound equal to the one held keeps its bits (rz_refit.hip: keep_equal)
+                const float mn = gmin(A.boundsMin[a], B.boundsMin[a]), mx = gmax(A.boundsMax[a], B.boundsMax[a]);
+                if (!(mn == N.boundsMin[a])) N.boundsMin[a] = mn;
+                if (!(mx == N.boundsMax[a])) N.boundsMax[a] = mx;
+            }
         }
     }
     return true;

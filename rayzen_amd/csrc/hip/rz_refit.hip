@@ -13,7 +13,7 @@
 //   * rz_refit_level, deepest level first, one launch per level (a kernel boundary is the only hand-off between levels:
 //     no data crosses workgroups inside a launch): a leaf child's box from its triangles (computeBounds), an internal
 //     child's box as the previous launch left it in the node array; both go into the DevPair, their glm::min / glm::max
-//     into the node's own 32-byte record, the "irregular child box" bit is or-ed as rl_write does;
+//     into the node's own 32-byte record (a bound equal to the one held keeps its bits), the "irregular child box" bit is or-ed as rl_write does;
 //   * rz_refit_roots: every instance's root box (and its "may hold glass" flag) from its view, and the views' root
 //     nodes gathered for the host; rz_tlas_refit (rz_tlas_device.hip) then rebuilds world boxes and TLAS as it is.
 // Every index these kernels use was range-checked when the view was laid out, and the topology has not changed since.
@@ -29,6 +29,11 @@ namespace {
 
 __device__ inline float gmin(float a, float b) { return (b < a) ? b : a; }   // glm::min
 __device__ inline float gmax(float a, float b) { return (a < b) ? b : a; }   // glm::max
+// An internal node's refitted bound: the union's, unless it compares equal to the bound the node holds -- then the node's own
+// bits stay.  Only the sign of a zero can differ.  BVH::buildBLAS folds a node's box over its triangles in the order they had
+// BEFORE the node's range was sorted for its children (BVH.cpp:112, 131-133), an order a refit cannot know; the union of the
+// children keeps the first zero of the FINAL order.  With this rule a refit of unmoved vertices is the identity.
+__device__ inline float keep_equal(float held, float fresh) { return (fresh == held) ? held : fresh; }
 
 struct Box { float mn[3], mx[3]; };
 
@@ -127,8 +132,15 @@ __global__ __launch_bounds__(256) void rz_refit_level(rz_bvh_node* __restrict__ 
         P[2] = make_float4(b[1].mn[1], b[1].mx[1], b[1].mn[2], b[1].mx[2]);
         irregular = !(b[0].mn[0] <= b[0].mx[0] && b[0].mn[1] <= b[0].mx[1] && b[0].mn[2] <= b[0].mx[2] &&
                       b[1].mn[0] <= b[1].mx[0] && b[1].mn[1] <= b[1].mx[1] && b[1].mn[2] <= b[1].mx[2]);
+        // a bound that compares equal to the one the node holds keeps the node's bits (the sign of a zero: keep_equal)
+        const float4* Pn = reinterpret_cast<const float4*>(nodes + n);
+        const float4 olo = Pn[0], ohi = Pn[1];
+        const float omn[3] = {olo.x, olo.y, olo.z}, omx[3] = {ohi.x, ohi.y, ohi.z};
         Box u;
-        for (int a = 0; a < 3; ++a) { u.mn[a] = gmin(b[0].mn[a], b[1].mn[a]); u.mx[a] = gmax(b[0].mx[a], b[1].mx[a]); }
+        for (int a = 0; a < 3; ++a) {
+            u.mn[a] = keep_equal(omn[a], gmin(b[0].mn[a], b[1].mn[a]));
+            u.mx[a] = keep_equal(omx[a], gmax(b[0].mx[a], b[1].mx[a]));
+        }
         store_node(nodes + n, u, L, own);
     }
     or_flag(vflags, irregular, 2u);

@@ -248,8 +248,14 @@ void BVH::refit(const Triangle* tris, BVHNode* nodes, int nNodes, const int* idx
         } else if (N.count < 0) {
             const BVHNode& L = nodes[N.leftFirst];
             const BVHNode& R = nodes[N.leftFirst + 1];
-            N.boundsMin = vmin(L.boundsMin, R.boundsMin);
-            N.boundsMax = vmax(L.boundsMax, R.boundsMax);
+            // A bound that compares equal to the one the node holds keeps the node's bits (only the sign of a zero can
+            // differ): buildBLAS folded this box over the triangles in the order they had before the range was sorted for
+            // the children, which the union of the children cannot reproduce.  A refit of unmoved vertices is the identity.
+            const vec3 mn = vmin(L.boundsMin, R.boundsMin), mx = vmax(L.boundsMax, R.boundsMax);
+            for (int a = 0; a < 3; ++a) {
+                if (!(mn[a] == N.boundsMin[a])) N.boundsMin[a] = mn[a];
+                if (!(mx[a] == N.boundsMax[a])) N.boundsMax[a] = mx[a];
+            }
         }
     }
 }

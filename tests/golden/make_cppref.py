@@ -1,0 +1,92 @@
+"""Writes tests/golden/cppref_*.npz: what RayZen's own BVH.cpp and Mesh.cpp (compiled by oracle/cppref) compute for the
+inputs of tests/cppref_cases.py.  Needs the reference checkout (oracle/cppref/README.md); run from the repository root:
+
+    python tests/golden/make_cppref.py [--skip-slow]
+
+Files: cppref_suite / cppref_adversarial / cppref_sizes (BLAS: input, nodes, indices, count of axis == -1 reads), cppref_large
+(digests of the big blobs), cppref_tlas (root boxes, nodes, indices), cppref_obj (texts, the reader's output, which components
+may be asserted).  Each file stays under 1 MB.  --skip-slow keeps the 1 M-triangle entry of an existing cppref_large.npz.
+"""
+import os
+import sys
+import time
+
+import numpy as np
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path[:0] = [os.path.dirname(os.path.dirname(HERE)), os.path.dirname(HERE)]
+
+import cppref_cases as K                                  # noqa: E402
+from oracle.cppref import cppref                          # noqa: E402
+from rayzen_amd import scene as S                         # noqa: E402
+
+
+def save(group, arrays):
+    path = K.fixture(group)
+    np.savez_compressed(path, **arrays)
+    size = os.path.getsize(path)
+    print(f"{os.path.basename(path)}: {len(arrays)} arrays, {size} bytes")
+    assert size < 1000000, "fixture over 1 MB: move cases to the digest file"
+    return size
+
+
+def main():
+    assert cppref.available(), "the reference's sources are not here"
+    cppref.build()
+    total = 0
+    for group, make in K.BLAS_GROUPS.items():
+        out, flagged = {}, []
+        for name, ctor in make():
+            tris = np.ascontiguousarray(ctor())
+            assert np.isfinite(np.stack([tris["v0"], tris["v1"], tris["v2"]])).all(), name
+            nodes, idx, oob = cppref.build_blas(tris, want_axis_minus_one=True)
+            out[f"{name}__tris"] = tris.view(np.uint8)
+            out[f"{name}__nodes"] = nodes.view(np.uint8)
+            out[f"{name}__idx"] = idx
+            out[f"{name}__oob"] = np.int64(oob)
+            if oob:
+                flagged.append(name)
+        print(f"{group}: {len(out) // 4} cases; axis == -1 reached in {len(flagged)}: {' '.join(flagged)}")
+        total += save(group, out)
+
+    large = {}
+    old = K.load_large() if os.path.exists(K.fixture("large")) else {}
+    for name, ctor, slow in K.LARGE:
+        if slow and "--skip-slow" in sys.argv and f"{name}__digest" in old:
+            large[f"{name}__digest"], large[f"{name}__seconds"] = old[f"{name}__digest"], old[f"{name}__seconds"]
+            continue
+        tris = ctor()
+        t = time.perf_counter()
+        nodes, idx = cppref.build_blas(tris)
+        dt = time.perf_counter() - t
+        large[f"{name}__digest"] = np.array([K.sha(tris), K.sha(nodes), K.sha(idx), str(len(tris)), str(len(nodes)),
+                                             str(K.depth_of(nodes))])
+        large[f"{name}__seconds"] = np.float64(dt)
+        print(f"large {name}: {len(tris)} triangles, {len(nodes)} nodes, reference build {dt:.2f} s")
+    total += save("large", large)
+
+    tlas = {}
+    for name, ctor in K.tlas_cases():
+        roots = np.ascontiguousarray(ctor())
+        nodes, idx = cppref.build_tlas(roots)
+        tlas[f"{name}__roots"], tlas[f"{name}__nodes"], tlas[f"{name}__idx"] = roots.view(np.uint8), nodes.view(np.uint8), idx
+    total += save("tlas", tlas)
+
+    obj = {}
+    for mesh in K.OBJ_MESHES:
+        t = cppref.load_obj(os.path.join(K.MESHES, mesh), 1)
+        obj[f"mesh__{mesh}__sha"] = np.array([K.sha(t), str(len(t))])     # pads and tail zero: the defined bytes only
+    for name, (text, asserted) in K.obj_texts().items():
+        t = cppref.load_obj_text(text, 2)
+        mask = K.obj_asserted_mask(text, asserted)
+        assert mask.shape[0] == len(t), (name, mask.shape, len(t))
+        obj[f"text__{name}__bytes"] = np.frombuffer(text, np.uint8)
+        obj[f"text__{name}__tris"] = t.view(np.uint8)
+        obj[f"text__{name}__mask"] = mask
+    total += save("obj", obj)
+    print(f"total {total} bytes")
+    assert total < 3000000
+
+
+if __name__ == "__main__":
+    main()

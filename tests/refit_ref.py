@@ -4,7 +4,9 @@
 A refit keeps every leftFirst, count and the index array, and recomputes only the boxes:
   * a leaf (count > 0): computeBounds (RayZen/src/BVH.cpp:11-19) over its own slots, in order, from +-FLT_MAX:
     bmin = glm::min(bmin, glm::min(v0, glm::min(v1, v2))), bmax likewise;
-  * an internal node: glm::min(left.min, right.min), glm::max(left.max, right.max);
+  * an internal node: glm::min(left.min, right.min), glm::max(left.max, right.max) -- except that a bound which compares
+    equal to the one the node holds keeps the node's bits (the sign of a zero: the builder folded the node's box in an order
+    a refit cannot know, so only this makes a refit of unmoved vertices the identity on RayZen's own nodes);
   * a leaf with count == 0 is left as it is.
 glm::min(a, b) = (b < a) ? b : a and glm::max(a, b) = (a < b) ? b : a -- NOT numpy's minimum / maximum, which differ on NaN
 and on the sign of a zero."""
@@ -58,8 +60,9 @@ def refit(tris, nodes, idx):
         inner = np.nonzero((depth == d) & (count < 0))[0]
         if inner.size:
             a, b = left[inner], left[inner] + 1
-            bmin[inner] = gmin(bmin[a], bmin[b])
-            bmax[inner] = gmax(bmax[a], bmax[b])
+            mn, mx = gmin(bmin[a], bmin[b]), gmax(bmax[a], bmax[b])
+            bmin[inner] = np.where(mn == bmin[inner], bmin[inner], mn)        # equal to what the node holds: its bits stay
+            bmax[inner] = np.where(mx == bmax[inner], bmax[inner], mx)
     return out
 
 

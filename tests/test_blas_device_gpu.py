@@ -1,5 +1,6 @@
 """rz_build_blas (device) vs BVH::buildBLAS as restated by the oracle (oracle/rz_oracle_bvh.c, literal O(N log^2 N)
-sort-per-node version of RayZen/src/BVH.cpp:22-175) and by the host library: nodes and indices byte for byte."""
+sort-per-node version of RayZen/src/BVH.cpp:22-175) and by the host library: nodes and indices byte for byte.  The same meshes
+are held against the output of RayZen's own BVH.cpp (compiled by oracle/cppref) in tests/test_cppref_gpu.py."""
 import numpy as np
 import pytest
 

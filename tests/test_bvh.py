@@ -1,6 +1,7 @@
 """Host BVH builders (product, O(N log N)) against the oracle's literal restatement of RayZen/src/BVH.cpp
 (O(N log^2 N)): byte-identical node and index arrays; plus the node counts the survey measured by running
-the reference's own BVH.cpp and structural invariants."""
+the reference's own BVH.cpp and structural invariants.  The same inputs are held against a build of
+RayZen's own BVH.cpp / Mesh.cpp in tests/test_cppref.py (oracle/cppref): both sides of the comparisons below equal it."""
 import os
 
 import numpy as np
