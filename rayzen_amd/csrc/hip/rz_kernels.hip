@@ -339,9 +339,14 @@ __device__ __forceinline__ void render_samples_group(const KParams& K, const uns
                 // the wave's rays have spread once every running lane is on its third or a later segment (rz_trace.h: trace_spread)
                 const bool spread = RZ_SPREAD_ON(K) && rz_ballot(P.mode != MODE_DONE && !(P.mode == MODE_SEGMENT && P.bounce >= 2)) == 0ull;
                 if (P.mode != MODE_DONE) {
-                    RZ_SITE(c, 6);
                     HitRec h;
-                    const bool found = spread ? trace_spread<COUNT, OVF>(K, P.o, P.d, h, bstk, c) : trace_closest<COUNT, OVF>(K, P.o, P.d, h, bstk, c);
+                    bool found = false;
+                    // (the shadow ray of a light behind the surface is not traced -- rz_path.h, RZ_BACKFACE_SKIP; a wave is a few
+                    //  pixels' samples with near-identical hit points, so this is mostly one scalar branch around the whole query)
+                    if (!shadow_candidate<COUNT, false>(P)) {
+                        RZ_SITE(c, 6);
+                        found = spread ? trace_spread<COUNT, OVF>(K, P.o, P.d, h, bstk, c) : trace_closest<COUNT, OVF>(K, P.o, P.d, h, bstk, c);
+                    }
 #ifdef RZ_PROF
                     t2 = __builtin_amdgcn_s_memtime();
 #endif
@@ -874,11 +879,15 @@ __device__ __forceinline__ void render_claim_compact(const KParams& K, const Cla
             while (anyRun) {
                 if (run) {
                     HitRec h;
+                    bool found = false;
 #ifdef RZ_PROF
-                    RZ_SITE(c, 6);
                     const unsigned long long tq0_ = __builtin_amdgcn_s_memtime();
 #endif
-                    const bool found = trace_closest<COUNT, OVF>(K, P.o, P.d, h, bstk, tu);
+                    // (not for the shadow ray of a light behind the surface: rz_path.h, RZ_BACKFACE_SKIP)
+                    if (!shadow_candidate<COUNT, GLASS>(P)) {
+                        RZ_SITE(c, 6);
+                        found = trace_closest<COUNT, OVF>(K, P.o, P.d, h, bstk, tu);
+                    }
 #ifdef RZ_PROF
                     c.rt[c.rnd & 7] += __builtin_amdgcn_s_memtime() - tq0_;
 #endif

@@ -164,6 +164,41 @@ __device__ __forceinline__ v3 random_hemisphere_direction(const KParams& K, v3 n
     return hemisphere_world(normal, dir);
 }
 
+// RZ_BACKFACE_SKIP (round 6, profiles/r06_backface/): the shader traces the shadow ray of a light before it looks at NdotL
+// (FS:622-659).  For an opaque surface that faces away from the light NdotL = max(dot(n, l), 0) is 0, the whole term is zeros,
+// and a lit light and an occluded one leave finalColor with the same bits: the query -- a ray that starts inside the densest
+// part of the BVH and crosses the whole mesh -- is work the image does not need.  The rule is a GUARD, not an argument about
+// the BRDF, so that it holds bit for bit for NaN and -0 too:
+//   start_light  marks a lane whose dot(hn, dir) > 0 is false as a CANDIDATE (P.iter = -1: the field is free there);
+//   the loops    do not trace for a candidate (shadow_candidate) and hand advance found = false;
+//   advance      takes the candidate to "lit, vis = 1" through the one shade_light site and compares lacc's three words with
+//                what they were.  Equal: lit and occluded agree (an opaque kernel never multiplies vis, so lit means vis == 1.0f
+//                exactly) and the light is done.  Not equal (NaN terms of roughness 0, lacc = -0 of an albedo of -0, ...): lacc is
+//                put back, P.iter = 0, the mode stays, and the next trip traces the query as before.
+// Opaque instantiations only (GLASS == false; rz_render_pixels is compiled with GLASS == true and keeps tracing), and not the
+// counting ones: their tallies are the reference algorithm's.  (The RZ_PROF diagnostic build has counted frames skip too, so
+// that its per-round lines show what the product's kernel does; its tallies are then not the oracle's.)
+// RZ_BACKFACE_CHAIN 1: a path whose next light is a candidate deals with it inside the same advance call (a bounded loop over
+// P.li) instead of coming back for a trip of its own -- measured in profiles/r06_backface/, see there for the default.
+#ifndef RZ_BACKFACE_SKIP
+#define RZ_BACKFACE_SKIP 1
+#endif
+#ifndef RZ_BACKFACE_CHAIN
+#define RZ_BACKFACE_CHAIN 0
+#endif
+#ifdef RZ_PROF
+#define RZ_BACKFACE_COUNTED 1
+#else
+#define RZ_BACKFACE_COUNTED 0
+#endif
+template <bool COUNT, bool GLASS>
+constexpr bool backface_skip = RZ_BACKFACE_SKIP && !GLASS && (!COUNT || RZ_BACKFACE_COUNTED);
+// The path's pending query is the shadow ray of a light behind its surface: the caller does not trace it (found = false).
+template <bool COUNT, bool GLASS>
+__device__ __forceinline__ bool shadow_candidate(const Path& P) {
+    return backface_skip<COUNT, GLASS> && P.mode == MODE_SHADOW && P.iter < 0;
+}
+
 // Set up the shadow query of light P.li for the parked surface point
 // (FS:578-588 transparent branch, FS:622-635 opaque branch).
 // GLASS = false: the caller guarantees that no triangle of the scene uses a transparent material, so every
@@ -189,6 +224,9 @@ __device__ __forceinline__ void start_light(const KParams& K, Path& P, Tally& c)
     P.vis = 1.0f;
     P.traveled = 0.0f;
     P.iter = 0;
+    if constexpr (backface_skip<COUNT, GLASS>) {
+        if (!(dot(P.hn, dir) > 0.0f)) P.iter = -1;     // a candidate (RZ_BACKFACE_SKIP above): NaN is one too, the guard in advance decides
+    }
     P.mode = MODE_SHADOW;
     RZ_T1(c, 5);
 }
@@ -438,27 +476,50 @@ __device__ __forceinline__ void advance(const KParams& K, Path& P, bool found, c
         return;
     }
     // MODE_SHADOW: the body of one iteration of FS:511-526
-    bool done = false, lit = false;
-    if (!found) { done = true; lit = true; }
-    else if (h.t < 0.001f) { P.o = P.o + P.d * 0.001f; }
-    else {
-        P.traveled += h.t;
-        if (P.traveled >= P.maxDist) { done = true; lit = true; }
+    constexpr bool BFS = backface_skip<COUNT, GLASS>;
+    // a candidate of RZ_BACKFACE_SKIP: its query was not traced (the caller passed found = false, h is not read)
+    bool cand = BFS && P.iter < 0;
+#pragma nounroll
+    for (;;) {      // (one trip, but for RZ_BACKFACE_CHAIN: there one per light dealt with in this call, at most nLights)
+        bool done = false, lit = false;
+        if (cand || !found) { done = true; lit = true; }
+        else if (h.t < 0.001f) { P.o = P.o + P.d * 0.001f; }
         else {
-            if (COUNT) c.materials += 1;
-            const float tr = K.materials[h.mat].transparency;
-            if (GLASS && tr > 0.0f) { P.vis *= tr; P.o = h.p + P.d * 0.001f; }
-            else { P.vis = 0.0f; done = true; lit = false; }
+            P.traveled += h.t;
+            if (P.traveled >= P.maxDist) { done = true; lit = true; }
+            else {
+                if (COUNT) c.materials += 1;
+                const float tr = K.materials[h.mat].transparency;
+                if (GLASS && tr > 0.0f) { P.vis *= tr; P.o = h.p + P.d * 0.001f; }
+                else { P.vis = 0.0f; done = true; lit = false; }
+            }
         }
+        if (!done) {
+            P.iter += 1;
+            if (P.iter < 32 && P.vis > 0.05f) return;   // next iteration: trace again
+            lit = P.vis > 0.05f;                         // FS:527
+        }
+        const v3 lacc0 = P.lacc;
+        if (lit) { RZ_T0(); if (COUNT && !cand) c.lit_lights += 1; shade_light<GLASS>(K, P); RZ_T1(c, 6); }
+        if (BFS && cand) {
+            // the guard: "lit with vis == 1" (P.vis is start_light's 1.0f) must leave lacc as "occluded" does, word for word
+            if (__float_as_uint(P.lacc.x) != __float_as_uint(lacc0.x) || __float_as_uint(P.lacc.y) != __float_as_uint(lacc0.y) ||
+                __float_as_uint(P.lacc.z) != __float_as_uint(lacc0.z)) {
+                P.lacc = lacc0;     // it does not: the query decides.  o, d, vis, traveled, maxDist are as start_light left them
+                P.iter = 0;
+                return;
+            }
+            // Nothing downstream reads what the skipped shadow loop would have left in P.o, P.d, P.vis, P.traveled or P.iter:
+            // start_light rewrites all five for the next light, and finish_lighting -> scatter reads hp, hn, pdir, hmat, seed, samp,
+            // bounce, throughput and lacc only, and overwrites o and d (mode, bounce, samp: end_sample).  A path is parked or
+            // snapshotted in MODE_SEGMENT alone, never between start_light and here.
+        }
+        P.li += 1;
+        if (P.li >= K.nLights) break;
+        start_light<COUNT, GLASS>(K, P, c);
+        cand = BFS && RZ_BACKFACE_CHAIN && P.iter < 0;
+        if (!cand) return;
     }
-    if (!done) {
-        P.iter += 1;
-        if (P.iter < 32 && P.vis > 0.05f) return;   // next iteration: trace again
-        lit = P.vis > 0.05f;                         // FS:527
-    }
-    if (lit) { RZ_T0(); if (COUNT) c.lit_lights += 1; shade_light<GLASS>(K, P); RZ_T1(c, 6); }
-    P.li += 1;
-    if (P.li < K.nLights) { start_light<COUNT, GLASS>(K, P, c); return; }
     finish_lighting<COUNT, GLASS, GMODE>(K, P, c);
 }
 
