@@ -653,6 +653,91 @@ int rz_temporal_reset(rz_ctx* ctx);
  * 4: per instance 24 floats: inverseTransform then transform, each as columns 0..3, rows 0..2. */
 int rz_debug_read_temporal(rz_ctx* ctx, int which, void* out, size_t bytes, size_t* needed);
 
+/* ------------------------------------------------------------------------ */
+/* Display transform (new: the reference has none)                           */
+/* ------------------------------------------------------------------------ */
+/* The reference shows a frame by clamping it (FS:772-773), and so does rz_present.  This stage turns linear HDR colour -- the
+ * accumulation, or what rz_denoise / rz_denoise_temporal write -- into display colour on the device: an exposure (manual, or
+ * metered from the frame and adapted over calls), a tone curve and a transfer function (rz_display.hip).  Per pixel p, row 0 =
+ * the bottom row; binary32, every expression evaluated as written (no fused multiply-add), unless binary64 is said:
+ *  1 luminance   l_p = (0.2126 r + 0.7152 g) + 0.0722 b of the input colour (rz_denoise_temporal's expression).
+ *  2 metering (auto)  u = the bit pattern of l_p, b = (int)(u >> 21) - 444.  A set sign bit or b < 0 counts in `below`, b > 127
+ *            in `above` (a positive NaN or infinity lands there), otherwise histogram[b] is incremented: 128 bins over
+ *            [2^-16, 2^16), four per octave, edges at the mantissa quarters (1.0 -> 64, 1.25 -> 65, 2^-16 -> 0).  The counts
+ *            are integers added with integer atomics: exact, whatever the scheduling.
+ *  3 target      N = the sum of the bins.  N == 0: the exposure stays what it was (1 on a fresh state) and `target` reports it.
+ *            Otherwise, in 64-bit integers, lo = N * low_permille / 1000, hi = N - N * high_permille / 1000, C_b the prefix
+ *            count, kept_b = max(0, min(C_{b+1}, hi) - max(C_b, lo)), K = hi - lo (> 0), I = sum kept_b * (b >> 2), M_m = the
+ *            sum of kept_b over b % 4 == m; in binary64, left to right,
+ *              log2_mean = I / K - 16 + (((M_0 g_0 + M_1 g_1) + M_2 g_2) + M_3 g_3) / K,
+ *            g_m = (log2(1 + m/4) + log2(1 + (m+1)/4)) / 2, the log2 mid-point of a bin: 0x1.49a784bcd1b8bp-3,
+ *            0x1.d053f6d260896p-2, 0x1.646eea247c5c2p-1, 0x1.ceaecfea8085ap-1;
+ *              T = clamp((float)(key / exp2(log2_mean)), min_exposure, max_exposure).
+ *  4 adaptation  E = E_prev + adapt * (T - E_prev); E = T exactly on a fresh state or when adapt == 1.  Manual mode: E = exposure.
+ *  5 tone        per channel x = c * E.  curve 0: y = x.  curve 1 (extended Reinhard): x = max(x, 0),
+ *            y = (x * (1 + x / (white * white))) / (1 + x).  curve 2 (the ACES fit of Narkowicz 2015): x = max(x, 0),
+ *            y = (x * (2.51 x + 0.03)) / (x * (2.43 x + 0.59) + 0.14).  Then y = clamp(y, 0, 1) (rz_present's clamp).
+ *  6 transfer 1  y <= 0.0031308 ? 12.92 y : 1.055 * powf(y, 1 / 2.4f) - 0.055 (the sRGB OETF).
+ * With params NULL x = c * 1 = c, so the stage is the reference's clamp.
+ *
+ * rz_display is the asynchronous building block, with rz_denoise's conventions: device pointers by default (4-byte aligned),
+ * the work is enqueued on the context's stream, the call returns at once and the exposure never visits the host; width and
+ * height come from the last rz_set_frame (no scene is needed).  rgb_in is width*height*3 floats of linear colour; rgb_in NULL
+ * reads the context's accumulation as c = rgb / n, n = a > 0 ? a : 1 (refused for a frame with tile_nranks > 1, as rz_denoise
+ * refuses it).  Outputs, each optional:
+ *   rgb32f   width*height*3 floats: the encoded colour before quantisation (may be rgb_in itself: in place)
+ *   rgba8    width*height*4 B: rint(clamp(c, 0, 1) * 255), alpha 255
+ * With RZ_DISPLAY_HOST the pointers are host memory, staged through buffers of the context, and the call returns when the
+ * outputs are written.  A call with every output NULL still meters and adapts.
+ * rz_present_display is to rz_display what rz_present_denoised is to rz_denoise.  source selects the colour: 0 the accumulation
+ * (filter_params must be NULL), 1 rz_denoise's output (filter_params: an rz_denoise_params* or NULL), 2 rz_denoise_temporal's
+ * (an rz_temporal_params* or NULL; the history advances exactly as rz_present_temporal advances it).  The stage writes
+ * (encoded colour, 1) to a buffer of the context and rz_present's kernel runs on it, so the overlays are drawn on top of the
+ * tone-mapped image, not through it.  Outputs are host memory and the call synchronises, as rz_present does.  With display
+ * NULL the bytes are rz_present's, rz_present_denoised's or rz_present_temporal's exactly.
+ * State: the context carries, on the device, the exposure last applied and whether one exists.  Every call commits its E
+ * (a manual call too) unless RZ_DISPLAY_KEEP is set, which computes the same outputs and leaves the state -- rz_display_state's
+ * record included -- as it was.  Only rz_display_reset drops it (the next auto call then jumps to its target) and rz_destroy
+ * frees it; uploads, frame changes and the denoisers do not touch it.  A fresh state reports exposure = target = 1.  The display
+ * calls touch no render state: the accumulation, currentIor, the pools, the frame, rz_debug_last_plan and the temporal history
+ * stay as they were (except through source 2).
+ * RZ_ERR_INVALID_ARG: null context, exposure_mode, curve or transfer unknown, a field of the mode or curve in use outside its
+ * range (manual: exposure; auto: key, min_exposure, max_exposure, adapt, low_permille, high_permille; curve 1: white), non-zero
+ * reserved words, unknown flags, a misaligned device pointer, an unknown source, filter_params with source 0.
+ * RZ_ERR_BUFFER_SIZE: a buffer that is too small.  RZ_ERR_NOT_READY: no rz_set_frame (sources 1 and 2: what their denoiser
+ * says).  A failing call launches nothing and leaves the state as it was.
+ * (Additive: RZ_ABI_VERSION stays 5.) */
+typedef struct rz_display_params {      /* NULL = the reference's display: manual exposure 1, clamp, linear */
+    int32_t exposure_mode;              /* 0 manual, 1 auto (metered from this call's input) */
+    float   exposure;                   /* manual: the multiplier, finite, > 0 */
+    float   key;                        /* auto: the value the log-average luminance is brought to (0.18); finite, > 0 */
+    float   min_exposure, max_exposure; /* auto: clamp of the target, 0 < min <= max, finite */
+    float   adapt;                      /* auto: share of the way to the target taken per call, 0..1 (1 = jump) */
+    int32_t low_permille, high_permille;/* auto: darkest / brightest share of the counted pixels ignored; >= 0, sum < 1000 */
+    int32_t curve;                      /* 0 clamp, 1 extended Reinhard, 2 ACES fit (Narkowicz 2015) */
+    float   white;                      /* curve 1: the value mapped to 1; finite, > 0 */
+    int32_t transfer;                   /* 0 linear (the reference), 1 sRGB OETF */
+    int32_t reserved[5];                /* must be 0 */
+} rz_display_params;                    /* 64 B; rz_sizeof(14) */
+
+typedef struct rz_display_info {
+    float    exposure;                  /* E applied by the last call */
+    float    target;                    /* T of the last auto call (E for a manual call) */
+    float    log2_mean;                 /* (float) of step 3's mean; 0 when nothing was counted or manual */
+    uint32_t counted, below, above;     /* of the last auto call */
+    uint32_t histogram[128];            /* of the last auto call */
+} rz_display_info;                      /* 536 B; rz_sizeof(15) */
+
+#define RZ_DISPLAY_HOST 1u              /* pointers are host memory: staged, returns when written */
+#define RZ_DISPLAY_KEEP 4u              /* compute the outputs, leave the adaptation state as it was */
+int rz_display(rz_ctx* ctx, const rz_display_params* params, const float* rgb_in, size_t rgb_in_bytes,
+               float* rgb32f, size_t rgb32f_bytes, uint8_t* rgba8, size_t rgba8_bytes, unsigned flags);
+int rz_present_display(rz_ctx* ctx, const rz_present_params* present, const rz_display_params* display,
+                       int source, const void* filter_params,
+                       uint8_t* rgba8, size_t rgba8_bytes, float* rgb32f, size_t rgb32f_bytes);
+int rz_display_reset(rz_ctx* ctx);
+int rz_display_state(rz_ctx* ctx, rz_display_info* out);   /* synchronises */
+
 /* Number of HIP devices visible to the process (0 without a GPU). */
 int rz_device_count(void);
 
@@ -675,7 +760,8 @@ const char* rz_source_hash(void);
 /* sizeof() of the ABI structs as compiled into the library, for layout
  * checks from other languages: which = 0 triangle, 1 node, 2 instance,
  * 3 material, 4 light, 5 frame_params, 6 counters, 7 ray, 8 hit,
- * 9 visibility, 10 editor_params, 11 denoise_params, 12 temporal_params. */
+ * 9 visibility, 10 editor_params, 11 denoise_params, 12 temporal_params,
+ * 14 display_params, 15 display_info (13 is unassigned and returns 0, as every unknown index does). */
 size_t rz_sizeof(int which);
 
 #ifdef __cplusplus

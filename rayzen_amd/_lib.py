@@ -23,6 +23,7 @@ HIP_SYMBOLS = (
     "rz_group_frame_device_ptr", "rz_group_last_reduce_ms", "rz_group_transport", "rz_group_set_transport", "rz_abi_version", "rz_debug_poke_backstop", "rz_math_flavour",
     "rz_trace_rays", "rz_shadow_rays", "rz_render_editor", "rz_denoise", "rz_present_denoised", "rz_refit_geometry",
     "rz_denoise_temporal", "rz_present_temporal", "rz_temporal_reset", "rz_debug_read_temporal",
+    "rz_display", "rz_present_display", "rz_display_reset", "rz_display_state",
 )
 ABI_VERSION = 5         # RZ_ABI_VERSION of the include/rayzen_hip.h this file mirrors
 # the symbols include/rayzen_host.h declares
@@ -125,6 +126,25 @@ TEMPORAL_HOST, TEMPORAL_KEEP = 1, 4     # RZ_TEMPORAL_HOST, RZ_TEMPORAL_KEEP
 REFIT_HOST = 1                          # RZ_REFIT_HOST
 
 
+class DisplayParams(C.Structure):
+    """rz_display_params of include/rayzen_hip.h (64 B)."""
+    _fields_ = [("exposure_mode", C.c_int32), ("exposure", C.c_float), ("key", C.c_float), ("min_exposure", C.c_float),
+                ("max_exposure", C.c_float), ("adapt", C.c_float), ("low_permille", C.c_int32), ("high_permille", C.c_int32),
+                ("curve", C.c_int32), ("white", C.c_float), ("transfer", C.c_int32), ("reserved", C.c_int32 * 5)]
+
+
+class DisplayInfo(C.Structure):
+    """rz_display_info of include/rayzen_hip.h (536 B)."""
+    _fields_ = [("exposure", C.c_float), ("target", C.c_float), ("log2_mean", C.c_float), ("counted", C.c_uint32),
+                ("below", C.c_uint32), ("above", C.c_uint32), ("histogram", C.c_uint32 * 128)]
+
+
+DISPLAY_HOST, DISPLAY_KEEP = 1, 4       # RZ_DISPLAY_HOST, RZ_DISPLAY_KEEP
+DISPLAY_CURVES = {"clamp": 0, "reinhard": 1, "aces": 2}
+DISPLAY_TRANSFERS = {"linear": 0, "srgb": 1}
+DISPLAY_SOURCES = {"accum": 0, "denoise": 1, "temporal": 2}
+
+
 class Counters(C.Structure):
     """rz_counters of include/rayzen_hip.h."""
     _fields_ = [(n, C.c_uint64) for n in COUNTER_FIELDS]
@@ -206,7 +226,11 @@ def hip():
                                 ("rz_denoise_temporal", i, [vp, vp, vp, sz, vp, sz, vp, sz, vp, sz, C.c_uint]),
                                 ("rz_present_temporal", i, [vp, C.POINTER(PresentParams), vp, vp, sz, vp, sz]),
                                 ("rz_temporal_reset", i, [vp]),
-                                ("rz_debug_read_temporal", i, [vp, i, vp, sz, C.POINTER(sz)])):
+                                ("rz_debug_read_temporal", i, [vp, i, vp, sz, C.POINTER(sz)]),
+                                ("rz_display", i, [vp, vp, vp, sz, vp, sz, vp, sz, C.c_uint]),
+                                ("rz_present_display", i, [vp, C.POINTER(PresentParams), vp, i, vp, vp, sz, vp, sz]),
+                                ("rz_display_reset", i, [vp]),
+                                ("rz_display_state", i, [vp, C.POINTER(DisplayInfo)])):
             try:
                 fn = getattr(L, name)
                 fn.restype, fn.argtypes = res, args

@@ -158,6 +158,9 @@ struct rz_ctx {
     int tmpW = 0, tmpH = 0;
     size_t tmpInst = 0;
     float tmpView[16] = {}, tmpProj[16] = {}, tmpInvProj[16] = {}, tmpCam[3] = {};
+    // the display stage (rz_display / rz_present_display, rz_display.hip): one DisplayState -- the exposure last applied, the
+    // rz_display_info record and the working histogram -- allocated and zeroed by the first call that needs it
+    DevBuf dDisplay;
     // rz_refit_geometry (rz_refit.hip)
     bool trisHostStale = false;         // binding 0 on the device (dRawTris) is newer than the host copy: fetched on demand (sync_tris_host)
     unsigned long long layoutGen = 0;   // counts the times the views / instances were laid out
@@ -1006,6 +1009,8 @@ size_t rz_sizeof(int which) {
         case 10: return sizeof(rz_editor_params);
         case 11: return sizeof(rz_denoise_params);
         case 12: return sizeof(rz_temporal_params);
+        case 14: return sizeof(rz_display_params);       // (13 stays unassigned: callers probe it as the first unknown index)
+        case 15: return sizeof(rz_display_info);
         default: return 0;
     }
 }
@@ -1049,7 +1054,7 @@ void rz_destroy(rz_ctx* c) {
                       &c->dRayOvf, &c->dRayIn, &c->dRayOut, &c->dRayInstOff, &c->dDnGuide, &c->dDnPing, &c->dDnPong, &c->dDnOut,
                       &c->dRefitRank, &c->dRefitInstView, &c->dRefitViewOff, &c->dRefitFlags, &c->dRefitRoots,
                       &c->dTmpCol[0], &c->dTmpCol[1], &c->dTmpMom[0], &c->dTmpMom[1], &c->dTmpHits[0], &c->dTmpHits[1],
-                      &c->dTmpInst[0], &c->dTmpInst[1], &c->dTmpSame})
+                      &c->dTmpInst[0], &c->dTmpInst[1], &c->dTmpSame, &c->dDisplay})
         b->release();
     if (c->refitPinned) (void)hipHostFree(c->refitPinned);
     if (c->tlasHostCounts) (void)hipHostFree(c->tlasHostCounts);
@@ -2413,6 +2418,191 @@ static int present_temporal_impl(rz_ctx* c, const rz_present_params* pp, const r
     return denoise_backstop(c, what);
 }
 
+// rz_display / rz_present_display (rz_display.hip).  Of the frame they read the size only; they need no scene (rz_present_display
+// needs what its source and rz_present need) and touch no render state.  What they keep is one DisplayState on the device.
+static const rz_display_params kDisplayDefaults = {0, 1.0f, 0.18f, 1.0f / 64.0f, 64.0f, 1.0f, 0, 0, 0, 4.0f, 0, {0, 0, 0, 0, 0}};
+
+static int display_check(rz_ctx* c, const char* what, const rz_display_params& P) {
+    auto positive = [](float v) { return v > 0.0f && v < INFINITY; };
+    if (P.exposure_mode != 0 && P.exposure_mode != 1) return fail(c, RZ_ERR_INVALID_ARG, "%s: exposure_mode %d (0 manual, 1 auto)", what, P.exposure_mode);
+    if (P.exposure_mode == 0 && !positive(P.exposure)) return fail(c, RZ_ERR_INVALID_ARG, "%s: exposure %g (finite, > 0)", what, (double)P.exposure);
+    if (P.exposure_mode == 1) {
+        if (!positive(P.key)) return fail(c, RZ_ERR_INVALID_ARG, "%s: key %g (finite, > 0)", what, (double)P.key);
+        if (!positive(P.min_exposure) || !positive(P.max_exposure) || !(P.min_exposure <= P.max_exposure))
+            return fail(c, RZ_ERR_INVALID_ARG, "%s: min_exposure %g, max_exposure %g (finite, 0 < min <= max)", what, (double)P.min_exposure, (double)P.max_exposure);
+        if (!(P.adapt >= 0.0f && P.adapt <= 1.0f)) return fail(c, RZ_ERR_INVALID_ARG, "%s: adapt %g outside [0, 1]", what, (double)P.adapt);
+        if (P.low_permille < 0 || P.high_permille < 0 || (long long)P.low_permille + P.high_permille >= 1000)
+            return fail(c, RZ_ERR_INVALID_ARG, "%s: low_permille %d, high_permille %d (>= 0, sum < 1000)", what, P.low_permille, P.high_permille);
+    }
+    if (P.curve < 0 || P.curve > 2) return fail(c, RZ_ERR_INVALID_ARG, "%s: curve %d (0 clamp, 1 Reinhard, 2 ACES)", what, P.curve);
+    if (P.curve == 1 && !positive(P.white)) return fail(c, RZ_ERR_INVALID_ARG, "%s: white %g (finite, > 0)", what, (double)P.white);
+    if (P.transfer != 0 && P.transfer != 1) return fail(c, RZ_ERR_INVALID_ARG, "%s: transfer %d (0 linear, 1 sRGB)", what, P.transfer);
+    for (int r : P.reserved)
+        if (r) return fail(c, RZ_ERR_INVALID_ARG, "%s: reserved words must be 0", what);
+    if (!c->haveFrame) return fail(c, RZ_ERR_NOT_READY, "%s: rz_set_frame has not been called", what);
+    return RZ_OK;
+}
+
+static int ensure_display_state(rz_ctx* c) {
+    if (c->dDisplay.p) return RZ_OK;
+    int rc = ensure(c, c->dDisplay, sizeof(DisplayState));
+    if (rc != RZ_OK) return rc;
+    RZ_HIP(c, hipMemsetAsync(c->dDisplay.p, 0, sizeof(DisplayState), c->stream));     // fresh: no exposure yet, an empty histogram
+    return RZ_OK;
+}
+
+// Meters and adapts (auto) or commits the manual exposure, then tones, on the stream.  The input (device) is rgb (3 floats per
+// pixel) or in4 (RGBA32F sum and count); outputs (device, each optional): rgb, rgba8, out4 ((colour, 1); may be in4 itself).
+static int display_run(rz_ctx* c, const rz_display_params& P, const float* in, const float4* in4, float* rgb, uchar4* rgba8,
+                       float4* out4, bool keep) {
+    const long long np = (long long)c->frame.width * c->frame.height;
+    const bool metered = P.exposure_mode == 1;
+    DisplayState* S = nullptr;
+    if (metered || !keep) {
+        int rc = ensure_display_state(c);
+        if (rc != RZ_OK) return rc;
+        S = static_cast<DisplayState*>(c->dDisplay.p);
+    }
+    if (metered) {
+        launch_display_meter(in, in4, np, S, c->stream);
+        RZ_HIP(c, hipGetLastError());
+    }
+    if (S) {
+        DisplayExpose X{};
+        X.mode = metered ? 1 : 0;
+        X.keep = keep ? 1 : 0;
+        X.manual = P.exposure;
+        X.key = P.key; X.minExposure = P.min_exposure; X.maxExposure = P.max_exposure; X.adapt = P.adapt;
+        X.lowPermille = P.low_permille; X.highPermille = P.high_permille;
+        launch_display_expose(S, X, c->stream);
+        RZ_HIP(c, hipGetLastError());
+    }
+    if (!rgb && !rgba8 && !out4) return RZ_OK;
+    DisplayTone T{};
+    T.in = in; T.in4 = in4;
+    T.state = metered ? S : nullptr;
+    T.exposure = P.exposure;
+    T.curve = P.curve;
+    T.white2 = P.white * P.white;
+    T.transfer = P.transfer;
+    T.n = np;
+    T.rgb = rgb; T.rgba8 = rgba8; T.out4 = out4;
+    launch_display_tone(T, c->stream);
+    RZ_HIP(c, hipGetLastError());
+    return RZ_OK;
+}
+
+static int display_impl(rz_ctx* c, const rz_display_params* pp, const float* rgb_in, size_t rgb_in_bytes, float* rgb32f,
+                        size_t rgb32f_bytes, uint8_t* rgba8, size_t rgba8_bytes, unsigned flags) {
+    const char* what = "rz_display";
+    if (!c) return fail(nullptr, RZ_ERR_INVALID_ARG, "%s: null context", what);
+    if (flags & ~(RZ_DISPLAY_HOST | RZ_DISPLAY_KEEP)) return fail(c, RZ_ERR_INVALID_ARG, "%s: unknown flags 0x%x", what, flags);
+    const rz_display_params& P = pp ? *pp : kDisplayDefaults;
+    int rc = display_check(c, what, P);
+    if (rc != RZ_OK) return rc;
+    if (!rgb_in && c->frame.tile_nranks > 1)
+        return fail(c, RZ_ERR_INVALID_ARG, "%s: the frame is tile %d of %d; the accumulation is not the whole frame", what, c->frame.tile_rank, c->frame.tile_nranks);
+    const bool host = (flags & RZ_DISPLAY_HOST) != 0;
+    if (!host && ((reinterpret_cast<uintptr_t>(rgb_in) | reinterpret_cast<uintptr_t>(rgb32f) | reinterpret_cast<uintptr_t>(rgba8)) & 3u))
+        return fail(c, RZ_ERR_INVALID_ARG, "%s: device pointers must be 4-byte aligned", what);
+    const size_t np = (size_t)c->frame.width * c->frame.height;
+    const size_t bRgb = np * 3 * sizeof(float), bRgba8 = np * 4;
+    if (rgb_in && rgb_in_bytes < bRgb) return fail(c, RZ_ERR_BUFFER_SIZE, "%s: rgb_in needs %zu bytes, got %zu", what, bRgb, rgb_in_bytes);
+    if (!rgb_in && c->extAccum && c->extAccumBytes < np * 16)
+        return fail(c, RZ_ERR_BUFFER_SIZE, "%s: bound accumulation buffer holds %zu bytes, frame needs %zu", what, c->extAccumBytes, np * 16);
+    if (rgb32f && rgb32f_bytes < bRgb) return fail(c, RZ_ERR_BUFFER_SIZE, "%s: rgb32f needs %zu bytes, got %zu", what, bRgb, rgb32f_bytes);
+    if (rgba8 && rgba8_bytes < bRgba8) return fail(c, RZ_ERR_BUFFER_SIZE, "%s: rgba8 needs %zu bytes, got %zu", what, bRgba8, rgba8_bytes);
+    RZ_HIP(c, hipSetDevice(c->device));
+    const float* in = rgb_in;
+    const float4* in4 = rgb_in ? nullptr : static_cast<const float4*>(rz_accum_device_ptr(c));
+    float* dRgb = rgb32f;
+    uchar4* dRgba8 = reinterpret_cast<uchar4*>(rgba8);
+    // host buffers are staged as rz_denoise stages them: the input in dRayIn; rgb32f, then rgba8 in dRayOut
+    const size_t oRgba8 = rgb32f ? (bRgb + 15) & ~size_t(15) : 0;
+    if (host) {
+        if (rgb_in) {
+            rc = ensure(c, c->dRayIn, bRgb);
+            if (rc != RZ_OK) return rc;
+            RZ_HIP(c, hipMemcpyAsync(c->dRayIn.p, rgb_in, bRgb, hipMemcpyHostToDevice, c->stream));
+            in = static_cast<const float*>(c->dRayIn.p);
+        }
+        rc = ensure(c, c->dRayOut, oRgba8 + (rgba8 ? bRgba8 : 0));
+        if (rc != RZ_OK) return rc;
+        char* base = static_cast<char*>(c->dRayOut.p);
+        dRgb = rgb32f ? reinterpret_cast<float*>(base) : nullptr;
+        dRgba8 = rgba8 ? reinterpret_cast<uchar4*>(base + oRgba8) : nullptr;
+    }
+    rc = display_run(c, P, in, in4, dRgb, dRgba8, nullptr, (flags & RZ_DISPLAY_KEEP) != 0);
+    if (rc != RZ_OK) return rc;
+    if (!host) return RZ_OK;
+    const char* base = static_cast<const char*>(c->dRayOut.p);
+    if (rgb32f) RZ_HIP(c, hipMemcpyAsync(rgb32f, base, bRgb, hipMemcpyDeviceToHost, c->stream));
+    if (rgba8) RZ_HIP(c, hipMemcpyAsync(rgba8, base + oRgba8, bRgba8, hipMemcpyDeviceToHost, c->stream));
+    RZ_HIP(c, hipStreamSynchronize(c->stream));
+    return RZ_OK;
+}
+
+static int present_display_impl(rz_ctx* c, const rz_present_params* pp, const rz_display_params* dp, int source,
+                                const void* filter_params, uint8_t* rgba8, size_t rgba8_bytes, float* rgb32f, size_t rgb32f_bytes) {
+    const char* what = "rz_present_display";
+    if (!c) return fail(nullptr, RZ_ERR_INVALID_ARG, "%s: null context", what);
+    if (!pp) return fail(c, RZ_ERR_INVALID_ARG, "%s: null present params", what);
+    if (source < 0 || source > 2) return fail(c, RZ_ERR_INVALID_ARG, "%s: source %d (0 accumulation, 1 rz_denoise, 2 rz_denoise_temporal)", what, source);
+    if (source == 0 && filter_params) return fail(c, RZ_ERR_INVALID_ARG, "%s: filter_params must be NULL for source 0", what);
+    const rz_display_params& D = dp ? *dp : kDisplayDefaults;
+    int rc = display_check(c, what, D);
+    if (rc != RZ_OK) return rc;
+    const rz_denoise_params& P1 = (source == 1 && filter_params) ? *static_cast<const rz_denoise_params*>(filter_params) : kDenoiseDefaults;
+    const rz_temporal_params& P2 = (source == 2 && filter_params) ? *static_cast<const rz_temporal_params*>(filter_params) : kTemporalDefaults;
+    if (source == 1) rc = denoise_check(c, what, P1);
+    if (source == 2) rc = temporal_check(c, what, P2);
+    if (rc != RZ_OK) return rc;
+    if (source == 0 && D.exposure_mode == 1 && c->frame.tile_nranks > 1)
+        return fail(c, RZ_ERR_INVALID_ARG, "%s: the frame is tile %d of %d; metering needs the whole frame", what, c->frame.tile_rank, c->frame.tile_nranks);
+    const size_t np = (size_t)c->frame.width * c->frame.height;
+    if (c->extAccum && c->extAccumBytes < np * 16)
+        return fail(c, RZ_ERR_BUFFER_SIZE, "%s: bound accumulation buffer holds %zu bytes, frame needs %zu", what, c->extAccumBytes, np * 16);
+    if (rgba8 && rgba8_bytes < np * 4) return fail(c, RZ_ERR_BUFFER_SIZE, "%s: rgba8 buffer needs %zu bytes", what, np * 4);
+    if (rgb32f && rgb32f_bytes < np * 12) return fail(c, RZ_ERR_BUFFER_SIZE, "%s: rgb32f buffer needs %zu bytes", what, np * 12);
+    RZ_HIP(c, hipSetDevice(c->device));
+    rc = ensure(c, c->dDnOut, np * 16);
+    if (rc != RZ_OK) return rc;
+    float4* out4 = static_cast<float4*>(c->dDnOut.p);
+    const float4* accum = static_cast<const float4*>(rz_accum_device_ptr(c));
+    // sources 1 and 2 leave (colour, 1) in out4, which the tone kernel then rewrites in place: (colour, 1) resolves to colour
+    if (source == 1) rc = denoise_run(c, P1, accum, nullptr, out4, nullptr);
+    if (source == 2) rc = temporal_run(c, P2, accum, nullptr, out4, nullptr, nullptr, false);
+    if (rc != RZ_OK) return rc;
+    rc = display_run(c, D, nullptr, source == 0 ? accum : out4, nullptr, nullptr, out4, false);
+    if (rc != RZ_OK) return rc;
+    rc = present_impl(c, pp, rgba8, rgba8_bytes, rgb32f, rgb32f_bytes, out4);
+    if (rc != RZ_OK) return rc;
+    return source == 0 ? RZ_OK : denoise_backstop(c, what);
+}
+
+static int display_reset_impl(rz_ctx* c) {
+    if (!c) return fail(nullptr, RZ_ERR_INVALID_ARG, "rz_display_reset: null context");
+    if (!c->dDisplay.p) return RZ_OK;       // (nothing to drop)
+    RZ_HIP(c, hipSetDevice(c->device));
+    RZ_HIP(c, hipMemsetAsync(c->dDisplay.p, 0, sizeof(DisplayState), c->stream));
+    return RZ_OK;
+}
+
+static int display_state_impl(rz_ctx* c, rz_display_info* out) {
+    if (!c) return fail(nullptr, RZ_ERR_INVALID_ARG, "rz_display_state: null context");
+    if (!out) return fail(c, RZ_ERR_INVALID_ARG, "rz_display_state: null out");
+    std::memset(out, 0, sizeof *out);
+    out->exposure = out->target = 1.0f;     // a fresh state
+    if (!c->dDisplay.p) return RZ_OK;
+    RZ_HIP(c, hipSetDevice(c->device));
+    RZ_HIP(c, hipStreamSynchronize(c->stream));
+    struct { float exposure; unsigned have; float call; unsigned pad; rz_display_info info; } head;
+    static_assert(sizeof head == offsetof(DisplayState, work), "the head of DisplayState");
+    RZ_HIP(c, hipMemcpy(&head, c->dDisplay.p, sizeof head, hipMemcpyDeviceToHost));
+    if (head.have || head.info.exposure != 0.0f) *out = head.info;      // (else: zeroed by rz_display_reset, or never written)
+    return RZ_OK;
+}
+
 static int debug_read_temporal_impl(rz_ctx* c, int which, void* out, size_t bytes, size_t* needed) {
     if (!c) return fail(nullptr, RZ_ERR_INVALID_ARG, "null context");
     if (which < 0 || which > 4) return fail(c, RZ_ERR_INVALID_ARG, "which = %d", which);
@@ -2562,6 +2752,24 @@ int rz_temporal_reset(rz_ctx* c) {
 }
 int rz_debug_read_temporal(rz_ctx* c, int which, void* out, size_t bytes, size_t* needed) {
     return guarded(c, "rz_debug_read_temporal", [&] { return debug_read_temporal_impl(c, which, out, bytes, needed); });
+}
+int rz_display(rz_ctx* c, const rz_display_params* params, const float* rgb_in, size_t rgb_in_bytes, float* rgb32f,
+               size_t rgb32f_bytes, uint8_t* rgba8, size_t rgba8_bytes, unsigned flags) {
+    return guarded(c, "rz_display", [&] {
+        return display_impl(c, params, rgb_in, rgb_in_bytes, rgb32f, rgb32f_bytes, rgba8, rgba8_bytes, flags);
+    });
+}
+int rz_present_display(rz_ctx* c, const rz_present_params* present, const rz_display_params* display, int source,
+                       const void* filter_params, uint8_t* rgba8, size_t rgba8_bytes, float* rgb32f, size_t rgb32f_bytes) {
+    return guarded(c, "rz_present_display", [&] {
+        return present_display_impl(c, present, display, source, filter_params, rgba8, rgba8_bytes, rgb32f, rgb32f_bytes);
+    });
+}
+int rz_display_reset(rz_ctx* c) {
+    return guarded(c, "rz_display_reset", [&] { return display_reset_impl(c); });
+}
+int rz_display_state(rz_ctx* c, rz_display_info* out) {
+    return guarded(c, "rz_display_state", [&] { return display_state_impl(c, out); });
 }
 int rz_debug_read_layout(rz_ctx* c, int which, void* out, size_t bytes, size_t* needed) {
     return guarded(c, "rz_debug_read_layout", [&]() -> int {

@@ -137,6 +137,40 @@ void launch_temporal_accumulate(const TemporalLaunch& T, hipStream_t stream);
 void launch_temporal_variance(const TemporalVarLaunch& V, hipStream_t stream);
 void launch_temporal_pass(const TemporalFilterLaunch& F, bool last, hipStream_t stream);
 
+// ---- rz_display.hip
+constexpr int RZ_DISPLAY_BINS = 128;    // rz_display_info::histogram
+struct DisplayState {           // the context's display state, device memory (zeroed = fresh: no exposure yet)
+    float exposure;             // the exposure last committed
+    unsigned have;              // 1: `exposure` holds one
+    float call;                 // the exposure of the auto call in flight (what its tone kernel reads; RZ_DISPLAY_KEEP commits nothing else)
+    unsigned pad;
+    rz_display_info info;       // what rz_display_state reports
+    unsigned work[RZ_DISPLAY_BINS + 2];   // the working histogram: the bins, below, above; zero between calls
+};
+struct DisplayExpose {          // rz_display_expose
+    int mode;                   // 0: commit `manual`; 1: meter-driven (steps 3 and 4)
+    int keep;                   // RZ_DISPLAY_KEEP
+    float manual;
+    float key, minExposure, maxExposure, adapt;
+    int lowPermille, highPermille;
+};
+struct DisplayTone {            // rz_display_tone
+    const float* in;            // width x height x 3 linear colour, or
+    const float4* in4;          // RGBA32F sum and count (then `in` is unused)
+    const DisplayState* state;  // auto: the exposure is state->call; null: `exposure`
+    float exposure;
+    int curve;
+    float white2;               // white * white
+    int transfer;
+    long long n;                // pixels
+    float* rgb;                 // outputs, each optional: width x height x 3,
+    uchar4* rgba8;              //   width x height,
+    float4* out4;               //   (colour, 1) per pixel
+};
+void launch_display_meter(const float* rgb, const float4* rgba, long long n, DisplayState* S, hipStream_t s);
+void launch_display_expose(DisplayState* S, const DisplayExpose& X, hipStream_t s);
+void launch_display_tone(const DisplayTone& T, hipStream_t s);
+
 // ---- rz_tlas_device.hip
 void launch_tlas_refit(const TlasWork& W, hipStream_t s);
 

@@ -11,6 +11,7 @@
 //   denoise() / presentDenoised()      <- new: the a-trous denoiser of the 1-spp frame (rz_denoise / rz_present_denoised)
 //   denoiseTemporal() / presentTemporal() / resetTemporal()
 //                                      <- new: temporal accumulation + the variance-guided filter (rz_denoise_temporal)
+//   presentDisplay() / resetDisplay()  <- new: exposure, tone curve and sRGB encode in front of present (rz_present_display)
 // Unlike the reference's per-frame path, updateDynamicBVHAndSSBOs re-uploads
 // only what changed (instances + TLAS, a few KB), not all geometry.
 #pragma once
@@ -245,6 +246,17 @@ public:
     }
     // Drops the history (a cut: the next frame starts every pixel anew).
     void resetTemporal() { check(rz_temporal_reset(ctx_), "rz_temporal_reset"); }
+    // present() behind the display stage: exposure (manual, or metered from the frame and adapted from call to call), tone
+    // curve, transfer.  source 0: the accumulation; 1: rz_denoise's output (filter: an rz_denoise_params* or null); 2:
+    // rz_denoise_temporal's (an rz_temporal_params* or null; the history advances).  display null: present()'s bytes.
+    std::vector<uint8_t> presentDisplay(const rz_present_params& present, const rz_display_params* display = nullptr, int source = 0,
+                                        const void* filter = nullptr) {
+        std::vector<uint8_t> out((size_t)width_ * (size_t)height_ * 4);
+        check(rz_present_display(ctx_, &present, display, source, filter, out.data(), out.size(), nullptr, 0), "rz_present_display");
+        return out;
+    }
+    // Drops the adapted exposure (a cut: the next metered call jumps to its target).
+    void resetDisplay() { check(rz_display_reset(ctx_), "rz_display_reset"); }
     float lastRenderMs() { float ms = 0; int n = 0; check(rz_last_render_ms(ctx_, &ms, &n), "rz_last_render_ms"); return ms; }
     rz_ctx* context() { return ctx_; }
     const SceneBuffers& buffers() const { return buffers_; }

@@ -540,6 +540,112 @@ class Renderer:
             return f.reshape(self.height, self.width, 2)
         return f.reshape(-1, 2, 4, 3) if which == 4 else f
 
+    # -- display transform (rz_display / rz_present_display) -------------------------
+    @staticmethod
+    def _display_params(auto=False, exposure=1.0, key=0.18, min_exposure=1 / 64, max_exposure=64.0, adapt=1.0, low=0.0,
+                        high=0.0, curve="clamp", white=4.0, transfer="linear"):
+        """rz_display_params from the keyword arguments of display() / present_display(), every field checked here (ValueError)
+        whatever the mode; None (params NULL: the reference's display) when nothing departs from the defaults."""
+        def positive(name, v):
+            v = float(v)
+            if not (0.0 < v < float("inf")):
+                raise ValueError(f"{name} = {v!r}: must be finite and > 0")
+            return v
+
+        if curve not in _lib.DISPLAY_CURVES:
+            raise ValueError(f"curve = {curve!r}: one of {sorted(_lib.DISPLAY_CURVES)}")
+        if transfer not in _lib.DISPLAY_TRANSFERS:
+            raise ValueError(f"transfer = {transfer!r}: one of {sorted(_lib.DISPLAY_TRANSFERS)}")
+        p = _lib.DisplayParams()
+        p.exposure_mode = int(bool(auto))
+        p.exposure = positive("exposure", exposure)
+        p.key = positive("key", key)
+        p.min_exposure, p.max_exposure = positive("min_exposure", min_exposure), positive("max_exposure", max_exposure)
+        if not p.min_exposure <= p.max_exposure:
+            raise ValueError(f"min_exposure {min_exposure!r} > max_exposure {max_exposure!r}")
+        if not 0.0 <= float(adapt) <= 1.0:
+            raise ValueError(f"adapt = {adapt!r}: outside [0, 1]")
+        p.adapt = float(adapt)
+        if not (float(low) >= 0.0 and float(high) >= 0.0):
+            raise ValueError(f"low = {low!r}, high = {high!r}: shares must be >= 0")
+        p.low_permille, p.high_permille = int(round(float(low) * 1000)), int(round(float(high) * 1000))
+        if p.low_permille + p.high_permille >= 1000:
+            raise ValueError(f"low + high = {float(low) + float(high)!r}: must leave something to count (< 1)")
+        p.curve = _lib.DISPLAY_CURVES[curve]
+        p.white = positive("white", white)
+        p.transfer = _lib.DISPLAY_TRANSFERS[transfer]
+        d = _lib.DisplayParams(0, 1.0, 0.18, 1 / 64, 64.0, 1.0, 0, 0, 0, 4.0, 0)
+        return None if bytes(p) == bytes(d) else p
+
+    def display(self, rgb=None, *, keep=False, **params):
+        """The display stage (include/rayzen_hip.h: rz_display) on rgb ((H, W, 3) float32 linear colour, what denoise() and
+        denoise_temporal() return) or, with rgb None, on the accumulation; host memory, returns when done.  params: auto=False,
+        exposure=1.0, key=0.18, min_exposure=1/64, max_exposure=64.0, adapt=1.0, low=0.0, high=0.0 (the darkest / brightest share
+        of the metered pixels left out), curve="clamp"|"reinhard"|"aces", white=4.0, transfer="linear"|"srgb"; with none of them
+        it is the reference's display (clamp, linear).  keep=True leaves the adaptation state as it was.  Returns (rgb32f (H, W, 3)
+        float32: the encoded colour; rgba8 (H, W, 4) uint8); row 0 = bottom row."""
+        dp = self._display_params(**params)
+        src = None if rgb is None else np.ascontiguousarray(rgb, np.float32)
+        out = np.empty((self.height, self.width, 3), np.float32)
+        rgba8 = np.empty((self.height, self.width, 4), np.uint8)
+        flags = _lib.DISPLAY_HOST | (_lib.DISPLAY_KEEP if keep else 0)
+        self._check(self._L.rz_display(self._c, None if dp is None else C.byref(dp), None if src is None else src.ctypes.data,
+                                       0 if src is None else src.nbytes, out.ctypes.data, out.nbytes, rgba8.ctypes.data,
+                                       rgba8.nbytes, flags), "rz_display")
+        return out, rgba8
+
+    def display_device(self, rgb_in_ptr=None, rgb32f_ptr=None, rgba8_ptr=None, *, keep=False, **params):
+        """rz_display on device memory (4-byte aligned; each optional): enqueued on the context's stream, asynchronous -- the
+        exposure is metered, adapted and applied without visiting the host.  Sizes: rgb_in and rgb32f W*H*12 B, rgba8 W*H*4 B."""
+        dp = self._display_params(**params)
+        n = self.width * self.height
+        self._check(self._L.rz_display(self._c, None if dp is None else C.byref(dp), C.c_void_p(rgb_in_ptr),
+                                       n * 12 if rgb_in_ptr else 0, C.c_void_p(rgb32f_ptr), n * 12 if rgb32f_ptr else 0,
+                                       C.c_void_p(rgba8_ptr), n * 4 if rgba8_ptr else 0, _lib.DISPLAY_KEEP if keep else 0),
+                    "rz_display")
+
+    def present_display(self, source="accum", fps=0.0, show_fps=True, show_lights=False, show_bvh=False, bvh_mode=0,
+                        selected_blas=0, selected_tri=0, filter=None, **params):
+        """present() behind the display stage: the colour of `source` ("accum", "denoise": denoise()'s, "temporal":
+        denoise_temporal()'s, whose history advances) is exposed, toned and encoded (params: as display()), and the overlays are
+        drawn on top.  filter: a dict of the denoiser's own parameters (present_denoised's / present_temporal's).  Returns (rgb
+        float32 (H,W,3), rgba8 uint8 (H,W,4)); with no display parameters, present()'s / present_denoised()'s /
+        present_temporal()'s bytes."""
+        if source not in _lib.DISPLAY_SOURCES:
+            raise ValueError(f"source = {source!r}: one of {sorted(_lib.DISPLAY_SOURCES)}")
+        if source == "accum" and filter:
+            raise ValueError("filter parameters need source 'denoise' or 'temporal'")
+        p = _lib.PresentParams(float(fps), int(bool(show_fps)), int(bool(show_lights)), int(bool(show_bvh)),
+                               int(bvh_mode), int(selected_blas), int(selected_tri))
+        dp = self._display_params(**params)
+        fp = None
+        if source == "denoise":
+            f = dict(filter or {})
+            fp = self._denoise_params(*(f.pop(k, None) for k in ("iterations", "sigma_color", "sigma_normal", "sigma_plane", "demodulate")))
+            if f:
+                raise TypeError(f"unknown denoise parameter(s): {sorted(f)}")
+        elif source == "temporal":
+            fp = self._temporal_params(dict(filter or {}))
+        rgb = np.empty((self.height, self.width, 3), np.float32)
+        rgba8 = np.empty((self.height, self.width, 4), np.uint8)
+        self._check(self._L.rz_present_display(self._c, C.byref(p), None if dp is None else C.byref(dp),
+                                               _lib.DISPLAY_SOURCES[source], fp, rgba8.ctypes.data, rgba8.nbytes,
+                                               rgb.ctypes.data, rgb.nbytes), "rz_present_display")
+        return rgb, rgba8
+
+    def display_state(self):
+        """rz_display_state (synchronises): dict(exposure, target, log2_mean, counted, below, above, histogram (128,) uint32) --
+        the exposure last applied and what the last metered call saw.  A fresh state: exposure = target = 1."""
+        info = _lib.DisplayInfo()
+        self._check(self._L.rz_display_state(self._c, C.byref(info)), "rz_display_state")
+        return dict(exposure=np.float32(info.exposure), target=np.float32(info.target), log2_mean=np.float32(info.log2_mean),
+                    counted=int(info.counted), below=int(info.below), above=int(info.above),
+                    histogram=np.array(info.histogram, np.uint32))
+
+    def display_reset(self):
+        """Drops the adapted exposure: the next metered call jumps to its target."""
+        self._check(self._L.rz_display_reset(self._c), "rz_display_reset")
+
     # -- convenience -----------------------------------------------------------
     def render_scene(self, scene, width, height, spp, bounce_budget, num_lights=None, tile_rank=0, tile_nranks=1,
                      chunk=None):
