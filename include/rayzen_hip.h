@@ -261,6 +261,66 @@ int rz_build_geometry(rz_ctx* ctx, const rz_triangle* triangles, size_t n_triang
 #define RZ_REFIT_HOST 1u   /* `triangles` is host memory: staged through a context buffer */
 int rz_refit_geometry(rz_ctx* ctx, const rz_triangle* triangles, size_t first_triangle, size_t n_triangles, unsigned flags);
 
+/* Skinned meshes: the moved triangles of rz_refit_geometry PRODUCED on the device.  (No counterpart in the reference, which
+ * deforms nothing.)  A RIG is context-owned device state for one triangle range of binding 0: a private copy of the range's
+ * rest pose, per-corner bone indices and weights (linear-blend skinning) and / or morph targets (blend shapes).
+ * rz_skin_create copies everything it is given to the device (`rest` NULL: what binding 0 holds in that range right now);
+ * nothing of the caller's is retained, and *rig_out is an id that is never reused within the context.
+ *
+ * rz_skin_pose runs the skinning kernel (rz_skin.hip) from the rig's rest pose into a triangle buffer of the context and then
+ * takes exactly the path of rz_refit_geometry(ctx, that buffer, first_triangle, n_triangles, 0): afterwards the context is
+ * indistinguishable from one that was given the same triangles through rz_refit_geometry, and ordering, synchronisation
+ * and RZ_ERR_BAD_SCENE (a bad materialIndex in the rest pose) are the refit's.  `bones` is n_bones x 16 floats, column-major
+ * like rz_update_transforms; `morph_weights` is n_morphs floats; both are host memory that is not retained, or -- with
+ * RZ_SKIN_DEVICE_ARGS -- device memory read on the context's stream (bones 16-byte aligned, morph_weights 4-byte aligned).
+ * The rest pose is private to the rig, so posing is never cumulative.  Several rigs may exist on disjoint ranges;
+ * rz_skin_destroy frees one, rz_destroy all of them.
+ *
+ * THE POSED TRIANGLE, bit for bit.  Binary32, one rounding per operation, no fused multiply-add.  All 64 bytes of the output
+ * triangle are the rest triangle's -- materialIndex and every pad word included -- except the xyz of the three corners.  Per corner:
+ *   morph   p = the rest corner; for k = 0 .. n_morphs-1 in order, per component c: p.c = p.c + w_k * d_k.c, with d_k the
+ *           corner's delta in target k (rz_morph_triangle.d, 4th word ignored).  Every target is applied, a zero weight included.
+ *   skin    with m the column-major matrix of a bone:  q.x = ((m[0]*p.x + m[4]*p.y) + m[8]*p.z) + m[12],
+ *           q.y = ((m[1]*p.x + m[5]*p.y) + m[9]*p.z) + m[13],  q.z = ((m[2]*p.x + m[6]*p.y) + m[10]*p.z) + m[14]; the fourth
+ *           row is ignored.  The corner's influences j = 0..3 are taken in order (bone index = bits 8j..8j+7 of the corner's word in
+ *           rz_skin_triangle.bones, weight = weights[corner][j]): an influence whose weight compares equal to 0 is skipped and
+ *           its bone is not read; the first kept influence gives out = w*q (three products), each later one out = out + w*q;
+ *           with no influence kept -- and in a rig without bones -- out = p.
+ * Weights are used as given: not normalised, negative and non-finite values flow through, and NaN or Inf in bones or weights
+ * gives whatever this arithmetic gives.  rzh_skin_triangles (librayzen_host.so) states the same on the host and the device
+ * result is held to its bytes.
+ *
+ * Every error below launches nothing and leaves the context as it was.  RZ_ERR_INVALID_ARG: a null context, NULL rig_out,
+ * n_triangles == 0, n_bones outside 1..256 with `skin` (or != 0 without), skin == NULL with n_morphs == 0, a negative n_morphs,
+ * NULL morphs with n_morphs > 0, an unknown (or destroyed) rig id, NULL bones for a rig with bones, NULL morph_weights for a rig
+ * with morphs, unknown flags, misaligned device arguments.  RZ_ERR_NOT_READY: binding 0 has not been uploaded (at pose: any
+ * binding the refit needs).  RZ_ERR_OUT_OF_RANGE: the range reaches past the end of binding 0 -- checked at create and again at
+ * pose, since binding 0 may have been uploaded anew and smaller -- or, at create, the bone index of a kept influence is
+ * >= n_bones (validated on the host there, so the kernel indexes without checks).  RZ_ERR_NO_MEMORY as everywhere.
+ * rz_skin_last_kernel_ms: device time of the skinning kernel of the context's last successful rz_skin_pose (synchronises on
+ * it); RZ_ERR_NOT_READY before the first.
+ * (Additive: no existing struct changed, so RZ_ABI_VERSION stays 5.) */
+typedef struct rz_skin_triangle {   /* 64 B, one per triangle of the rig; rz_sizeof(17) */
+    uint32_t bones[3];              /* per corner v0,v1,v2: four 8-bit bone indices, influence j in bits 8j..8j+7 */
+    uint32_t pad;
+    float    weights[3][4];         /* per corner: the four weights */
+} rz_skin_triangle;
+
+typedef struct rz_morph_triangle {  /* 48 B, one per triangle per target; rz_sizeof(18) */
+    float d[3][4];                  /* per corner: delta xyz, 4th word ignored */
+} rz_morph_triangle;
+
+#define RZ_SKIN_DEVICE_ARGS 1u   /* bones / morph_weights are device memory, read on the context's stream */
+int rz_skin_create(rz_ctx* ctx, size_t first_triangle, size_t n_triangles,
+                   const rz_triangle* rest,            /* host; NULL = binding 0's current content of that range */
+                   const rz_skin_triangle* skin,       /* host; NULL = a morph-only rig */
+                   int n_bones,                        /* 1..256 when skin != NULL, else 0 */
+                   const rz_morph_triangle* morphs,    /* host, target-major [n_morphs][n_triangles]; NULL with n_morphs 0 */
+                   int n_morphs, int* rig_out);
+int rz_skin_pose(rz_ctx* ctx, int rig, const float* bones, const float* morph_weights, unsigned flags);
+int rz_skin_destroy(rz_ctx* ctx, int rig);
+int rz_skin_last_kernel_ms(rz_ctx* ctx, float* ms);
+
 /* Copy a binding's current content back to the host in RayZen's own layout (after rz_update_transforms: the
  * instances / TLAS nodes / TLAS indices the device built).  out == NULL: only *needed is set. */
 int rz_read_binding(rz_ctx* ctx, rz_binding binding, void* out, size_t bytes, size_t* needed);
@@ -761,7 +821,8 @@ const char* rz_source_hash(void);
  * checks from other languages: which = 0 triangle, 1 node, 2 instance,
  * 3 material, 4 light, 5 frame_params, 6 counters, 7 ray, 8 hit,
  * 9 visibility, 10 editor_params, 11 denoise_params, 12 temporal_params,
- * 14 display_params, 15 display_info (13 is unassigned and returns 0, as every unknown index does). */
+ * 14 display_params, 15 display_info, 17 skin_triangle, 18 morph_triangle (13 and 16 are unassigned and return 0, as
+ * every unknown index does). */
 size_t rz_sizeof(int which);
 
 #ifdef __cplusplus

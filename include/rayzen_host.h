@@ -63,6 +63,13 @@ int  rzh_scene_update_dynamic(rzh_scene* s);
  * gets them and a refitted BLAS, then the world boxes and the TLAS are rebuilt with the transforms in force.  The byte
  * partner of rz_refit_geometry, as rzh_scene_update_dynamic is of rz_update_transforms.  0, or -1 (nothing touched). */
 int  rzh_scene_refit_mesh(rzh_scene* s, int mesh_id, const rz_triangle* tris, int n);
+/* Mesh::skin (no counterpart in the reference): out[t] = rest[t] posed by linear-blend skinning and / or morph targets,
+ * every bit as rayzen_hip.h states it for rz_skin_pose ("THE POSED TRIANGLE") -- the byte partner the device kernel is held
+ * to, as rzh_refit_blas is for the refit.  skin NULL: morphs only (n_bones 0); n_morphs 0: skin only; bones: n_bones x 16
+ * column-major floats; morphs: target-major [n_morphs][n].  out may be rest.  The result feeds rzh_scene_refit_mesh.
+ * 0; -1 on a null / inconsistent argument, -2 if a kept influence (weight != 0) names a bone >= n_bones (nothing is written). */
+int rzh_skin_triangles(const rz_triangle* rest, const rz_skin_triangle* skin, int n, const float* bones, int n_bones,
+                       const rz_morph_triangle* morphs, const float* morph_weights, int n_morphs, rz_triangle* out);
 /* pointer/size of a geometry array (bindings 0, 5, 6, 7, 8, 9); valid until
  * the next build/update/destroy */
 const void* rzh_scene_buffer(const rzh_scene* s, rz_binding b, size_t* bytes);

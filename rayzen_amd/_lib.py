@@ -24,6 +24,7 @@ HIP_SYMBOLS = (
     "rz_trace_rays", "rz_shadow_rays", "rz_render_editor", "rz_denoise", "rz_present_denoised", "rz_refit_geometry",
     "rz_denoise_temporal", "rz_present_temporal", "rz_temporal_reset", "rz_debug_read_temporal",
     "rz_display", "rz_present_display", "rz_display_reset", "rz_display_state",
+    "rz_skin_create", "rz_skin_pose", "rz_skin_destroy", "rz_skin_last_kernel_ms",
 )
 ABI_VERSION = 5         # RZ_ABI_VERSION of the include/rayzen_hip.h this file mirrors
 # the symbols include/rayzen_host.h declares
@@ -33,7 +34,7 @@ HOST_SYMBOLS = (
     "rzh_scene_build", "rzh_scene_set_blas_builder", "rzh_scene_update_dynamic", "rzh_scene_buffer", "rzh_scene_depths",
     "rzh_scene_save_cache", "rzh_scene_load_cache", "rzh_scene_build_cached",
     "rzh_camera_matrices", "rzh_mat_translate", "rzh_mat_scale", "rzh_mat_rotate", "rzh_mat_inverse",
-    "rzh_make_cube", "rzh_make_blob", "rzh_version", "rzh_refit_blas", "rzh_scene_refit_mesh",
+    "rzh_make_cube", "rzh_make_blob", "rzh_version", "rzh_refit_blas", "rzh_scene_refit_mesh", "rzh_skin_triangles",
 )
 
 
@@ -145,6 +146,20 @@ DISPLAY_TRANSFERS = {"linear": 0, "srgb": 1}
 DISPLAY_SOURCES = {"accum": 0, "denoise": 1, "temporal": 2}
 
 
+class SkinTriangle(C.Structure):
+    """rz_skin_triangle of include/rayzen_hip.h (64 B)."""
+    _fields_ = [("bones", C.c_uint32 * 3), ("pad", C.c_uint32), ("weights", (C.c_float * 4) * 3)]
+
+
+class MorphTriangle(C.Structure):
+    """rz_morph_triangle of include/rayzen_hip.h (48 B)."""
+    _fields_ = [("d", (C.c_float * 4) * 3)]
+
+
+SKIN_DEVICE_ARGS = 1                    # RZ_SKIN_DEVICE_ARGS
+SIZEOF_SKIN_TRIANGLE, SIZEOF_MORPH_TRIANGLE = 17, 18    # their rz_sizeof indices
+
+
 class Counters(C.Structure):
     """rz_counters of include/rayzen_hip.h."""
     _fields_ = [(n, C.c_uint64) for n in COUNTER_FIELDS]
@@ -230,7 +245,11 @@ def hip():
                                 ("rz_display", i, [vp, vp, vp, sz, vp, sz, vp, sz, C.c_uint]),
                                 ("rz_present_display", i, [vp, C.POINTER(PresentParams), vp, i, vp, vp, sz, vp, sz]),
                                 ("rz_display_reset", i, [vp]),
-                                ("rz_display_state", i, [vp, C.POINTER(DisplayInfo)])):
+                                ("rz_display_state", i, [vp, C.POINTER(DisplayInfo)]),
+                                ("rz_skin_create", i, [vp, sz, sz, vp, vp, i, vp, i, C.POINTER(i)]),
+                                ("rz_skin_pose", i, [vp, i, vp, vp, C.c_uint]),
+                                ("rz_skin_destroy", i, [vp, i]),
+                                ("rz_skin_last_kernel_ms", i, [vp, C.POINTER(C.c_float)])):
             try:
                 fn = getattr(L, name)
                 fn.restype, fn.argtypes = res, args
@@ -257,6 +276,7 @@ def host():
         L.rzh_build_tlas.restype, L.rzh_build_tlas.argtypes = i, [vp, i, vp, vp, C.POINTER(i)]
         L.rzh_refit_blas.restype, L.rzh_refit_blas.argtypes = i, [vp, i, vp, i, vp]
         L.rzh_scene_refit_mesh.restype, L.rzh_scene_refit_mesh.argtypes = i, [vp, i, vp, i]
+        L.rzh_skin_triangles.restype, L.rzh_skin_triangles.argtypes = i, [vp, vp, i, vp, i, vp, vp, i, vp]
         L.rzh_world_bounds.restype, L.rzh_world_bounds.argtypes = None, [vp, vp, vp, vp]
         L.rzh_scene_create.restype, L.rzh_scene_create.argtypes = vp, []
         L.rzh_scene_destroy.restype, L.rzh_scene_destroy.argtypes = None, [vp]

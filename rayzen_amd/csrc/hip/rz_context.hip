@@ -62,6 +62,14 @@ struct RefitView {
     std::vector<int> levelStart;    // ranks of tree level d: [levelStart[d], levelStart[d + 1]); empty: the root is a leaf
 };
 
+// One rig of rz_skin_create: the device copies rz_skin_pose's kernel reads (rz_skin.hip)
+struct SkinRig {
+    size_t first = 0, n = 0;        // its triangle range of binding 0
+    int nBones = 0, nMorphs = 0;    // nBones == 0: a morph-only rig (dSkin is empty)
+    DevBuf dRest, dSkin, dMorphs;
+    void release() { dRest.release(); dSkin.release(); dMorphs.release(); }
+};
+
 constexpr int kNumBindings = 10;
 size_t elem_size(int b) {
     switch (b) {
@@ -169,6 +177,13 @@ struct rz_ctx {
     DevBuf dRefitRank, dRefitInstView, dRefitViewOff, dRefitFlags, dRefitRoots;
     unsigned char* refitPinned = nullptr;   // per view: 4 flag words, then per view: its root node
     size_t refitPinnedCap = 0;
+    // rz_skin_create / rz_skin_pose (rz_skin.hip): the rigs by id, the posed triangles the refit is given, the bones and morph
+    // weights of a host-argument pose, and the events around the last pose's kernel
+    std::map<int, SkinRig> rigs;
+    int nextRig = 0;
+    DevBuf dSkinOut, dSkinBones, dSkinWeights;
+    hipEvent_t evSkin[2] = {nullptr, nullptr};
+    bool skinTimed = false;
 };
 
 namespace {
@@ -1011,6 +1026,8 @@ size_t rz_sizeof(int which) {
         case 12: return sizeof(rz_temporal_params);
         case 14: return sizeof(rz_display_params);       // (13 stays unassigned: callers probe it as the first unknown index)
         case 15: return sizeof(rz_display_info);
+        case 17: return sizeof(rz_skin_triangle);        // (16 stays unassigned too: probed as an unknown index)
+        case 18: return sizeof(rz_morph_triangle);
         default: return 0;
     }
 }
@@ -1054,8 +1071,10 @@ void rz_destroy(rz_ctx* c) {
                       &c->dRayOvf, &c->dRayIn, &c->dRayOut, &c->dRayInstOff, &c->dDnGuide, &c->dDnPing, &c->dDnPong, &c->dDnOut,
                       &c->dRefitRank, &c->dRefitInstView, &c->dRefitViewOff, &c->dRefitFlags, &c->dRefitRoots,
                       &c->dTmpCol[0], &c->dTmpCol[1], &c->dTmpMom[0], &c->dTmpMom[1], &c->dTmpHits[0], &c->dTmpHits[1],
-                      &c->dTmpInst[0], &c->dTmpInst[1], &c->dTmpSame, &c->dDisplay})
+                      &c->dTmpInst[0], &c->dTmpInst[1], &c->dTmpSame, &c->dDisplay, &c->dSkinOut, &c->dSkinBones, &c->dSkinWeights})
         b->release();
+    for (auto& kv : c->rigs) kv.second.release();
+    for (hipEvent_t e : c->evSkin) if (e) (void)hipEventDestroy(e);
     if (c->refitPinned) (void)hipHostFree(c->refitPinned);
     if (c->tlasHostCounts) (void)hipHostFree(c->tlasHostCounts);
     if (c->relayoutPinned) (void)hipHostFree(c->relayoutPinned);
@@ -1369,6 +1388,14 @@ static int refit_on_host(rz_ctx* c, const rz_triangle* triangles, size_t first, 
     return refit_tlas_step(c);
 }
 
+// the first binding a refit needs that has not been uploaded, or -1 (rz_skin_pose asks before it launches anything)
+static int refit_missing_binding(const rz_ctx* c) {
+    for (int b : {RZ_BIND_TRIANGLES, RZ_BIND_BLAS_NODES, RZ_BIND_BLAS_INDICES, RZ_BIND_INSTANCES, RZ_BIND_MATERIALS, RZ_BIND_LIGHTS,
+                  RZ_BIND_TLAS_NODES, RZ_BIND_TLAS_INDICES})
+        if (!c->present[b]) return b;
+    return -1;
+}
+
 static int refit_geometry_impl(rz_ctx* c, const rz_triangle* triangles, size_t first, size_t n, unsigned flags) {
     const char* what = "rz_refit_geometry";
     if (!c) return fail(nullptr, RZ_ERR_INVALID_ARG, "%s: null context", what);
@@ -1376,9 +1403,7 @@ static int refit_geometry_impl(rz_ctx* c, const rz_triangle* triangles, size_t f
     if (n && !triangles) return fail(c, RZ_ERR_INVALID_ARG, "%s: null triangles", what);
     const bool hostPtr = (flags & RZ_REFIT_HOST) != 0;
     if (n && !hostPtr && (reinterpret_cast<uintptr_t>(triangles) & 15u)) return fail(c, RZ_ERR_INVALID_ARG, "%s: the device pointer must be 16-byte aligned", what);
-    for (int b : {RZ_BIND_TRIANGLES, RZ_BIND_BLAS_NODES, RZ_BIND_BLAS_INDICES, RZ_BIND_INSTANCES, RZ_BIND_MATERIALS, RZ_BIND_LIGHTS,
-                  RZ_BIND_TLAS_NODES, RZ_BIND_TLAS_INDICES})
-        if (!c->present[b]) return fail(c, RZ_ERR_NOT_READY, "%s: no scene (binding %d has not been uploaded)", what, b);
+    { const int b = refit_missing_binding(c); if (b >= 0) return fail(c, RZ_ERR_NOT_READY, "%s: no scene (binding %d has not been uploaded)", what, b); }
     const size_t nTris = hostCount<rz_triangle>(c, RZ_BIND_TRIANGLES);
     if (first > nTris || n > nTris - first)
         return fail(c, RZ_ERR_OUT_OF_RANGE, "%s: triangles [%zu,+%zu) past the %zu of binding 0", what, first, n, nTris);
@@ -1503,6 +1528,143 @@ static int refit_geometry_impl(rz_ctx* c, const rz_triangle* triangles, size_t f
         c->geomDirty = true;            // what a fresh upload of these triangles says, now and at every later call
         return fail(c, RZ_ERR_BAD_SCENE, "%s: triangle %d has a materialIndex outside the %d materials uploaded", what, badTri, nMat);
     }
+    return RZ_OK;
+}
+
+// ---- rz_skin_create / rz_skin_pose / rz_skin_destroy ---------------------------------------------------------------
+static int skin_create_impl(rz_ctx* c, size_t first, size_t n, const rz_triangle* rest, const rz_skin_triangle* skin, int nBones,
+                            const rz_morph_triangle* morphs, int nMorphs, int* rigOut) {
+    const char* what = "rz_skin_create";
+    if (!c) return fail(nullptr, RZ_ERR_INVALID_ARG, "%s: null context", what);
+    if (!rigOut) return fail(c, RZ_ERR_INVALID_ARG, "%s: null rig_out", what);
+    if (n == 0) return fail(c, RZ_ERR_INVALID_ARG, "%s: no triangles", what);
+    if (skin ? (nBones < 1 || nBones > 256) : nBones != 0)
+        return fail(c, RZ_ERR_INVALID_ARG, "%s: n_bones = %d (1..256 with skin, 0 without)", what, nBones);
+    if (nMorphs < 0 || (nMorphs > 0 && !morphs)) return fail(c, RZ_ERR_INVALID_ARG, "%s: n_morphs = %d, morphs %s", what, nMorphs, morphs ? "given" : "NULL");
+    if (!skin && nMorphs == 0) return fail(c, RZ_ERR_INVALID_ARG, "%s: neither skin nor morph targets", what);
+    if (!c->present[RZ_BIND_TRIANGLES]) return fail(c, RZ_ERR_NOT_READY, "%s: binding 0 has not been uploaded", what);
+    const size_t nTris = hostCount<rz_triangle>(c, RZ_BIND_TRIANGLES);
+    if (first > nTris || n > nTris - first)
+        return fail(c, RZ_ERR_OUT_OF_RANGE, "%s: triangles [%zu,+%zu) past the %zu of binding 0", what, first, n, nTris);
+    if ((size_t)nMorphs > (std::numeric_limits<size_t>::max() / sizeof(rz_morph_triangle)) / n)
+        return fail(c, RZ_ERR_INVALID_ARG, "%s: %d morph targets of %zu triangles", what, nMorphs, n);
+    if (skin) {
+        for (size_t t = 0; t < n; ++t)
+            for (int k = 0; k < 3; ++k)
+                for (int j = 0; j < 4; ++j) {
+                    const int b = (int)((skin[t].bones[k] >> (8 * j)) & 255u);
+                    if (!(skin[t].weights[k][j] == 0.0f) && b >= nBones)
+                        return fail(c, RZ_ERR_OUT_OF_RANGE, "%s: triangle %zu, corner %d, influence %d names bone %d of %d", what, t, k, j, b, nBones);
+                }
+    }
+    if (!rest) {        // binding 0 as it stands (after a device-pointer refit only the device holds it: fetched first)
+        const int rc = sync_tris_host(c);
+        if (rc != RZ_OK) return rc;
+        rest = hostArr<rz_triangle>(c, RZ_BIND_TRIANGLES) + first;
+    }
+    RZ_HIP(c, hipSetDevice(c->device));
+    alloc_point(c);
+    SkinRig R;
+    R.first = first; R.n = n; R.nBones = nBones; R.nMorphs = nMorphs;
+    struct Part { DevBuf* buf; const void* src; size_t bytes; };
+    const Part parts[3] = {{&R.dRest, rest, n * sizeof(rz_triangle)},
+                           {&R.dSkin, skin, skin ? n * sizeof(rz_skin_triangle) : 0},
+                           {&R.dMorphs, morphs, (size_t)nMorphs * n * sizeof(rz_morph_triangle)}};
+    for (const Part& P : parts) {
+        if (!P.bytes) continue;
+        hipError_t e = hipMalloc(&P.buf->p, P.bytes);
+        if (e == hipSuccess) { P.buf->cap = P.bytes; e = hipMemcpy(P.buf->p, P.src, P.bytes, hipMemcpyHostToDevice); }
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            R.release();
+            return fail(c, RZ_ERR_HIP, "%s: %zu bytes of device memory: %s", what, P.bytes, hipGetErrorString(e));
+        }
+    }
+    const int id = c->nextRig;
+    try { c->rigs.emplace(id, R); } catch (...) { R.release(); throw; }
+    ++c->nextRig;
+    *rigOut = id;
+    return RZ_OK;
+}
+
+static int skin_pose_impl(rz_ctx* c, int rig, const float* bones, const float* morphWeights, unsigned flags) {
+    const char* what = "rz_skin_pose";
+    if (!c) return fail(nullptr, RZ_ERR_INVALID_ARG, "%s: null context", what);
+    if (flags & ~RZ_SKIN_DEVICE_ARGS) return fail(c, RZ_ERR_INVALID_ARG, "%s: unknown flags 0x%x", what, flags);
+    const auto it = c->rigs.find(rig);
+    if (it == c->rigs.end()) return fail(c, RZ_ERR_INVALID_ARG, "%s: no rig %d", what, rig);
+    const SkinRig& R = it->second;
+    if (R.nBones && !bones) return fail(c, RZ_ERR_INVALID_ARG, "%s: null bones for a rig with %d bones", what, R.nBones);
+    if (R.nMorphs && !morphWeights) return fail(c, RZ_ERR_INVALID_ARG, "%s: null morph_weights for a rig with %d targets", what, R.nMorphs);
+    const bool devArgs = (flags & RZ_SKIN_DEVICE_ARGS) != 0;
+    if (devArgs && ((R.nBones && (reinterpret_cast<uintptr_t>(bones) & 15u)) || (R.nMorphs && (reinterpret_cast<uintptr_t>(morphWeights) & 3u))))
+        return fail(c, RZ_ERR_INVALID_ARG, "%s: device bones must be 16-byte aligned, device morph_weights 4-byte aligned", what);
+    { const int b = refit_missing_binding(c); if (b >= 0) return fail(c, RZ_ERR_NOT_READY, "%s: no scene (binding %d has not been uploaded)", what, b); }
+    const size_t nTris = hostCount<rz_triangle>(c, RZ_BIND_TRIANGLES);
+    if (R.first > nTris || R.n > nTris - R.first)
+        return fail(c, RZ_ERR_OUT_OF_RANGE, "%s: rig %d poses triangles [%zu,+%zu), binding 0 has %zu now", what, rig, R.first, R.n, nTris);
+    RZ_HIP(c, hipSetDevice(c->device));
+    alloc_point(c);
+    int rc;
+    if ((rc = ensure(c, c->dSkinOut, R.n * sizeof(rz_triangle))) != RZ_OK) return rc;
+    for (hipEvent_t& e : c->evSkin)
+        if (!e) RZ_HIP(c, hipEventCreate(&e));
+    bool staged = false;            // a host argument is on its way to the device: the caller's memory must outlive the copy
+    if (!devArgs) {
+        if (R.nBones) {
+            if ((rc = ensure(c, c->dSkinBones, (size_t)R.nBones * 64)) != RZ_OK) return rc;
+        }
+        if (R.nMorphs) {
+            if ((rc = ensure(c, c->dSkinWeights, (size_t)R.nMorphs * 4)) != RZ_OK) return rc;
+        }
+        if (R.nBones) RZ_HIP(c, hipMemcpyAsync(c->dSkinBones.p, bones, (size_t)R.nBones * 64, hipMemcpyHostToDevice, c->stream));
+        if (R.nMorphs) {
+            const hipError_t e = hipMemcpyAsync(c->dSkinWeights.p, morphWeights, (size_t)R.nMorphs * 4, hipMemcpyHostToDevice, c->stream);
+            if (e != hipSuccess) { (void)hipStreamSynchronize(c->stream); return fail(c, RZ_ERR_HIP, "%s: %s", what, hipGetErrorString(e)); }
+        }
+        staged = true;
+    }
+    SkinWork W{};
+    W.rest = static_cast<const rz_triangle*>(R.dRest.p);
+    W.skin = R.nBones ? static_cast<const rz_skin_triangle*>(R.dSkin.p) : nullptr;
+    W.bones = devArgs ? bones : static_cast<const float*>(c->dSkinBones.p);
+    W.nBones = R.nBones;
+    W.morphs = static_cast<const rz_morph_triangle*>(R.dMorphs.p);
+    W.morphWeights = devArgs ? morphWeights : static_cast<const float*>(c->dSkinWeights.p);
+    W.nMorphs = R.nMorphs;
+    W.n = (long long)R.n;
+    W.out = static_cast<rz_triangle*>(c->dSkinOut.p);
+    c->skinTimed = false;
+    hipError_t e = hipEventRecord(c->evSkin[0], c->stream);
+    const int ke = e == hipSuccess ? skin_device(W, c->stream) : 0;
+    if (e == hipSuccess && ke == 0) e = hipEventRecord(c->evSkin[1], c->stream);
+    if (e != hipSuccess || ke != 0) {
+        if (staged) (void)hipStreamSynchronize(c->stream);
+        return fail(c, RZ_ERR_HIP, "%s: %s", what, hipGetErrorString(e != hipSuccess ? e : (hipError_t)(-ke)));
+    }
+    c->skinTimed = true;
+    // ... and from here on the call IS rz_refit_geometry on a device pointer (its TLAS step synchronises the stream)
+    rc = refit_geometry_impl(c, W.out, R.first, R.n, 0);
+    if (rc != RZ_OK && staged) (void)hipStreamSynchronize(c->stream);
+    return rc;
+}
+
+static int skin_destroy_impl(rz_ctx* c, int rig) {
+    if (!c) return fail(nullptr, RZ_ERR_INVALID_ARG, "rz_skin_destroy: null context");
+    const auto it = c->rigs.find(rig);
+    if (it == c->rigs.end()) return fail(c, RZ_ERR_INVALID_ARG, "rz_skin_destroy: no rig %d", rig);
+    RZ_HIP(c, hipSetDevice(c->device));
+    RZ_HIP(c, hipStreamSynchronize(c->stream));     // (a pose in flight reads the rig's buffers)
+    it->second.release();
+    c->rigs.erase(it);
+    return RZ_OK;
+}
+
+static int skin_last_kernel_ms_impl(rz_ctx* c, float* ms) {
+    if (!c || !ms) return fail(c, RZ_ERR_INVALID_ARG, "rz_skin_last_kernel_ms: null argument");
+    if (!c->skinTimed) return fail(c, RZ_ERR_NOT_READY, "rz_skin_last_kernel_ms: no rz_skin_pose has run yet");
+    RZ_HIP(c, hipEventSynchronize(c->evSkin[1]));
+    RZ_HIP(c, hipEventElapsedTime(ms, c->evSkin[0], c->evSkin[1]));
     return RZ_OK;
 }
 
@@ -2678,6 +2840,19 @@ int rz_update_transforms(rz_ctx* c, const float* transforms, size_t n) {
 }
 int rz_refit_geometry(rz_ctx* c, const rz_triangle* triangles, size_t first_triangle, size_t n_triangles, unsigned flags) {
     return guarded(c, "rz_refit_geometry", [&] { return refit_geometry_impl(c, triangles, first_triangle, n_triangles, flags); });
+}
+int rz_skin_create(rz_ctx* c, size_t first_triangle, size_t n_triangles, const rz_triangle* rest, const rz_skin_triangle* skin, int n_bones,
+                   const rz_morph_triangle* morphs, int n_morphs, int* rig_out) {
+    return guarded(c, "rz_skin_create", [&] { return skin_create_impl(c, first_triangle, n_triangles, rest, skin, n_bones, morphs, n_morphs, rig_out); });
+}
+int rz_skin_pose(rz_ctx* c, int rig, const float* bones, const float* morph_weights, unsigned flags) {
+    return guarded(c, "rz_skin_pose", [&] { return skin_pose_impl(c, rig, bones, morph_weights, flags); });
+}
+int rz_skin_destroy(rz_ctx* c, int rig) {
+    return guarded(c, "rz_skin_destroy", [&] { return skin_destroy_impl(c, rig); });
+}
+int rz_skin_last_kernel_ms(rz_ctx* c, float* ms) {
+    return guarded(c, "rz_skin_last_kernel_ms", [&] { return skin_last_kernel_ms_impl(c, ms); });
 }
 int rz_build_blas(rz_ctx* c, const rz_triangle* tris, size_t n, rz_bvh_node* nodes_out, size_t nodes_cap, int32_t* indices_out, size_t* n_nodes, int* depth, float* device_ms) {
     return guarded(c, "rz_build_blas", [&] { return build_blas_impl(c, tris, n, nodes_out, nodes_cap, indices_out, n_nodes, depth, device_ms); });

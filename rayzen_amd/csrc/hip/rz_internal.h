@@ -217,6 +217,20 @@ int refit_view_device(const RefitViewWork& W, hipStream_t s);
 int refit_roots_device(DevInstance* inst, int nInst, const int32_t* instView, const int32_t* viewNodeOff, int nViews,
                        const rz_bvh_node* nodes, const unsigned* vflags, rz_bvh_node* rootsOut, hipStream_t s);
 
+// ---- rz_skin.hip
+struct SkinWork {               // one rig posed: every pointer is device memory
+    const rz_triangle* rest;            // n rest triangles
+    const rz_skin_triangle* skin;       // n, or null: a morph-only rig
+    const float* bones;                 // nBones x 16, column-major, 16-byte aligned (unused without `skin`)
+    int nBones;
+    const rz_morph_triangle* morphs;    // target-major [nMorphs][n]
+    const float* morphWeights;          // nMorphs
+    int nMorphs;
+    long long n;
+    rz_triangle* out;                   // n posed triangles
+};
+int skin_device(const SkinWork& W, hipStream_t s);
+
 // ---- rz_present.hip
 struct ProjBox;                 // screen-space corners of one box (rz_present.hip)
 struct PresentParams {

@@ -36,6 +36,15 @@ public:
     std::vector<Triangle> triangles;
     // Mesh.cpp:6-50.  Returns false (and leaves the mesh empty) if the file cannot be opened.
     bool loadFromOBJ(const std::string& filename, int materialIndex);
+    // Linear-blend skinning and morph targets (no counterpart in the reference): out[t] = rest[t] posed, every bit as
+    // include/rayzen_hip.h states it for rz_skin_pose -- the byte partner of that call's kernel.  skin may be null (morphs
+    // only), nMorphs may be 0; bones: 16 column-major floats each; morphs: target-major [nMorphs][n].  Nothing is
+    // range-checked here (rzh_skin_triangles checks the bone indices of kept influences first).  out may be rest.
+    static void skin(const Triangle* rest, size_t n, const rz_skin_triangle* skin, const float* bones, const rz_morph_triangle* morphs,
+                     const float* morphWeights, int nMorphs, Triangle* out);
+    // ... this mesh = restPose posed (skinData empty: morphs only; morphs holds morphWeights.size() targets of restPose's size)
+    void pose(const Mesh& restPose, const std::vector<rz_skin_triangle>& skinData, const std::vector<mat4>& bones,
+              const std::vector<rz_morph_triangle>& morphs, const std::vector<float>& morphWeights);
 };
 
 struct BVHNode {

@@ -137,6 +137,25 @@ public:
               "rz_refit_geometry");
     }
     void refitAll() { check(rz_refit_geometry(ctx_, nullptr, 0, 0, 0), "rz_refit_geometry"); }
+    // Skinned meshes (rz_skin_create / rz_skin_pose; the reference has no counterpart): a rig keeps the rest pose of the
+    // triangles [firstTriangle, +rest.size()) of binding 0 on the device with their bone indices / weights (skin, one per
+    // triangle; empty: a morph-only rig) and morph targets (target-major, morphs.size() / rest.size() of them).  poseRig
+    // skins on the device and refits what moved, TLAS included; nothing but the bones (64 B each) and the morph weights
+    // crosses to the device per frame.  As with refitMesh the host copies in buffers_ are NOT updated.
+    int createRig(size_t firstTriangle, const std::vector<Triangle>& rest, const std::vector<rz_skin_triangle>& skin, int nBones,
+                  const std::vector<rz_morph_triangle>& morphs = {}) {
+        int rig = -1;
+        const size_t n = rest.size();
+        check(rz_skin_create(ctx_, firstTriangle, n, reinterpret_cast<const rz_triangle*>(rest.data()), skin.empty() ? nullptr : skin.data(),
+                             nBones, morphs.empty() ? nullptr : morphs.data(), n ? (int)(morphs.size() / n) : 0, &rig),
+              "rz_skin_create");
+        return rig;
+    }
+    void poseRig(int rig, const std::vector<mat4>& bones, const std::vector<float>& morphWeights = {}) {
+        check(rz_skin_pose(ctx_, rig, bones.empty() ? nullptr : bones[0].m, morphWeights.empty() ? nullptr : morphWeights.data(), 0),
+              "rz_skin_pose");
+    }
+    void destroyRig(int rig) { check(rz_skin_destroy(ctx_, rig), "rz_skin_destroy"); }
     void sendSceneDataToShader(const Scene& scene, int width, int height, int bounceBudget, int spp = 1,
                                int sampleBase = 0, int tileRank = 0, int tileNRanks = 1) {
         rz_frame_params p{};

@@ -145,6 +145,20 @@ int rzh_scene_refit_mesh(rzh_scene* s, int mesh_id, const rz_triangle* tris, int
     return s->buffers.refitMesh(s->scene, &m) ? 0 : -1;
 }
 
+int rzh_skin_triangles(const rz_triangle* rest, const rz_skin_triangle* skin, int n, const float* bones, int n_bones,
+                       const rz_morph_triangle* morphs, const float* morph_weights, int n_morphs, rz_triangle* out) {
+    if (n < 0 || n_morphs < 0 || (n > 0 && (!rest || !out))) return -1;
+    if (skin ? (n_bones < 1 || n_bones > 256 || !bones) : n_bones != 0) return -1;
+    if (n_morphs > 0 && (!morph_weights || (n > 0 && !morphs))) return -1;
+    if (skin)
+        for (int t = 0; t < n; ++t)
+            for (int k = 0; k < 3; ++k)
+                for (int j = 0; j < 4; ++j)
+                    if (!(skin[t].weights[k][j] == 0.0f) && (int)((skin[t].bones[k] >> (8 * j)) & 255u) >= n_bones) return -2;
+    Mesh::skin(reinterpret_cast<const Triangle*>(rest), (size_t)n, skin, bones, morphs, morph_weights, n_morphs, reinterpret_cast<Triangle*>(out));
+    return 0;
+}
+
 const void* rzh_scene_buffer(const rzh_scene* s, rz_binding b, size_t* bytes) {
     if (!s || !s->built) { if (bytes) *bytes = 0; return nullptr; }
     const SceneBuffers& B = s->buffers;

@@ -11,7 +11,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .scene import BINDING_DTYPES, BIND_INSTANCES, BIND_TLAS_INDICES, BIND_TLAS_NODES
+from .scene import BINDING_DTYPES, BIND_INSTANCES, BIND_TLAS_INDICES, BIND_TLAS_NODES, MORPH_TRIANGLE, SKIN_TRIANGLE
 
 
 class RayZenError(RuntimeError):
@@ -157,6 +157,53 @@ class Renderer:
     def refit_geometry_device(self, ptr, first, n):
         """rz_refit_geometry on device memory (rz_triangle[n], 16-B aligned), enqueued on the context's stream."""
         self._check(self._L.rz_refit_geometry(self._c, C.c_void_p(ptr), int(first), int(n), 0), "rz_refit_geometry")
+
+    def skin_create(self, first, rest, skin, n_bones, morphs=None):
+        """rz_skin_create: a rig for the triangles [first, first + n) of binding 0.  rest: their rest pose (TRIANGLE dtype), or
+        an int n -- then binding 0's current content of that range is the rest pose; skin: SKIN_TRIANGLE per triangle, or None
+        for a morph-only rig (n_bones 0); morphs: MORPH_TRIANGLE [n_morphs, n] or None.  Everything is copied to the device.
+        Returns the rig id."""
+        if isinstance(rest, (int, np.integer)):
+            n, rest_ptr = int(rest), None
+        else:
+            rest = np.ascontiguousarray(rest)
+            assert rest.dtype.itemsize == 64
+            n, rest_ptr = rest.shape[0], rest.ctypes.data
+        skin_ptr = None
+        if skin is not None:
+            skin = np.ascontiguousarray(skin, SKIN_TRIANGLE)
+            assert skin.shape == (n,)
+            skin_ptr = skin.ctypes.data
+        n_morphs, morph_ptr = 0, None
+        if morphs is not None and len(morphs):
+            morphs = np.ascontiguousarray(morphs, MORPH_TRIANGLE).reshape(-1, n)
+            n_morphs, morph_ptr = morphs.shape[0], morphs.ctypes.data
+        rig = C.c_int(-1)
+        self._check(self._L.rz_skin_create(self._c, int(first), n, rest_ptr, skin_ptr, int(n_bones), morph_ptr, n_morphs, C.byref(rig)),
+                    "rz_skin_create")
+        return rig.value
+
+    def skin_pose(self, rig, bones=None, morph_weights=None):
+        """rz_skin_pose from host memory: the rig's mesh is posed on the device (bones: n_bones x 16 column-major floats,
+        morph_weights: n_morphs floats) and refitted as rz_refit_geometry refits it, TLAS included."""
+        b = None if bones is None else np.ascontiguousarray(bones, np.float32).reshape(-1)
+        w = None if morph_weights is None else np.ascontiguousarray(morph_weights, np.float32).reshape(-1)
+        self._check(self._L.rz_skin_pose(self._c, int(rig), None if b is None else b.ctypes.data, None if w is None else w.ctypes.data, 0),
+                    "rz_skin_pose")
+
+    def skin_pose_device(self, rig, bones_ptr, weights_ptr):
+        """rz_skin_pose with RZ_SKIN_DEVICE_ARGS: bones (16-B aligned) and morph weights are device memory, read on the stream."""
+        self._check(self._L.rz_skin_pose(self._c, int(rig), C.c_void_p(bones_ptr), C.c_void_p(weights_ptr), _lib.SKIN_DEVICE_ARGS),
+                    "rz_skin_pose")
+
+    def skin_destroy(self, rig):
+        self._check(self._L.rz_skin_destroy(self._c, int(rig)), "rz_skin_destroy")
+
+    def skin_last_kernel_ms(self):
+        """Device time of the skinning kernel of the last skin_pose (synchronises on it)."""
+        ms = C.c_float(0)
+        self._check(self._L.rz_skin_last_kernel_ms(self._c, C.byref(ms)), "rz_skin_last_kernel_ms")
+        return ms.value
 
     def build_blas(self, triangles):
         """BVH::buildBLAS (BVH.cpp:99-175, SAH) on the device.  triangles: TRIANGLE_DTYPE array.

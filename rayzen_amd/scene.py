@@ -16,6 +16,8 @@ from . import _lib
 # SSBO element types (include/rayzen_hip.h; RayZen/include/{Mesh,BVH,Material,Light}.h)
 TRIANGLE = np.dtype([("v0", "<f4", 3), ("pad0", "<f4"), ("v1", "<f4", 3), ("pad1", "<f4"),
                      ("v2", "<f4", 3), ("pad2", "<f4"), ("materialIndex", "<i4"), ("tail_pad", "<i4", 3)])
+SKIN_TRIANGLE = np.dtype([("bones", "<u4", 3), ("pad", "<u4"), ("weights", "<f4", (3, 4))])      # rz_skin_triangle
+MORPH_TRIANGLE = np.dtype([("d", "<f4", (3, 4))])                                                   # rz_morph_triangle
 BVH_NODE = np.dtype([("boundsMin", "<f4", 3), ("leftFirst", "<i4"), ("boundsMax", "<f4", 3), ("count", "<i4")])
 BVH_INSTANCE = np.dtype([("blasNodeOffset", "<i4"), ("blasTriOffset", "<i4"), ("meshIndex", "<i4"),
                          ("globalTriOffset", "<i4"), ("transform", "<f4", 16), ("inverseTransform", "<f4", 16)])
@@ -134,6 +136,39 @@ def refit_blas(tris, nodes, idx):
     n = tris.shape[0]
     if _lib.host().rzh_refit_blas(_p(tris) if n else None, n, _p(out), out.shape[0], _p(idx) if n else None) != 0:
         raise RuntimeError("rzh_refit_blas failed (inconsistent arrays)")
+    return out
+
+
+def pack_bones(indices):
+    """Four 8-bit bone indices per corner -> the words of SKIN_TRIANGLE["bones"]: indices[..., j] goes to bits 8j..8j+7."""
+    b = np.asarray(indices).astype(np.uint32)
+    assert b.shape[-1] == 4 and (b < 256).all()
+    return (b[..., 0] | (b[..., 1] << 8) | (b[..., 2] << 16) | (b[..., 3] << 24)).astype(np.uint32)
+
+
+def skin_triangles(rest, skin=None, bones=None, morphs=None, morph_weights=None):
+    """Mesh::skin (librayzen_host.so: rzh_skin_triangles): `rest` posed by linear-blend skinning (skin: SKIN_TRIANGLE per
+    triangle, bones: n_bones x 16 column-major) and / or morph targets (morphs: MORPH_TRIANGLE [n_morphs, n], morph_weights).
+    The byte partner of Renderer.skin_pose; its result is what Scene.refit_mesh takes."""
+    rest = np.ascontiguousarray(rest, TRIANGLE)
+    n = rest.shape[0]
+    out = np.zeros(n, TRIANGLE)
+    sk = bn = mo = mw = None
+    n_bones = n_morphs = 0
+    if skin is not None:
+        sk = np.ascontiguousarray(skin, SKIN_TRIANGLE)
+        bn = np.ascontiguousarray(bones, np.float32).reshape(-1, 16)
+        n_bones = bn.shape[0]
+        assert sk.shape == (n,)
+    if morphs is not None and len(morphs):
+        mo = np.ascontiguousarray(morphs, MORPH_TRIANGLE).reshape(-1, n)
+        mw = np.ascontiguousarray(morph_weights, np.float32).reshape(-1)
+        n_morphs = mo.shape[0]
+        assert mw.shape[0] == n_morphs
+    rc = _lib.host().rzh_skin_triangles(_p(rest) if n else None, None if sk is None else _p(sk), n, None if bn is None else _p(bn), n_bones,
+                                        None if mo is None or not n else _p(mo), None if mw is None else _p(mw), n_morphs, _p(out) if n else None)
+    if rc != 0:
+        raise RuntimeError("rzh_skin_triangles: " + ("a kept influence names a bone outside the table" if rc == -2 else "inconsistent arguments"))
     return out
 
 
