@@ -321,6 +321,84 @@ int rz_skin_pose(rz_ctx* ctx, int rig, const float* bones, const float* morph_we
 int rz_skin_destroy(rz_ctx* ctx, int rig);
 int rz_skin_last_kernel_ms(rz_ctx* ctx, float* ms);
 
+/* BLAS quality: how far the tree of every mesh has degraded, measured on the device.  (No counterpart in the reference, which
+ * deforms nothing.)  rz_refit_geometry and rz_skin_pose keep a tree's topology while its boxes grow; the measure is the tree's
+ * SAH cost, the quantity BVH::buildBLAS minimises greedily, next to the cost the same tree had when it was handed over.
+ *
+ * One record per mesh -- a distinct (blasNodeOffset, blasTriOffset, globalTriOffset) among the uploaded instances, however
+ * many instances share it -- in ascending order of (node_offset_before, index_offset, tri_offset).  out == NULL: only
+ * *n_meshes is set.  `cap` smaller than the mesh count: RZ_ERR_INVALID_ARG, nothing done.
+ *
+ * THE COST.  Area of a node's box, from its binary32 bounds in binding 7: d = (double)max - (double)min per axis,
+ * A = 2 (dx dy + dy dz + dz dx) in binary64 (the expression of BVH.cpp:32-35); A = 0 when any d fails d >= 0 (an inverted or
+ * NaN box, the count == 0 root of an empty mesh).  Over the nodes reachable from the mesh's root, with traversal and
+ * intersection cost both 1:
+ *     cost = (sum over internal nodes of A(n) + sum over leaves of A(n) * count) / A(root),     cost = 0 when A(root) == 0.
+ * Infinities flow through IEEE arithmetic.  The order of the sum is not fixed; the result is within 1e-9 relative of the
+ * exactly rounded sum (at most 2^21 non-negative terms x 2^-53 per addition, plus the few roundings per term), and two calls
+ * on an unchanged context return identical bytes: the device sums per-workgroup partials that are stored and then added in
+ * index order, without floating-point atomics (rz_quality.hip).  BVH::sahCost / rzh_blas_sah_cost (librayzen_host.so)
+ * state the same on the host.
+ *
+ * sah_cost_built is the cost measured the first time the library looks at the mesh after its tree was last handed over or
+ * built: after rz_upload / rz_update on binding 7 or 8, after rz_build_geometry, after an instance upload that introduces
+ * a new triple.  rz_refit_geometry and rz_skin_pose take that look before they move a box of a mesh, on either of their
+ * routes; upload -> refit -> refit -> quality therefore reports the uploaded tree's cost.  That look is one extra pass in the
+ * first refit after a hand-over, the only thing existing calls gain, and it changes none of their results.
+ *
+ * The call needs the bindings the refit needs (else RZ_ERR_NOT_READY), brings a pending layout up to date as the refit
+ * does, runs on the context's stream -- ordered with refits and renders on it -- and synchronises it, because the records
+ * come back.  It touches no scene, layout or render state: rz_read_binding, rz_debug_read_layout, the accumulation buffer
+ * and rz_debug_last_plan are byte-identical before and after.  A context whose layout is host-side (RZ_FLAG_HOST_RELAYOUT,
+ * or the fallback) computes the same definition on its host copies.
+ * (Additive: no existing struct changed, so RZ_ABI_VERSION stays 5.) */
+#define RZ_QUALITY_REBUILT 1u           /* rz_mesh_quality::flags: this call rebuilt the mesh (rz_rebuild_geometry only) */
+typedef struct rz_mesh_quality {        /* 64 B; rz_sizeof(20) */
+    int32_t  node_offset, index_offset, tri_offset;  /* the mesh = its instances' (blasNodeOffset, blasTriOffset, globalTriOffset), AFTER the call */
+    int32_t  node_offset_before;        /* blasNodeOffset before the call (differs only after a rebuild of this or an earlier mesh) */
+    int32_t  n_triangles;               /* the slots its leaves name */
+    int32_t  n_nodes;                   /* nodes reachable from its root */
+    int32_t  depth;                     /* longest root-to-leaf path, in nodes (a root that is a leaf: 1) */
+    uint32_t flags;                     /* RZ_QUALITY_REBUILT */
+    double   sah_cost;                  /* of the tree as it stands after the call */
+    double   sah_cost_built;            /* of the tree when it was last built or handed over (above) */
+    double   sah_cost_before;           /* of the tree at entry (== sah_cost unless rebuilt) */
+    double   reserved;                  /* 0 */
+} rz_mesh_quality;
+int rz_geometry_quality(rz_ctx* ctx, rz_mesh_quality* out, size_t cap, size_t* n_meshes);
+
+/* The exit from the refit's steady state: rebuild, on the device, only the meshes whose tree has degraded, from binding 0 as it
+ * stands there -- triangles posed by rz_skin_pose never visit the host -- with instances and TLAS following.
+ *   1. measures as rz_geometry_quality does (same records, same `out` / `cap` / `n_meshes` rules);
+ *   2. selects every mesh for which  sah_cost <= max_ratio * sah_cost_built  is false: max_ratio == 0 selects every mesh with
+ *      a non-zero cost.  A greedy SAH rebuild is not always cheaper than the refitted tree, so the call reports both costs
+ *      and promises no gain;
+ *   3. nothing selected: the context is untouched, RZ_OK, all flags clear;
+ *   4. else builds new bindings 7 and 8.  Meshes are taken in ascending blasNodeOffset; a mesh's node extent is
+ *      [blasNodeOffset, the next larger distinct blasNodeOffset or the end of binding 7).  A selected mesh contributes
+ *      BVH::buildBLAS (the device builder of rz_build_blas: RayZen's bytes) of triangles [globalTriOffset, + n_triangles) of
+ *      binding 0, and its n_triangles indices go to [blasTriOffset, + n_triangles) of binding 8, which keeps its size; an
+ *      unselected mesh contributes its extent verbatim (leftFirst is mesh-relative), shifted -- a rebuilt tree has another
+ *      node count.  Nodes in front of the first mesh stay.  The blasNodeOffset of every instance is patched; nothing else in
+ *      binding 9 changes.  Then the re-layout runs and world boxes and TLAS are rebuilt with the transforms in force,
+ *      exactly as rz_refit_geometry does.  Where the layout is made on the device, builder and re-layout both read
+ *      binding 0 from the device copy as it stands: it is neither fetched to the host nor uploaded again (a context with
+ *      RZ_FLAG_HOST_RELAYOUT works on its host copies throughout).
+ * Afterwards the context is indistinguishable from a fresh one given binding 0 as it stands and the new 7, 8 and 9, followed
+ * by rz_update_transforms with the transforms in force: bindings, layout arrays, frames, ray queries, the editor preview,
+ * the denoiser's guide and the wireframe.  (Closest-hit ties depend on visiting order, so frames on the rebuilt tree are
+ * bit-identical to that fresh context's, not to frames on the refitted tree.)  Accumulation, currentIor, the frame and the
+ * pools are untouched; rigs stay valid (they name triangle ranges) and a later rz_skin_pose refits the new tree;
+ * rz_denoise_temporal's history is dropped when something was rebuilt, as after rz_build_geometry; sah_cost_built of a
+ * rebuilt mesh becomes its new cost.  SceneBuffers::rebuildMesh / rzh_scene_rebuild_mesh (librayzen_host.so) produce the
+ * same bytes on the host: what keeps a host mirror in step.
+ * The call builds into fresh buffers and swaps them in last; any failure (RZ_ERR_NO_MEMORY, a HIP error) leaves the context
+ * as it was.  RZ_ERR_INVALID_ARG, nothing changed: a negative or NaN max_ratio, flags != 0, a short `cap`, and a scene
+ * that is not rebuildable this way -- a mesh's reachable nodes leave its extent, or two distinct triples share a node or
+ * index extent (rz_geometry_quality still works there).  RZ_ERR_NOT_READY: a binding the refit needs is missing.
+ * Synchronises the context's stream.  (Additive: RZ_ABI_VERSION stays 5.) */
+int rz_rebuild_geometry(rz_ctx* ctx, double max_ratio, rz_mesh_quality* out, size_t cap, size_t* n_meshes, unsigned flags /* 0 */);
+
 /* Copy a binding's current content back to the host in RayZen's own layout (after rz_update_transforms: the
  * instances / TLAS nodes / TLAS indices the device built).  out == NULL: only *needed is set. */
 int rz_read_binding(rz_ctx* ctx, rz_binding binding, void* out, size_t bytes, size_t* needed);
@@ -821,8 +899,8 @@ const char* rz_source_hash(void);
  * checks from other languages: which = 0 triangle, 1 node, 2 instance,
  * 3 material, 4 light, 5 frame_params, 6 counters, 7 ray, 8 hit,
  * 9 visibility, 10 editor_params, 11 denoise_params, 12 temporal_params,
- * 14 display_params, 15 display_info, 17 skin_triangle, 18 morph_triangle (13 and 16 are unassigned and return 0, as
- * every unknown index does). */
+ * 14 display_params, 15 display_info, 17 skin_triangle, 18 morph_triangle, 20 mesh_quality (13, 16 and 19 are unassigned
+ * and return 0, as every unknown index does). */
 size_t rz_sizeof(int which);
 
 #ifdef __cplusplus

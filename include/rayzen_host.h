@@ -30,6 +30,11 @@ int rzh_build_blas(const rz_triangle* tris, int n, rz_bvh_node* nodes_out, int32
  * byte is rz_refit_geometry's in rayzen_hip.h.  0, or -1 on a null / inconsistent argument (nothing is written). */
 int rzh_refit_blas(const rz_triangle* tris, int n, rz_bvh_node* nodes_inout, int n_nodes, const int32_t* idx);
 
+/* BVH::sahCost (no counterpart in the reference): the SAH cost of one BLAS over the nodes reachable from nodes[0] (child
+ * indices relative to the array), as rayzen_hip.h states it for rz_geometry_quality ("THE COST") -- the host partner the
+ * device kernels are held to within 1e-9 relative.  -1 on a null argument or if the nodes do not form a tree inside the array. */
+double rzh_blas_sah_cost(const rz_bvh_node* nodes, int n_nodes);
+
 /* BVH::buildTLAS (src/BVH.cpp:178-240) over world-space instance boxes
  * (only boundsMin/boundsMax of world_roots are read).  nodes_out capacity
  * 2*n, idx_out capacity n.  Returns the node count. */
@@ -63,6 +68,11 @@ int  rzh_scene_update_dynamic(rzh_scene* s);
  * gets them and a refitted BLAS, then the world boxes and the TLAS are rebuilt with the transforms in force.  The byte
  * partner of rz_refit_geometry, as rzh_scene_update_dynamic is of rz_update_transforms.  0, or -1 (nothing touched). */
 int  rzh_scene_refit_mesh(rzh_scene* s, int mesh_id, const rz_triangle* tris, int n);
+/* The mesh has degraded under refits: every stored copy of it gets a fresh BLAS of its current triangles (those of the last
+ * rzh_scene_refit_mesh), binding 8 is patched in place, binding 7 is flattened again in the same order with every later
+ * BLAS moved, every instance's blasNodeOffset follows, and the world boxes and the TLAS are rebuilt with the transforms in
+ * force.  The byte partner of rz_rebuild_geometry: what keeps a host mirror in step with it.  0, or -1 (nothing touched). */
+int  rzh_scene_rebuild_mesh(rzh_scene* s, int mesh_id);
 /* Mesh::skin (no counterpart in the reference): out[t] = rest[t] posed by linear-blend skinning and / or morph targets,
  * every bit as rayzen_hip.h states it for rz_skin_pose ("THE POSED TRIANGLE") -- the byte partner the device kernel is held
  * to, as rzh_refit_blas is for the refit.  skin NULL: morphs only (n_bones 0); n_morphs 0: skin only; bones: n_bones x 16

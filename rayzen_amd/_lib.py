@@ -25,6 +25,7 @@ HIP_SYMBOLS = (
     "rz_denoise_temporal", "rz_present_temporal", "rz_temporal_reset", "rz_debug_read_temporal",
     "rz_display", "rz_present_display", "rz_display_reset", "rz_display_state",
     "rz_skin_create", "rz_skin_pose", "rz_skin_destroy", "rz_skin_last_kernel_ms",
+    "rz_geometry_quality", "rz_rebuild_geometry",
 )
 ABI_VERSION = 5         # RZ_ABI_VERSION of the include/rayzen_hip.h this file mirrors
 # the symbols include/rayzen_host.h declares
@@ -35,6 +36,7 @@ HOST_SYMBOLS = (
     "rzh_scene_save_cache", "rzh_scene_load_cache", "rzh_scene_build_cached",
     "rzh_camera_matrices", "rzh_mat_translate", "rzh_mat_scale", "rzh_mat_rotate", "rzh_mat_inverse",
     "rzh_make_cube", "rzh_make_blob", "rzh_version", "rzh_refit_blas", "rzh_scene_refit_mesh", "rzh_skin_triangles",
+    "rzh_blas_sah_cost", "rzh_scene_rebuild_mesh",
 )
 
 
@@ -160,6 +162,17 @@ SKIN_DEVICE_ARGS = 1                    # RZ_SKIN_DEVICE_ARGS
 SIZEOF_SKIN_TRIANGLE, SIZEOF_MORPH_TRIANGLE = 17, 18    # their rz_sizeof indices
 
 
+class MeshQuality(C.Structure):
+    """rz_mesh_quality of include/rayzen_hip.h (64 B)."""
+    _fields_ = [("node_offset", C.c_int32), ("index_offset", C.c_int32), ("tri_offset", C.c_int32), ("node_offset_before", C.c_int32),
+                ("n_triangles", C.c_int32), ("n_nodes", C.c_int32), ("depth", C.c_int32), ("flags", C.c_uint32),
+                ("sah_cost", C.c_double), ("sah_cost_built", C.c_double), ("sah_cost_before", C.c_double), ("reserved", C.c_double)]
+
+
+QUALITY_REBUILT = 1                     # RZ_QUALITY_REBUILT
+SIZEOF_MESH_QUALITY = 20                # its rz_sizeof index
+
+
 class Counters(C.Structure):
     """rz_counters of include/rayzen_hip.h."""
     _fields_ = [(n, C.c_uint64) for n in COUNTER_FIELDS]
@@ -249,7 +262,9 @@ def hip():
                                 ("rz_skin_create", i, [vp, sz, sz, vp, vp, i, vp, i, C.POINTER(i)]),
                                 ("rz_skin_pose", i, [vp, i, vp, vp, C.c_uint]),
                                 ("rz_skin_destroy", i, [vp, i]),
-                                ("rz_skin_last_kernel_ms", i, [vp, C.POINTER(C.c_float)])):
+                                ("rz_skin_last_kernel_ms", i, [vp, C.POINTER(C.c_float)]),
+                                ("rz_geometry_quality", i, [vp, vp, sz, C.POINTER(sz)]),
+                                ("rz_rebuild_geometry", i, [vp, C.c_double, vp, sz, C.POINTER(sz), C.c_uint])):
             try:
                 fn = getattr(L, name)
                 fn.restype, fn.argtypes = res, args
@@ -276,6 +291,8 @@ def host():
         L.rzh_build_tlas.restype, L.rzh_build_tlas.argtypes = i, [vp, i, vp, vp, C.POINTER(i)]
         L.rzh_refit_blas.restype, L.rzh_refit_blas.argtypes = i, [vp, i, vp, i, vp]
         L.rzh_scene_refit_mesh.restype, L.rzh_scene_refit_mesh.argtypes = i, [vp, i, vp, i]
+        L.rzh_blas_sah_cost.restype, L.rzh_blas_sah_cost.argtypes = C.c_double, [vp, i]
+        L.rzh_scene_rebuild_mesh.restype, L.rzh_scene_rebuild_mesh.argtypes = i, [vp, i]
         L.rzh_skin_triangles.restype, L.rzh_skin_triangles.argtypes = i, [vp, vp, i, vp, i, vp, vp, i, vp]
         L.rzh_world_bounds.restype, L.rzh_world_bounds.argtypes = None, [vp, vp, vp, vp]
         L.rzh_scene_create.restype, L.rzh_scene_create.argtypes = vp, []

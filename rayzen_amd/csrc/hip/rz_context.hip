@@ -60,6 +60,7 @@ struct RefitView {
     std::tuple<int, int, int> key;
     int rankBase = 0;               // where its rankToNode entries start in dRefitRank
     std::vector<int> levelStart;    // ranks of tree level d: [levelStart[d], levelStart[d + 1]); empty: the root is a leaf
+    int maxNode = 0;                // the largest node index (relative to the view) its root reaches
 };
 
 // One rig of rz_skin_create: the device copies rz_skin_pose's kernel reads (rz_skin.hip)
@@ -184,6 +185,14 @@ struct rz_ctx {
     DevBuf dSkinOut, dSkinBones, dSkinWeights;
     hipEvent_t evSkin[2] = {nullptr, nullptr};
     bool skinTimed = false;
+    // rz_geometry_quality (rz_quality.hip): the views as its kernels see them (derived with the refit topology), the
+    // per-workgroup partial sums and the costs; and the cost of every laid-out mesh's tree as it was when it was last handed
+    // over or built -- measured at the library's first look at it (note_built_costs), dropped with the tree
+    DevBuf dQualViews, dQualPartials, dQualCost;
+    int qualBlocks = 0;
+    std::map<std::tuple<int, int, int>, double> costBuilt;
+    unsigned long long costGen = ~0ull;  // the layout whose views all have their entry in costBuilt
+    bool keepDevTris = false;           // rz_rebuild_geometry's re-layout: dRawTris is binding 0 as it stands, neither fetched nor uploaded again
 };
 
 namespace {
@@ -479,7 +488,7 @@ bool host_relayout_forced(const rz_ctx* c) {
     return e && *e && *e != '0';
 }
 
-int prepare_device_relayout(rz_ctx* c) {       // raw arrays + materials on the device, output buffers sized, scratch
+int prepare_device_relayout(rz_ctx* c, bool keepTris) {       // raw arrays + materials on the device, output buffers sized, scratch
     const size_t nNodes = blasNodeCount(c), nIdx = blasIdxCount(c);
     int rc;
     if (!c->geomOnDevice) {                    // (rz_build_geometry left nodes and indices there already)
@@ -488,8 +497,10 @@ int prepare_device_relayout(rz_ctx* c) {       // raw arrays + materials on the 
         rc = upload_vec(c, c->dRawIdx, c->host[RZ_BIND_BLAS_INDICES].data(), c->host[RZ_BIND_BLAS_INDICES].size());
         if (rc != RZ_OK) return rc;
     }
-    rc = upload_vec(c, c->dRawTris, c->host[RZ_BIND_TRIANGLES].data(), c->host[RZ_BIND_TRIANGLES].size());
-    if (rc != RZ_OK) return rc;
+    if (!keepTris) {                           // (rz_rebuild_geometry: dRawTris holds binding 0 as it stands, possibly newer than the host copy)
+        rc = upload_vec(c, c->dRawTris, c->host[RZ_BIND_TRIANGLES].data(), c->host[RZ_BIND_TRIANGLES].size());
+        if (rc != RZ_OK) return rc;
+    }
     rc = ensure(c, c->dPairs, std::max<size_t>(nNodes, 1) * sizeof(DevPair));
     if (rc != RZ_OK) return rc;
     rc = ensure(c, c->dTris, std::max<size_t>(nIdx, 1) * sizeof(DevTri));
@@ -542,7 +553,9 @@ int finalize_body(rz_ctx* c) {
         if (!c->present[b]) return fail(c, RZ_ERR_NOT_READY, "binding %d has not been uploaded", b);
 
     // (the per-view "may hold transparent triangles" hints were taken from the materials of the moment the views were laid out)
-    if (c->geomDirty) { int rc = sync_tris_host(c); if (rc != RZ_OK) return rc; }
+    // (after a rebuild of meshes on the device the device layout reads binding 0 where it is: posed triangles stay there)
+    const bool keepTris = c->geomDirty && c->keepDevTris && !host_relayout_forced(c);
+    if (c->geomDirty && !keepTris) { int rc = sync_tris_host(c); if (rc != RZ_OK) return rc; }
     if (c->geomDirty) c->matChangedSinceLayout = false;
     else if (c->matDirty && !c->matChangedSinceLayout) { c->matChangedSinceLayout = true; c->instDirty = true; }
     // materials first: the device re-layout checks triangle material indices against them
@@ -559,7 +572,7 @@ int finalize_body(rz_ctx* c) {
         c->triNValid = -1;
         c->devPairsUsed = c->devTrisUsed = 0; c->devTransparent = 0; c->irregularBoxes = false;
         c->layoutOnDevice = !host_relayout_forced(c);
-        if (c->layoutOnDevice) { int rc = prepare_device_relayout(c); if (rc != RZ_OK) return rc; }
+        if (c->layoutOnDevice) { int rc = prepare_device_relayout(c, keepTris); if (rc != RZ_OK) return rc; }
     }
     if (c->instDirty) {
         const rz_bvh_instance* inst = hostArr<rz_bvh_instance>(c, RZ_BIND_INSTANCES);
@@ -580,6 +593,7 @@ int finalize_body(rz_ctx* c) {
                 if (c->layoutOnDevice) {
                     rc = device_view(c, inst[i].blasNodeOffset, inst[i].blasTriOffset, inst[i].globalTriOffset, V);
                     if (rc == 1) {          // start over on the host
+                        if (keepTris) { const int src = sync_tris_host(c); if (src != RZ_OK) return src; }     // (the host layout reads the host copy)
                         c->layoutOnDevice = false;
                         c->views.clear(); c->hPairs.clear(); c->hTris.clear(); c->triNValid = -1;
                         redo = true;
@@ -1028,6 +1042,7 @@ size_t rz_sizeof(int which) {
         case 15: return sizeof(rz_display_info);
         case 17: return sizeof(rz_skin_triangle);        // (16 stays unassigned too: probed as an unknown index)
         case 18: return sizeof(rz_morph_triangle);
+        case 20: return sizeof(rz_mesh_quality);         // (19 stays unassigned: probed as an unknown index)
         default: return 0;
     }
 }
@@ -1071,7 +1086,8 @@ void rz_destroy(rz_ctx* c) {
                       &c->dRayOvf, &c->dRayIn, &c->dRayOut, &c->dRayInstOff, &c->dDnGuide, &c->dDnPing, &c->dDnPong, &c->dDnOut,
                       &c->dRefitRank, &c->dRefitInstView, &c->dRefitViewOff, &c->dRefitFlags, &c->dRefitRoots,
                       &c->dTmpCol[0], &c->dTmpCol[1], &c->dTmpMom[0], &c->dTmpMom[1], &c->dTmpHits[0], &c->dTmpHits[1],
-                      &c->dTmpInst[0], &c->dTmpInst[1], &c->dTmpSame, &c->dDisplay, &c->dSkinOut, &c->dSkinBones, &c->dSkinWeights})
+                      &c->dTmpInst[0], &c->dTmpInst[1], &c->dTmpSame, &c->dDisplay, &c->dSkinOut, &c->dSkinBones, &c->dSkinWeights,
+                      &c->dQualViews, &c->dQualPartials, &c->dQualCost})
         b->release();
     for (auto& kv : c->rigs) kv.second.release();
     for (hipEvent_t e : c->evSkin) if (e) (void)hipEventDestroy(e);
@@ -1101,6 +1117,7 @@ static int upload_impl(rz_ctx* c, rz_binding binding, const void* data, size_t b
     alloc_point(c);
     c->host[binding].assign(static_cast<const unsigned char*>(data), static_cast<const unsigned char*>(data) + bytes);
     if (binding == RZ_BIND_TRIANGLES) c->trisHostStale = false;
+    if (binding == RZ_BIND_BLAS_NODES || binding == RZ_BIND_BLAS_INDICES) { c->costBuilt.clear(); c->costGen = ~0ull; }   // trees handed over
     if (binding == RZ_BIND_TRIANGLES || binding == RZ_BIND_BLAS_NODES || binding == RZ_BIND_BLAS_INDICES || binding == RZ_BIND_INSTANCES)
         c->tmpValid = false;                // new geometry or instances: rz_denoise_temporal's history describes another scene
     c->present[binding] = true;
@@ -1131,6 +1148,7 @@ static int update_impl(rz_ctx* c, rz_binding binding, size_t offset, const void*
     if (bytes == 0) return RZ_OK;
     if (std::memcmp(c->host[binding].data() + offset, data, bytes) == 0) return RZ_OK;   // unchanged: nothing to redo
     std::memcpy(c->host[binding].data() + offset, data, bytes);
+    if (binding == RZ_BIND_BLAS_NODES || binding == RZ_BIND_BLAS_INDICES) { c->costBuilt.clear(); c->costGen = ~0ull; }   // trees handed over
     switch (binding) {
         case RZ_BIND_MATERIALS: c->matDirty = true; break;
         case RZ_BIND_LIGHTS: c->lightDirty = true; break;
@@ -1237,6 +1255,7 @@ static int refit_topology(rz_ctx* c) {
                 const int L = nodes[nodeOff + rank[head++]].leftFirst;
                 if (L < 1 || (long long)nodeOff + L + 1 >= nNodes || rank.size() - (size_t)R.rankBase > (size_t)nNodes)
                     return fail(c, RZ_ERR_INTERNAL, "rz_refit_geometry: a laid-out view is not a tree");
+                R.maxNode = std::max(R.maxNode, L + 1);
                 for (int k = 0; k < 2; ++k)
                     if (nodes[nodeOff + L + k].count < 0) { if ((rank.size() & 4095) == 0) alloc_point(c); rank.push_back(L + k); }
             }
@@ -1266,7 +1285,20 @@ static int refit_topology(rz_ctx* c) {
     if ((rc = upload_vec(c, c->dRefitViewOff, viewOff.data(), viewOff.size() * sizeof(int32_t))) != RZ_OK) return rc;
     if ((rc = upload_vec(c, c->dRefitFlags, flags.data(), flags.size() * sizeof(unsigned))) != RZ_OK) return rc;
     if ((rc = ensure(c, c->dRefitRoots, std::max<size_t>(rv.size(), 1) * sizeof(rz_bvh_node))) != RZ_OK) return rc;
-    const size_t pinnedNeed = rv.size() * (16 + sizeof(rz_bvh_node)) + 64;
+    // rz_geometry_quality's view of the same lists (rz_quality.hip): every view owns a run of whole workgroups
+    std::vector<QualityView> qv(rv.size() + 1);
+    long long blocks = 0;
+    for (size_t v = 0; v < rv.size(); ++v) {
+        const int nPairs = rv[v].levelStart.empty() ? 0 : rv[v].levelStart.back();
+        qv[v] = QualityView{viewOff[v], rv[v].rankBase, nPairs, (int32_t)blocks};
+        blocks += (nPairs + 255) / 256;
+    }
+    qv[rv.size()] = QualityView{0, 0, 0, (int32_t)blocks};
+    if ((rc = upload_vec(c, c->dQualViews, qv.data(), qv.size() * sizeof(QualityView))) != RZ_OK) return rc;
+    if ((rc = ensure(c, c->dQualPartials, (size_t)std::max<long long>(blocks, 1) * sizeof(double))) != RZ_OK) return rc;
+    if ((rc = ensure(c, c->dQualCost, std::max<size_t>(rv.size(), 1) * sizeof(double))) != RZ_OK) return rc;
+    c->qualBlocks = (int)blocks;
+    const size_t pinnedNeed = rv.size() * (16 + sizeof(rz_bvh_node) + sizeof(double)) + 64;      // flag words, root nodes, costs
     if (pinnedNeed > c->refitPinnedCap) {
         if (c->refitPinned) (void)hipHostFree(c->refitPinned);
         c->refitPinned = nullptr; c->refitPinnedCap = 0;
@@ -1348,6 +1380,93 @@ static int refit_tlas_step(rz_ctx* c) {
     return tlas_rebuild(c, xf.data(), nInst);      // (synchronises before xf dies)
 }
 
+// ---- the SAH cost of the laid-out trees (rz_geometry_quality) -------------------------------------------------------
+
+// The cost of include/rayzen_hip.h on the host copy of one mesh (the partner of BVH::sahCost for node arrays whose children
+// need not be numbered after their parents): breadth first from the root.  false: the nodes do not form a tree inside the array.
+static bool host_sah_cost(rz_ctx* c, const rz_bvh_node* nodes, long long nNodes, int nodeOff, double* cost) {
+    if (nodeOff < 0 || nodeOff >= nNodes) return false;
+    auto area = [](const rz_bvh_node& N) {
+        const double dx = (double)N.boundsMax[0] - (double)N.boundsMin[0], dy = (double)N.boundsMax[1] - (double)N.boundsMin[1],
+                     dz = (double)N.boundsMax[2] - (double)N.boundsMin[2];
+        if (!(dx >= 0.0) || !(dy >= 0.0) || !(dz >= 0.0)) return 0.0;
+        return 2.0 * (dx * dy + dy * dz + dz * dx);
+    };
+    alloc_point(c);
+    std::vector<int> order;
+    order.push_back(0);
+    double sum = 0.0;
+    for (size_t head = 0; head < order.size(); ++head) {
+        const rz_bvh_node& N = nodes[nodeOff + order[head]];
+        if (N.count >= 0) { sum += area(N) * (double)N.count; continue; }
+        const int L = N.leftFirst;
+        if (L < 1 || (long long)nodeOff + L + 1 >= nNodes || order.size() > (size_t)nNodes) return false;
+        sum += area(N);
+        if ((order.size() & 4095) == 0) alloc_point(c);
+        order.push_back(L);
+        order.push_back(L + 1);
+    }
+    const double rootArea = area(nodes[nodeOff]);
+    *cost = rootArea == 0.0 ? 0.0 : sum / rootArea;
+    return true;
+}
+
+// The cost of every laid-out view, in the order of `views`, measured now: on the device where the layout lives there (two
+// launches on the context's stream, rz_quality.hip), else on the host copies.  Synchronises; `costs` gets views.size()
+// doubles.  The layout must be current (finalize).
+static int measure_costs(rz_ctx* c, std::vector<double>& costs) {
+    int rc;
+    const size_t nViews = c->views.size();
+    alloc_point(c);
+    costs.assign(nViews, 0.0);
+    if (c->layoutOnDevice) {
+        if ((rc = refit_topology(c)) != RZ_OK) return rc;
+        double* h = reinterpret_cast<double*>(c->refitPinned + nViews * (16 + sizeof(rz_bvh_node)));
+        if (nViews) {
+            const int e = quality_device(static_cast<const rz_bvh_node*>(c->dRawNodes.p), static_cast<const int32_t*>(c->dRefitRank.p),
+                                         static_cast<const QualityView*>(c->dQualViews.p), (int)nViews, c->qualBlocks,
+                                         static_cast<double*>(c->dQualPartials.p), static_cast<double*>(c->dQualCost.p), c->stream);
+            if (e != 0) return fail(c, RZ_ERR_HIP, "rz_geometry_quality: %s", hipGetErrorString((hipError_t)(-e)));
+            RZ_HIP(c, hipMemcpyAsync(h, c->dQualCost.p, nViews * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        }
+        RZ_HIP(c, hipStreamSynchronize(c->stream));
+        if (nViews) std::memcpy(costs.data(), h, nViews * sizeof(double));
+        return RZ_OK;
+    }
+    if ((rc = sync_geom_host(c)) != RZ_OK) return rc;
+    size_t v = 0;
+    for (const auto& kv : c->views) {
+        if (!host_sah_cost(c, hostArr<rz_bvh_node>(c, RZ_BIND_BLAS_NODES), (long long)hostCount<rz_bvh_node>(c, RZ_BIND_BLAS_NODES),
+                           std::get<0>(kv.first), &costs[v]))
+            return fail(c, RZ_ERR_INTERNAL, "rz_geometry_quality: a laid-out view is not a tree");
+        ++v;
+    }
+    RZ_HIP(c, hipStreamSynchronize(c->stream));
+    return RZ_OK;
+}
+
+// The first look at every tree that was handed over or built since the last one: its cost becomes rz_mesh_quality::sah_cost_built.
+// rz_refit_geometry and rz_skin_pose call this before they move a box; `costs` (measure_costs) may be passed by a caller
+// that has measured already.  Trees that are no longer laid out lose their entry.
+static int note_built_costs(rz_ctx* c, const std::vector<double>* measured) {
+    if (c->costGen == c->layoutGen) return RZ_OK;
+    bool missing = false;
+    for (const auto& kv : c->views) missing = missing || !c->costBuilt.count(kv.first);
+    std::vector<double> own;
+    if (missing && !measured) { const int rc = measure_costs(c, own); if (rc != RZ_OK) return rc; measured = &own; }
+    alloc_point(c);
+    std::map<std::tuple<int, int, int>, double> kept;
+    size_t v = 0;
+    for (const auto& kv : c->views) {
+        const auto it = c->costBuilt.find(kv.first);
+        kept[kv.first] = it != c->costBuilt.end() ? it->second : (*measured)[v];
+        ++v;
+    }
+    c->costBuilt.swap(kept);
+    c->costGen = c->layoutGen;
+    return RZ_OK;
+}
+
 // The host route: patch the host copies, refit there, and let the re-layout run (RZ_FLAG_HOST_RELAYOUT; a layout that
 // fell back to the host; materials changed since the views were laid out).  Same bytes as the device route.
 static int refit_on_host(rz_ctx* c, const rz_triangle* triangles, size_t first, size_t n, bool hostPtr) {
@@ -1355,6 +1474,7 @@ static int refit_on_host(rz_ctx* c, const rz_triangle* triangles, size_t first, 
     if (rc != RZ_OK) return rc;
     if ((rc = sync_tris_host(c)) != RZ_OK) return rc;
     if ((rc = sync_geom_host(c)) != RZ_OK) return rc;
+    if ((rc = note_built_costs(c, nullptr)) != RZ_OK) return rc;       // (before a box moves: rz_geometry_quality's sah_cost_built)
     c->geomOnDevice = false;            // the host copies are the truth again
     if (n) {
         unsigned char* dst = c->host[RZ_BIND_TRIANGLES].data() + first * sizeof(rz_triangle);
@@ -1426,6 +1546,7 @@ static int refit_geometry_impl(rz_ctx* c, const rz_triangle* triangles, size_t f
     if (rc != RZ_OK) return rc;
     if (!c->layoutOnDevice || c->matChangedSinceLayout) return refit_on_host(c, triangles, first, n, hostPtr);
     if ((rc = refit_topology(c)) != RZ_OK) return rc;
+    if ((rc = note_built_costs(c, nullptr)) != RZ_OK) return rc;       // (before a box moves: rz_geometry_quality's sah_cost_built)
     // (every host allocation of the call happens before anything is enqueued: a failure leaves the context as it was)
     const size_t nInst = hostCount<rz_bvh_instance>(c, RZ_BIND_INSTANCES);
     alloc_point(c);
@@ -1668,6 +1789,255 @@ static int skin_last_kernel_ms_impl(rz_ctx* c, float* ms) {
     return RZ_OK;
 }
 
+// ---- rz_geometry_quality / rz_rebuild_geometry ------------------------------------------------------------------------
+
+// One mesh of the scene -- a distinct triple among the uploaded instances -- with the cost of its tree as measured now
+struct QualityMesh {
+    std::tuple<int, int, int> key;
+    int nSlots = 0, nPairs = 0, depth = 1;
+    double cost = 0.0;
+};
+
+typedef std::map<std::tuple<int, int, int>, bool> NamedMeshes;
+
+// the distinct triples among the uploaded instances
+static void named_meshes(rz_ctx* c, NamedMeshes& named) {
+    const rz_bvh_instance* inst = hostArr<rz_bvh_instance>(c, RZ_BIND_INSTANCES);
+    const size_t nInst = hostCount<rz_bvh_instance>(c, RZ_BIND_INSTANCES);
+    alloc_point(c);
+    named.clear();
+    for (size_t i = 0; i < nInst; ++i) named[std::make_tuple(inst[i].blasNodeOffset, inst[i].blasTriOffset, inst[i].globalTriOffset)] = true;
+}
+
+// The meshes in ascending order of their triple, measured on the context's stream (synchronises); every tree that has not been
+// looked at since it was handed over gets its sah_cost_built here.  Views the instances no longer name are not reported.
+static int measure_meshes(rz_ctx* c, const NamedMeshes& named, std::vector<QualityMesh>& out) {
+    std::vector<double> costs;
+    int rc;
+    if ((rc = measure_costs(c, costs)) != RZ_OK) return rc;
+    if ((rc = note_built_costs(c, &costs)) != RZ_OK) return rc;
+    out.clear();
+    out.reserve(named.size());
+    size_t v = 0;
+    for (const auto& kv : c->views) {
+        if (named.count(kv.first)) {
+            QualityMesh m;
+            m.key = kv.first;
+            m.nSlots = kv.second.nSlots; m.nPairs = kv.second.nPairs; m.depth = kv.second.depth;
+            m.cost = costs[v];
+            out.push_back(m);
+        }
+        ++v;
+    }
+    return RZ_OK;
+}
+
+static rz_mesh_quality quality_record(const rz_ctx* c, const QualityMesh& m) {
+    rz_mesh_quality q{};
+    q.node_offset = q.node_offset_before = std::get<0>(m.key);
+    q.index_offset = std::get<1>(m.key);
+    q.tri_offset = std::get<2>(m.key);
+    q.n_triangles = m.nSlots;
+    q.n_nodes = 2 * m.nPairs + 1;
+    q.depth = m.depth;
+    q.flags = 0;
+    q.sah_cost = q.sah_cost_before = m.cost;
+    q.sah_cost_built = c->costBuilt.at(m.key);
+    q.reserved = 0.0;
+    return q;
+}
+
+static int geometry_quality_impl(rz_ctx* c, rz_mesh_quality* out, size_t cap, size_t* nMeshes) {
+    const char* what = "rz_geometry_quality";
+    if (!c) return fail(nullptr, RZ_ERR_INVALID_ARG, "%s: null context", what);
+    if (!out && !nMeshes) return fail(c, RZ_ERR_INVALID_ARG, "%s: neither out nor n_meshes", what);
+    { const int b = refit_missing_binding(c); if (b >= 0) return fail(c, RZ_ERR_NOT_READY, "%s: no scene (binding %d has not been uploaded)", what, b); }
+    RZ_HIP(c, hipSetDevice(c->device));
+    int rc = finalize(c);               // a pending layout is brought up to date, as the refit does
+    if (rc != RZ_OK) return rc;
+    NamedMeshes named;
+    named_meshes(c, named);
+    const size_t n = named.size();
+    if (nMeshes) *nMeshes = n;
+    if (!out) return RZ_OK;
+    if (cap < n) return fail(c, RZ_ERR_INVALID_ARG, "%s: out holds %zu records, the scene has %zu meshes", what, cap, n);
+    std::vector<QualityMesh> M;
+    if ((rc = measure_meshes(c, named, M)) != RZ_OK) return rc;
+    for (size_t k = 0; k < M.size(); ++k) out[k] = quality_record(c, M[k]);
+    return RZ_OK;
+}
+
+// What the rebuild replaces, kept until the new state has been laid out: a failure after the swap puts everything back
+struct RebuildSaved {
+    DevBuf nodes, idx;              // the fresh buffers before the swap, the context's old ones after it
+    std::vector<unsigned char> host7, host8, host9;
+    std::map<int, rz_bvh_node> devRoots;
+    std::map<std::tuple<int, int, int>, double> costBuilt;
+    bool geomOnDevice = false, geomHostFresh = false, tmpValid = false;
+    size_t devNodes = 0, devIdx = 0;
+    ~RebuildSaved() { nodes.release(); idx.release(); }
+};
+
+static void rebuild_swap(rz_ctx* c, RebuildSaved& S) {
+    std::swap(c->dRawNodes, S.nodes);
+    std::swap(c->dRawIdx, S.idx);
+    c->host[RZ_BIND_BLAS_NODES].swap(S.host7);
+    c->host[RZ_BIND_BLAS_INDICES].swap(S.host8);
+    c->host[RZ_BIND_INSTANCES].swap(S.host9);
+    c->devRoots.swap(S.devRoots);
+    c->costBuilt.swap(S.costBuilt);
+    std::swap(c->geomOnDevice, S.geomOnDevice);
+    std::swap(c->geomHostFresh, S.geomHostFresh);
+    std::swap(c->tmpValid, S.tmpValid);
+    std::swap(c->devNodes, S.devNodes);
+    std::swap(c->devIdx, S.devIdx);
+    c->costGen = ~0ull;
+    c->deviceOwnsTlas = false;      // (the host copies of instances and TLAS were brought up to date before the first swap)
+    c->geomDirty = true;            // the views are laid out again from whichever arrays are in place now
+}
+
+static int rebuild_geometry_impl(rz_ctx* c, double maxRatio, rz_mesh_quality* out, size_t cap, size_t* nMeshes, unsigned flags) {
+    const char* what = "rz_rebuild_geometry";
+    if (!c) return fail(nullptr, RZ_ERR_INVALID_ARG, "%s: null context", what);
+    if (flags) return fail(c, RZ_ERR_INVALID_ARG, "%s: unknown flags 0x%x", what, flags);
+    if (!(maxRatio >= 0.0)) return fail(c, RZ_ERR_INVALID_ARG, "%s: max_ratio must be >= 0", what);
+    if (!out && !nMeshes) return fail(c, RZ_ERR_INVALID_ARG, "%s: neither out nor n_meshes", what);
+    { const int b = refit_missing_binding(c); if (b >= 0) return fail(c, RZ_ERR_NOT_READY, "%s: no scene (binding %d has not been uploaded)", what, b); }
+    RZ_HIP(c, hipSetDevice(c->device));
+    int rc = finalize(c);
+    if (rc != RZ_OK) return rc;
+    NamedMeshes named;
+    named_meshes(c, named);
+    const size_t nM = named.size();
+    if (nMeshes) *nMeshes = nM;
+    if (!out) return RZ_OK;
+    if (cap < nM) return fail(c, RZ_ERR_INVALID_ARG, "%s: out holds %zu records, the scene has %zu meshes", what, cap, nM);
+    // 1. measure; 2. select
+    std::vector<QualityMesh> M;
+    if ((rc = measure_meshes(c, named, M)) != RZ_OK) return rc;
+    alloc_point(c);
+    std::vector<char> sel(M.size(), 0);
+    bool any = false;
+    for (size_t k = 0; k < M.size(); ++k) {
+        sel[k] = !(M[k].cost <= maxRatio * c->costBuilt.at(M[k].key));
+        any = any || sel[k];
+    }
+    if (!any) {                         // 3. the context is untouched
+        for (size_t k = 0; k < M.size(); ++k) out[k] = quality_record(c, M[k]);
+        return RZ_OK;
+    }
+    // Is the scene rebuildable this way?  Meshes in ascending blasNodeOffset; a mesh's node extent is [its offset, the next
+    // larger distinct offset or the end of binding 7); its index extent is [blasTriOffset, + its slots).
+    if ((rc = refit_topology(c)) != RZ_OK) return rc;
+    const long long nNodes = (long long)blasNodeCount(c), nIdx = (long long)blasIdxCount(c);
+    const long long nTris = (long long)hostCount<rz_triangle>(c, RZ_BIND_TRIANGLES);
+    std::map<std::tuple<int, int, int>, int> maxNode;
+    for (const RefitView& R : c->refitViews) maxNode[R.key] = R.maxNode;
+    std::vector<std::pair<long long, long long>> idxExtents;
+    for (size_t k = 0; k < M.size(); ++k) {
+        const long long off = std::get<0>(M[k].key), end = k + 1 < M.size() ? std::get<0>(M[k + 1].key) : nNodes;
+        if (end == off) return fail(c, RZ_ERR_INVALID_ARG, "%s: two meshes share the node extent at %lld", what, off);
+        if (maxNode.at(M[k].key) >= end - off)
+            return fail(c, RZ_ERR_INVALID_ARG, "%s: the mesh at node %lld reaches node %d, outside its extent of %lld", what, off, maxNode.at(M[k].key), end - off);
+        const long long t0 = std::get<1>(M[k].key), g0 = std::get<2>(M[k].key);
+        if (t0 < 0 || t0 + M[k].nSlots > nIdx || g0 < 0 || g0 + M[k].nSlots > nTris)
+            return fail(c, RZ_ERR_INVALID_ARG, "%s: the mesh at node %lld names indices or triangles outside their arrays", what, off);
+        if (M[k].nSlots > 0) idxExtents.push_back({t0, t0 + M[k].nSlots});
+    }
+    std::sort(idxExtents.begin(), idxExtents.end());
+    for (size_t k = 1; k < idxExtents.size(); ++k)
+        if (idxExtents[k].first < idxExtents[k - 1].second)
+            return fail(c, RZ_ERR_INVALID_ARG, "%s: two meshes share the index extent at %lld", what, idxExtents[k].first);
+    // 4. new bindings 7 and 8 in fresh buffers (as rz_build_geometry: the context's arrays are never written to)
+    if (c->deviceOwnsTlas) { rc = sync_host_from_device(c); if (rc != RZ_OK) return rc; }      // the instances with the transforms in force
+    if (!c->layoutOnDevice) { rc = sync_tris_host(c); if (rc != RZ_OK) return rc; }
+    const bool devGeom = c->geomOnDevice || c->layoutOnDevice;         // (a device layout keeps a current copy of host-owned arrays)
+    const rz_bvh_node* srcNodes = devGeom ? static_cast<const rz_bvh_node*>(c->dRawNodes.p) : hostArr<rz_bvh_node>(c, RZ_BIND_BLAS_NODES);
+    const int32_t* srcIdx = devGeom ? static_cast<const int32_t*>(c->dRawIdx.p) : hostArr<int32_t>(c, RZ_BIND_BLAS_INDICES);
+    const rz_triangle* srcTris = c->layoutOnDevice ? static_cast<const rz_triangle*>(c->dRawTris.p) : hostArr<rz_triangle>(c, RZ_BIND_TRIANGLES);
+    const long long lead = M.empty() ? nNodes : std::get<0>(M[0].key);  // (nodes in front of the first mesh stay)
+    size_t capNodes = (size_t)lead, maxN = 0;
+    for (size_t k = 0; k < M.size(); ++k) {
+        const long long off = std::get<0>(M[k].key), end = k + 1 < M.size() ? std::get<0>(M[k + 1].key) : nNodes;
+        capNodes += sel[k] ? (M[k].nSlots ? 2 * (size_t)M[k].nSlots - 1 : 1) : (size_t)(end - off);
+        if (sel[k]) maxN = std::max(maxN, (size_t)M[k].nSlots);
+    }
+    if (capNodes >= ((size_t)1 << 27)) return fail(c, RZ_ERR_INVALID_ARG, "%s: too many nodes", what);
+    RebuildSaved S;
+    if ((rc = ensure(c, S.nodes, std::max<size_t>(capNodes, 1) * sizeof(rz_bvh_node))) != RZ_OK) return rc;
+    if ((rc = ensure(c, S.idx, std::max<size_t>((size_t)nIdx, 1) * sizeof(int32_t))) != RZ_OK) return rc;
+    if (maxN) { rc = ensure(c, c->dBuildWs, blas_build_workspace_bytes(maxN)); if (rc != RZ_OK) return rc; }
+    rz_bvh_node* dNodes = static_cast<rz_bvh_node*>(S.nodes.p);
+    int32_t* dIdx = static_cast<int32_t*>(S.idx.p);
+    if (nIdx) RZ_HIP(c, hipMemcpyAsync(dIdx, srcIdx, (size_t)nIdx * sizeof(int32_t), hipMemcpyDefault, c->stream));
+    if (lead) RZ_HIP(c, hipMemcpyAsync(dNodes, srcNodes, (size_t)lead * sizeof(rz_bvh_node), hipMemcpyDefault, c->stream));
+    std::vector<int> newOff(M.size(), 0);
+    rz_bvh_node emptyRoot{};            // BVH.cpp:101-118 on an empty mesh: one root with an inverted box and no triangles
+    for (int a = 0; a < 3; ++a) { emptyRoot.boundsMin[a] = std::numeric_limits<float>::max(); emptyRoot.boundsMax[a] = -std::numeric_limits<float>::max(); }
+    size_t at = (size_t)lead;
+    for (size_t k = 0; k < M.size(); ++k) {
+        const long long off = std::get<0>(M[k].key), end = k + 1 < M.size() ? std::get<0>(M[k + 1].key) : nNodes;
+        newOff[k] = (int)at;
+        if (!sel[k]) {                  // its extent verbatim (leftFirst is mesh-relative), shifted
+            RZ_HIP(c, hipMemcpyAsync(dNodes + at, srcNodes + off, (size_t)(end - off) * sizeof(rz_bvh_node), hipMemcpyDefault, c->stream));
+            at += (size_t)(end - off);
+        } else if (M[k].nSlots == 0) {  // (its cost is 0: only max_ratio = +inf selects it, inf * 0 being NaN)
+            RZ_HIP(c, hipMemcpyAsync(dNodes + at, &emptyRoot, sizeof emptyRoot, hipMemcpyHostToDevice, c->stream));   // (left by the synchronisation below)
+            at += 1;
+        } else {                        // BVH::buildBLAS of its triangles of binding 0 as it stands, by the device builder
+            int nn = 0, depth = 0;
+            const int e = blas_build_device(srcTris + std::get<2>(M[k].key), (size_t)M[k].nSlots, c->dBuildWs.p, c->dBuildWs.cap, dNodes + at,
+                                            dIdx + std::get<1>(M[k].key), &nn, &depth, nullptr, c->stream);
+            if (e > 0) return fail(c, RZ_ERR_HIP, "%s: device BLAS build of the mesh at node %lld: %s", what, off, hipGetErrorString((hipError_t)e));
+            if (e < 0) return fail(c, RZ_ERR_HIP, "%s: device BLAS build of the mesh at node %lld: internal limit", what, off);
+            at += (size_t)nn;
+        }
+    }
+    RZ_HIP(c, hipStreamSynchronize(c->stream));        // the copies have left the host arrays; nothing in flight reads the old ones
+    // the new instances, root nodes and built costs: every allocation that can fail, before anything of the context changes
+    alloc_point(c);
+    S.host9 = c->host[RZ_BIND_INSTANCES];
+    {
+        rz_bvh_instance* inst = reinterpret_cast<rz_bvh_instance*>(S.host9.data());
+        const size_t nInst = S.host9.size() / sizeof(rz_bvh_instance);
+        std::map<int, int> moved;
+        for (size_t k = 0; k < M.size(); ++k) moved[std::get<0>(M[k].key)] = newOff[k];
+        for (size_t i = 0; i < nInst; ++i) inst[i].blasNodeOffset = moved.at(inst[i].blasNodeOffset);
+    }
+    for (size_t k = 0; k < M.size(); ++k) {
+        rz_bvh_node root;
+        RZ_HIP(c, hipMemcpy(&root, dNodes + newOff[k], sizeof root, hipMemcpyDeviceToHost));
+        S.devRoots[newOff[k]] = root;
+        if (!sel[k]) S.costBuilt[std::make_tuple(newOff[k], std::get<1>(M[k].key), std::get<2>(M[k].key))] = c->costBuilt.at(M[k].key);
+    }
+    S.geomOnDevice = true; S.geomHostFresh = false; S.tmpValid = false;
+    S.devNodes = at; S.devIdx = (size_t)nIdx;
+    // the swap, then the re-layout and world boxes + TLAS with the transforms in force, exactly as rz_refit_geometry's host route
+    rebuild_swap(c, S);
+    std::vector<QualityMesh> After;
+    c->keepDevTris = c->layoutOnDevice;     // (a device layout's dRawTris is binding 0 as it stands: the builder above read it too)
+    try {
+        rc = finalize(c);
+        c->keepDevTris = false;
+        if (rc == RZ_OK) rc = refit_tlas_step(c);
+        if (rc == RZ_OK) { named_meshes(c, named); rc = measure_meshes(c, named, After); }
+        if (rc == RZ_OK && After.size() != M.size()) rc = fail(c, RZ_ERR_INTERNAL, "%s: the rebuilt scene has %zu meshes, not %zu", what, After.size(), M.size());
+    } catch (...) {
+        c->keepDevTris = false;
+        rebuild_swap(c, S);
+        throw;
+    }
+    if (rc != RZ_OK) { rebuild_swap(c, S); return rc; }
+    for (size_t k = 0; k < M.size(); ++k) {
+        rz_mesh_quality q = quality_record(c, After[k]);
+        q.node_offset_before = std::get<0>(M[k].key);
+        q.sah_cost_before = M[k].cost;
+        q.flags = sel[k] ? RZ_QUALITY_REBUILT : 0u;
+        out[k] = q;
+    }
+    return RZ_OK;
+}
+
 static int build_geometry_impl(rz_ctx* c, const rz_triangle* triangles, size_t nTris, rz_mesh_build* meshes, size_t nMeshes) {
     if (!c) return fail(nullptr, RZ_ERR_INVALID_ARG, "null context");
     if ((nTris && !triangles) || (nMeshes && !meshes)) return fail(c, RZ_ERR_INVALID_ARG, "null argument");
@@ -1737,6 +2107,7 @@ static int build_geometry_impl(rz_ctx* c, const rz_triangle* triangles, size_t n
     c->tmpValid = false;                    // (rz_denoise_temporal's history)
     c->devNodes = nodeOff; c->devIdx = idxOff;
     c->devRoots.swap(roots);
+    c->costBuilt.clear(); c->costGen = ~0ull;   // new trees: rz_geometry_quality's "built" costs are measured again
     c->geomDirty = true;
     return RZ_OK;
 }
@@ -2853,6 +3224,12 @@ int rz_skin_destroy(rz_ctx* c, int rig) {
 }
 int rz_skin_last_kernel_ms(rz_ctx* c, float* ms) {
     return guarded(c, "rz_skin_last_kernel_ms", [&] { return skin_last_kernel_ms_impl(c, ms); });
+}
+int rz_geometry_quality(rz_ctx* c, rz_mesh_quality* out, size_t cap, size_t* n_meshes) {
+    return guarded(c, "rz_geometry_quality", [&] { return geometry_quality_impl(c, out, cap, n_meshes); });
+}
+int rz_rebuild_geometry(rz_ctx* c, double max_ratio, rz_mesh_quality* out, size_t cap, size_t* n_meshes, unsigned flags) {
+    return guarded(c, "rz_rebuild_geometry", [&] { return rebuild_geometry_impl(c, max_ratio, out, cap, n_meshes, flags); });
 }
 int rz_build_blas(rz_ctx* c, const rz_triangle* tris, size_t n, rz_bvh_node* nodes_out, size_t nodes_cap, int32_t* indices_out, size_t* n_nodes, int* depth, float* device_ms) {
     return guarded(c, "rz_build_blas", [&] { return build_blas_impl(c, tris, n, nodes_out, nodes_cap, indices_out, n_nodes, depth, device_ms); });

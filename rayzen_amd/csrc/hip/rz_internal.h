@@ -217,6 +217,16 @@ int refit_view_device(const RefitViewWork& W, hipStream_t s);
 int refit_roots_device(DevInstance* inst, int nInst, const int32_t* instView, const int32_t* viewNodeOff, int nViews,
                        const rz_bvh_node* nodes, const unsigned* vflags, rz_bvh_node* rootsOut, hipStream_t s);
 
+// ---- rz_quality.hip
+struct QualityView {            // one BLAS view as the cost kernels see it; the array ends with a sentinel that carries the total block count
+    int32_t nodeOff;            // blasNodeOffset
+    int32_t rankBase;           // where its rankToNode entries start (RefitViewWork::rankToNode)
+    int32_t nPairs;             // its internal nodes
+    int32_t blockBase;          // the first of its ceil(nPairs / 256) workgroups in rz_quality_partials' grid
+};
+int quality_device(const rz_bvh_node* nodes, const int32_t* rank, const QualityView* views, int nViews, int nBlocks, double* partials,
+                   double* cost, hipStream_t s);
+
 // ---- rz_skin.hip
 struct SkinWork {               // one rig posed: every pointer is device memory
     const rz_triangle* rest;            // n rest triangles

@@ -260,6 +260,38 @@ void BVH::refit(const Triangle* tris, BVHNode* nodes, int nNodes, const int* idx
     }
 }
 
+// The SAH cost of include/rayzen_hip.h (rz_geometry_quality), the quantity buildBLAS minimises greedily, over the nodes
+// reachable from the root: (sum of A over internal nodes + sum of A * count over leaves) / A(root), areas in binary64 from
+// the binary32 bounds (the expression of `surface` above), 0 for an inverted or NaN box.  The device half
+// (rz_quality.hip) is held to this within 1e-9 relative.
+double BVH::sahCost() const { return nodes.empty() ? 0.0 : sahCost(nodes.data(), (int)nodes.size()); }
+
+double BVH::sahCost(const BVHNode* nodes, int nNodes) {
+    auto area = [](const BVHNode& N) {
+        const double dx = (double)N.boundsMax.x - (double)N.boundsMin.x, dy = (double)N.boundsMax.y - (double)N.boundsMin.y,
+                     dz = (double)N.boundsMax.z - (double)N.boundsMin.z;
+        if (!(dx >= 0.0) || !(dy >= 0.0) || !(dz >= 0.0)) return 0.0;
+        return 2.0 * (dx * dy + dy * dz + dz * dx);
+    };
+    if (nNodes < 1) return 0.0;
+    double sum = 0.0;
+    std::vector<int> st;
+    st.push_back(0);
+    size_t visited = 0;
+    while (!st.empty()) {
+        const int n = st.back();
+        st.pop_back();
+        if (n < 0 || n >= nNodes || ++visited > (size_t)nNodes) return -1.0;       // not a tree inside the array
+        const BVHNode& N = nodes[n];
+        if (N.count >= 0) { sum += area(N) * (double)N.count; continue; }
+        sum += area(N);
+        st.push_back(N.leftFirst);
+        st.push_back(N.leftFirst + 1);
+    }
+    const double rootArea = area(nodes[0]);
+    return rootArea == 0.0 ? 0.0 : sum / rootArea;
+}
+
 int BVH::depth() const {
     if (nodes.empty()) return 0;
     int best = 1;

@@ -84,6 +84,10 @@ public:
     void refit(const std::vector<Triangle>& tris);
     // ... the same on raw arrays: child indices relative to `nodes`, `idx` the mesh's index array, triangle = tris[idx[slot]]
     static void refit(const Triangle* tris, BVHNode* nodes, int nNodes, const int* idx);
+    // The tree's SAH cost as rz_geometry_quality reports it (include/rayzen_hip.h states it): what a refit lets grow and a
+    // rebuild brings back.  On raw arrays: -1 if the nodes do not form a tree inside the array.
+    double sahCost() const;
+    static double sahCost(const BVHNode* nodes, int nNodes);
     // Longest root-to-leaf path, in nodes (root alone = 1).  The render
     // library sizes its LDS traversal stacks from this.
     int depth() const;
@@ -188,6 +192,12 @@ struct SceneBuffers {
     // the TLAS are rebuilt with the transforms in force, as updateDynamic does.  false: the mesh is not in the scene
     // or its triangle count changed (nothing is touched then).  The byte partner of rz_refit_geometry.
     bool refitMesh(const Scene& scene, const Mesh* mesh);
+    // A refitted mesh has degraded enough: every stored copy of it gets a fresh BLAS (buildBLAS, or `blasBuilder`) of its
+    // triangles as allTriangles holds them now, its indices are replaced in place, the node array is flattened again in the
+    // same order -- a rebuilt tree has another node count, so every later BLAS moves and every instance's blasNodeOffset is
+    // patched -- and the world boxes and the TLAS are rebuilt with the transforms in force.  false: the mesh is not in the
+    // scene (nothing is touched then).  The byte partner of rz_rebuild_geometry.
+    bool rebuildMesh(const Scene& scene, const Mesh* mesh);
 
     // Optional replacement for BVH::buildBLAS, e.g. rz_build_blas of include/rayzen_hip.h bound to a context (the
     // device builder, byte-identical output).  Fills `out.nodes` / `out.triIndices`; returns false on failure.

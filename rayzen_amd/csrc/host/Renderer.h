@@ -156,6 +156,28 @@ public:
               "rz_skin_pose");
     }
     void destroyRig(int rig) { check(rz_skin_destroy(ctx_, rig), "rz_skin_destroy"); }
+    // How far refits have degraded each mesh's tree (rz_geometry_quality): one record per mesh with its SAH cost as it stands
+    // and the cost it had when it was last handed over or built.  Measured on the device; synchronises.
+    std::vector<rz_mesh_quality> meshQuality() {
+        size_t n = 0;
+        check(rz_geometry_quality(ctx_, nullptr, 0, &n), "rz_geometry_quality");
+        std::vector<rz_mesh_quality> out(n);
+        check(rz_geometry_quality(ctx_, out.data(), out.size(), &n), "rz_geometry_quality");
+        out.resize(n);
+        return out;
+    }
+    // The exit from the refit's steady state (rz_rebuild_geometry): every mesh whose cost exceeds maxRatio times the cost it
+    // was built with is rebuilt on the device from binding 0 as it stands there (posed triangles never visit the host);
+    // instances and TLAS follow.  Returns the records; RZ_QUALITY_REBUILT marks what was rebuilt.  As with refitMesh the
+    // host copies in buffers_ are NOT updated (SceneBuffers::rebuildMesh is the host partner).
+    std::vector<rz_mesh_quality> rebuildDegraded(double maxRatio) {
+        size_t n = 0;
+        check(rz_geometry_quality(ctx_, nullptr, 0, &n), "rz_geometry_quality");
+        std::vector<rz_mesh_quality> out(n);
+        check(rz_rebuild_geometry(ctx_, maxRatio, out.data(), out.size(), &n, 0), "rz_rebuild_geometry");
+        out.resize(n);
+        return out;
+    }
     void sendSceneDataToShader(const Scene& scene, int width, int height, int bounceBudget, int spp = 1,
                                int sampleBase = 0, int tileRank = 0, int tileNRanks = 1) {
         rz_frame_params p{};

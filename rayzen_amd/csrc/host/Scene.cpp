@@ -7,6 +7,8 @@
 
 #include <algorithm>
 #include <map>
+#include <utility>
+#include <vector>
 
 namespace rayzen {
 
@@ -126,6 +128,75 @@ bool SceneBuffers::refitMesh(const Scene& scene, const Mesh* mesh) {
     }
     for (size_t i = 0; i < meshInstances.size(); ++i)
         if (copies.count(meshInstances[i].blasNodeOffset)) blasRoots[i] = allBLASNodes[(size_t)meshInstances[i].blasNodeOffset];
+    std::vector<BVHNode> worldRootNodes(meshInstances.size());
+    for (size_t i = 0; i < meshInstances.size(); ++i) worldRootNodes[i] = worldRootNode(blasRoots[i], meshInstances[i].transform);
+    BVH tlas;
+    tlas.buildTLAS(meshInstances, worldRootNodes);
+    tlasNodes = tlas.nodes;
+    tlasTriIndices = tlas.triIndices;
+    tlasDepth = tlas.depth();
+    return true;
+}
+
+bool SceneBuffers::rebuildMesh(const Scene& scene, const Mesh* mesh) {
+    const size_t nObj = std::min(meshInstances.size(), scene.gameObjects.size());
+    const int nTris = (int)mesh->triangles.size();
+    // the node extents of every stored BLAS, ascending: [start, the next larger distinct start or the end of the array)
+    std::vector<int> starts;
+    for (const BVHInstance& inst : meshInstances) starts.push_back(inst.blasNodeOffset);
+    std::sort(starts.begin(), starts.end());
+    starts.erase(std::unique(starts.begin(), starts.end()), starts.end());
+    if (starts.empty() || starts.front() < 0 || (size_t)starts.back() >= allBLASNodes.size()) return false;
+    starts.push_back((int)allBLASNodes.size());
+    struct Copy { int triOffset, triBase; };
+    std::map<int, Copy> copies;             // the copies of this mesh, by node offset
+    for (size_t i = 0; i < nObj; ++i) {
+        if (scene.gameObjects[i].mesh.get() != mesh) continue;
+        const BVHInstance& inst = meshInstances[i];
+        if (inst.blasTriOffset < 0 || (size_t)inst.blasTriOffset + (size_t)nTris > allBLASTriIndices.size() || inst.globalTriOffset < 0 ||
+            (size_t)inst.globalTriOffset + (size_t)nTris > allTriangles.size())
+            return false;
+        copies[inst.blasNodeOffset] = {inst.blasTriOffset, inst.globalTriOffset};
+    }
+    if (copies.empty()) return false;
+    std::vector<BVHNode> nodes(allBLASNodes.begin(), allBLASNodes.begin() + starts.front());   // (nodes no instance names stay)
+    std::map<int, int> moved;               // node offset before -> after
+    for (size_t k = 0; k + 1 < starts.size(); ++k) {
+        const int at = starts[k], end = starts[k + 1];
+        moved[at] = (int)nodes.size();
+        const auto it = copies.find(at);
+        if (it == copies.end()) {
+            nodes.insert(nodes.end(), allBLASNodes.begin() + at, allBLASNodes.begin() + end);
+            continue;
+        }
+        BVH blas;
+        if (blasBuilder) {
+            Mesh current;
+            current.triangles.assign(allTriangles.begin() + it->second.triBase, allTriangles.begin() + it->second.triBase + nTris);
+            if (!blasBuilder(current, blas)) return false;
+        } else {
+            blas.buildBLAS(allTriangles.data() + it->second.triBase, nTris);
+        }
+        nodes.insert(nodes.end(), blas.nodes.begin(), blas.nodes.end());
+        std::copy(blas.triIndices.begin(), blas.triIndices.end(), allBLASTriIndices.begin() + it->second.triOffset);
+    }
+    allBLASNodes.swap(nodes);
+    // the deepest BLAS now stored, as build() would find it on these triangles (the rebuilt tree may be shallower than the old one)
+    maxBLASDepth = 1;
+    for (const auto& kv : moved) {
+        std::vector<std::pair<int, int>> st{{kv.second, 1}};
+        while (!st.empty()) {
+            const auto [n, d] = st.back();
+            st.pop_back();
+            maxBLASDepth = std::max(maxBLASDepth, d);
+            const BVHNode& N = allBLASNodes[(size_t)n];
+            if (N.count < 0) { st.push_back({kv.second + N.leftFirst, d + 1}); st.push_back({kv.second + N.leftFirst + 1, d + 1}); }
+        }
+    }
+    for (size_t i = 0; i < meshInstances.size(); ++i) {
+        meshInstances[i].blasNodeOffset = moved.at(meshInstances[i].blasNodeOffset);
+        blasRoots[i] = allBLASNodes[(size_t)meshInstances[i].blasNodeOffset];
+    }
     std::vector<BVHNode> worldRootNodes(meshInstances.size());
     for (size_t i = 0; i < meshInstances.size(); ++i) worldRootNodes[i] = worldRootNode(blasRoots[i], meshInstances[i].transform);
     BVH tlas;

@@ -60,6 +60,11 @@ int rzh_refit_blas(const rz_triangle* tris, int n, rz_bvh_node* nodes_inout, int
     return 0;
 }
 
+double rzh_blas_sah_cost(const rz_bvh_node* nodes, int n_nodes) {
+    if (!nodes || n_nodes < 1) return -1.0;
+    return BVH::sahCost(reinterpret_cast<const BVHNode*>(nodes), n_nodes);
+}
+
 int rzh_build_tlas(const rz_bvh_node* world_roots, int n, rz_bvh_node* nodes_out, int32_t* idx_out, int* n_idx_out) {
     if (n < 0 || !nodes_out || (n > 0 && (!world_roots || !idx_out))) return -1;
     std::vector<BVHInstance> inst((size_t)n);
@@ -143,6 +148,11 @@ int rzh_scene_refit_mesh(rzh_scene* s, int mesh_id, const rz_triangle* tris, int
     if ((size_t)n != m.triangles.size()) return -1;
     if (n > 0) std::memcpy(static_cast<void*>(m.triangles.data()), tris, (size_t)n * sizeof(Triangle));
     return s->buffers.refitMesh(s->scene, &m) ? 0 : -1;
+}
+
+int rzh_scene_rebuild_mesh(rzh_scene* s, int mesh_id) {
+    if (!s || !s->built || mesh_id < 0 || mesh_id >= (int)s->meshes.size()) return -1;
+    return s->buffers.rebuildMesh(s->scene, s->meshes[(size_t)mesh_id].get()) ? 0 : -1;
 }
 
 int rzh_skin_triangles(const rz_triangle* rest, const rz_skin_triangle* skin, int n, const float* bones, int n_bones,

@@ -38,6 +38,9 @@ RAY_DTYPE = np.dtype([("origin", "<f4", 3), ("max_dist", "<f4"), ("dir", "<f4", 
 HIT_DTYPE = np.dtype([("t", "<f4"), ("point", "<f4", 3), ("normal", "<f4", 3), ("material", "<i4"), ("instance", "<i4"),
                       ("triangle", "<i4"), ("prim", "<i4"), ("reserved", "<i4")])                                # rz_hit
 VISIBILITY_DTYPE = np.dtype([("visibility", "<f4"), ("lit", "<i4")])                                         # rz_visibility
+MESH_QUALITY = np.dtype([("node_offset", "<i4"), ("index_offset", "<i4"), ("tri_offset", "<i4"), ("node_offset_before", "<i4"),
+                         ("n_triangles", "<i4"), ("n_nodes", "<i4"), ("depth", "<i4"), ("flags", "<u4"), ("sah_cost", "<f8"),
+                         ("sah_cost_built", "<f8"), ("sah_cost_before", "<f8"), ("reserved", "<f8")])        # rz_mesh_quality
 
 
 def make_rays(origins, dirs, max_dist=1e30):
@@ -204,6 +207,28 @@ class Renderer:
         ms = C.c_float(0)
         self._check(self._L.rz_skin_last_kernel_ms(self._c, C.byref(ms)), "rz_skin_last_kernel_ms")
         return ms.value
+
+    def geometry_quality(self):
+        """rz_geometry_quality: one MESH_QUALITY record per mesh (a distinct offset triple among the instances), in ascending
+        order of the triple: its SAH cost as the tree stands, the cost it had when it was last handed over or built, its
+        triangle and node counts and its depth.  Measured on the device; synchronises."""
+        n = C.c_size_t(0)
+        self._check(self._L.rz_geometry_quality(self._c, None, 0, C.byref(n)), "rz_geometry_quality")
+        out = np.zeros(n.value, MESH_QUALITY)
+        self._check(self._L.rz_geometry_quality(self._c, out.ctypes.data if n.value else None, n.value, C.byref(n)), "rz_geometry_quality")
+        return out[:n.value]
+
+    def rebuild_geometry(self, max_ratio=0.0):
+        """rz_rebuild_geometry: every mesh whose SAH cost exceeds max_ratio times the cost it was built with gets a fresh BLAS
+        on the device from binding 0 as it stands there; later meshes move in binding 7, the instances' offsets are patched
+        and the TLAS follows with the transforms in force.  max_ratio = 0 rebuilds every mesh with a non-zero cost.  Returns
+        the MESH_QUALITY records (flags & QUALITY_REBUILT: rebuilt by this call; both costs are reported)."""
+        n = C.c_size_t(0)
+        self._check(self._L.rz_geometry_quality(self._c, None, 0, C.byref(n)), "rz_geometry_quality")
+        out = np.zeros(n.value, MESH_QUALITY)
+        self._check(self._L.rz_rebuild_geometry(self._c, float(max_ratio), out.ctypes.data if n.value else None, n.value, C.byref(n), 0),
+                    "rz_rebuild_geometry")
+        return out[:n.value]
 
     def build_blas(self, triangles):
         """BVH::buildBLAS (BVH.cpp:99-175, SAH) on the device.  triangles: TRIANGLE_DTYPE array.

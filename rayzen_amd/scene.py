@@ -139,6 +139,16 @@ def refit_blas(tris, nodes, idx):
     return out
 
 
+def sah_cost(nodes):
+    """BVH::sahCost (librayzen_host.so: rzh_blas_sah_cost): the SAH cost of one BLAS over the nodes its root reaches, as
+    include/rayzen_hip.h states it for rz_geometry_quality.  The host partner of Renderer.geometry_quality."""
+    nodes = np.ascontiguousarray(nodes, BVH_NODE)
+    cost = _lib.host().rzh_blas_sah_cost(_p(nodes) if nodes.shape[0] else None, nodes.shape[0])
+    if cost < 0:
+        raise RuntimeError("rzh_blas_sah_cost failed (the nodes do not form a tree)")
+    return cost
+
+
 def pack_bones(indices):
     """Four 8-bit bone indices per corner -> the words of SKIN_TRIANGLE["bones"]: indices[..., j] goes to bits 8j..8j+7."""
     b = np.asarray(indices).astype(np.uint32)
@@ -335,6 +345,15 @@ class Scene:
         assert tris.dtype.itemsize == 64
         if _lib.host().rzh_scene_refit_mesh(self._h, int(mesh_id), _p(tris) if tris.shape[0] else None, tris.shape[0]) != 0:
             raise RuntimeError("rzh_scene_refit_mesh failed (unknown mesh, or its triangle count changed)")
+        self._pull(GEOMETRY_BINDINGS)
+        return self
+
+    def rebuild_mesh(self, mesh_id):
+        """A refitted mesh gets a fresh BLAS of its current triangles in every stored copy; bindings 7, 8 and 9 are patched (a
+        rebuilt tree has another node count, so later meshes move) and the world boxes and the TLAS are rebuilt with the
+        transforms in force.  The host partner of Renderer.rebuild_geometry."""
+        if _lib.host().rzh_scene_rebuild_mesh(self._h, int(mesh_id)) != 0:
+            raise RuntimeError("rzh_scene_rebuild_mesh failed (unknown mesh)")
         self._pull(GEOMETRY_BINDINGS)
         return self
 
