@@ -672,6 +672,15 @@ int rz_render_editor(rz_ctx* ctx, const rz_frame_params* frame, const rz_editor_
  *            A hit and a miss never mix; different instances may (the normal and plane terms separate them where the geometry
  *            does).  The centre weight 9/64 keeps every sum non-empty.
  *   K = 0: no filtering, the output is exactly c_p.
+ *   Non-finite samples.  A pixel p is BAD in a call iff a channel of c_p (after the divide by n) is NaN or +-Inf, decided on
+ *            the bit pattern (exponent field all ones).  A bad sample never leaves its pixel: only pass 0 changes, and for an
+ *            input without bad pixels every output byte is what it would be without this rule.  In pass 0 a bad tap q is
+ *            dropped exactly as a tap outside the image is.  A bad centre p drops its own centre term as well (num and den start
+ *            at 0), takes the colour weight of every remaining tap as 1 (h_a h_b, the hit-or-miss rule and W_geom apply as
+ *            written), and d'_p = num / den where den > 0, otherwise (0, 0, 0); d_p of a bad pixel is never used in arithmetic.
+ *            Pass 0's output is therefore finite, and passes 1..K-1 and the re-modulation are as written.  K = 0 stays "the
+ *            output is exactly c_p", bad or not (rz_present_denoised at K = 0 keeps rz_present's bytes).  (n = NaN counts as
+ *            n = 1; a finite sum over n = +Inf is c = 0, not bad.)
  * Defaults (params NULL): K = 5, sigma_color = 0.5, sigma_normal = 128, sigma_plane = 1, demodulate = 1 -- chosen by the CPU
  * measurement of tests/test_denoise_abi.py.  Arithmetic is binary32.
  * Camera and size come from the last rz_set_frame (width, height, inv_view, inv_proj, cam_pos), as rz_present takes them.
@@ -748,6 +757,15 @@ int rz_present_denoised(rz_ctx* ctx, const rz_present_params* present, const rz_
  *            After the last pass a hit's colour is multiplied by alpha_p again (demodulate).
  *            K = 0: the output is D_p alpha_p (demodulate and a hit; else D_p) where history was accepted and c_p itself where
  *            it was not -- so a call on an empty history returns exactly what rz_denoise returns for K = 0.
+ *  Non-finite samples.  p is BAD iff a channel of c_p is NaN or +-Inf (rz_denoise's definition, on the bit pattern).  A bad
+ *            sample never outlives its frame: steps 2 and 3 are as written (they never read d_p); then, for a bad p,
+ *            d_p := D_h where history was accepted, otherwise (0, 0, 0), and l_p is taken from that d_p.  Step 4 is as written:
+ *            with d_p = D_h the blend returns D_h exactly and N counts on; steps 5 and 6 see a finite D.  The K = 0 rule
+ *            stays: D_p alpha_p where history was accepted, c_p itself where not -- so a bad pixel shows through at K = 0 on a
+ *            pixel without history, and only there.  Consequence: a bad sample without history is stored as black with N = 1
+ *            and fades as 1 / N afterwards (it is not filled from its neighbours).  For an input without bad pixels every
+ *            output byte is what it would be without this rule.  rz_present_temporal, and rz_present_display with source 1 or
+ *            2, run these kernels and follow.
  * The history -- D | N, the moments, the guide (rz_hit records), the frame's view, proj, inv_proj and cam_pos, and every
  * instance's transform and inverseTransform -- lives in the context: allocated by the first call, sized by the frame, freed by
  * rz_destroy.  A call commits what it computed as the new history (two sets of buffers swap roles; no frame is copied) unless

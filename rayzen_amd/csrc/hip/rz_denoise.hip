@@ -23,6 +23,9 @@
 //     W_geom = max(0, n_p.n_q)^sigma_n exp(-|n_p.(x_q - x_p)| / (sigma_x t_p f s max(|a|, |b|)))  when both are hits,
 //              1 when both are misses and for the centre tap;  f = 2 |inv_proj[5]| / height
 //   out_p = d_p alpha_p after the last pass (demodulate = 1), else d_p;  K = 0: out_p = c_p exactly.
+// A pixel whose c has a NaN or an infinite channel is bad: pass 0 drops it as a tap (as a tap outside the image), and as a centre
+// it drops its own term, takes every remaining tap at colour weight 1 and becomes num / den, or (0, 0, 0) when no tap is left.  So
+// pass 0's output is finite and the later passes need no test (include/rayzen_hip.h states the rule).
 // Arithmetic is binary32 (tests/denoise_ref.py restates it in binary64; tests/test_denoise_gpu.py states the tolerance).
 #include "rz_internal.h"
 #include "rz_query.h"
@@ -82,14 +85,17 @@ __device__ __forceinline__ v3 albedo_of(const DenoiseLaunch& D, int word) {
     const DevMaterial& m = D.materials[word];
     return mk3(m.albedo[0], m.albedo[1], m.albedo[2]);
 }
-// the colour d_q a pass filters: pass 0 resolves (and demodulates) the input; later passes read the previous pass's output
+// the colour d_q a pass filters: pass 0 resolves (and demodulates) the input and says whether c_q is bad; later passes read the
+// previous pass's output, which is finite
 template <bool FIRST>
-__device__ __forceinline__ v3 pass_input(const DenoiseLaunch& D, size_t q, int word) {
+__device__ __forceinline__ v3 pass_input(const DenoiseLaunch& D, size_t q, int word, bool& bad) {
+    bad = false;
     if (!FIRST) {
         const float4 s = D.src[q];
         return mk3(s.x, s.y, s.z);
     }
     v3 c = resolve_px(D.accum[q]);
+    bad = nonfinite_(c);
     if (D.demodulate && word >= 0) {
         const v3 al = albedo_of(D, word);
         c = mk3(c.x / fmax_(al.x, 1e-3f), c.y / fmax_(al.y, 1e-3f), c.z / fmax_(al.z, 1e-3f));
@@ -109,12 +115,17 @@ __global__ __launch_bounds__(256) void rz_denoise_atrous(const DenoiseLaunch D) 
     const int wordP = __float_as_int(g1.w);
     const bool hitP = wordP >= 0;
     const v3 np_ = mk3(g0.x, g0.y, g0.z), xp = mk3(g1.x, g1.y, g1.z);
-    const v3 dp = pass_input<FIRST>(D, p, wordP);
+    bool badP, badQ;
+    const v3 dp = pass_input<FIRST>(D, p, wordP, badP);
     // 1 / (sigma_x t_p f s): the plane term's denominator without max(|a|, |b|)
     const float invPlane = hitP ? D.planeScale / g0.w : 0.0f;
     const float centre = atrous_h(0) * atrous_h(0);
     v3 num = dp * centre;
     float den = centre;
+    if (FIRST && badP) {        // a bad centre leaves its own term out
+        num = mk3(0.0f, 0.0f, 0.0f);
+        den = 0.0f;
+    }
 #pragma unroll
     for (int b = -2; b <= 2; ++b) {
         const int qy = py + b * D.step;
@@ -137,14 +148,18 @@ __global__ __launch_bounds__(256) void rz_denoise_atrous(const DenoiseLaunch D) 
                 const float pl = __builtin_fabsf(dot(np_, mk3(h1.x, h1.y, h1.z) - xp)) * (invPlane * m);
                 w *= wn * __builtin_expf(-pl);
             }
-            const v3 dq = pass_input<FIRST>(D, q, wordQ);
-            const v3 e = dp - dq;
-            w *= __builtin_expf(-dot(e, e) * D.invColor);
+            const v3 dq = pass_input<FIRST>(D, q, wordQ, badQ);
+            if (FIRST && badQ) continue;                        // a bad tap is dropped like one outside the image
+            if (!(FIRST && badP)) {                             // (a bad centre has no colour to compare with: weight 1)
+                const v3 e = dp - dq;
+                w *= __builtin_expf(-dot(e, e) * D.invColor);
+            }
             num = num + dq * w;
             den += w;
         }
     }
     v3 out = mk3(num.x / den, num.y / den, num.z / den);
+    if (FIRST && badP && !(den > 0.0f)) out = mk3(0.0f, 0.0f, 0.0f);       // every tap dropped
     if (LAST && D.demodulate) {
         const v3 al = albedo_of(D, wordP);
         out = mk3(out.x * al.x, out.y * al.y, out.z * al.z);

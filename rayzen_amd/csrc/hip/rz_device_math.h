@@ -45,6 +45,9 @@ __device__ __forceinline__ float fmin_(float a, float b) { return __builtin_fmin
 __device__ __forceinline__ float fmax_(float a, float b) { return __builtin_fmaxf(a, b); }
 __device__ __forceinline__ float clamp_(float x, float lo, float hi) { return fmin_(fmax_(x, lo), hi); }
 __device__ __forceinline__ float mix_(float a, float b, float t) { return a * (1.0f - t) + b * t; }
+// NaN or +-Inf, read off the exponent field: a test on the bits, which no floating-point flag lets the compiler fold away
+__device__ __forceinline__ bool nonfinite_(float x) { return (__float_as_uint(x) & 0x7f800000u) == 0x7f800000u; }
+__device__ __forceinline__ bool nonfinite_(v3 a) { return nonfinite_(a.x) || nonfinite_(a.y) || nonfinite_(a.z); }
 __device__ __forceinline__ float fract_(float x) { return x - __builtin_floorf(x); }
 __device__ __forceinline__ float pow2_(float x) { return x * x; }
 __device__ __forceinline__ float pow5_(float x) { float x2 = x * x; float x4 = x2 * x2; return x4 * x; }

@@ -9,7 +9,8 @@
 //   rz_temporal_accumulate  one lane per pixel, 64 x 4 pixels per workgroup: resolves and demodulates the pixel, reprojects it
 //                           into the previous frame (through the instance's previous transform), gathers the (up to) four
 //                           bilinear taps of the previous guide, colour and moments, and blends.  Writes the new colour | N and
-//                           the new moments; K = 0: the outputs too.
+//                           the new moments; K = 0: the outputs too.  A sample with a NaN or infinite channel is replaced by
+//                           the reprojected history colour (black without one) before the blend: what is stored is finite.
 //   rz_temporal_variance    one lane per pixel: the variance the filter is guided by -- the temporal one where N >= 4 (two loads,
 //                           one store: the steady state), a 7 x 7 spatial estimate elsewhere (a fresh history only) -- as the .w
 //                           of the filter's input (colour | variance), and the stats.
@@ -67,7 +68,7 @@ __global__ __launch_bounds__(256) void rz_temporal_accumulate(const TemporalLaun
     }
     v3 d = c;
     if (T.demodulate && hit) d = mk3(c.x / fmax_(al.x, 1e-3f), c.y / fmax_(al.y, 1e-3f), c.z / fmax_(al.z, 1e-3f));
-    const float l = lum_of(d);
+    float l = lum_of(d);
 
     // ---- the history: reprojection, the taps
     float S = 0.0f, nH = 0.0f, n0 = 0.0f, m1 = 0.0f, m2 = 0.0f;
@@ -142,11 +143,15 @@ __global__ __launch_bounds__(256) void rz_temporal_accumulate(const TemporalLaun
             }
         }
     }
+    const bool accepted = S >= 0.01f;
+    if (accepted) dH = mk3(dH.x / S, dH.y / S, dH.z / S);
+    if (nonfinite_(c)) {        // a bad sample (NaN or Inf in c_p): the history's colour stands in for it, black without one
+        d = accepted ? dH : mk3(0.0f, 0.0f, 0.0f);
+        l = lum_of(d);
+    }
     float N = 1.0f, M1 = l, M2 = l * l;
     v3 D = d;
-    const bool accepted = S >= 0.01f;
     if (accepted) {
-        dH = mk3(dH.x / S, dH.y / S, dH.z / S);
         nH = n0 + nH / S; m1 = m1 / S; m2 = m2 / S;
         N = fmin_(nH + 1.0f, T.maxHistory);
         const float a = fmax_(T.alpha, 1.0f / N), am = fmax_(T.alphaMoments, 1.0f / N);

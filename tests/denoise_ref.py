@@ -16,6 +16,12 @@ def resolve(accum):
     return (a[..., :3] / n[..., None]).astype(np.float32)
 
 
+def bad_pixels(color):
+    """The pixels the header calls bad: a channel of the binary32 c is NaN or +-Inf (the exponent field all ones)."""
+    bits = np.ascontiguousarray(color, np.float32).view(np.uint32)
+    return ((bits & 0x7F800000) == 0x7F800000).any(-1)
+
+
 def pixel_scale(inv_proj, height):
     """f = 2 |inv_proj[5]| / height: the world size of one pixel at unit distance."""
     return 2.0 * abs(float(np.float32(np.asarray(inv_proj, np.float32).reshape(16)[5]))) / float(height)
@@ -43,10 +49,14 @@ def _shift(a, dx, dy, fill):
     return out, valid
 
 
-def atrous_pass(d, hit, n, x, t, f, i, sigma_color, sigma_normal, sigma_plane, want_weights=False):
-    """Pass i (step s = 2^i) on the colour d (H, W, 3).  Returns d' (and, with want_weights, the normalised weight of every tap:
-    a dict (a, b) -> (H, W) array)."""
+def atrous_pass(d, hit, n, x, t, f, i, sigma_color, sigma_normal, sigma_plane, want_weights=False, bad=None, want_den=False):
+    """Pass i (step s = 2^i) on the colour d (H, W, 3).  bad (H, W) bool: the bad pixels of pass 0 (None: none) -- dropped as
+    taps; as centres they drop their own term, weigh every remaining tap's colour term as 1 and come out as num / den, or 0
+    where den is 0.  Their d is masked to 0 before any arithmetic touches it.  Returns d' (and, with want_weights, the normalised
+    weight of every tap: a dict (a, b) -> (H, W) array; with want_den, the pass's den)."""
     s = 1 << i
+    bad = np.zeros(d.shape[:2], bool) if bad is None else np.asarray(bad, bool)
+    d = np.where(bad[..., None], 0.0, d)
     num = np.zeros_like(d)
     den = np.zeros(d.shape[:2])
     raw = {}
@@ -56,7 +66,8 @@ def atrous_pass(d, hit, n, x, t, f, i, sigma_color, sigma_normal, sigma_plane, w
             for a in range(-2, 3):
                 dq, valid = _shift(d, a * s, b * s, 0.0)
                 hq, _ = _shift(hit, a * s, b * s, False)
-                w = H_KERNEL[a + 2] * H_KERNEL[b + 2] * (valid & (hq == hit))
+                bq, _ = _shift(bad, a * s, b * s, False)
+                w = H_KERNEL[a + 2] * H_KERNEL[b + 2] * (valid & (hq == hit) & ~bq)
                 if a != 0 or b != 0:
                     nq, _ = _shift(n, a * s, b * s, 0.0)
                     xq, _ = _shift(x, a * s, b * s, 0.0)
@@ -65,24 +76,30 @@ def atrous_pass(d, hit, n, x, t, f, i, sigma_color, sigma_normal, sigma_plane, w
                     wn = nd ** sigma_normal
                     plane = np.abs(np.sum(n * (xq - x), -1)) / (sigma_plane * t * f * s * max(abs(a), abs(b)))
                     w = w * np.where(both, wn * np.exp(-plane), 1.0)
-                w = w * np.exp(-np.sum((d - dq) ** 2, -1) * inv_c)
-                w = np.where(w > 0, w, 0.0)         # (a dropped tap stays at 0 whatever its 0 * inf gave)
+                w = w * np.where(bad, 1.0, np.exp(-np.sum((d - dq) ** 2, -1) * inv_c))
+                w = np.where(w > 0, w, 0.0)         # (a dropped tap stays at 0 whatever the 0 * inf of its geometry gave)
                 num += w[..., None] * dq
                 den += w
                 if want_weights:
                     raw[(a, b)] = w
-    out = num / den[..., None]
+        out = np.where((bad & ~(den > 0))[..., None], 0.0, num / den[..., None])
+    res = (out,)
     if want_weights:
-        return out, {k: v / den for k, v in raw.items()}
-    return out
+        res += ({k: v / den for k, v in raw.items()},)
+    if want_den:
+        res += (den,)
+    return res if len(res) > 1 else out
 
 
 def denoise(color, guides, materials, inv_proj, iterations=DEFAULTS["iterations"], sigma_color=DEFAULTS["sigma_color"],
-            sigma_normal=DEFAULTS["sigma_normal"], sigma_plane=DEFAULTS["sigma_plane"], demodulate=DEFAULTS["demodulate"]):
-    """The filtered colour (H, W, 3) float64.  iterations = 0 returns c itself."""
+            sigma_normal=DEFAULTS["sigma_normal"], sigma_plane=DEFAULTS["sigma_plane"], demodulate=DEFAULTS["demodulate"],
+            want_den=False):
+    """The filtered colour (H, W, 3) float64.  iterations = 0 returns c itself.  The bad pixels (bad_pixels of the binary32 c)
+    are contained by pass 0, so the result is finite for iterations >= 1.  want_den: also pass 0's den (0 where a bad pixel
+    found no tap: its pass-0 colour is exactly 0)."""
     c = np.asarray(color, np.float64)
     if iterations == 0:
-        return c.copy()
+        return (c.copy(), None) if want_den else c.copy()
     g = np.asarray(guides)
     H = c.shape[0]
     hit = g["instance"] >= 0
@@ -90,11 +107,15 @@ def denoise(color, guides, materials, inv_proj, iterations=DEFAULTS["iterations"
     x = g["point"].astype(np.float64)
     t = g["t"].astype(np.float64)
     f = pixel_scale(inv_proj, H)
+    bad = bad_pixels(color)
     alpha = albedo(g, materials) if demodulate else np.ones_like(c)
-    d = c / np.maximum(alpha, 1e-3) if demodulate else c.copy()
-    for i in range(iterations):
+    with np.errstate(invalid="ignore", over="ignore"):
+        d = c / np.maximum(alpha, 1e-3) if demodulate else c.copy()
+    d, den0 = atrous_pass(d, hit, n, x, t, f, 0, sigma_color, sigma_normal, sigma_plane, bad=bad, want_den=True)
+    for i in range(1, iterations):
         d = atrous_pass(d, hit, n, x, t, f, i, sigma_color, sigma_normal, sigma_plane)
-    return d * alpha if demodulate else d
+    out = d * alpha if demodulate else d
+    return (out, den0) if want_den else out
 
 
 def mse(a, b):

@@ -68,15 +68,19 @@ def accumulate(hist, color, guides, materials, view, proj, inst, miss_dir, p):
     """Steps 1-4 of the header.  color: c (H, W, 3); guides: this frame's rz_hit records; view, proj: this frame's; inst: this
     frame's (n, 2, 4, 3); miss_dir (H, W, 3): the unit direction of every pixel-centre ray (renderer.editor_rays).
     Returns a dict: D (H, W, 3), N, M (H, W, 2), accepted, S, out0 (the K = 0 output), ambiguous, scale (the largest magnitude
-    among the colours a pixel's result was formed from: the m_p of the tolerance), alpha, d."""
+    among the colours a pixel's result was formed from: the m_p of the tolerance), alpha, d, bad.
+    A bad pixel (DR.bad_pixels of the binary32 c) takes d := D_h where history is accepted and 0 where not; until then its d is
+    masked to 0, so no arithmetic touches the sample, and scale and the ambiguous masks stay finite and do not depend on it."""
     c = np.asarray(color, np.float64)
+    bad = DR.bad_pixels(color)
     g = np.asarray(guides)
     H, W = c.shape[:2]
     hit = g["instance"] >= 0
     demod = bool(p["demodulate"])
     alpha = DR.albedo(g, materials) if demod else np.ones_like(c)
-    d = np.where(hit[..., None] & demod, c / np.maximum(alpha, 1e-3), c)
-    l = lum(d)
+    with np.errstate(invalid="ignore", over="ignore"):
+        d = np.where(hit[..., None] & demod, c / np.maximum(alpha, 1e-3), c)
+    d = np.where(bad[..., None], 0.0, d)
     amb = np.zeros((H, W), bool)
     parts = {k: np.zeros((H, W), bool) for k in ("clip_w", "floor", "normal", "plane", "S")}
     S = np.zeros((H, W))
@@ -165,6 +169,8 @@ def accumulate(hist, color, guides, materials, view, proj, inst, miss_dir, p):
     with np.errstate(invalid="ignore", divide="ignore"):
         Ssafe = np.where(accepted, S, 1.0)
         dH, nH, m1, m2 = dH / Ssafe[..., None], n0 + nH / Ssafe, m1 / Ssafe, m2 / Ssafe
+    d = np.where(bad[..., None], np.where(accepted[..., None], dH, 0.0), d)
+    l = lum(d)
     N = np.where(accepted, np.minimum(nH + 1.0, float(p["max_history"])), 1.0)
     a = np.maximum(p["alpha"], 1.0 / N)
     am = np.maximum(p["alpha_moments"], 1.0 / N)
@@ -174,7 +180,7 @@ def accumulate(hist, color, guides, materials, view, proj, inst, miss_dir, p):
     out0 = np.where(accepted[..., None], D * alpha, c)
     # N >= 4 (the variance's branch): exact where every counted tap had one length, else open when N is within EPS of 4
     amb_n = accepted & (n_spread > 0) & _near(N, 4.0)
-    return dict(D=D, N=N, M=np.stack([M1, M2], -1), accepted=accepted, S=S, ambiguous_n=amb_n, ambiguous_parts=parts, out0=out0, ambiguous=amb, scale=scale, alpha=alpha, d=d)
+    return dict(D=D, N=N, M=np.stack([M1, M2], -1), accepted=accepted, S=S, ambiguous_n=amb_n, ambiguous_parts=parts, out0=out0, ambiguous=amb, scale=scale, alpha=alpha, d=d, bad=bad)
 
 
 def _geometry(guides, inv_proj):

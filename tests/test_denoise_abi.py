@@ -184,3 +184,116 @@ def test_quality_cornell_defaults_do_no_harm(cornell_frames):
     sc, c1, tgt, g = cornell_frames
     out = DR.denoise(c1, g, sc.materials, sc.camera.inv_proj)
     assert DR.mse(c1, tgt) / DR.mse(out, tgt) >= 0.99
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# non-finite samples (include/rayzen_hip.h, "Non-finite samples"): a bad pixel never leaves its pixel
+
+BAD_VALUES = {"nan": np.nan, "+inf": np.inf, "-inf": -np.inf}
+
+
+def bad_pattern(H, W):
+    """An isolated interior pixel, the corner (0, 0) and a 5 x 5 block: 27 pixels."""
+    m = np.zeros((H, W), bool)
+    m[5, 20] = m[0, 0] = True
+    m[12:17, 8:13] = True
+    return m
+
+
+def _reach(mask, r):
+    """The pixels within r (Chebyshev) of a pixel of mask."""
+    out = np.zeros_like(mask)
+    for y, x in zip(*np.nonzero(mask)):
+        out[max(0, y - r):y + r + 1, max(0, x - r):x + r + 1] = True
+    return out
+
+
+@pytest.mark.parametrize("value", sorted(BAD_VALUES))
+def test_ref_bad_samples_are_contained(value):
+    rng = np.random.default_rng(11)
+    H, W = 24, 32
+    g = _guides_plane(H, W)
+    g["instance"][:, 28:] = -1                      # some sky
+    mats = _mats((0.5, 0.6, 0.7))
+    clean = rng.random((H, W, 3)).astype(np.float32)
+    bad = bad_pattern(H, W)
+    c = clean.copy()
+    c[bad, 1] = BAD_VALUES[value]                   # one channel
+    c[5, 20] = BAD_VALUES[value]                    # ... and all three
+    assert np.array_equal(DR.bad_pixels(c), bad) and not DR.bad_pixels(clean).any()
+    assert np.array_equal(DR.denoise(c, g, mats, INV_PROJ, iterations=0), c.astype(np.float64), equal_nan=True)
+    for demod in (True, False):
+        for K in (1, 2, 5):
+            out, den = DR.denoise(c, g, mats, INV_PROJ, iterations=K, demodulate=demod, want_den=True)
+            assert np.isfinite(out).all() and np.isfinite(den).all(), (value, demod, K)
+            assert (den[~bad] >= 9 / 64).all()                  # a good pixel keeps its centre term
+            if K == 1:
+                # beyond the reach of one pass nothing changed at all; the block's centre found no tap: exactly 0
+                want = DR.denoise(clean, g, mats, INV_PROJ, iterations=1, demodulate=demod)
+                far = ~_reach(bad, 2)
+                assert far.any() and np.array_equal(out[far], want[far])
+                assert den[14, 10] == 0 and (out[14, 10] == 0).all() and (den[bad] == 0).sum() == 1
+
+
+def test_ref_bad_centre_is_the_geometry_weighted_mean_of_its_taps():
+    H, W = 9, 9
+    g = _guides_plane(H, W)
+    mats = _mats((1.0, 1.0, 1.0))
+    c = np.full((H, W, 3), 0.3, np.float32)
+    c[4, 4] = np.nan
+    for demod in (True, False):
+        out = DR.denoise(c, g, mats, INV_PROJ, iterations=1, demodulate=demod)
+        assert np.allclose(out, np.float32(0.3), rtol=1e-12, atol=0)
+    # the colour weight of a bad centre's taps is 1: with colours far apart (which a good centre would weigh down to nothing)
+    # the result is the h-weighted mean of the 24 taps on this plane (W_geom = 1 on it)
+    rng = np.random.default_rng(12)
+    c = (100.0 * rng.random((H, W, 3))).astype(np.float32)
+    c[4, 4, 2] = np.inf
+    out = DR.denoise(c, g, mats, INV_PROJ, iterations=1, sigma_color=0.01, demodulate=False)
+    h = np.outer(DR.H_KERNEL, DR.H_KERNEL)
+    h[2, 2] = 0.0
+    taps = c[2:7, 2:7].astype(np.float64)
+    taps[2, 2] = 0.0
+    want = (h[..., None] * taps).sum((0, 1)) / h.sum()
+    assert np.allclose(out[4, 4], want, rtol=1e-12, atol=0)
+    # every tap dropped (the whole frame bad): exactly 0 everywhere
+    out = DR.denoise(np.full((H, W, 3), -np.inf, np.float32), g, mats, INV_PROJ, iterations=3)
+    assert (out == 0).all()
+
+
+def test_ref_equals_its_former_self_on_finite_input(monkeypatch, cornell_frames):
+    """The restatement before the bad-pixel rule (restatement_before.py), run beside the current one on every call the tests of
+    this file make with a finite input: equal bit for bit."""
+    import restatement_before as RB
+    new_pass, new_denoise = DR.atrous_pass, DR.denoise
+    calls = {"pass": 0, "denoise": 0}
+
+    def both_pass(*a, **kw):
+        res = new_pass(*a, **kw)
+        if kw.get("bad") is None or not np.asarray(kw["bad"]).any():
+            old = RB.atrous_pass(*a, **{k: v for k, v in kw.items() if k == "want_weights"})
+            new = res if isinstance(res, tuple) else (res,)
+            old = old if isinstance(old, tuple) else (old,)
+            assert np.array_equal(new[0], old[0], equal_nan=True)
+            if kw.get("want_weights"):
+                assert all(np.array_equal(new[1][k], old[1][k], equal_nan=True) for k in old[1])
+            calls["pass"] += 1
+        return res
+
+    def both_denoise(color, *a, **kw):
+        res = new_denoise(color, *a, **kw)
+        assert not DR.bad_pixels(color).any()
+        assert np.array_equal(res, RB.denoise(color, *a, **kw))
+        calls["denoise"] += 1
+        return res
+
+    monkeypatch.setattr(DR, "atrous_pass", both_pass)
+    monkeypatch.setattr(DR, "denoise", both_denoise)
+    test_ref_k0_is_identity_and_constant_stays_constant()
+    test_ref_weights_are_a_partition_of_unity()
+    test_ref_hits_and_misses_never_exchange_colour()
+    test_ref_parallel_planes_at_different_depths_do_not_bleed()
+    test_ref_slanted_plane_with_noise_is_smoothed()
+    test_quality_cornell_tuned_setting_reduces_mse(cornell_frames)
+    test_quality_cornell_defaults_do_no_harm(cornell_frames)
+    assert calls["denoise"] >= 8 and calls["pass"] >= 30, calls

@@ -250,6 +250,117 @@ def test_ref_variance_and_filter_weights():
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# non-finite samples (include/rayzen_hip.h, "Non-finite samples"): a bad sample never outlives its frame
+
+BAD_VALUES = {"nan": np.nan, "+inf": np.inf, "-inf": -np.inf}
+
+
+def bad_pattern(H, W):
+    """An isolated interior pixel, the corner (0, 0) and a 5 x 5 block: 27 pixels."""
+    m = np.zeros((H, W), bool)
+    m[5, 20] = m[0, 0] = True
+    m[12:17, 8:13] = True
+    return m
+
+
+def _bad_sequence(value, K, frames=5, bad_frames=(0, 2)):
+    """32 x 24, the camera moving 0.05 to the left per frame (the previous position of every pixel but the rightmost columns is
+    inside the frame), the 27 pixels of bad_pattern set to `value` in bad_frames (one channel; the isolated pixel all three).
+    Yields (frame, bad mask, result, history)."""
+    rng = np.random.default_rng(21)
+    H, W = 24, 32
+    mats = _mats((0.5, 0.6, 0.7))
+    hist = None
+    for fr in range(frames):
+        cam = _look(cam=(-0.05 * fr, 0.0, 0.0), aspect=W / H)
+        g, md = _plane_guides(cam, W, H)
+        c = (0.2 + rng.random((H, W, 3))).astype(np.float32)
+        bad = bad_pattern(H, W) if fr in bad_frames else np.zeros((H, W), bool)
+        c[bad, 1] = BAD_VALUES[value]
+        if bad.any():
+            c[5, 20] = BAD_VALUES[value]
+        r, hist = _step(hist, c, g, md, cam, mats=mats, iterations=K)
+        assert np.array_equal(r["bad"], bad)
+        yield fr, bad, r, hist
+
+
+@pytest.mark.parametrize("value", sorted(BAD_VALUES))
+def test_ref_bad_samples_do_not_outlive_their_frame(value):
+    for fr, bad, r, hist in _bad_sequence(value, 5):
+        for k in ("D", "N", "M", "var", "out", "scale", "S"):
+            assert np.isfinite(r[k]).all(), (value, fr, k)
+        assert np.isfinite(hist["col"]).all() and np.isfinite(hist["mom"]).all()
+        if fr == 0:
+            assert (r["D"][bad] == 0).all() and (r["N"] == 1).all() and (r["M"][bad] == 0).all()
+        if fr == 2:
+            assert r["accepted"][bad].all() and (r["N"][bad] > 2.5).all()        # N counts on
+    for fr, bad, r, hist in _bad_sequence(value, 0):
+        shows = ~np.isfinite(r["out"]).all(-1)
+        assert np.array_equal(shows, bad & ~r["accepted"])
+        assert shows.sum() == (27 if fr == 0 else 0)
+        assert np.isfinite(hist["col"]).all() and np.isfinite(hist["mom"]).all()
+
+
+def test_ref_bad_sample_equals_a_sample_of_the_history_colour():
+    """With d_p := D_h the call stores what a call whose sample was D_h stores: D, N and the moments, bit for bit."""
+    rng = np.random.default_rng(22)
+    H, W = 24, 32
+    cam0, cam1 = _look(aspect=W / H), _look(cam=(-0.05, 0.02, 0.0), aspect=W / H)
+    g0, md0 = _plane_guides(cam0, W, H)
+    g1, md1 = _plane_guides(cam1, W, H)
+    _, hist = _step(None, rng.random((H, W, 3)).astype(np.float32), g0, md0, cam0, iterations=0)
+    c = rng.random((H, W, 3)).astype(np.float32)
+    bad = bad_pattern(H, W)
+    cb = c.copy()
+    cb[bad, 2] = np.nan
+    r, _ = _step(hist, cb, g1, md1, cam1, iterations=0)          # (albedo 1: d = c)
+    assert r["accepted"][bad].all()
+    assert np.array_equal(r["out"][bad], r["D"][bad])           # K = 0 with history: D alpha, not the sample
+    sub = c.astype(np.float64)
+    sub[bad] = r["D"][bad]                                       # = D_h there
+    r2, _ = _step(hist, sub, g1, md1, cam1, iterations=0)
+    for k in ("D", "N", "M", "var", "accepted"):
+        assert np.array_equal(r[k], r2[k]), k
+    clean, _ = _step(hist, c, g1, md1, cam1, iterations=0)
+    assert np.array_equal(r["D"][~bad], clean["D"][~bad]) and np.array_equal(r["N"], clean["N"])
+    # without history: black, N = 1
+    r0, _ = _step(None, cb, g1, md1, cam1, iterations=0)
+    assert (r0["D"][bad] == 0).all() and (r0["M"][bad] == 0).all() and (r0["N"] == 1).all()
+    assert np.isnan(r0["out"][bad][:, 2]).all() and np.isfinite(r0["out"][~bad]).all()
+
+
+def test_ref_equals_its_former_self_on_finite_input(monkeypatch):
+    """accumulate() before the bad-pixel rule (restatement_before.py), run beside the current one on every call the tests of
+    this file make with a finite input (the synthetic ones and the cornell orbit of the GPU tests): equal bit for bit."""
+    import restatement_before as RB
+    new_acc = TR.accumulate
+    calls = [0]
+
+    def both(hist, color, *a, **kw):
+        res = new_acc(hist, color, *a, **kw)
+        assert not res["bad"].any()
+        old = RB.accumulate(hist, color, *a, **kw)
+        for k, v in old.items():
+            if k == "ambiguous_parts":
+                assert all(np.array_equal(v[m], res[k][m]) for m in v)
+            else:
+                assert np.array_equal(v, res[k]), k
+        calls[0] += 1
+        return res
+
+    monkeypatch.setattr(TR, "accumulate", both)
+    test_ref_static_sequence_is_a_running_mean()
+    test_ref_colour_never_crosses_a_hit_miss_edge_or_an_instance()
+    test_ref_translated_camera_finds_the_same_surface_point()
+    test_ref_moved_instance_is_followed_through_its_previous_transform()
+    test_ref_disocclusion_restarts_at_one()
+    test_ref_variance_and_filter_weights()
+    make, W, H, step_deg, transforms = gpu_sequences()["cornell"]
+    run_sequence(make(), W, H, GPU_FRAMES, step_deg, TR.params(), transforms, CORNELL_PIVOT, CORNELL_LIFT)
+    assert calls[0] >= 30, calls
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # quality on the oracle's frames (the GPU's frames equal the oracle's bit for bit), and the ambiguity cap
 
 QW, QH, FRAMES = 160, 120, 16

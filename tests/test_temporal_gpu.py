@@ -70,14 +70,15 @@ def _rel(got, want, scale):
     return np.abs(np.asarray(got, np.float64) - want) / (np.abs(want) + scale + 1e-30)
 
 
-def _check_frame(r, sc, W, H, p, what):
-    """One committing K = 0 call, compared with the restatement stepped from the history read before it.  Returns the worst
-    relative error and the ambiguous share."""
+def _check_frame(r, sc, W, H, p, what, rgba_in=None):
+    """One committing K = 0 call (on the accumulation, or on rgba_in), compared with the restatement stepped from the history
+    read before it.  Returns the worst relative error, the ambiguous share and the restatement's result.  Where the restatement's
+    K = 0 output is not finite (a bad sample without history: c_p itself) the output is held to c_p's bytes, not to TOL."""
     cam = sc.camera
     hist = _history(r)
-    acc = r.read_accum()
+    acc = r.read_accum() if rgba_in is None else np.ascontiguousarray(rgba_in, F32)
     kw = {k: v for k, v in p.items() if k != "iterations"}
-    rgb, g, st = r.denoise_temporal(guides=True, stats=True, iterations=0, **kw)
+    rgb, g, st = r.denoise_temporal(rgba_in=rgba_in, guides=True, stats=True, iterations=0, **kw)
     new = _history(r)
     assert new["guide"].tobytes() == g.tobytes()
     assert new["view"].tobytes() == np.asarray(cam.view, F32).tobytes() and new["cam_pos"].tobytes() == np.asarray(cam.position, F32).tobytes()
@@ -89,13 +90,16 @@ def _check_frame(r, sc, W, H, p, what):
     share = float(ref["ambiguous_var"].mean())
     m = ref["scale"]
     nmax = float(hist["col"][..., 3].max()) if hist is not None else 1.0
+    shown = np.isfinite(ref["out0"]).all(-1)
+    assert np.array_equal(~shown, ref["bad"] & ~ref["accepted"])
+    assert rgb[ok & ~shown].tobytes() == DR.resolve(acc)[ok & ~shown].tobytes()
     m7 = _maxfilter(m, 7)
     errs = {
         "D": _rel(new["col"][..., :3], ref["D"], m[..., None])[ok],
         "N": _rel(new["col"][..., 3], ref["N"], nmax)[ok],
         "M1": _rel(new["mom"][..., 0], ref["M"][..., 0], m)[ok],
         "M2": _rel(new["mom"][..., 1], ref["M"][..., 1], m * m)[ok],
-        "out": _rel(rgb, ref["out0"], m[..., None])[ok],
+        "out": _rel(rgb, ref["out0"], m[..., None])[ok & shown],
         "var": _rel(st[..., 1], ref["var"], m7 * m7)[okv],
     }
     assert np.array_equal(st[..., 0], new["col"][..., 3])
