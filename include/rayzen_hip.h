@@ -894,6 +894,78 @@ int rz_present_display(rz_ctx* ctx, const rz_present_params* present, const rz_d
 int rz_display_reset(rz_ctx* ctx);
 int rz_display_state(rz_ctx* ctx, rz_display_info* out);   /* synchronises */
 
+/* ------------------------------------------------------------------------ */
+/* Rendering below display size: guided upsampling (new: the reference has none) */
+/* ------------------------------------------------------------------------ */
+/* The path loop is the one cost that scales with pixels x samples.  This stage lets a frame be rendered at 1 / s of the display
+ * size and reconstructed at display size from a full-resolution G-buffer, so that silhouettes and material boundaries are as
+ * sharp as in a native frame and only the slowly varying, demodulated colour is interpolated (rz_upscale.hip).
+ * The frame of the last rz_set_frame is the LOW frame, w x h: the one that was rendered.  The output is W x H = s w x s h; the
+ * aspect is unchanged, so inv_view, inv_proj and cam_pos serve both sizes.  Row 0 = the bottom row.  Arithmetic is binary32
+ * without fused multiply-add.  The footprint, the bilinear weights, admissibility and the choice of stage are evaluated exactly as
+ * written, one rounding per operation; W_geom is evaluated in the form given under "as evaluated", whose exp, exp2 and log2
+ * are the device's (not correctly rounded), so the colours are held to the float64 restatement within a tolerance
+ * (tests/test_upscale_gpu.py), not bit for bit.
+ *  guides    g_q = rz_denoise's guide record of low pixel q at w x h; G_P = the same for high pixel P = (X, Y) at W x H: hit or
+ *            miss, world point x, unit world normal n, world distance t, material m -- both cast by rz_denoise's guide kernel,
+ *            unchanged, with only the width and height differing.  alpha(m) = materials[clamp(m)].albedo for a hit, (1, 1, 1)
+ *            for a miss.
+ *  colours   c_q = the low colour; d_q = c_q / max(alpha(m_q), 1e-3) per channel when demodulating, else c_q.  A low pixel is BAD
+ *            by rz_denoise's rule: a channel of c_q is NaN or +-Inf, decided on the bit pattern.
+ *  footprint, in integers: r_x = 2X + 1 - s, i0 = floor(r_x / 2s) (integer floor division), fx = (float)(r_x - 2s i0) /
+ *            (float)(2s); likewise r_y, j0, fy.  No floating-point floor is taken.
+ *  a tap q is ADMISSIBLE iff it lies inside the low image, is not bad, and hit_q == hit_P (a hit and a miss never mix).
+ *  W_geom    max(0, n_P.n_q)^sigma_normal exp(-|n_P.(x_q - x_P)| / (sigma_plane t_P f)) when both are hits (0^0 = 1), 1 when
+ *            both are misses; f = 2 |inv_proj[5]| / h, the world size of one LOW pixel at unit distance.
+ *            As evaluated (rz_denoise_atrous's form): k = (float)(1 / (sigma_plane f)), computed in binary64 on the host;
+ *            nd = max(0, n_P.n_q); the power is exp2f(sigma_normal * log2f(nd)) for nd > 0, else 1 if sigma_normal == 0, else 0;
+ *            W_geom = power * expf(-(|n_P.(x_q - x_P)| * (k / t_P))); dot(a, b) = (a.x b.x + a.y b.y) + a.z b.z.
+ *  stage 1   the taps q = (i0 + a, j0 + b), a, b in {0, 1}, with bilinear weight B = (a ? fx : 1 - fx)(b ? fy : 1 - fy); a tap with
+ *            B == 0 is skipped.  w = B max(W_geom, 1e-4) over the admissible taps, b outer, a inner, and
+ *            out = alpha(m_P) sum w d_q / sum w when demodulating, else sum w d_q / sum w.  The floor makes the sum non-empty
+ *            whenever a tap is admissible, and makes every stage decision a function of exact data: flags, bit patterns, integers.
+ *  stage 2   only if stage 1 found no admissible tap (with B > 0): the same with the twelve outer taps of the 4 x 4 window
+ *            i0-1..i0+2 x j0-1..j0+2 and w = max(W_geom, 1e-4).
+ *  stage 3   only if stage 2 found none either: out = c_q of the nearest low pixel q = (X / s, Y / s) (integer division), not
+ *            demodulated; (0, 0, 0) if that pixel is bad.  A bad low pixel therefore reaches no output: it is no tap in stages 1
+ *            and 2 and reads as black in stage 3.
+ *  s = 1     out = c_p exactly and nothing is cast (unless the guide is asked for), as K = 0 in rz_denoise.
+ * KNOWN LIMIT.  The guide is the FIRST hit.  Reflections in the metals and everything seen through glass are upsampled as
+ * colour on the reflecting or refracting surface: they are blurred to the low resolution.
+ * Defaults (params NULL): factor 2, sigma_normal = 128, sigma_plane = 1 (rz_denoise's), demodulate = 1.
+ * rz_upscale.  rgb_in is w*h*3 floats of linear colour in rz_display's convention (what both denoisers write); rgb_in NULL reads
+ * the context's accumulation as c = rgb / n, n = a > 0 ? a : 1.  Outputs, each optional:
+ *   rgb32f   W*H*3 floats: the reconstructed linear colour, unclamped
+ *   guides   W*H rz_hit: the high-size guide, bit for bit what rz_trace_rays returns for those pixel-centre rays
+ * Device pointers by default (guides 16-byte aligned, rgb_in and rgb32f 4-byte): enqueued on the context's stream, returns at
+ * once (a walk cut short at its backstop is reported by rz_sync).  With RZ_UPSCALE_HOST they are host memory: staged through
+ * buffers of the context, the call returns when the outputs are written and reports a cut walk itself (RZ_ERR_INTERNAL).  No
+ * render state, temporal history or display state is touched; the buffers of the high size live in the context, allocated on
+ * first use and kept.
+ * rz_present_upscaled is rz_present_display at the display size: source and filter_params are rz_present_display's (0 the
+ * accumulation, 1 rz_denoise, 2 rz_denoise_temporal, whose history advances as rz_present_temporal advances it) and the
+ * denoisers run at w x h; then the upscale; then the display stage at W x H (display NULL: clamp and linear); then rz_present's
+ * kernel on (colour, 1) at W x H, with the overlays drawn at the high size.  Outputs are host memory of W x H and the call
+ * synchronises.  With factor = 1 the bytes are rz_present_display's exactly, for every source.  Like rz_present_display it
+ * commits its exposure to the context's display state (a metered one is metered from the W x H colour); rz_upscale does not.
+ * RZ_ERR_INVALID_ARG: null context, factor outside 1..4, a sigma that is negative, NaN or infinite (sigma_plane must be > 0),
+ * demodulate other than 0 or 1, non-zero reserved words, unknown flags, a misaligned device pointer, a frame with tile_nranks > 1,
+ * more than INT32_MAX high pixels (rz_present_upscaled: also what rz_present_display says).  RZ_ERR_BUFFER_SIZE: a buffer that is
+ * too small.  RZ_ERR_NOT_READY: no scene, no materials, or no rz_set_frame.  A failing call launches nothing.
+ * (Additive: RZ_ABI_VERSION stays 5.) */
+typedef struct rz_upscale_params {      /* NULL = defaults */
+    int32_t factor;                     /* s, 1..4 */
+    float   sigma_normal, sigma_plane;  /* rz_denoise's: sigma_normal >= 0, sigma_plane > 0, finite */
+    int32_t demodulate;                 /* 1 = interpolate the colour divided by the first hit's albedo */
+    int32_t reserved[4];                /* must be 0 */
+} rz_upscale_params;                    /* 32 B; rz_sizeof(21) */
+#define RZ_UPSCALE_HOST 1u              /* pointers are host memory: staged, returns when written */
+int rz_upscale(rz_ctx* ctx, const rz_upscale_params* params, const float* rgb_in, size_t rgb_in_bytes,
+               float* rgb32f, size_t rgb32f_bytes, rz_hit* guides, size_t guides_bytes, unsigned flags);
+int rz_present_upscaled(rz_ctx* ctx, const rz_present_params* present, const rz_upscale_params* upscale,
+                        const rz_display_params* display, int source, const void* filter_params,
+                        uint8_t* rgba8, size_t rgba8_bytes, float* rgb32f, size_t rgb32f_bytes);
+
 /* Number of HIP devices visible to the process (0 without a GPU). */
 int rz_device_count(void);
 
@@ -917,8 +989,8 @@ const char* rz_source_hash(void);
  * checks from other languages: which = 0 triangle, 1 node, 2 instance,
  * 3 material, 4 light, 5 frame_params, 6 counters, 7 ray, 8 hit,
  * 9 visibility, 10 editor_params, 11 denoise_params, 12 temporal_params,
- * 14 display_params, 15 display_info, 17 skin_triangle, 18 morph_triangle, 20 mesh_quality (13, 16 and 19 are unassigned
- * and return 0, as every unknown index does). */
+ * 14 display_params, 15 display_info, 17 skin_triangle, 18 morph_triangle, 20 mesh_quality,
+ * 21 upscale_params (13, 16 and 19 are unassigned and return 0, as every unknown index does). */
 size_t rz_sizeof(int which);
 
 #ifdef __cplusplus

@@ -26,6 +26,7 @@ HIP_SYMBOLS = (
     "rz_display", "rz_present_display", "rz_display_reset", "rz_display_state",
     "rz_skin_create", "rz_skin_pose", "rz_skin_destroy", "rz_skin_last_kernel_ms",
     "rz_geometry_quality", "rz_rebuild_geometry",
+    "rz_upscale", "rz_present_upscaled",
 )
 ABI_VERSION = 5         # RZ_ABI_VERSION of the include/rayzen_hip.h this file mirrors
 # the symbols include/rayzen_host.h declares
@@ -148,6 +149,17 @@ DISPLAY_TRANSFERS = {"linear": 0, "srgb": 1}
 DISPLAY_SOURCES = {"accum": 0, "denoise": 1, "temporal": 2}
 
 
+class UpscaleParams(C.Structure):
+    """rz_upscale_params of include/rayzen_hip.h (32 B)."""
+    _fields_ = [("factor", C.c_int32), ("sigma_normal", C.c_float), ("sigma_plane", C.c_float), ("demodulate", C.c_int32),
+                ("reserved", C.c_int32 * 4)]
+
+
+UPSCALE_DEFAULTS = dict(factor=2, sigma_normal=128.0, sigma_plane=1.0, demodulate=1)
+UPSCALE_HOST = 1                        # RZ_UPSCALE_HOST
+SIZEOF_UPSCALE_PARAMS = 21              # its rz_sizeof index
+
+
 class SkinTriangle(C.Structure):
     """rz_skin_triangle of include/rayzen_hip.h (64 B)."""
     _fields_ = [("bones", C.c_uint32 * 3), ("pad", C.c_uint32), ("weights", (C.c_float * 4) * 3)]
@@ -264,7 +276,9 @@ def hip():
                                 ("rz_skin_destroy", i, [vp, i]),
                                 ("rz_skin_last_kernel_ms", i, [vp, C.POINTER(C.c_float)]),
                                 ("rz_geometry_quality", i, [vp, vp, sz, C.POINTER(sz)]),
-                                ("rz_rebuild_geometry", i, [vp, C.c_double, vp, sz, C.POINTER(sz), C.c_uint])):
+                                ("rz_rebuild_geometry", i, [vp, C.c_double, vp, sz, C.POINTER(sz), C.c_uint]),
+                                ("rz_upscale", i, [vp, vp, vp, sz, vp, sz, vp, sz, C.c_uint]),
+                                ("rz_present_upscaled", i, [vp, C.POINTER(PresentParams), vp, vp, i, vp, vp, sz, vp, sz])):
             try:
                 fn = getattr(L, name)
                 fn.restype, fn.argtypes = res, args

@@ -170,6 +170,9 @@ struct rz_ctx {
     // the display stage (rz_display / rz_present_display, rz_display.hip): one DisplayState -- the exposure last applied, the
     // rz_display_info record and the working histogram -- allocated and zeroed by the first call that needs it
     DevBuf dDisplay;
+    // rz_upscale / rz_present_upscaled (rz_upscale.hip): the guides cast at the low and at the high size (2 float4 per pixel
+    // each) and the high-size (colour, 1) buffer rz_present_upscaled presents; allocated on first use and kept
+    DevBuf dUpGuideLo, dUpGuideHi, dUpOut;
     // rz_refit_geometry (rz_refit.hip)
     bool trisHostStale = false;         // binding 0 on the device (dRawTris) is newer than the host copy: fetched on demand (sync_tris_host)
     unsigned long long layoutGen = 0;   // counts the times the views / instances were laid out
@@ -1043,6 +1046,7 @@ size_t rz_sizeof(int which) {
         case 17: return sizeof(rz_skin_triangle);        // (16 stays unassigned too: probed as an unknown index)
         case 18: return sizeof(rz_morph_triangle);
         case 20: return sizeof(rz_mesh_quality);         // (19 stays unassigned: probed as an unknown index)
+        case 21: return sizeof(rz_upscale_params);
         default: return 0;
     }
 }
@@ -1087,7 +1091,7 @@ void rz_destroy(rz_ctx* c) {
                       &c->dRefitRank, &c->dRefitInstView, &c->dRefitViewOff, &c->dRefitFlags, &c->dRefitRoots,
                       &c->dTmpCol[0], &c->dTmpCol[1], &c->dTmpMom[0], &c->dTmpMom[1], &c->dTmpHits[0], &c->dTmpHits[1],
                       &c->dTmpInst[0], &c->dTmpInst[1], &c->dTmpSame, &c->dDisplay, &c->dSkinOut, &c->dSkinBones, &c->dSkinWeights,
-                      &c->dQualViews, &c->dQualPartials, &c->dQualCost})
+                      &c->dQualViews, &c->dQualPartials, &c->dQualCost, &c->dUpGuideLo, &c->dUpGuideHi, &c->dUpOut})
         b->release();
     for (auto& kv : c->rigs) kv.second.release();
     for (hipEvent_t e : c->evSkin) if (e) (void)hipEventDestroy(e);
@@ -2297,16 +2301,18 @@ static int resolve_rgba8_impl(rz_ctx* c, uint8_t* rgba8, size_t bytes) {
     return RZ_OK;
 }
 
-// (accum: what to resolve -- the context's accumulation when null; rz_present_denoised passes the denoised (colour, 1))
+// (accum: what to resolve -- the context's accumulation when null; rz_present_denoised passes the denoised (colour, 1).
+//  width, height: the size of `accum` and of the outputs -- the frame's when 0; rz_present_upscaled passes the high size)
 static int present_impl(rz_ctx* c, const rz_present_params* pp, uint8_t* rgba8, size_t rgba8_bytes, float* rgb32f, size_t rgb32f_bytes,
-                        const float4* accum = nullptr) {
+                        const float4* accum = nullptr, int width = 0, int height = 0) {
     if (!c) return fail(nullptr, RZ_ERR_INVALID_ARG, "null context");
     if (!pp) return fail(c, RZ_ERR_INVALID_ARG, "null params");
     if (!c->haveFrame) return fail(c, RZ_ERR_NOT_READY, "rz_set_frame has not been called");
     RZ_HIP(c, hipSetDevice(c->device));
     int rc = finalize(c);
     if (rc != RZ_OK) return rc;
-    const size_t nPix = (size_t)c->frame.width * c->frame.height;
+    if (width <= 0 || height <= 0) { width = c->frame.width; height = c->frame.height; }
+    const size_t nPix = (size_t)width * height;
     if (rgba8 && rgba8_bytes < nPix * 4) return fail(c, RZ_ERR_BUFFER_SIZE, "rgba8 buffer needs %zu bytes", nPix * 4);
     if (rgb32f && rgb32f_bytes < nPix * 12) return fail(c, RZ_ERR_BUFFER_SIZE, "rgb32f buffer needs %zu bytes", nPix * 12);
     rc = ensure(c, c->dResolve, nPix * 4 + nPix * 12);
@@ -2319,7 +2325,7 @@ static int present_impl(rz_ctx* c, const rz_present_params* pp, uint8_t* rgba8, 
     P.tlasIndices = static_cast<const int32_t*>(c->dTlasIdx.p);
     P.instances = static_cast<const DevInstance*>(c->dInst.p);
     P.lights = static_cast<const DevLight*>(c->dLight.p);
-    P.width = c->frame.width; P.height = c->frame.height;
+    P.width = width; P.height = height;
     P.nTlasNodes = c->deviceOwnsTlas ? c->devTlasNodes : (int)hostCount<rz_bvh_node>(c, RZ_BIND_TLAS_NODES);
     P.nInstances = (int)hostCount<rz_bvh_instance>(c, RZ_BIND_INSTANCES);
     P.nLights = std::max(0, std::min<int>(c->frame.num_lights, (int)hostCount<rz_light>(c, RZ_BIND_LIGHTS)));
@@ -2986,9 +2992,10 @@ static int ensure_display_state(rz_ctx* c) {
 
 // Meters and adapts (auto) or commits the manual exposure, then tones, on the stream.  The input (device) is rgb (3 floats per
 // pixel) or in4 (RGBA32F sum and count); outputs (device, each optional): rgb, rgba8, out4 ((colour, 1); may be in4 itself).
+// pixels: how many the buffers hold -- the frame's when 0; rz_present_upscaled passes the high size.
 static int display_run(rz_ctx* c, const rz_display_params& P, const float* in, const float4* in4, float* rgb, uchar4* rgba8,
-                       float4* out4, bool keep) {
-    const long long np = (long long)c->frame.width * c->frame.height;
+                       float4* out4, bool keep, long long pixels = 0) {
+    const long long np = pixels > 0 ? pixels : (long long)c->frame.width * c->frame.height;
     const bool metered = P.exposure_mode == 1;
     DisplayState* S = nullptr;
     if (metered || !keep) {
@@ -3111,6 +3118,209 @@ static int present_display_impl(rz_ctx* c, const rz_present_params* pp, const rz
     rc = present_impl(c, pp, rgba8, rgba8_bytes, rgb32f, rgb32f_bytes, out4);
     if (rc != RZ_OK) return rc;
     return source == 0 ? RZ_OK : denoise_backstop(c, what);
+}
+
+// rz_upscale / rz_present_upscaled (rz_upscale.hip).  The frame rz_set_frame set is the LOW one; they read its size and camera,
+// the device scene as finalize left it, and touch no render state.  What they keep is buffers of the high size.
+static const rz_upscale_params kUpscaleDefaults = {2, 128.0f, 1.0f, 1, {0, 0, 0, 0}};
+
+static int upscale_check(rz_ctx* c, const char* what, const rz_upscale_params& P) {
+    if (P.factor < 1 || P.factor > 4) return fail(c, RZ_ERR_INVALID_ARG, "%s: factor %d outside 1..4", what, P.factor);
+    if (P.reserved[0] || P.reserved[1] || P.reserved[2] || P.reserved[3]) return fail(c, RZ_ERR_INVALID_ARG, "%s: reserved words must be 0", what);
+    // the rest is rz_denoise's: the sigmas, demodulate, the frame, the scene, the whole frame (no colour sigma, no passes here)
+    const rz_denoise_params D = {1, 1.0f, P.sigma_normal, P.sigma_plane, P.demodulate, {0, 0, 0}};
+    const int rc = denoise_check(c, what, D);
+    if (rc != RZ_OK) return rc;
+    if ((long long)c->frame.width * P.factor * ((long long)c->frame.height * P.factor) > 0x7fffffffLL)
+        return fail(c, RZ_ERR_INVALID_ARG, "%s: %d x %d times %d is more than INT32_MAX pixels", what, c->frame.width, c->frame.height, P.factor);
+    return RZ_OK;
+}
+
+// One launch of rz_denoise's guide kernel at width x height with the frame's camera: the guide records, and the rz_hit records
+// when asked.
+static int upscale_cast(rz_ctx* c, int width, int height, float4* guide, float4* hits) {
+    const rz_frame_params& f = c->frame;
+    KParams K{};
+    scene_kparams(c, K);
+    K.width = width; K.height = height;
+    std::memcpy(K.invView, f.inv_view, 64);
+    std::memcpy(K.invProj, f.inv_proj, 64);
+    std::memcpy(K.camPos, f.cam_pos, 12);
+    DenoiseGuideLaunch G{};
+    G.unitsX = (width + 63) / 64;
+    G.units = (long long)G.unitsX * height;
+    G.grid = rays_grid(G.units * 64);
+    G.guide = guide;
+    G.hits = hits;
+    G.instTriOff = static_cast<const int32_t*>(c->dRayInstOff.p);
+    G.errWord = static_cast<unsigned*>(c->dGroupCtr.p) + RZ_ERRWORD;
+    const int rc = size_blas_stack(c, K, 0, RZ_RAYS_WAVES_PER_CU, G.grid, c->dRayOvf);
+    if (rc != RZ_OK) return rc;
+    launch_denoise_guides(K, G, c->stream);
+    RZ_HIP(c, hipGetLastError());
+    return RZ_OK;
+}
+
+// Casts both guides and gathers, on the stream; factor >= 2.  The low frame (device) is in3 (3 floats per pixel) or in4 (RGBA32F
+// sum and count); outputs (device, high size, each optional): rgb (3 floats per pixel), out4 ((colour, 1)), hits (rz_hit).
+static int upscale_run(rz_ctx* c, const rz_upscale_params& P, const float* in3, const float4* in4, float* rgb, float4* out4, float4* hits) {
+    if (!rgb && !out4 && !hits) return RZ_OK;
+    const rz_frame_params& f = c->frame;
+    const int W = f.width * P.factor, H = f.height * P.factor;
+    int rc = finalize(c);
+    if (rc != RZ_OK) return rc;
+    rc = ensure_group_counter(c);           // (only its backstop word: the claim counter is the render's)
+    if (rc != RZ_OK) return rc;
+    rc = ensure_ray_inst_off(c);
+    if (rc != RZ_OK) return rc;
+    rc = ensure(c, c->dUpGuideHi, (size_t)W * H * 32);
+    if (rc != RZ_OK) return rc;
+    if (rgb || out4) {
+        rc = ensure(c, c->dUpGuideLo, (size_t)f.width * f.height * 32);
+        if (rc != RZ_OK) return rc;
+    }
+    // the high cast first: its overflow columns (size_blas_stack) are the larger ones, so the low cast finds them in place
+    rc = upscale_cast(c, W, H, static_cast<float4*>(c->dUpGuideHi.p), hits);
+    if (rc != RZ_OK) return rc;
+    if (!rgb && !out4) return RZ_OK;
+    rc = upscale_cast(c, f.width, f.height, static_cast<float4*>(c->dUpGuideLo.p), nullptr);
+    if (rc != RZ_OK) return rc;
+    UpscaleLaunch U{};
+    U.in3 = in4 ? nullptr : in3;
+    U.in4 = in4;
+    U.guideLo = static_cast<const float4*>(c->dUpGuideLo.p);
+    U.guideHi = static_cast<const float4*>(c->dUpGuideHi.p);
+    U.materials = static_cast<const DevMaterial*>(c->dMat.p);
+    U.dst = out4;
+    U.rgb = rgb;
+    U.w = f.width; U.h = f.height;
+    U.s = P.factor;
+    U.sigmaNormal = P.sigma_normal;
+    const double fpx = 2.0 * std::fabs((double)f.inv_proj[5]) / (double)f.height;     // world size of a LOW pixel at unit distance
+    U.planeScale = (float)(1.0 / ((double)P.sigma_plane * fpx));
+    U.demodulate = P.demodulate;
+    launch_upscale_gather(U, c->stream);
+    RZ_HIP(c, hipGetLastError());
+    return RZ_OK;
+}
+
+static int upscale_impl(rz_ctx* c, const rz_upscale_params* pp, const float* rgb_in, size_t rgb_in_bytes, float* rgb32f,
+                        size_t rgb32f_bytes, rz_hit* guides, size_t guides_bytes, unsigned flags) {
+    const char* what = "rz_upscale";
+    if (!c) return fail(nullptr, RZ_ERR_INVALID_ARG, "%s: null context", what);
+    if (flags & ~RZ_UPSCALE_HOST) return fail(c, RZ_ERR_INVALID_ARG, "%s: unknown flags 0x%x", what, flags);
+    const rz_upscale_params& P = pp ? *pp : kUpscaleDefaults;
+    int rc = upscale_check(c, what, P);
+    if (rc != RZ_OK) return rc;
+    const bool host = (flags & RZ_UPSCALE_HOST) != 0;
+    if (!host && ((reinterpret_cast<uintptr_t>(guides) & 15u) || ((reinterpret_cast<uintptr_t>(rgb_in) | reinterpret_cast<uintptr_t>(rgb32f)) & 3u)))
+        return fail(c, RZ_ERR_INVALID_ARG, "%s: device pointers must be 16-byte (guides) or 4-byte (rgb_in, rgb32f) aligned", what);
+    const size_t np = (size_t)c->frame.width * c->frame.height, nP = np * P.factor * P.factor;
+    const size_t bIn = np * 3 * sizeof(float), bRgb = nP * 3 * sizeof(float), bHits = nP * sizeof(rz_hit);
+    if (rgb_in && rgb_in_bytes < bIn) return fail(c, RZ_ERR_BUFFER_SIZE, "%s: rgb_in needs %zu bytes, got %zu", what, bIn, rgb_in_bytes);
+    if (!rgb_in && c->extAccum && c->extAccumBytes < np * 16)
+        return fail(c, RZ_ERR_BUFFER_SIZE, "%s: bound accumulation buffer holds %zu bytes, frame needs %zu", what, c->extAccumBytes, np * 16);
+    if (rgb32f && rgb32f_bytes < bRgb) return fail(c, RZ_ERR_BUFFER_SIZE, "%s: rgb32f needs %zu bytes, got %zu", what, bRgb, rgb32f_bytes);
+    if (guides && guides_bytes < bHits) return fail(c, RZ_ERR_BUFFER_SIZE, "%s: guides needs %zu bytes, got %zu", what, bHits, guides_bytes);
+    if (!rgb32f && !guides) return RZ_OK;
+    RZ_HIP(c, hipSetDevice(c->device));
+    const float* in3 = rgb_in;
+    const float4* in4 = rgb_in ? nullptr : static_cast<const float4*>(rz_accum_device_ptr(c));
+    float* dRgb = rgb32f;
+    float4* dHits = reinterpret_cast<float4*>(guides);
+    // host buffers are staged as rz_denoise stages them: the input in dRayIn; hits, then rgb32f in dRayOut
+    const size_t oRgb = guides ? (bHits + 15) & ~size_t(15) : 0;
+    if (host) {
+        if (rgb_in) {
+            rc = ensure(c, c->dRayIn, bIn);
+            if (rc != RZ_OK) return rc;
+            RZ_HIP(c, hipMemcpyAsync(c->dRayIn.p, rgb_in, bIn, hipMemcpyHostToDevice, c->stream));
+            in3 = static_cast<const float*>(c->dRayIn.p);
+        }
+        rc = ensure(c, c->dRayOut, oRgb + (rgb32f ? bRgb : 0));
+        if (rc != RZ_OK) return rc;
+        char* base = static_cast<char*>(c->dRayOut.p);
+        dHits = guides ? reinterpret_cast<float4*>(base) : nullptr;
+        dRgb = rgb32f ? reinterpret_cast<float*>(base + oRgb) : nullptr;
+    }
+    if (P.factor == 1) {                    // c_p itself, and nothing is cast unless the guide is asked for
+        if (dRgb && in4) {
+            DenoiseLaunch D{};
+            D.accum = in4;
+            D.rgb = dRgb;
+            D.width = c->frame.width; D.height = c->frame.height;
+            launch_denoise_resolve(D, c->stream);
+            RZ_HIP(c, hipGetLastError());
+        } else if (dRgb && dRgb != in3) {
+            RZ_HIP(c, hipMemcpyAsync(dRgb, in3, bIn, hipMemcpyDeviceToDevice, c->stream));
+        }
+        if (dHits) {
+            rc = finalize(c);
+            if (rc == RZ_OK) rc = ensure_group_counter(c);
+            if (rc == RZ_OK) rc = ensure_ray_inst_off(c);
+            if (rc == RZ_OK) rc = ensure(c, c->dUpGuideHi, np * 32);
+            if (rc == RZ_OK) rc = upscale_cast(c, c->frame.width, c->frame.height, static_cast<float4*>(c->dUpGuideHi.p), dHits);
+        }
+    } else {
+        rc = upscale_run(c, P, in3, in4, dRgb, nullptr, dHits);
+    }
+    if (rc != RZ_OK) return rc;
+    if (!host) return RZ_OK;
+    const char* base = static_cast<const char*>(c->dRayOut.p);
+    if (guides) RZ_HIP(c, hipMemcpyAsync(guides, base, bHits, hipMemcpyDeviceToHost, c->stream));
+    if (rgb32f) RZ_HIP(c, hipMemcpyAsync(rgb32f, base + oRgb, bRgb, hipMemcpyDeviceToHost, c->stream));
+    RZ_HIP(c, hipStreamSynchronize(c->stream));
+    return denoise_backstop(c, what);
+}
+
+static int present_upscaled_impl(rz_ctx* c, const rz_present_params* pp, const rz_upscale_params* up, const rz_display_params* dp,
+                                 int source, const void* filter_params, uint8_t* rgba8, size_t rgba8_bytes, float* rgb32f,
+                                 size_t rgb32f_bytes) {
+    const char* what = "rz_present_upscaled";
+    if (!c) return fail(nullptr, RZ_ERR_INVALID_ARG, "%s: null context", what);
+    if (!pp) return fail(c, RZ_ERR_INVALID_ARG, "%s: null present params", what);
+    if (source < 0 || source > 2) return fail(c, RZ_ERR_INVALID_ARG, "%s: source %d (0 accumulation, 1 rz_denoise, 2 rz_denoise_temporal)", what, source);
+    if (source == 0 && filter_params) return fail(c, RZ_ERR_INVALID_ARG, "%s: filter_params must be NULL for source 0", what);
+    const rz_upscale_params& U = up ? *up : kUpscaleDefaults;
+    const rz_display_params& D = dp ? *dp : kDisplayDefaults;
+    int rc = display_check(c, what, D);
+    if (rc != RZ_OK) return rc;
+    const rz_denoise_params& P1 = (source == 1 && filter_params) ? *static_cast<const rz_denoise_params*>(filter_params) : kDenoiseDefaults;
+    const rz_temporal_params& P2 = (source == 2 && filter_params) ? *static_cast<const rz_temporal_params*>(filter_params) : kTemporalDefaults;
+    if (source == 1) rc = denoise_check(c, what, P1);
+    if (source == 2) rc = temporal_check(c, what, P2);
+    if (rc != RZ_OK) return rc;
+    rc = upscale_check(c, what, U);
+    if (rc != RZ_OK) return rc;
+    // factor 1: nothing to reconstruct, the call IS rz_present_display (its bytes exactly, for every source)
+    if (U.factor == 1) return present_display_impl(c, pp, dp, source, filter_params, rgba8, rgba8_bytes, rgb32f, rgb32f_bytes);
+    const int W = c->frame.width * U.factor, H = c->frame.height * U.factor;
+    const size_t np = (size_t)c->frame.width * c->frame.height, nP = (size_t)W * H;
+    if (c->extAccum && c->extAccumBytes < np * 16)
+        return fail(c, RZ_ERR_BUFFER_SIZE, "%s: bound accumulation buffer holds %zu bytes, frame needs %zu", what, c->extAccumBytes, np * 16);
+    if (rgba8 && rgba8_bytes < nP * 4) return fail(c, RZ_ERR_BUFFER_SIZE, "%s: rgba8 buffer needs %zu bytes", what, nP * 4);
+    if (rgb32f && rgb32f_bytes < nP * 12) return fail(c, RZ_ERR_BUFFER_SIZE, "%s: rgb32f buffer needs %zu bytes", what, nP * 12);
+    RZ_HIP(c, hipSetDevice(c->device));
+    rc = ensure(c, c->dUpOut, nP * 16);
+    if (rc != RZ_OK) return rc;
+    float4* hi4 = static_cast<float4*>(c->dUpOut.p);
+    const float4* low4 = static_cast<const float4*>(rz_accum_device_ptr(c));
+    if (source != 0) {                      // the denoisers run at the low size and leave (colour, 1), which resolves to the colour
+        rc = ensure(c, c->dDnOut, np * 16);
+        if (rc != RZ_OK) return rc;
+        float4* out4 = static_cast<float4*>(c->dDnOut.p);
+        if (source == 1) rc = denoise_run(c, P1, low4, nullptr, out4, nullptr);
+        else rc = temporal_run(c, P2, low4, nullptr, out4, nullptr, nullptr, false);
+        if (rc != RZ_OK) return rc;
+        low4 = out4;
+    }
+    rc = upscale_run(c, U, nullptr, low4, nullptr, hi4, nullptr);
+    if (rc != RZ_OK) return rc;
+    rc = display_run(c, D, nullptr, hi4, nullptr, nullptr, hi4, false, (long long)nP);
+    if (rc != RZ_OK) return rc;
+    rc = present_impl(c, pp, rgba8, rgba8_bytes, rgb32f, rgb32f_bytes, hi4, W, H);
+    if (rc != RZ_OK) return rc;
+    return denoise_backstop(c, what);
 }
 
 static int display_reset_impl(rz_ctx* c) {
@@ -3315,6 +3525,18 @@ int rz_present_display(rz_ctx* c, const rz_present_params* present, const rz_dis
                        const void* filter_params, uint8_t* rgba8, size_t rgba8_bytes, float* rgb32f, size_t rgb32f_bytes) {
     return guarded(c, "rz_present_display", [&] {
         return present_display_impl(c, present, display, source, filter_params, rgba8, rgba8_bytes, rgb32f, rgb32f_bytes);
+    });
+}
+int rz_upscale(rz_ctx* c, const rz_upscale_params* params, const float* rgb_in, size_t rgb_in_bytes, float* rgb32f,
+               size_t rgb32f_bytes, rz_hit* guides, size_t guides_bytes, unsigned flags) {
+    return guarded(c, "rz_upscale", [&] {
+        return upscale_impl(c, params, rgb_in, rgb_in_bytes, rgb32f, rgb32f_bytes, guides, guides_bytes, flags);
+    });
+}
+int rz_present_upscaled(rz_ctx* c, const rz_present_params* present, const rz_upscale_params* upscale, const rz_display_params* display,
+                        int source, const void* filter_params, uint8_t* rgba8, size_t rgba8_bytes, float* rgb32f, size_t rgb32f_bytes) {
+    return guarded(c, "rz_present_upscaled", [&] {
+        return present_upscaled_impl(c, present, upscale, display, source, filter_params, rgba8, rgba8_bytes, rgb32f, rgb32f_bytes);
     });
 }
 int rz_display_reset(rz_ctx* c) {

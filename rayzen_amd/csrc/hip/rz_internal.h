@@ -84,6 +84,23 @@ struct DenoiseLaunch {
 void launch_denoise_pass(const DenoiseLaunch& D, bool first, bool last, hipStream_t stream);
 void launch_denoise_resolve(const DenoiseLaunch& D, hipStream_t stream);
 
+// ---- rz_upscale.hip
+struct UpscaleLaunch {          // rz_upscale_gather
+    const float* in3;           // the low frame: w x h x 3 linear colour, or
+    const float4* in4;          // RGBA32F sum and count (then `in3` is unused)
+    const float4* guideLo;      // DenoiseGuideLaunch::guide cast at w x h
+    const float4* guideHi;      // ... and at W x H = s w x s h
+    const DevMaterial* materials;
+    float4* dst;                // W x H (colour, 1), optional
+    float* rgb;                 // W x H x 3 floats, optional
+    int w, h;                   // the low frame
+    int s;                      // the factor, 2..4
+    float sigmaNormal;
+    float planeScale;           // 1 / (sigma_plane f), f = 2 |inv_proj[5]| / h
+    int demodulate;
+};
+void launch_upscale_gather(const UpscaleLaunch& U, hipStream_t stream);
+
 // ---- rz_temporal.hip
 struct TemporalLaunch {         // rz_temporal_accumulate
     const float4* accum;        // RGBA32F sum and count

@@ -11,6 +11,7 @@
 //   denoise() / presentDenoised()      <- new: the a-trous denoiser of the 1-spp frame (rz_denoise / rz_present_denoised)
 //   denoiseTemporal() / presentTemporal() / resetTemporal()
 //                                      <- new: temporal accumulation + the variance-guided filter (rz_denoise_temporal)
+//   presentUpscaled()                  <- new: render below display size, reconstruct at display size (rz_present_upscaled)
 //   presentDisplay() / resetDisplay()  <- new: exposure, tone curve and sRGB encode in front of present (rz_present_display)
 // Unlike the reference's per-frame path, updateDynamicBVHAndSSBOs re-uploads
 // only what changed (instances + TLAS, a few KB), not all geometry.
@@ -294,6 +295,16 @@ public:
                                         const void* filter = nullptr) {
         std::vector<uint8_t> out((size_t)width_ * (size_t)height_ * 4);
         check(rz_present_display(ctx_, &present, display, source, filter, out.data(), out.size(), nullptr, 0), "rz_present_display");
+        return out;
+    }
+    // presentDisplay() at display size for a frame rendered below it: the frame last set is the LOW one (width x height), the
+    // result is RGBA8 of factor * width x factor * height (row 0 = bottom), reconstructed from a G-buffer cast at that size, with
+    // the overlays drawn there.  upscale null: factor 2 and rz_denoise's sigmas; factor 1: presentDisplay()'s bytes.
+    std::vector<uint8_t> presentUpscaled(const rz_present_params& present, const rz_upscale_params* upscale = nullptr,
+                                         const rz_display_params* display = nullptr, int source = 0, const void* filter = nullptr) {
+        const size_t s = upscale ? (size_t)std::max(upscale->factor, 0) : 2;
+        std::vector<uint8_t> out((size_t)width_ * s * (size_t)height_ * s * 4);
+        check(rz_present_upscaled(ctx_, &present, upscale, display, source, filter, out.data(), out.size(), nullptr, 0), "rz_present_upscaled");
         return out;
     }
     // Drops the adapted exposure (a cut: the next metered call jumps to its target).

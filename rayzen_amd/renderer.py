@@ -718,6 +718,81 @@ class Renderer:
         """Drops the adapted exposure: the next metered call jumps to its target."""
         self._check(self._L.rz_display_reset(self._c), "rz_display_reset")
 
+    # -- guided upsampling (rz_upscale / rz_present_upscaled) -------------------------
+    @staticmethod
+    def _upscale_params(factor, sigma_normal, sigma_plane, demodulate):
+        # all None: the library's defaults (params NULL)
+        if factor is None and sigma_normal is None and sigma_plane is None and demodulate is None:
+            return None
+        d = _lib.UPSCALE_DEFAULTS
+        p = _lib.UpscaleParams()
+        p.factor = d["factor"] if factor is None else int(factor)
+        p.sigma_normal = d["sigma_normal"] if sigma_normal is None else float(sigma_normal)
+        p.sigma_plane = d["sigma_plane"] if sigma_plane is None else float(sigma_plane)
+        p.demodulate = d["demodulate"] if demodulate is None else int(bool(demodulate))
+        return p
+
+    def upscale(self, rgb=None, factor=None, sigma_normal=None, sigma_plane=None, demodulate=None, guides=False):
+        """Guided upsampling (include/rayzen_hip.h: rz_upscale) of rgb ((h, w, 3) float32 linear colour, what denoise() and
+        denoise_temporal() return) or, with rgb None, of the accumulation: the frame of the last set_frame is the LOW frame w x h,
+        the result is (factor * h, factor * w, 3) float32, reconstructed from a G-buffer cast at that size (host memory; returns
+        when done).  With guides=True also that G-buffer as (H, W) HIT_DTYPE records (what trace_rays returns for the pixel-centre
+        rays of editor_rays at W x H); row 0 = bottom row.  Parameters left None take the library's defaults (factor 2,
+        sigma_normal 128, sigma_plane 1, demodulate on)."""
+        up = self._upscale_params(factor, sigma_normal, sigma_plane, demodulate)
+        s = _lib.UPSCALE_DEFAULTS["factor"] if up is None else up.factor
+        src = None if rgb is None else np.ascontiguousarray(rgb, np.float32)
+        out = np.empty((max(s, 0) * self.height, max(s, 0) * self.width, 3), np.float32)
+        hh = np.empty(out.shape[:2], HIT_DTYPE) if guides else None
+        self._check(self._L.rz_upscale(self._c, None if up is None else C.byref(up), None if src is None else src.ctypes.data,
+                                       0 if src is None else src.nbytes, out.ctypes.data, out.nbytes,
+                                       None if hh is None else hh.ctypes.data, 0 if hh is None else hh.nbytes, _lib.UPSCALE_HOST),
+                    "rz_upscale")
+        return (out, hh) if guides else out
+
+    def upscale_device(self, rgb_in_ptr=None, rgb32f_ptr=None, guides_ptr=None, factor=None, sigma_normal=None, sigma_plane=None,
+                       demodulate=None):
+        """rz_upscale on device memory (guides 16-B aligned, rgb_in and rgb32f 4-B; each optional): enqueued on the context's
+        stream, asynchronous.  Sizes: rgb_in w*h*12 B, rgb32f W*H*12 B, guides W*H*48 B, with W x H = factor * (w x h)."""
+        up = self._upscale_params(factor, sigma_normal, sigma_plane, demodulate)
+        s = _lib.UPSCALE_DEFAULTS["factor"] if up is None else up.factor
+        n = self.width * self.height
+        N = n * s * s
+        self._check(self._L.rz_upscale(self._c, None if up is None else C.byref(up), C.c_void_p(rgb_in_ptr), n * 12 if rgb_in_ptr else 0,
+                                       C.c_void_p(rgb32f_ptr), N * 12 if rgb32f_ptr else 0, C.c_void_p(guides_ptr),
+                                       N * 48 if guides_ptr else 0, 0), "rz_upscale")
+
+    def present_upscaled(self, source="accum", factor=None, sigma_normal=None, sigma_plane=None, demodulate=None, fps=0.0,
+                         show_fps=True, show_lights=False, show_bvh=False, bvh_mode=0, selected_blas=0, selected_tri=0,
+                         filter=None, **params):
+        """present_display() at display size: the colour of `source` (as present_display: the denoisers run at the low size
+        w x h of the last set_frame) is upsampled by `factor`, then exposed, toned and encoded (params: as display()), and the
+        overlays are drawn at the high size.  Returns (rgb float32 (H,W,3), rgba8 uint8 (H,W,4)) with H x W = factor * (h x w);
+        factor=1 gives present_display()'s bytes."""
+        if source not in _lib.DISPLAY_SOURCES:
+            raise ValueError(f"source = {source!r}: one of {sorted(_lib.DISPLAY_SOURCES)}")
+        if source == "accum" and filter:
+            raise ValueError("filter parameters need source 'denoise' or 'temporal'")
+        p = _lib.PresentParams(float(fps), int(bool(show_fps)), int(bool(show_lights)), int(bool(show_bvh)),
+                               int(bvh_mode), int(selected_blas), int(selected_tri))
+        up = self._upscale_params(factor, sigma_normal, sigma_plane, demodulate)
+        s = _lib.UPSCALE_DEFAULTS["factor"] if up is None else up.factor
+        dp = self._display_params(**params)
+        fp = None
+        if source == "denoise":
+            f = dict(filter or {})
+            fp = self._denoise_params(*(f.pop(k, None) for k in ("iterations", "sigma_color", "sigma_normal", "sigma_plane", "demodulate")))
+            if f:
+                raise TypeError(f"unknown denoise parameter(s): {sorted(f)}")
+        elif source == "temporal":
+            fp = self._temporal_params(dict(filter or {}))
+        rgb = np.empty((max(s, 0) * self.height, max(s, 0) * self.width, 3), np.float32)
+        rgba8 = np.empty(rgb.shape[:2] + (4,), np.uint8)
+        self._check(self._L.rz_present_upscaled(self._c, C.byref(p), None if up is None else C.byref(up),
+                                                None if dp is None else C.byref(dp), _lib.DISPLAY_SOURCES[source], fp,
+                                                rgba8.ctypes.data, rgba8.nbytes, rgb.ctypes.data, rgb.nbytes), "rz_present_upscaled")
+        return rgb, rgba8
+
     # -- convenience -----------------------------------------------------------
     def render_scene(self, scene, width, height, spp, bounce_budget, num_lights=None, tile_rank=0, tile_nranks=1,
                      chunk=None):
