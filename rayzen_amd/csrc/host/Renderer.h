@@ -15,6 +15,12 @@
 //   presentDisplay() / resetDisplay()  <- new: exposure, tone curve and sRGB encode in front of present (rz_present_display)
 // Unlike the reference's per-frame path, updateDynamicBVHAndSSBOs re-uploads
 // only what changed (instances + TLAS, a few KB), not all geometry.
+//
+// Deformation and the per-frame update: refitMesh, refitAll, poseRig and rebuildDegraded change the geometry ON THE DEVICE
+// and leave the host copies in buffers() as they were handed over.  From then on, until the next initializeSSBOs /
+// initializeSSBOsOnDevice, updateDynamicBVHAndSSBOs does its work on the device too (rz_update_transforms, the route of
+// updateDynamicBVHAndSSBOsOnDevice): both routes leave the context with identical bindings, and those are the deformed
+// geometry's -- world boxes and TLAS from the refitted roots, blasNodeOffset as a rebuild left it.
 #pragma once
 #include <algorithm>
 #include <cstring>
@@ -65,6 +71,7 @@ public:
         up(RZ_BIND_BLAS_NODES, buffers_.allBLASNodes);
         up(RZ_BIND_BLAS_INDICES, buffers_.allBLASTriIndices);
         up(RZ_BIND_INSTANCES, buffers_.meshInstances);
+        deviceGeometryNewer_ = false;
     }
     // initializeSSBOs with the geometry half on the GPU (rz_build_geometry): one BLAS per distinct Mesh is built on the
     // device and stays there as bindings 7 / 8; only instances, the TLAS, materials and lights are assembled here and
@@ -114,8 +121,13 @@ public:
         up(RZ_BIND_TLAS_NODES, buffers_.tlasNodes);
         up(RZ_BIND_TLAS_INDICES, buffers_.tlasTriIndices);
         up(RZ_BIND_INSTANCES, buffers_.meshInstances);
+        deviceGeometryNewer_ = false;
     }
+    // After a deforming call (refitMesh, refitAll, poseRig, rebuildDegraded) the root boxes and node offsets in buffers_ are
+    // those of the undeformed geometry: a TLAS built from them would cull what has left the old boxes.  The device has the
+    // current ones, so the step is forwarded to it (byte-identical to the host builder on equal inputs).
     void updateDynamicBVHAndSSBOs(const Scene& scene) {
+        if (deviceGeometryNewer_) { updateDynamicBVHAndSSBOsOnDevice(scene); return; }
         buffers_.updateDynamic(scene);
         // the TLAS keeps its node count (2*I-1) and index count (I) for a fixed instance count
         upd(RZ_BIND_INSTANCES, buffers_.meshInstances);
@@ -132,27 +144,37 @@ public:
     // Deforming meshes (rz_refit_geometry; the reference has no counterpart): `triangles` replace binding 0 from element
     // firstTriangle on, every mesh they touch is refitted on the device and the TLAS follows with the transforms in force.
     // refitAll: every mesh from binding 0 as it stands (after an rz_update of binding 0).  The host copies in buffers_
-    // are NOT updated: rz_read_binding returns the refitted arrays.
+    // are NOT updated (rz_read_binding returns the refitted arrays); a later updateDynamicBVHAndSSBOs therefore takes the
+    // device route, like updateDynamicBVHAndSSBOsOnDevice, and keeps the refitted boxes.
     void refitMesh(size_t firstTriangle, const std::vector<Triangle>& triangles) {
+        deviceGeometryNewer_ = true;
         check(rz_refit_geometry(ctx_, reinterpret_cast<const rz_triangle*>(triangles.data()), firstTriangle, triangles.size(), RZ_REFIT_HOST),
               "rz_refit_geometry");
     }
-    void refitAll() { check(rz_refit_geometry(ctx_, nullptr, 0, 0, 0), "rz_refit_geometry"); }
+    void refitAll() { deviceGeometryNewer_ = true; check(rz_refit_geometry(ctx_, nullptr, 0, 0, 0), "rz_refit_geometry"); }
     // Skinned meshes (rz_skin_create / rz_skin_pose; the reference has no counterpart): a rig keeps the rest pose of the
     // triangles [firstTriangle, +rest.size()) of binding 0 on the device with their bone indices / weights (skin, one per
     // triangle; empty: a morph-only rig) and morph targets (target-major, morphs.size() / rest.size() of them).  poseRig
     // skins on the device and refits what moved, TLAS included; nothing but the bones (64 B each) and the morph weights
-    // crosses to the device per frame.  As with refitMesh the host copies in buffers_ are NOT updated.
+    // crosses to the device per frame.  As with refitMesh the host copies in buffers_ are NOT updated and a later
+    // updateDynamicBVHAndSSBOs takes the device route.  skin holds rest.size() records or none, morphs a whole number of
+    // targets of rest.size() records each: anything else throws before the library is given a pointer it would read past.
     int createRig(size_t firstTriangle, const std::vector<Triangle>& rest, const std::vector<rz_skin_triangle>& skin, int nBones,
                   const std::vector<rz_morph_triangle>& morphs = {}) {
         int rig = -1;
         const size_t n = rest.size();
+        if (!skin.empty() && skin.size() != n)
+            throw std::runtime_error("createRig: skin holds " + std::to_string(skin.size()) + " records for " + std::to_string(n) + " rest triangles");
+        if (!morphs.empty() && (n == 0 || morphs.size() % n != 0))
+            throw std::runtime_error("createRig: morphs holds " + std::to_string(morphs.size()) + " records, not a multiple of the " +
+                                     std::to_string(n) + " rest triangles");
         check(rz_skin_create(ctx_, firstTriangle, n, reinterpret_cast<const rz_triangle*>(rest.data()), skin.empty() ? nullptr : skin.data(),
                              nBones, morphs.empty() ? nullptr : morphs.data(), n ? (int)(morphs.size() / n) : 0, &rig),
               "rz_skin_create");
         return rig;
     }
     void poseRig(int rig, const std::vector<mat4>& bones, const std::vector<float>& morphWeights = {}) {
+        deviceGeometryNewer_ = true;
         check(rz_skin_pose(ctx_, rig, bones.empty() ? nullptr : bones[0].m, morphWeights.empty() ? nullptr : morphWeights.data(), 0),
               "rz_skin_pose");
     }
@@ -170,8 +192,10 @@ public:
     // The exit from the refit's steady state (rz_rebuild_geometry): every mesh whose cost exceeds maxRatio times the cost it
     // was built with is rebuilt on the device from binding 0 as it stands there (posed triangles never visit the host);
     // instances and TLAS follow.  Returns the records; RZ_QUALITY_REBUILT marks what was rebuilt.  As with refitMesh the
-    // host copies in buffers_ are NOT updated (SceneBuffers::rebuildMesh is the host partner).
+    // host copies in buffers_ are NOT updated (SceneBuffers::rebuildMesh is the host partner): their blasNodeOffset values
+    // are those from before later meshes moved, so a later updateDynamicBVHAndSSBOs takes the device route.
     std::vector<rz_mesh_quality> rebuildDegraded(double maxRatio) {
+        deviceGeometryNewer_ = true;
         size_t n = 0;
         check(rz_geometry_quality(ctx_, nullptr, 0, &n), "rz_geometry_quality");
         std::vector<rz_mesh_quality> out(n);
@@ -235,7 +259,9 @@ public:
     // rz_present_params.selected_blas / selected_tri take -- or nothing on a miss (the reference then keeps its previous
     // selection: main.cpp:548).  The screen is the frame of the last sendSceneDataToShader.  World distances decide, not the
     // reference's object-local t; |a| < 1e-4 rejects as in the shader; empty BLAS are never hit ("Picking").
+    // Before the first sendSceneDataToShader there is no screen to place the cursor on: that throws.
     std::optional<std::pair<int, int>> pick(double mouseX, double mouseY, const Scene& scene) {
+        if (width_ <= 0 || height_ <= 0) throw std::runtime_error("pick: no frame has been set (sendSceneDataToShader comes first)");
         const std::vector<rz_ray> ray{pickRay(mouseX, mouseY, width_, height_, scene.camera)};
         const rz_hit h = traceRays(ray)[0];
         if (h.instance < 0) return std::nullopt;
@@ -311,6 +337,8 @@ public:
     void resetDisplay() { check(rz_display_reset(ctx_), "rz_display_reset"); }
     float lastRenderMs() { float ms = 0; int n = 0; check(rz_last_render_ms(ctx_, &ms, &n), "rz_last_render_ms"); return ms; }
     rz_ctx* context() { return ctx_; }
+    // The geometry as it was last HANDED OVER (initializeSSBOs / initializeSSBOsOnDevice) with the transforms of the last
+    // host-side update: deforming calls do not reach it.  rz_read_binding on context() returns what the device holds.
     const SceneBuffers& buffers() const { return buffers_; }
 
 private:
@@ -326,6 +354,7 @@ private:
     rz_ctx* ctx_;
     SceneBuffers buffers_;
     int width_ = 0, height_ = 0;
+    bool deviceGeometryNewer_ = false;      // a deforming call ran since the last hand-over: the device's geometry is newer than buffers_
 };
 
 // The same frontend glue for N GPUs of one node driven by ONE process: every device holds the whole scene, renders the

@@ -217,6 +217,22 @@ def test_cpp_frontend_example_builds_and_renders(tmp_path):
     out = subprocess.run([exe, ppm2, "96", "54", "2", "2", "device"], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0, out.stderr
     assert open(ppm2, "rb").read() == data
+    # and the pixels are those the Python binding resolves for the same scene: the example's last frame (its glass blob at
+    # x = 4.5 - 0.5 * 1), 2 samples from sample 0, bounce budget 5; the PPM's first row is the top row
+    from rayzen_amd.renderer import Renderer
+    I = S.identity()
+    sc = S.Scene(camera=S.Camera(position=(0.0, 2.5, 10.0), target=(0.0, 0.0, -1.0), fov=70.0, aspect=np.float32(96) / np.float32(54)))
+    floor, bunny, glass = sc.add_mesh(S.make_cube(4)), sc.add_mesh(S.make_blob(40, 2.8, 0)), sc.add_mesh(S.make_blob(12, 1.2, 3))
+    sc.add_object(floor, S.translate(S.scale(I, (8.0, 0.5, 8.0)), (0.0, -3.0, 0.0)))
+    sc.add_object(bunny, S.translate(I, (0.0, 2.0, 0.0)))
+    sc.add_object(glass, S.translate(I, (4.0, 0.6, 3.0)))
+    sc.build(share_meshes=True)
+    r = Renderer(0)
+    r.upload_scene(sc)
+    r.render_scene(sc, 96, 54, 2, 5)
+    rgba = r.resolve_rgba8()
+    r.close()
+    assert np.array_equal(px, rgba[::-1, :, :3])
 
 
 # ---- the one-lane-per-sample path (scenes without transparent triangles) ------------------------------------
