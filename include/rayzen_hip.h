@@ -931,7 +931,8 @@ int rz_display_state(rz_ctx* ctx, rz_display_info* out);   /* synchronises */
  *            and 2 and reads as black in stage 3.
  *  s = 1     out = c_p exactly and nothing is cast (unless the guide is asked for), as K = 0 in rz_denoise.
  * KNOWN LIMIT.  The guide is the FIRST hit.  Reflections in the metals and everything seen through glass are upsampled as
- * colour on the reflecting or refracting surface: they are blurred to the low resolution.
+ * colour on the reflecting or refracting surface: they are blurred to the low resolution.  (rz_upscale_seethrough below follows
+ * glass and perfect mirrors.)
  * Defaults (params NULL): factor 2, sigma_normal = 128, sigma_plane = 1 (rz_denoise's), demodulate = 1.
  * rz_upscale.  rgb_in is w*h*3 floats of linear colour in rz_display's convention (what both denoisers write); rgb_in NULL reads
  * the context's accumulation as c = rgb / n, n = a > 0 ? a : 1.  Outputs, each optional:
@@ -966,6 +967,60 @@ int rz_present_upscaled(rz_ctx* ctx, const rz_present_params* present, const rz_
                         const rz_display_params* display, int source, const void* filter_params,
                         uint8_t* rgba8, size_t rgba8_bytes, float* rgb32f, size_t rgb32f_bytes);
 
+/* ------------------------------------------------------------------------ */
+/* See-through guides for the upsampler: glass and mirrors (new)            */
+/* ------------------------------------------------------------------------ */
+/* rz_upscale's guide is the first hit (its KNOWN LIMIT).  Two events of the path loop are deterministic: a transparent surface
+ * always refracts, or reflects on total internal reflection, and a surface with reflectivity >= 1 always mirrors (its test is
+ * rand < reflectivity with rand in [0, 1)).  These entry points follow the pixel-centre ray through such surfaces to the first
+ * surface that scatters diffusely and interpolate there (rz_seethrough.hip).  Everything of rz_upscale stands as written
+ * except the guide, alpha and one more admissibility term.
+ *  chain     of a pixel, at either size.  o = cam_pos, d = the direction rz_denoise's guide casts for the pixel centre, ior = 1,
+ *            T = (1, 1, 1), L = 0, k = 0.  Repeat: h = the closest hit of (o, d) by rz_trace_rays' query.  A miss ends the chain
+ *            with final = miss.  Otherwise L = L + t (binary32, in order) and M = materials[clamp(h.material)]; m_first is the
+ *            clamped material of the first hit.  If k == max_depth the chain ends at this hit.  Else if M.transparency > 0: the
+ *            dielectric step of the path loop (rz_path.h: scatter) verbatim -- entering = dot(-d, n) > 0, N = entering ? n : -n,
+ *            next = entering ? M.ior : 1, eta = ior / next, cosi = clamp(dot(-d, N), 0, 1), F0 = ((ior - next) / (ior + next))^2,
+ *            fresnel = F0 + (1 - F0)(1 - cosi)^5 with x^5 = (x^2)^2 x; on total internal reflection d = d - N (2 dot(d, N)) and
+ *            T = T * 0.98; else d = the refracted direction, ior = next, tint = mix(1, albedo, transparency) per channel and
+ *            T = T * clamp((tint * transparency) * (1 - fresnel), 0, 1).  Else if M.reflectivity >= 1: d = d - n (2 dot(d, n)) and
+ *            T = T * 0.95.  Else the chain ends at this hit.  After a step o = hp + (n * (dot(d, n) > 0 ? 1 : -1)) * 0.003 and
+ *            k = k + 1.  NaN parameters fail both comparisons and end the chain.  The bounce budget and Russian roulette play no
+ *            part: this is a guide, not a sample.  Binary32, one rounding per operation, no fused multiply-add, operands in
+ *            scatter()'s order.
+ *  guide     G = (hit or miss of the FINAL query; x, n and material of the final hit; t = L).
+ *  class     cls = 0 if k == 0, else m_first + 1.
+ *  alpha     T * albedo(final material) per channel for a final hit, T for a final miss (a miss is demodulated too).  With
+ *            k = 0 this is rz_upscale's alpha bit for bit.
+ *  a tap q is ADMISSIBLE iff rz_upscale admits it on these guides AND cls_q == cls_P.  W_geom (on the final hits, t_P = L_P),
+ *            the 1e-4 floor, stages 1 to 3, demodulation by max(alpha, 1e-3) and re-modulation by alpha_P are rz_upscale's.
+ * So max_depth = 0, or a scene in which no pixel's chain moves, gives rz_upscale's / rz_present_upscaled's bytes exactly, and
+ * factor 1 gives c exactly (rz_present_upscaled_seethrough: rz_present_display's bytes).
+ * LIMITS.  Surfaces with 0 < reflectivity < 1 are not followed.  The first surface's direct-light term (a highlight on the glass)
+ * is interpolated within its class.  The denoisers that run in front of the upscale (sources 1 and 2) keep first-hit guides.
+ * rz_upscale_seethrough is rz_upscale with: seethrough (NULL: max_depth 8); guides = the rz_hit of the FINAL hit with t = L (a
+ * final miss is the miss record); chains, optional, W*H rz_chain, 16-byte aligned on the device path.  Pointer conventions,
+ * RZ_UPSCALE_HOST, the error codes and "a failing call launches nothing" are rz_upscale's; in addition a max_depth outside 0..8
+ * or a non-zero reserved word is RZ_ERR_INVALID_ARG and a chains buffer that is too small RZ_ERR_BUFFER_SIZE.  The calls touch no
+ * render, temporal or display state beyond what their first-hit twins touch; their guide buffers live in the context beside
+ * the first-hit ones, allocated on first use and kept.
+ * (Additive: RZ_ABI_VERSION stays 5.) */
+typedef struct rz_seethrough_params {   /* NULL = defaults */
+    int32_t max_depth;                  /* specular steps followed at most, 0..8 (default 8) */
+    int32_t reserved[7];                /* must be 0 */
+} rz_seethrough_params;                 /* 32 B; rz_sizeof(23) */
+typedef struct rz_chain {
+    float   throughput[3];              /* T */
+    int32_t word;                       /* k | (m_first + 1) << 8; 0 for a primary miss */
+} rz_chain;                             /* 16 B; rz_sizeof(24) */
+int rz_upscale_seethrough(rz_ctx* ctx, const rz_upscale_params* params, const rz_seethrough_params* seethrough,
+                          const float* rgb_in, size_t rgb_in_bytes, float* rgb32f, size_t rgb32f_bytes,
+                          rz_hit* guides, size_t guides_bytes, rz_chain* chains, size_t chains_bytes, unsigned flags);
+int rz_present_upscaled_seethrough(rz_ctx* ctx, const rz_present_params* present, const rz_upscale_params* upscale,
+                                   const rz_seethrough_params* seethrough, const rz_display_params* display, int source,
+                                   const void* filter_params, uint8_t* rgba8, size_t rgba8_bytes,
+                                   float* rgb32f, size_t rgb32f_bytes);
+
 /* Number of HIP devices visible to the process (0 without a GPU). */
 int rz_device_count(void);
 
@@ -990,7 +1045,8 @@ const char* rz_source_hash(void);
  * 3 material, 4 light, 5 frame_params, 6 counters, 7 ray, 8 hit,
  * 9 visibility, 10 editor_params, 11 denoise_params, 12 temporal_params,
  * 14 display_params, 15 display_info, 17 skin_triangle, 18 morph_triangle, 20 mesh_quality,
- * 21 upscale_params (13, 16 and 19 are unassigned and return 0, as every unknown index does). */
+ * 21 upscale_params, 23 seethrough_params, 24 chain (13, 16, 19 and 22 are unassigned and return 0, as every unknown index
+ * does). */
 size_t rz_sizeof(int which);
 
 #ifdef __cplusplus

@@ -6,6 +6,8 @@ no GPU to talk to, the calls fail loudly.
 import ctypes as C
 import os
 
+import numpy as np
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 HIP_SO = os.environ.get("RAYZEN_HIP_SO") or os.path.join(_HERE, "lib", "librayzen_hip.so")   # override: A/B builds
 HOST_SO = os.path.join(_HERE, "lib", "librayzen_host.so")
@@ -26,7 +28,7 @@ HIP_SYMBOLS = (
     "rz_display", "rz_present_display", "rz_display_reset", "rz_display_state",
     "rz_skin_create", "rz_skin_pose", "rz_skin_destroy", "rz_skin_last_kernel_ms",
     "rz_geometry_quality", "rz_rebuild_geometry",
-    "rz_upscale", "rz_present_upscaled",
+    "rz_upscale", "rz_present_upscaled", "rz_upscale_seethrough", "rz_present_upscaled_seethrough",
 )
 ABI_VERSION = 5         # RZ_ABI_VERSION of the include/rayzen_hip.h this file mirrors
 # the symbols include/rayzen_host.h declares
@@ -160,6 +162,23 @@ UPSCALE_HOST = 1                        # RZ_UPSCALE_HOST
 SIZEOF_UPSCALE_PARAMS = 21              # its rz_sizeof index
 
 
+class SeethroughParams(C.Structure):
+    """rz_seethrough_params of include/rayzen_hip.h (32 B)."""
+    _fields_ = [("max_depth", C.c_int32), ("reserved", C.c_int32 * 7)]
+
+
+class Chain(C.Structure):
+    """rz_chain of include/rayzen_hip.h (16 B)."""
+    _fields_ = [("throughput", C.c_float * 3), ("word", C.c_int32)]
+
+
+# rz_chain as a numpy record: word = k | (m_first + 1) << 8, 0 for a primary miss
+CHAIN_DTYPE = np.dtype([("throughput", np.float32, (3,)), ("word", np.int32)])
+SEETHROUGH_DEFAULTS = dict(max_depth=8)
+SEETHROUGH_MAX_DEPTH = 8
+SIZEOF_SEETHROUGH_PARAMS, SIZEOF_CHAIN = 23, 24     # their rz_sizeof indices
+
+
 class SkinTriangle(C.Structure):
     """rz_skin_triangle of include/rayzen_hip.h (64 B)."""
     _fields_ = [("bones", C.c_uint32 * 3), ("pad", C.c_uint32), ("weights", (C.c_float * 4) * 3)]
@@ -278,7 +297,9 @@ def hip():
                                 ("rz_geometry_quality", i, [vp, vp, sz, C.POINTER(sz)]),
                                 ("rz_rebuild_geometry", i, [vp, C.c_double, vp, sz, C.POINTER(sz), C.c_uint]),
                                 ("rz_upscale", i, [vp, vp, vp, sz, vp, sz, vp, sz, C.c_uint]),
-                                ("rz_present_upscaled", i, [vp, C.POINTER(PresentParams), vp, vp, i, vp, vp, sz, vp, sz])):
+                                ("rz_present_upscaled", i, [vp, C.POINTER(PresentParams), vp, vp, i, vp, vp, sz, vp, sz]),
+                                ("rz_upscale_seethrough", i, [vp, vp, vp, vp, sz, vp, sz, vp, sz, vp, sz, C.c_uint]),
+                                ("rz_present_upscaled_seethrough", i, [vp, C.POINTER(PresentParams), vp, vp, vp, i, vp, vp, sz, vp, sz])):
             try:
                 fn = getattr(L, name)
                 fn.restype, fn.argtypes = res, args

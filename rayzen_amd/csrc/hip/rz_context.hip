@@ -173,6 +173,9 @@ struct rz_ctx {
     // rz_upscale / rz_present_upscaled (rz_upscale.hip): the guides cast at the low and at the high size (2 float4 per pixel
     // each) and the high-size (colour, 1) buffer rz_present_upscaled presents; allocated on first use and kept
     DevBuf dUpGuideLo, dUpGuideHi, dUpOut;
+    // rz_upscale_seethrough / rz_present_upscaled_seethrough (rz_seethrough.hip): the chain guides at both sizes (3 float4 per
+    // pixel each); allocated on first use and kept.  The first-hit buffers above are not touched by those calls.
+    DevBuf dStGuideLo, dStGuideHi;
     // rz_refit_geometry (rz_refit.hip)
     bool trisHostStale = false;         // binding 0 on the device (dRawTris) is newer than the host copy: fetched on demand (sync_tris_host)
     unsigned long long layoutGen = 0;   // counts the times the views / instances were laid out
@@ -1047,6 +1050,8 @@ size_t rz_sizeof(int which) {
         case 18: return sizeof(rz_morph_triangle);
         case 20: return sizeof(rz_mesh_quality);         // (19 stays unassigned: probed as an unknown index)
         case 21: return sizeof(rz_upscale_params);
+        case 23: return sizeof(rz_seethrough_params);    // (22 stays unassigned: probed as an unknown index)
+        case 24: return sizeof(rz_chain);
         default: return 0;
     }
 }
@@ -1091,7 +1096,8 @@ void rz_destroy(rz_ctx* c) {
                       &c->dRefitRank, &c->dRefitInstView, &c->dRefitViewOff, &c->dRefitFlags, &c->dRefitRoots,
                       &c->dTmpCol[0], &c->dTmpCol[1], &c->dTmpMom[0], &c->dTmpMom[1], &c->dTmpHits[0], &c->dTmpHits[1],
                       &c->dTmpInst[0], &c->dTmpInst[1], &c->dTmpSame, &c->dDisplay, &c->dSkinOut, &c->dSkinBones, &c->dSkinWeights,
-                      &c->dQualViews, &c->dQualPartials, &c->dQualCost, &c->dUpGuideLo, &c->dUpGuideHi, &c->dUpOut})
+                      &c->dQualViews, &c->dQualPartials, &c->dQualCost, &c->dUpGuideLo, &c->dUpGuideHi, &c->dUpOut,
+                      &c->dStGuideLo, &c->dStGuideHi})
         b->release();
     for (auto& kv : c->rigs) kv.second.release();
     for (hipEvent_t e : c->evSkin) if (e) (void)hipEventDestroy(e);
@@ -3161,10 +3167,49 @@ static int upscale_cast(rz_ctx* c, int width, int height, float4* guide, float4*
     return RZ_OK;
 }
 
+// rz_upscale_seethrough / rz_present_upscaled_seethrough (rz_seethrough.hip): the same calls with the guide cast along the
+// pixel's deterministic chain.  `st` below is null for the first-hit entry points, whose launches and buffers are unchanged.
+static const rz_seethrough_params kSeethroughDefaults = {8, {0, 0, 0, 0, 0, 0, 0}};
+
+static int seethrough_check(rz_ctx* c, const char* what, const rz_seethrough_params& S) {
+    if (S.max_depth < 0 || S.max_depth > 8) return fail(c, RZ_ERR_INVALID_ARG, "%s: max_depth %d outside 0..8", what, S.max_depth);
+    for (int k = 0; k < 7; ++k)
+        if (S.reserved[k]) return fail(c, RZ_ERR_INVALID_ARG, "%s: reserved words of rz_seethrough_params must be 0", what);
+    return RZ_OK;
+}
+
+// One launch of rz_seethrough_guides at width x height with the frame's camera: the 48-B records, and the rz_hit and rz_chain
+// records when asked.
+static int seethrough_cast(rz_ctx* c, int width, int height, int maxDepth, float4* rec, float4* hits, float4* chains) {
+    const rz_frame_params& f = c->frame;
+    KParams K{};
+    scene_kparams(c, K);
+    K.width = width; K.height = height;
+    std::memcpy(K.invView, f.inv_view, 64);
+    std::memcpy(K.invProj, f.inv_proj, 64);
+    std::memcpy(K.camPos, f.cam_pos, 12);
+    SeethroughGuideLaunch G{};
+    G.unitsX = (width + 63) / 64;
+    G.units = (long long)G.unitsX * height;
+    G.grid = rays_grid(G.units * 64);
+    G.maxDepth = maxDepth;
+    G.rec = rec;
+    G.hits = hits;
+    G.chains = chains;
+    G.instTriOff = static_cast<const int32_t*>(c->dRayInstOff.p);
+    G.errWord = static_cast<unsigned*>(c->dGroupCtr.p) + RZ_ERRWORD;
+    const int rc = size_blas_stack(c, K, 0, RZ_RAYS_WAVES_PER_CU, G.grid, c->dRayOvf);
+    if (rc != RZ_OK) return rc;
+    launch_seethrough_guides(K, G, c->stream);
+    RZ_HIP(c, hipGetLastError());
+    return RZ_OK;
+}
+
 // Casts both guides and gathers, on the stream; factor >= 2.  The low frame (device) is in3 (3 floats per pixel) or in4 (RGBA32F
 // sum and count); outputs (device, high size, each optional): rgb (3 floats per pixel), out4 ((colour, 1)), hits (rz_hit).
-static int upscale_run(rz_ctx* c, const rz_upscale_params& P, const float* in3, const float4* in4, float* rgb, float4* out4, float4* hits) {
-    if (!rgb && !out4 && !hits) return RZ_OK;
+static int upscale_run(rz_ctx* c, const rz_upscale_params& P, const float* in3, const float4* in4, float* rgb, float4* out4, float4* hits,
+                       const rz_seethrough_params* st = nullptr, float4* chains = nullptr) {
+    if (!rgb && !out4 && !hits && !chains) return RZ_OK;
     const rz_frame_params& f = c->frame;
     const int W = f.width * P.factor, H = f.height * P.factor;
     int rc = finalize(c);
@@ -3173,23 +3218,28 @@ static int upscale_run(rz_ctx* c, const rz_upscale_params& P, const float* in3, 
     if (rc != RZ_OK) return rc;
     rc = ensure_ray_inst_off(c);
     if (rc != RZ_OK) return rc;
-    rc = ensure(c, c->dUpGuideHi, (size_t)W * H * 32);
+    DevBuf& bufHi = st ? c->dStGuideHi : c->dUpGuideHi;
+    DevBuf& bufLo = st ? c->dStGuideLo : c->dUpGuideLo;
+    const size_t rec = st ? 48 : 32;
+    rc = ensure(c, bufHi, (size_t)W * H * rec);
     if (rc != RZ_OK) return rc;
     if (rgb || out4) {
-        rc = ensure(c, c->dUpGuideLo, (size_t)f.width * f.height * 32);
+        rc = ensure(c, bufLo, (size_t)f.width * f.height * rec);
         if (rc != RZ_OK) return rc;
     }
     // the high cast first: its overflow columns (size_blas_stack) are the larger ones, so the low cast finds them in place
-    rc = upscale_cast(c, W, H, static_cast<float4*>(c->dUpGuideHi.p), hits);
+    rc = st ? seethrough_cast(c, W, H, st->max_depth, static_cast<float4*>(bufHi.p), hits, chains)
+            : upscale_cast(c, W, H, static_cast<float4*>(bufHi.p), hits);
     if (rc != RZ_OK) return rc;
     if (!rgb && !out4) return RZ_OK;
-    rc = upscale_cast(c, f.width, f.height, static_cast<float4*>(c->dUpGuideLo.p), nullptr);
+    rc = st ? seethrough_cast(c, f.width, f.height, st->max_depth, static_cast<float4*>(bufLo.p), nullptr, nullptr)
+            : upscale_cast(c, f.width, f.height, static_cast<float4*>(bufLo.p), nullptr);
     if (rc != RZ_OK) return rc;
     UpscaleLaunch U{};
     U.in3 = in4 ? nullptr : in3;
     U.in4 = in4;
-    U.guideLo = static_cast<const float4*>(c->dUpGuideLo.p);
-    U.guideHi = static_cast<const float4*>(c->dUpGuideHi.p);
+    U.guideLo = static_cast<const float4*>(bufLo.p);
+    U.guideHi = static_cast<const float4*>(bufHi.p);
     U.materials = static_cast<const DevMaterial*>(c->dMat.p);
     U.dst = out4;
     U.rgb = rgb;
@@ -3199,37 +3249,48 @@ static int upscale_run(rz_ctx* c, const rz_upscale_params& P, const float* in3, 
     const double fpx = 2.0 * std::fabs((double)f.inv_proj[5]) / (double)f.height;     // world size of a LOW pixel at unit distance
     U.planeScale = (float)(1.0 / ((double)P.sigma_plane * fpx));
     U.demodulate = P.demodulate;
-    launch_upscale_gather(U, c->stream);
+    if (st) launch_seethrough_gather(U, c->stream);
+    else launch_upscale_gather(U, c->stream);
     RZ_HIP(c, hipGetLastError());
     return RZ_OK;
 }
 
 static int upscale_impl(rz_ctx* c, const rz_upscale_params* pp, const float* rgb_in, size_t rgb_in_bytes, float* rgb32f,
-                        size_t rgb32f_bytes, rz_hit* guides, size_t guides_bytes, unsigned flags) {
-    const char* what = "rz_upscale";
+                        size_t rgb32f_bytes, rz_hit* guides, size_t guides_bytes, unsigned flags,
+                        const rz_seethrough_params* st = nullptr, rz_chain* chains = nullptr, size_t chains_bytes = 0) {
+    const char* what = st ? "rz_upscale_seethrough" : "rz_upscale";
     if (!c) return fail(nullptr, RZ_ERR_INVALID_ARG, "%s: null context", what);
     if (flags & ~RZ_UPSCALE_HOST) return fail(c, RZ_ERR_INVALID_ARG, "%s: unknown flags 0x%x", what, flags);
     const rz_upscale_params& P = pp ? *pp : kUpscaleDefaults;
     int rc = upscale_check(c, what, P);
     if (rc != RZ_OK) return rc;
+    if (st) {
+        rc = seethrough_check(c, what, *st);
+        if (rc != RZ_OK) return rc;
+    }
     const bool host = (flags & RZ_UPSCALE_HOST) != 0;
-    if (!host && ((reinterpret_cast<uintptr_t>(guides) & 15u) || ((reinterpret_cast<uintptr_t>(rgb_in) | reinterpret_cast<uintptr_t>(rgb32f)) & 3u)))
-        return fail(c, RZ_ERR_INVALID_ARG, "%s: device pointers must be 16-byte (guides) or 4-byte (rgb_in, rgb32f) aligned", what);
+    if (!host && (((reinterpret_cast<uintptr_t>(guides) | reinterpret_cast<uintptr_t>(chains)) & 15u) ||
+                  ((reinterpret_cast<uintptr_t>(rgb_in) | reinterpret_cast<uintptr_t>(rgb32f)) & 3u)))
+        return fail(c, RZ_ERR_INVALID_ARG, "%s: device pointers must be 16-byte (guides%s) or 4-byte (rgb_in, rgb32f) aligned", what,
+                    st ? ", chains" : "");
     const size_t np = (size_t)c->frame.width * c->frame.height, nP = np * P.factor * P.factor;
-    const size_t bIn = np * 3 * sizeof(float), bRgb = nP * 3 * sizeof(float), bHits = nP * sizeof(rz_hit);
+    const size_t bIn = np * 3 * sizeof(float), bRgb = nP * 3 * sizeof(float), bHits = nP * sizeof(rz_hit), bChains = nP * sizeof(rz_chain);
     if (rgb_in && rgb_in_bytes < bIn) return fail(c, RZ_ERR_BUFFER_SIZE, "%s: rgb_in needs %zu bytes, got %zu", what, bIn, rgb_in_bytes);
     if (!rgb_in && c->extAccum && c->extAccumBytes < np * 16)
         return fail(c, RZ_ERR_BUFFER_SIZE, "%s: bound accumulation buffer holds %zu bytes, frame needs %zu", what, c->extAccumBytes, np * 16);
     if (rgb32f && rgb32f_bytes < bRgb) return fail(c, RZ_ERR_BUFFER_SIZE, "%s: rgb32f needs %zu bytes, got %zu", what, bRgb, rgb32f_bytes);
     if (guides && guides_bytes < bHits) return fail(c, RZ_ERR_BUFFER_SIZE, "%s: guides needs %zu bytes, got %zu", what, bHits, guides_bytes);
-    if (!rgb32f && !guides) return RZ_OK;
+    if (chains && chains_bytes < bChains) return fail(c, RZ_ERR_BUFFER_SIZE, "%s: chains needs %zu bytes, got %zu", what, bChains, chains_bytes);
+    if (!rgb32f && !guides && !chains) return RZ_OK;
     RZ_HIP(c, hipSetDevice(c->device));
     const float* in3 = rgb_in;
     const float4* in4 = rgb_in ? nullptr : static_cast<const float4*>(rz_accum_device_ptr(c));
     float* dRgb = rgb32f;
     float4* dHits = reinterpret_cast<float4*>(guides);
-    // host buffers are staged as rz_denoise stages them: the input in dRayIn; hits, then rgb32f in dRayOut
-    const size_t oRgb = guides ? (bHits + 15) & ~size_t(15) : 0;
+    float4* dChains = reinterpret_cast<float4*>(chains);
+    // host buffers are staged as rz_denoise stages them: the input in dRayIn; hits, then chains, then rgb32f in dRayOut
+    const size_t oChains = guides ? (bHits + 15) & ~size_t(15) : 0;
+    const size_t oRgb = oChains + (chains ? bChains : 0);
     if (host) {
         if (rgb_in) {
             rc = ensure(c, c->dRayIn, bIn);
@@ -3241,6 +3302,7 @@ static int upscale_impl(rz_ctx* c, const rz_upscale_params* pp, const float* rgb
         if (rc != RZ_OK) return rc;
         char* base = static_cast<char*>(c->dRayOut.p);
         dHits = guides ? reinterpret_cast<float4*>(base) : nullptr;
+        dChains = chains ? reinterpret_cast<float4*>(base + oChains) : nullptr;
         dRgb = rgb32f ? reinterpret_cast<float*>(base + oRgb) : nullptr;
     }
     if (P.factor == 1) {                    // c_p itself, and nothing is cast unless the guide is asked for
@@ -3254,20 +3316,23 @@ static int upscale_impl(rz_ctx* c, const rz_upscale_params* pp, const float* rgb
         } else if (dRgb && dRgb != in3) {
             RZ_HIP(c, hipMemcpyAsync(dRgb, in3, bIn, hipMemcpyDeviceToDevice, c->stream));
         }
-        if (dHits) {
+        if (dHits || dChains) {
             rc = finalize(c);
             if (rc == RZ_OK) rc = ensure_group_counter(c);
             if (rc == RZ_OK) rc = ensure_ray_inst_off(c);
-            if (rc == RZ_OK) rc = ensure(c, c->dUpGuideHi, np * 32);
-            if (rc == RZ_OK) rc = upscale_cast(c, c->frame.width, c->frame.height, static_cast<float4*>(c->dUpGuideHi.p), dHits);
+            if (rc == RZ_OK) rc = ensure(c, st ? c->dStGuideHi : c->dUpGuideHi, np * (st ? 48 : 32));
+            if (rc == RZ_OK)
+                rc = st ? seethrough_cast(c, c->frame.width, c->frame.height, st->max_depth, static_cast<float4*>(c->dStGuideHi.p), dHits, dChains)
+                        : upscale_cast(c, c->frame.width, c->frame.height, static_cast<float4*>(c->dUpGuideHi.p), dHits);
         }
     } else {
-        rc = upscale_run(c, P, in3, in4, dRgb, nullptr, dHits);
+        rc = upscale_run(c, P, in3, in4, dRgb, nullptr, dHits, st, dChains);
     }
     if (rc != RZ_OK) return rc;
     if (!host) return RZ_OK;
     const char* base = static_cast<const char*>(c->dRayOut.p);
     if (guides) RZ_HIP(c, hipMemcpyAsync(guides, base, bHits, hipMemcpyDeviceToHost, c->stream));
+    if (chains) RZ_HIP(c, hipMemcpyAsync(chains, base + oChains, bChains, hipMemcpyDeviceToHost, c->stream));
     if (rgb32f) RZ_HIP(c, hipMemcpyAsync(rgb32f, base + oRgb, bRgb, hipMemcpyDeviceToHost, c->stream));
     RZ_HIP(c, hipStreamSynchronize(c->stream));
     return denoise_backstop(c, what);
@@ -3275,8 +3340,8 @@ static int upscale_impl(rz_ctx* c, const rz_upscale_params* pp, const float* rgb
 
 static int present_upscaled_impl(rz_ctx* c, const rz_present_params* pp, const rz_upscale_params* up, const rz_display_params* dp,
                                  int source, const void* filter_params, uint8_t* rgba8, size_t rgba8_bytes, float* rgb32f,
-                                 size_t rgb32f_bytes) {
-    const char* what = "rz_present_upscaled";
+                                 size_t rgb32f_bytes, const rz_seethrough_params* st = nullptr) {
+    const char* what = st ? "rz_present_upscaled_seethrough" : "rz_present_upscaled";
     if (!c) return fail(nullptr, RZ_ERR_INVALID_ARG, "%s: null context", what);
     if (!pp) return fail(c, RZ_ERR_INVALID_ARG, "%s: null present params", what);
     if (source < 0 || source > 2) return fail(c, RZ_ERR_INVALID_ARG, "%s: source %d (0 accumulation, 1 rz_denoise, 2 rz_denoise_temporal)", what, source);
@@ -3292,6 +3357,10 @@ static int present_upscaled_impl(rz_ctx* c, const rz_present_params* pp, const r
     if (rc != RZ_OK) return rc;
     rc = upscale_check(c, what, U);
     if (rc != RZ_OK) return rc;
+    if (st) {
+        rc = seethrough_check(c, what, *st);
+        if (rc != RZ_OK) return rc;
+    }
     // factor 1: nothing to reconstruct, the call IS rz_present_display (its bytes exactly, for every source)
     if (U.factor == 1) return present_display_impl(c, pp, dp, source, filter_params, rgba8, rgba8_bytes, rgb32f, rgb32f_bytes);
     const int W = c->frame.width * U.factor, H = c->frame.height * U.factor;
@@ -3314,7 +3383,7 @@ static int present_upscaled_impl(rz_ctx* c, const rz_present_params* pp, const r
         if (rc != RZ_OK) return rc;
         low4 = out4;
     }
-    rc = upscale_run(c, U, nullptr, low4, nullptr, hi4, nullptr);
+    rc = upscale_run(c, U, nullptr, low4, nullptr, hi4, nullptr, st);
     if (rc != RZ_OK) return rc;
     rc = display_run(c, D, nullptr, hi4, nullptr, nullptr, hi4, false, (long long)nP);
     if (rc != RZ_OK) return rc;
@@ -3537,6 +3606,22 @@ int rz_present_upscaled(rz_ctx* c, const rz_present_params* present, const rz_up
                         int source, const void* filter_params, uint8_t* rgba8, size_t rgba8_bytes, float* rgb32f, size_t rgb32f_bytes) {
     return guarded(c, "rz_present_upscaled", [&] {
         return present_upscaled_impl(c, present, upscale, display, source, filter_params, rgba8, rgba8_bytes, rgb32f, rgb32f_bytes);
+    });
+}
+int rz_upscale_seethrough(rz_ctx* c, const rz_upscale_params* params, const rz_seethrough_params* seethrough, const float* rgb_in,
+                          size_t rgb_in_bytes, float* rgb32f, size_t rgb32f_bytes, rz_hit* guides, size_t guides_bytes, rz_chain* chains,
+                          size_t chains_bytes, unsigned flags) {
+    return guarded(c, "rz_upscale_seethrough", [&] {
+        return upscale_impl(c, params, rgb_in, rgb_in_bytes, rgb32f, rgb32f_bytes, guides, guides_bytes, flags,
+                            seethrough ? seethrough : &kSeethroughDefaults, chains, chains_bytes);
+    });
+}
+int rz_present_upscaled_seethrough(rz_ctx* c, const rz_present_params* present, const rz_upscale_params* upscale,
+                                   const rz_seethrough_params* seethrough, const rz_display_params* display, int source,
+                                   const void* filter_params, uint8_t* rgba8, size_t rgba8_bytes, float* rgb32f, size_t rgb32f_bytes) {
+    return guarded(c, "rz_present_upscaled_seethrough", [&] {
+        return present_upscaled_impl(c, present, upscale, display, source, filter_params, rgba8, rgba8_bytes, rgb32f, rgb32f_bytes,
+                                     seethrough ? seethrough : &kSeethroughDefaults);
     });
 }
 int rz_display_reset(rz_ctx* c) {

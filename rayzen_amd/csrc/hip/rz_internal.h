@@ -101,6 +101,21 @@ struct UpscaleLaunch {          // rz_upscale_gather
 };
 void launch_upscale_gather(const UpscaleLaunch& U, hipStream_t stream);
 
+// ---- rz_seethrough.hip
+struct SeethroughGuideLaunch {  // rz_seethrough_guides: DenoiseGuideLaunch with the chain's bound and outputs
+    long long units;            // 64-pixel runs of a row
+    int unitsX;                 // runs per row
+    long long grid;             // rays_grid(units * 64)
+    int maxDepth;               // rz_seethrough_params.max_depth, 0..8
+    float4* rec;                // width x height x 3 float4: (n, L), (x, final hit word: material index, -1 = miss), (T, cls)
+    float4* hits;               // width x height rz_hit (3 float4) of the final hit with t = L, optional
+    float4* chains;             // width x height rz_chain, optional
+    const int32_t* instTriOff;  // globalTriOffset of every instance (as RaysLaunch)
+    unsigned* errWord;          // the context's backstop word
+};
+void launch_seethrough_guides(const KParams& K, const SeethroughGuideLaunch& G, hipStream_t stream);
+void launch_seethrough_gather(const UpscaleLaunch& U, hipStream_t stream);     // guideLo / guideHi: SeethroughGuideLaunch::rec
+
 // ---- rz_temporal.hip
 struct TemporalLaunch {         // rz_temporal_accumulate
     const float4* accum;        // RGBA32F sum and count

@@ -1,0 +1,146 @@
+// rz_seethrough.hip -- see-through guides for the guided upsampler (include/rayzen_hip.h: rz_upscale_seethrough /
+// rz_present_upscaled_seethrough).  rz_upscale's guide is the first hit, so what is seen in a mirror or through glass is
+// interpolated as colour on the mirror or the glass.  Both events are deterministic in the path loop (rz_path.h: scatter): a
+// transparent surface always refracts (or reflects on total internal reflection) and a surface with reflectivity >= 1 always
+// mirrors.  The guide can therefore follow the pixel-centre ray through them to the first surface that scatters diffusely and
+// the colour is interpolated THERE.
+//
+//   rz_seethrough_guides   rz_denoise_guides' shape: a persistent grid of one-wave workgroups, 64 pixels of a row per step.  The
+//                          chain is a wave-uniform loop that runs while a ballot says a lane is live -- at most max_depth + 1
+//                          queries -- and a finished lane stays out of the query (the predicated body of rz_shadow_rays_kernel).
+//                          Per pixel a 48-B record, three 16-B stores: (n, L | x, final hit word | T, cls), and the rz_hit of
+//                          the final hit with t = L and the rz_chain when asked.
+//   rz_seethrough_gather   rz_upscale_gather's body (rz_upscale_body.h, CHAIN = true) on those records: alpha = T * albedo and
+//                          the class term.
+//
+// The chain of a pixel (the header states it; operands in scatter()'s order, binary32, no fused multiply-add):
+//   o = cam_pos, d = rz_denoise's guide direction, ior = 1, T = (1, 1, 1), L = 0, k = 0; repeat: h = closest hit of (o, d); a
+//   miss ends the chain (final = miss); L += t; M = materials[clamp(h.material)]; if k == max_depth the chain ends at h; else
+//   if M.transparency > 0 the dielectric step of scatter(); else if M.reflectivity >= 1 d = reflect(d, n), T *= 0.95; else the
+//   chain ends at h.  After a step o = hp + (hn * pushDir) * 0.003 and k += 1.  cls = 0 if k == 0, else m_first + 1.
+#include "rz_upscale_body.h"
+#include "rz_query.h"
+#include "rz_path.h"
+
+namespace rz {
+
+template <bool OVF>
+__global__ __launch_bounds__(64, RZ_RAYS_MIN_WAVES) void rz_seethrough_guides(const KParams K, const SeethroughGuideLaunch G) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
+    const BlasStackT<OVF> bstk = rays_stack<OVF>(K, lds_raw);
+    const int lane = threadIdx.x & 63;
+    const v3 cam = mk3(K.camPos[0], K.camPos[1], K.camPos[2]);
+    bool cut = false;
+    for (long long u = blockIdx.x; u < G.units; u += gridDim.x) {
+        const int py = (int)(u / G.unitsX), px = (int)(u - (long long)py * G.unitsX) * 64 + lane;
+        const bool inside = px < K.width;
+        v3 o = cam, d = mk3(0.0f, 0.0f, 0.0f);
+        if (inside) {
+            v2 uv;
+            uv.x = ((float)px + 0.5f) / (float)K.width;
+            uv.y = ((float)py + 0.5f) / (float)K.height;
+            d = camera_ray_centre(K.invProj, K.invView, uv);
+        }
+        float ior = 1.0f, L = 0.0f;
+        v3 T = mk3(1.0f, 1.0f, 1.0f);
+        int k = 0, first = -1, tri = 0;
+        bool found = false;
+        HitRec h = {};
+        bool run = inside;
+        while (rz_ballot(run) != 0ull) {        // at most max_depth + 1 trips: a lane with k == max_depth ends at its hit
+            if (run) {
+                HitRec hq;
+                TraceExtra x;
+                found = ray_query<OVF, false>(K, o, d, hq, bstk, x);
+                cut = cut || x.cut;
+                run = false;
+                if (found) {
+                    h = hq;
+                    tri = x.tri;
+                    L = L + hq.t;
+                    const int m = min(max(hq.mat, 0), K.nMaterials - 1);
+                    if (k == 0) first = m;
+                    const DevMaterial M = K.materials[m];
+                    const v3 hitNormal = hq.n;
+                    v3 dir = d;
+                    if (k == G.maxDepth) {
+                        // the chain is exhausted on this surface, specular or not
+                    } else if (M.transparency > 0.0f) {     // scatter(): FS:723-746
+                        const bool entering = dot(-dir, hitNormal) > 0.0f;
+                        const v3 N = entering ? hitNormal : -hitNormal;
+                        const float extIor = ior;
+                        const float nextIor = entering ? M.ior : 1.0f;
+                        const float eta = extIor / nextIor;
+                        const float cosi = clamp_(dot(-dir, N), 0.0f, 1.0f);
+                        const float F0 = pow2_((extIor - nextIor) / (extIor + nextIor));
+                        const float fresnel = F0 + (1.0f - F0) * pow5_(1.0f - cosi);
+                        v3 refr;
+                        if (!refract_dir(dir, N, eta, refr)) {
+                            dir = reflect_ray(dir, N);
+                            T = T * 0.98f;
+                        } else {
+                            dir = refr;
+                            ior = nextIor;
+                            const float tr = M.transparency;
+                            const v3 tint = mk3(mix_(1.0f, M.albedo[0], tr), mix_(1.0f, M.albedo[1], tr), mix_(1.0f, M.albedo[2], tr));
+                            const v3 tw = (tint * tr) * (1.0f - fresnel);
+                            T = T * mk3(clamp_(tw.x, 0.0f, 1.0f), clamp_(tw.y, 0.0f, 1.0f), clamp_(tw.z, 0.0f, 1.0f));
+                        }
+                        run = true;
+                    } else if (M.reflectivity >= 1.0f) {    // scatter(): randVal < reflectivity holds for every randVal in [0, 1)
+                        dir = reflect_ray(dir, hitNormal);
+                        T = T * 0.95f;
+                        run = true;
+                    }
+                    if (run) {
+                        const float pushDir = dot(dir, hitNormal) > 0.0f ? 1.0f : -1.0f;
+                        o = hq.p + (hitNormal * pushDir) * 0.003f;
+                        d = dir;
+                        k += 1;
+                    }
+                }
+            }
+        }
+        if (!inside) continue;
+        const size_t pix = (size_t)py * K.width + px;
+        const int word = found ? min(max(h.mat, 0), K.nMaterials - 1) : -1;
+        const int cls = k == 0 ? 0 : first + 1;
+        G.rec[3 * pix] = found ? make_float4(h.n.x, h.n.y, h.n.z, L) : make_float4(0.0f, 0.0f, 0.0f, 1e30f);
+        G.rec[3 * pix + 1] = found ? make_float4(h.p.x, h.p.y, h.p.z, __int_as_float(word))
+                                   : make_float4(0.0f, 0.0f, 0.0f, __int_as_float(-1));
+        G.rec[3 * pix + 2] = make_float4(T.x, T.y, T.z, __int_as_float(cls));
+        if (G.hits) {           // rz_trace_rays_kernel's record of the final query, with t = L
+            float4 r0 = make_float4(1e30f, 0.0f, 0.0f, 0.0f);
+            float4 r1 = make_float4(0.0f, 0.0f, 0.0f, __int_as_float(-1));
+            float4 r2 = make_float4(__int_as_float(-1), __int_as_float(-1), __int_as_float(-1), 0.0f);
+            if (found) {
+                const int prim = K.tris[tri].src;
+                r0 = make_float4(L, h.p.x, h.p.y, h.p.z);
+                r1 = make_float4(h.n.x, h.n.y, h.n.z, __int_as_float(h.mat));
+                r2 = make_float4(__int_as_float(h.inst), __int_as_float(prim - G.instTriOff[h.inst]), __int_as_float(prim), 0.0f);
+            }
+            G.hits[3 * pix] = r0;
+            G.hits[3 * pix + 1] = r1;
+            G.hits[3 * pix + 2] = r2;
+        }
+        if (G.chains) G.chains[pix] = make_float4(T.x, T.y, T.z, __int_as_float(k | ((first + 1) << 8)));
+    }
+    rays_backstop(G.errWord, cut);
+}
+
+__global__ __launch_bounds__(256) void rz_seethrough_gather(const UpscaleLaunch U) { upscale_gather_body<true>(U); }
+
+void launch_seethrough_guides(const KParams& K, const SeethroughGuideLaunch& G, hipStream_t stream) {
+    const dim3 g((unsigned)G.grid), b(64);
+    const size_t lds = (size_t)K.blasStackCap * 64 * sizeof(uint2);
+    if (K.blasOvfCap > 0) hipLaunchKernelGGL((rz_seethrough_guides<true>), g, b, lds, stream, K, G);
+    else hipLaunchKernelGGL((rz_seethrough_guides<false>), g, b, lds, stream, K, G);
+}
+
+void launch_seethrough_gather(const UpscaleLaunch& U, hipStream_t stream) {
+    const int W = U.w * U.s, H = U.h * U.s;
+    const dim3 g((unsigned)((W + 63) / 64), (unsigned)((H + 3) / 4)), b(64, 4);
+    hipLaunchKernelGGL(rz_seethrough_gather, g, b, 0, stream, U);
+}
+
+}  // namespace rz

@@ -11,7 +11,8 @@
 //   denoise() / presentDenoised()      <- new: the a-trous denoiser of the 1-spp frame (rz_denoise / rz_present_denoised)
 //   denoiseTemporal() / presentTemporal() / resetTemporal()
 //                                      <- new: temporal accumulation + the variance-guided filter (rz_denoise_temporal)
-//   presentUpscaled()                  <- new: render below display size, reconstruct at display size (rz_present_upscaled)
+//   presentUpscaled()                  <- new: render below display size, reconstruct at display size (rz_present_upscaled,
+//                                         and rz_present_upscaled_seethrough: guides that follow glass and mirrors)
 //   presentDisplay() / resetDisplay()  <- new: exposure, tone curve and sRGB encode in front of present (rz_present_display)
 // Unlike the reference's per-frame path, updateDynamicBVHAndSSBOs re-uploads
 // only what changed (instances + TLAS, a few KB), not all geometry.
@@ -33,6 +34,13 @@
 
 #include "RayZenScene.h"
 #include "rayzen_hip.h"
+
+// The one entry point of the front end that is referenced WEAKLY: a program linked against a library from before it, or against
+// a stand-in that defines only what it exercises, still links, and presentUpscaled(..., &seeThrough) throws there.
+extern "C" int rz_present_upscaled_seethrough(rz_ctx* ctx, const rz_present_params* present, const rz_upscale_params* upscale,
+                                              const rz_seethrough_params* seethrough, const rz_display_params* display, int source,
+                                              const void* filter_params, uint8_t* rgba8, size_t rgba8_bytes, float* rgb32f,
+                                              size_t rgb32f_bytes) __attribute__((weak));
 
 namespace rayzen {
 
@@ -326,11 +334,19 @@ public:
     // presentDisplay() at display size for a frame rendered below it: the frame last set is the LOW one (width x height), the
     // result is RGBA8 of factor * width x factor * height (row 0 = bottom), reconstructed from a G-buffer cast at that size, with
     // the overlays drawn there.  upscale null: factor 2 and rz_denoise's sigmas; factor 1: presentDisplay()'s bytes.
+    // seeThrough non-null: rz_present_upscaled_seethrough, whose guides follow glass and perfect mirrors for at most
+    // seeThrough->max_depth steps (0: the first-hit call's bytes); null: rz_present_upscaled.
     std::vector<uint8_t> presentUpscaled(const rz_present_params& present, const rz_upscale_params* upscale = nullptr,
-                                         const rz_display_params* display = nullptr, int source = 0, const void* filter = nullptr) {
+                                         const rz_display_params* display = nullptr, int source = 0, const void* filter = nullptr,
+                                         const rz_seethrough_params* seeThrough = nullptr) {
         const size_t s = upscale ? (size_t)std::max(upscale->factor, 0) : 2;
         std::vector<uint8_t> out((size_t)width_ * s * (size_t)height_ * s * 4);
-        check(rz_present_upscaled(ctx_, &present, upscale, display, source, filter, out.data(), out.size(), nullptr, 0), "rz_present_upscaled");
+        if (seeThrough) {
+            if (&rz_present_upscaled_seethrough == nullptr) throw std::runtime_error("rz_present_upscaled_seethrough: the linked library does not have it");
+            check(rz_present_upscaled_seethrough(ctx_, &present, upscale, seeThrough, display, source, filter, out.data(), out.size(), nullptr, 0),
+                  "rz_present_upscaled_seethrough");
+        } else
+            check(rz_present_upscaled(ctx_, &present, upscale, display, source, filter, out.data(), out.size(), nullptr, 0), "rz_present_upscaled");
         return out;
     }
     // Drops the adapted exposure (a cut: the next metered call jumps to its target).

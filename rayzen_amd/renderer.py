@@ -41,6 +41,7 @@ VISIBILITY_DTYPE = np.dtype([("visibility", "<f4"), ("lit", "<i4")])            
 MESH_QUALITY = np.dtype([("node_offset", "<i4"), ("index_offset", "<i4"), ("tri_offset", "<i4"), ("node_offset_before", "<i4"),
                          ("n_triangles", "<i4"), ("n_nodes", "<i4"), ("depth", "<i4"), ("flags", "<u4"), ("sah_cost", "<f8"),
                          ("sah_cost_built", "<f8"), ("sah_cost_before", "<f8"), ("reserved", "<f8")])        # rz_mesh_quality
+CHAIN_DTYPE = _lib.CHAIN_DTYPE           # rz_chain (16 B): what upscale(see_through=..., chains=True) returns
 
 
 def make_rays(origins, dirs, max_dist=1e30):
@@ -732,18 +733,41 @@ class Renderer:
         p.demodulate = d["demodulate"] if demodulate is None else int(bool(demodulate))
         return p
 
-    def upscale(self, rgb=None, factor=None, sigma_normal=None, sigma_plane=None, demodulate=None, guides=False):
+    @staticmethod
+    def _seethrough_params(see_through):
+        # True: the library's default depth; an int: max_depth (the library checks the range)
+        p = _lib.SeethroughParams()
+        p.max_depth = _lib.SEETHROUGH_DEFAULTS["max_depth"] if see_through is True else int(see_through)
+        return p
+
+    def upscale(self, rgb=None, factor=None, sigma_normal=None, sigma_plane=None, demodulate=None, guides=False, see_through=None,
+                chains=False):
         """Guided upsampling (include/rayzen_hip.h: rz_upscale) of rgb ((h, w, 3) float32 linear colour, what denoise() and
         denoise_temporal() return) or, with rgb None, of the accumulation: the frame of the last set_frame is the LOW frame w x h,
         the result is (factor * h, factor * w, 3) float32, reconstructed from a G-buffer cast at that size (host memory; returns
         when done).  With guides=True also that G-buffer as (H, W) HIT_DTYPE records (what trace_rays returns for the pixel-centre
         rays of editor_rays at W x H); row 0 = bottom row.  Parameters left None take the library's defaults (factor 2,
-        sigma_normal 128, sigma_plane 1, demodulate on)."""
+        sigma_normal 128, sigma_plane 1, demodulate on).
+        see_through = 0..8 (or True: 8) takes rz_upscale_seethrough instead: the guide follows glass and perfect mirrors for at
+        most that many steps; the guides are then the FINAL hits with t = the length of the chain, and chains=True appends the
+        (H, W) CHAIN_DTYPE records (throughput, k | (m_first + 1) << 8).  None is rz_upscale."""
         up = self._upscale_params(factor, sigma_normal, sigma_plane, demodulate)
         s = _lib.UPSCALE_DEFAULTS["factor"] if up is None else up.factor
         src = None if rgb is None else np.ascontiguousarray(rgb, np.float32)
         out = np.empty((max(s, 0) * self.height, max(s, 0) * self.width, 3), np.float32)
         hh = np.empty(out.shape[:2], HIT_DTYPE) if guides else None
+        if see_through is not None:
+            st = self._seethrough_params(see_through)
+            ch = np.empty(out.shape[:2], CHAIN_DTYPE) if chains else None
+            self._check(self._L.rz_upscale_seethrough(
+                self._c, None if up is None else C.byref(up), C.byref(st), None if src is None else src.ctypes.data,
+                0 if src is None else src.nbytes, out.ctypes.data, out.nbytes, None if hh is None else hh.ctypes.data,
+                0 if hh is None else hh.nbytes, None if ch is None else ch.ctypes.data, 0 if ch is None else ch.nbytes,
+                _lib.UPSCALE_HOST), "rz_upscale_seethrough")
+            res = (out,) + ((hh,) if guides else ()) + ((ch,) if chains else ())
+            return res if len(res) > 1 else out
+        if chains:
+            raise ValueError("chains=True needs see_through")
         self._check(self._L.rz_upscale(self._c, None if up is None else C.byref(up), None if src is None else src.ctypes.data,
                                        0 if src is None else src.nbytes, out.ctypes.data, out.nbytes,
                                        None if hh is None else hh.ctypes.data, 0 if hh is None else hh.nbytes, _lib.UPSCALE_HOST),
@@ -751,24 +775,35 @@ class Renderer:
         return (out, hh) if guides else out
 
     def upscale_device(self, rgb_in_ptr=None, rgb32f_ptr=None, guides_ptr=None, factor=None, sigma_normal=None, sigma_plane=None,
-                       demodulate=None):
+                       demodulate=None, see_through=None, chains_ptr=None):
         """rz_upscale on device memory (guides 16-B aligned, rgb_in and rgb32f 4-B; each optional): enqueued on the context's
-        stream, asynchronous.  Sizes: rgb_in w*h*12 B, rgb32f W*H*12 B, guides W*H*48 B, with W x H = factor * (w x h)."""
+        stream, asynchronous.  Sizes: rgb_in w*h*12 B, rgb32f W*H*12 B, guides W*H*48 B, with W x H = factor * (w x h).
+        see_through = 0..8 (or True): rz_upscale_seethrough, with chains_ptr (W*H*16 B, 16-B aligned) optional."""
         up = self._upscale_params(factor, sigma_normal, sigma_plane, demodulate)
         s = _lib.UPSCALE_DEFAULTS["factor"] if up is None else up.factor
         n = self.width * self.height
         N = n * s * s
+        if see_through is not None:
+            st = self._seethrough_params(see_through)
+            self._check(self._L.rz_upscale_seethrough(
+                self._c, None if up is None else C.byref(up), C.byref(st), C.c_void_p(rgb_in_ptr), n * 12 if rgb_in_ptr else 0,
+                C.c_void_p(rgb32f_ptr), N * 12 if rgb32f_ptr else 0, C.c_void_p(guides_ptr), N * 48 if guides_ptr else 0,
+                C.c_void_p(chains_ptr), N * 16 if chains_ptr else 0, 0), "rz_upscale_seethrough")
+            return
+        if chains_ptr:
+            raise ValueError("chains_ptr needs see_through")
         self._check(self._L.rz_upscale(self._c, None if up is None else C.byref(up), C.c_void_p(rgb_in_ptr), n * 12 if rgb_in_ptr else 0,
                                        C.c_void_p(rgb32f_ptr), N * 12 if rgb32f_ptr else 0, C.c_void_p(guides_ptr),
                                        N * 48 if guides_ptr else 0, 0), "rz_upscale")
 
     def present_upscaled(self, source="accum", factor=None, sigma_normal=None, sigma_plane=None, demodulate=None, fps=0.0,
                          show_fps=True, show_lights=False, show_bvh=False, bvh_mode=0, selected_blas=0, selected_tri=0,
-                         filter=None, **params):
+                         filter=None, see_through=None, **params):
         """present_display() at display size: the colour of `source` (as present_display: the denoisers run at the low size
         w x h of the last set_frame) is upsampled by `factor`, then exposed, toned and encoded (params: as display()), and the
         overlays are drawn at the high size.  Returns (rgb float32 (H,W,3), rgba8 uint8 (H,W,4)) with H x W = factor * (h x w);
-        factor=1 gives present_display()'s bytes."""
+        factor=1 gives present_display()'s bytes.  see_through = 0..8 (or True): rz_present_upscaled_seethrough, the upscale with
+        guides that follow glass and perfect mirrors (the denoisers keep their first-hit guides)."""
         if source not in _lib.DISPLAY_SOURCES:
             raise ValueError(f"source = {source!r}: one of {sorted(_lib.DISPLAY_SOURCES)}")
         if source == "accum" and filter:
@@ -788,6 +823,13 @@ class Renderer:
             fp = self._temporal_params(dict(filter or {}))
         rgb = np.empty((max(s, 0) * self.height, max(s, 0) * self.width, 3), np.float32)
         rgba8 = np.empty(rgb.shape[:2] + (4,), np.uint8)
+        if see_through is not None:
+            st = self._seethrough_params(see_through)
+            self._check(self._L.rz_present_upscaled_seethrough(
+                self._c, C.byref(p), None if up is None else C.byref(up), C.byref(st), None if dp is None else C.byref(dp),
+                _lib.DISPLAY_SOURCES[source], fp, rgba8.ctypes.data, rgba8.nbytes, rgb.ctypes.data, rgb.nbytes),
+                "rz_present_upscaled_seethrough")
+            return rgb, rgba8
         self._check(self._L.rz_present_upscaled(self._c, C.byref(p), None if up is None else C.byref(up),
                                                 None if dp is None else C.byref(dp), _lib.DISPLAY_SOURCES[source], fp,
                                                 rgba8.ctypes.data, rgba8.nbytes, rgb.ctypes.data, rgb.nbytes), "rz_present_upscaled")
