@@ -765,6 +765,28 @@ int ensure_group_counter(rz_ctx* c) {
     return RZ_OK;
 }
 
+unsigned* backstop_word(const rz_ctx* c) { return static_cast<unsigned*>(c->dGroupCtr.p) + RZ_ERRWORD; }
+
+// Did a kernel run into one of its "cannot happen" bounds?  (rz_kernels.hip: rz_backstop)  Reads the word on the idle device
+// (the caller has just synchronised) and clears it when set.  No counter yet: nothing that can set it has run, no bits.
+int take_backstop(rz_ctx* c, unsigned& bits) {
+    bits = 0;
+    if (!c->dGroupCtr.p) return RZ_OK;
+    unsigned* w = backstop_word(c);
+    RZ_HIP(c, hipMemcpy(&bits, w, sizeof bits, hipMemcpyDeviceToHost));
+    if (bits != 0u) RZ_HIP(c, hipMemset(w, 0, sizeof bits));
+    return RZ_OK;
+}
+
+// a host-path call reads (and clears) the backstop word its launches may have set
+int report_backstop(rz_ctx* c, const char* what, const char* consequence) {
+    unsigned bits = 0;
+    const int rc = take_backstop(c, bits);
+    if (rc != RZ_OK) return rc;
+    if (bits != 0u) return fail(c, RZ_ERR_INTERNAL, "%s: a kernel reached a backstop (bits 0x%x): %s", what, bits, consequence);
+    return RZ_OK;
+}
+
 // The BLAS stack of a launch of one-wave workgroups (K.blasStackCap entries per lane needed).  LDS budget: the stack's LDS
 // window is cut to what keeps `wavesPerCu` waves on a CU beside `fixedLds` bytes of other LDS per wave; deeper entries go to
 // global overflow columns in `ovf`, which are indexed by resident workgroup and therefore only exist for persistent launches
@@ -804,6 +826,73 @@ void scene_kparams(const rz_ctx* c, KParams& K) {
     K.traceRoundCap = (int)std::min<long long>(0x7fffffff, tlas_index_count(c) + (long long)c->nTlasDfs + 64);
     K.regularBoxes = c->irregularBoxes ? 0 : 1;
 }
+
+// ... and of the camera, for the kernels that cast one ray per pixel outside the frame loop: the scene as finalize left it,
+// seen through this camera at this size.
+void camera_kparams(const rz_ctx* c, KParams& K, int width, int height, const float* inv_view, const float* inv_proj, const float* cam_pos) {
+    scene_kparams(c, K);
+    K.width = width; K.height = height;
+    std::memcpy(K.invView, inv_view, 64);
+    std::memcpy(K.invProj, inv_proj, 64);
+    std::memcpy(K.camPos, cam_pos, 12);
+}
+
+// What the guide casts share: the frame's camera at width x height, a wave per 64-pixel run of a row, the offsets and the word
+// cast_ready made, and the BLAS stack of the launch.
+template <class Launch>
+int cast_wiring(rz_ctx* c, int width, int height, KParams& K, Launch& G) {
+    const rz_frame_params& f = c->frame;
+    camera_kparams(c, K, width, height, f.inv_view, f.inv_proj, f.cam_pos);
+    G.unitsX = (width + 63) / 64;
+    G.units = (long long)G.unitsX * height;
+    G.grid = rays_grid(G.units * 64);
+    G.instTriOff = static_cast<const int32_t*>(c->dRayInstOff.p);
+    G.errWord = backstop_word(c);
+    return size_blas_stack(c, K, 0, RZ_RAYS_WAVES_PER_CU, G.grid, c->dRayOvf);
+}
+
+// Where a pass reads its input and writes its outputs.  On the device path the caller's pointers are device pointers: nothing
+// is staged and dev() hands them back.  Host buffers are staged through the ray-query buffers of the context: the input in
+// dRayIn; in dRayOut the outputs that were asked for (a null pointer: not asked), in the order they were added, each starting
+// on a 16-byte boundary.
+struct HostStage {
+    rz_ctx* c;
+    bool host;
+    struct { void* ptr; size_t bytes, off; } out[4] = {};
+    int n = 0;
+    size_t total = 0;
+    HostStage(rz_ctx* ctx, bool hostPath) : c(ctx), host(hostPath) {}
+    int add(void* ptr, size_t bytes) {          // returns the output's slot
+        out[n] = {ptr, bytes, (total + 15) & ~size_t(15)};
+        if (ptr) total = out[n].off + bytes;
+        return n++;
+    }
+    // copies a host input (if given) to dRayIn on the stream and points `dev` at it
+    template <class T>
+    int input(const T* src, size_t bytes, const T*& dev) {
+        if (!host || !src) return RZ_OK;
+        const int rc = ensure(c, c->dRayIn, bytes);
+        if (rc != RZ_OK) return rc;
+        RZ_HIP(c, hipMemcpyAsync(c->dRayIn.p, src, bytes, hipMemcpyHostToDevice, c->stream));
+        dev = static_cast<const T*>(c->dRayIn.p);
+        return RZ_OK;
+    }
+    int place() { return host && total ? ensure(c, c->dRayOut, total) : RZ_OK; }
+    // where the kernels write an output, after place(); null when it was not asked for
+    template <class T>
+    T* dev(int slot) const {
+        if (!host || !out[slot].ptr) return static_cast<T*>(out[slot].ptr);
+        return reinterpret_cast<T*>(static_cast<char*>(c->dRayOut.p) + out[slot].off);
+    }
+    // host path: copies the outputs back in the order they were added and waits for the stream
+    int fetch() {
+        const char* base = static_cast<const char*>(c->dRayOut.p);
+        for (int k = 0; k < n; ++k)
+            if (out[k].ptr) RZ_HIP(c, hipMemcpyAsync(out[k].ptr, base + out[k].off, out[k].bytes, hipMemcpyDeviceToHost, c->stream));
+        RZ_HIP(c, hipStreamSynchronize(c->stream));
+        return RZ_OK;
+    }
+};
 
 int render_samples(rz_ctx* c, KParams K, bool counted, int evSlot) {
     K.nSlots = K.nLocalTiles * 64;
@@ -2242,17 +2331,13 @@ int rz_sync(rz_ctx* c) {
     if (!c) return fail(nullptr, RZ_ERR_INVALID_ARG, "null context");
     return guarded(c, "rz_sync", [&]() -> int {
         RZ_HIP(c, hipStreamSynchronize(c->stream));
-        if (c->dGroupCtr.p) {       // did a kernel run into one of its "cannot happen" bounds?  (rz_kernels.hip: rz_backstop)
-            unsigned bits = 0;
-            unsigned* w = static_cast<unsigned*>(c->dGroupCtr.p) + RZ_ERRWORD;
-            RZ_HIP(c, hipMemcpy(&bits, w, sizeof bits, hipMemcpyDeviceToHost));
-            if (bits != 0u) {
-                RZ_HIP(c, hipMemset(w, 0, sizeof bits));
-                return fail(c, RZ_ERR_INTERNAL, "a render kernel reached a backstop (bits 0x%x:%s%s%s%s): pixels of the last frame(s) may be missing",
-                            bits, (bits & 1u) ? " claim without wait slots" : "", (bits & 2u) ? " pool did not drain" : "", (bits & 4u) ? " currentIor chains did not resolve" : "",
-                            (bits & RZ_BACKSTOP_RAYS) ? " a ray query's walk was cut short" : "");
-            }
-        }
+        unsigned bits = 0;
+        const int rc = take_backstop(c, bits);
+        if (rc != RZ_OK) return rc;
+        if (bits != 0u)
+            return fail(c, RZ_ERR_INTERNAL, "a render kernel reached a backstop (bits 0x%x:%s%s%s%s): pixels of the last frame(s) may be missing",
+                        bits, (bits & 1u) ? " claim without wait slots" : "", (bits & 2u) ? " pool did not drain" : "", (bits & 4u) ? " currentIor chains did not resolve" : "",
+                        (bits & RZ_BACKSTOP_RAYS) ? " a ray query's walk was cut short" : "");
         return RZ_OK;
     });
 }
@@ -2314,7 +2399,6 @@ static int present_impl(rz_ctx* c, const rz_present_params* pp, uint8_t* rgba8, 
     if (!c) return fail(nullptr, RZ_ERR_INVALID_ARG, "null context");
     if (!pp) return fail(c, RZ_ERR_INVALID_ARG, "null params");
     if (!c->haveFrame) return fail(c, RZ_ERR_NOT_READY, "rz_set_frame has not been called");
-    RZ_HIP(c, hipSetDevice(c->device));
     int rc = finalize(c);
     if (rc != RZ_OK) return rc;
     if (width <= 0 || height <= 0) { width = c->frame.width; height = c->frame.height; }
@@ -2415,6 +2499,60 @@ static int ensure_ray_inst_off(rz_ctx* c) {
     return RZ_OK;
 }
 
+// The steps the off-frame passes below share (HostStage, cast_wiring, camera_kparams and report_backstop sit beside
+// scene_kparams).  A new pass calls them in this order: its argument checks, in the order its header documents, with scene_ready,
+// accum_fits and present_sizes among them; the early return when no output is asked for; HostStage (add every output, input,
+// place); then finalize, cast_ready, its own ensure()s, guide_cast or a cast of its own wired by cast_wiring, and its kernels;
+// on the host path HostStage::fetch, and report_backstop if a ray was cast.
+
+// The scene a cast walks: all eight bindings uploaded and, for a pass that shades, at least one material.
+static int scene_ready(rz_ctx* c, const char* what, bool materials) {
+    for (int b : {RZ_BIND_TRIANGLES, RZ_BIND_MATERIALS, RZ_BIND_LIGHTS, RZ_BIND_TLAS_NODES, RZ_BIND_TLAS_INDICES,
+                  RZ_BIND_BLAS_NODES, RZ_BIND_BLAS_INDICES, RZ_BIND_INSTANCES})
+        if (!c->present[b]) return fail(c, RZ_ERR_NOT_READY, "%s: no scene (binding %d has not been uploaded)", what, b);
+    if (materials && hostCount<rz_material>(c, RZ_BIND_MATERIALS) == 0) return fail(c, RZ_ERR_NOT_READY, "%s: no materials", what);
+    return RZ_OK;
+}
+
+// A bound accumulation buffer (rz_bind_accum) must hold the frame a pass is about to read from it.
+static int accum_fits(rz_ctx* c, const char* what) {
+    const size_t need = (size_t)c->frame.width * c->frame.height * 16;
+    if (c->extAccum && c->extAccumBytes < need)
+        return fail(c, RZ_ERR_BUFFER_SIZE, "%s: bound accumulation buffer holds %zu bytes, frame needs %zu", what, c->extAccumBytes, need);
+    return RZ_OK;
+}
+
+// The buffer checks of the rz_present_* family: the accumulation at the frame's size, the outputs at `pixels` (the frame's, or
+// rz_present_upscaled's high size).
+static int present_sizes(rz_ctx* c, const char* what, size_t pixels, const uint8_t* rgba8, size_t rgba8_bytes, const float* rgb32f,
+                         size_t rgb32f_bytes) {
+    const int rc = accum_fits(c, what);
+    if (rc != RZ_OK) return rc;
+    if (rgba8 && rgba8_bytes < pixels * 4) return fail(c, RZ_ERR_BUFFER_SIZE, "%s: rgba8 buffer needs %zu bytes", what, pixels * 4);
+    if (rgb32f && rgb32f_bytes < pixels * 12) return fail(c, RZ_ERR_BUFFER_SIZE, "%s: rgb32f buffer needs %zu bytes", what, pixels * 12);
+    return RZ_OK;
+}
+
+// What every cast needs on the device besides the scene: the backstop word and the instances' triangle offsets.
+static int cast_ready(rz_ctx* c) {
+    const int rc = ensure_group_counter(c);         // (only its backstop word: the claim counter is the render's)
+    return rc != RZ_OK ? rc : ensure_ray_inst_off(c);
+}
+
+// One launch of rz_denoise's guide kernel at width x height with the frame's camera: the guide records, and the rz_hit records
+// when asked.
+static int guide_cast(rz_ctx* c, int width, int height, float4* guide, float4* hits) {
+    KParams K{};
+    DenoiseGuideLaunch G{};
+    const int rc = cast_wiring(c, width, height, K, G);
+    if (rc != RZ_OK) return rc;
+    G.guide = guide;
+    G.hits = hits;
+    launch_denoise_guides(K, G, c->stream);
+    RZ_HIP(c, hipGetLastError());
+    return RZ_OK;
+}
+
 // rz_trace_rays / rz_shadow_rays (rz_rays.hip).  The queries read the device scene as the last upload / update / transform
 // update left it (finalize), and nothing of the frame: no rz_set_frame needed, no render state touched.
 static int rays_impl(rz_ctx* c, const rz_ray* rays, void* out, size_t n, unsigned flags, bool shadow) {
@@ -2426,11 +2564,10 @@ static int rays_impl(rz_ctx* c, const rz_ray* rays, void* out, size_t n, unsigne
     const bool host = (flags & RZ_RAYS_HOST) != 0;
     if (!host && ((reinterpret_cast<uintptr_t>(rays) | reinterpret_cast<uintptr_t>(out)) & 15u))
         return fail(c, RZ_ERR_INVALID_ARG, "%s: device pointers must be 16-byte aligned", what);
-    for (int b : {RZ_BIND_TRIANGLES, RZ_BIND_MATERIALS, RZ_BIND_LIGHTS, RZ_BIND_TLAS_NODES, RZ_BIND_TLAS_INDICES,
-                  RZ_BIND_BLAS_NODES, RZ_BIND_BLAS_INDICES, RZ_BIND_INSTANCES})
-        if (!c->present[b]) return fail(c, RZ_ERR_NOT_READY, "%s: no scene (binding %d has not been uploaded)", what, b);
+    int rc = scene_ready(c, what, false);
+    if (rc != RZ_OK) return rc;
     if (n == 0) return RZ_OK;
-    int rc = finalize(c);
+    rc = finalize(c);
     if (rc != RZ_OK) return rc;
     KParams K{};
     scene_kparams(c, K);
@@ -2446,7 +2583,7 @@ static int rays_impl(rz_ctx* c, const rz_ray* rays, void* out, size_t n, unsigne
     R.shadow = shadow;
     R.spread = (flags & RZ_RAYS_INCOHERENT) != 0;
     R.instTriOff = static_cast<const int32_t*>(c->dRayInstOff.p);
-    R.errWord = static_cast<unsigned*>(c->dGroupCtr.p) + RZ_ERRWORD;
+    R.errWord = backstop_word(c);
     rc = size_blas_stack(c, K, 0, RZ_RAYS_WAVES_PER_CU, R.grid, c->dRayOvf);
     if (rc != RZ_OK) return rc;
     const size_t inBytes = n * sizeof(rz_ray), outBytes = n * (shadow ? sizeof(rz_visibility) : sizeof(rz_hit));
@@ -2466,14 +2603,7 @@ static int rays_impl(rz_ctx* c, const rz_ray* rays, void* out, size_t n, unsigne
     if (!host) return RZ_OK;
     RZ_HIP(c, hipMemcpyAsync(out, c->dRayOut.p, outBytes, hipMemcpyDeviceToHost, c->stream));
     RZ_HIP(c, hipStreamSynchronize(c->stream));
-    unsigned bits = 0;
-    unsigned* w = static_cast<unsigned*>(c->dGroupCtr.p) + RZ_ERRWORD;
-    RZ_HIP(c, hipMemcpy(&bits, w, sizeof bits, hipMemcpyDeviceToHost));
-    if (bits != 0u) {
-        RZ_HIP(c, hipMemset(w, 0, sizeof bits));
-        return fail(c, RZ_ERR_INTERNAL, "%s: a kernel reached a backstop (bits 0x%x): results may be wrong", what, bits);
-    }
-    return RZ_OK;
+    return report_backstop(c, what, "results may be wrong");
 }
 
 // rz_render_editor (rz_editor.hip).  Like the ray queries it reads the device scene as finalize left it and touches no render
@@ -2495,22 +2625,14 @@ static int editor_impl(rz_ctx* c, const rz_frame_params* f, const rz_editor_para
     if (rgba8 && rgba8_bytes < bRgba) return fail(c, RZ_ERR_BUFFER_SIZE, "%s: rgba8 needs %zu bytes, got %zu", what, bRgba, rgba8_bytes);
     if (rgb32f && rgb32f_bytes < bRgb) return fail(c, RZ_ERR_BUFFER_SIZE, "%s: rgb32f needs %zu bytes, got %zu", what, bRgb, rgb32f_bytes);
     if (hits && hits_bytes < bHits) return fail(c, RZ_ERR_BUFFER_SIZE, "%s: hits needs %zu bytes, got %zu", what, bHits, hits_bytes);
-    for (int b : {RZ_BIND_TRIANGLES, RZ_BIND_MATERIALS, RZ_BIND_LIGHTS, RZ_BIND_TLAS_NODES, RZ_BIND_TLAS_INDICES,
-                  RZ_BIND_BLAS_NODES, RZ_BIND_BLAS_INDICES, RZ_BIND_INSTANCES})
-        if (!c->present[b]) return fail(c, RZ_ERR_NOT_READY, "%s: no scene (binding %d has not been uploaded)", what, b);
-    if (hostCount<rz_material>(c, RZ_BIND_MATERIALS) == 0) return fail(c, RZ_ERR_NOT_READY, "%s: no materials", what);
-    int rc = finalize(c);
+    int rc = scene_ready(c, what, true);
+    if (rc != RZ_OK) return rc;
+    rc = finalize(c);
     if (rc != RZ_OK) return rc;
     KParams K{};
-    scene_kparams(c, K);
-    K.width = f->width; K.height = f->height;
+    camera_kparams(c, K, f->width, f->height, f->inv_view, f->inv_proj, f->cam_pos);
     K.nLights = std::max(0, std::min<int>(f->num_lights, (int)hostCount<rz_light>(c, RZ_BIND_LIGHTS)));
-    std::memcpy(K.invView, f->inv_view, 64);
-    std::memcpy(K.invProj, f->inv_proj, 64);
-    std::memcpy(K.camPos, f->cam_pos, 12);
-    rc = ensure_group_counter(c);           // (only its backstop word: the claim counter is the render's)
-    if (rc != RZ_OK) return rc;
-    rc = ensure_ray_inst_off(c);
+    rc = cast_ready(c);
     if (rc != RZ_OK) return rc;
     EditorLaunch E{};
     std::memcpy(E.view, f->view, 64);
@@ -2530,40 +2652,23 @@ static int editor_impl(rz_ctx* c, const rz_frame_params* f, const rz_editor_para
     E.grid = rays_grid(E.units * 64);
     E.spread = (flags & RZ_EDITOR_INCOHERENT) != 0;
     E.instTriOff = static_cast<const int32_t*>(c->dRayInstOff.p);
-    E.errWord = static_cast<unsigned*>(c->dGroupCtr.p) + RZ_ERRWORD;
+    E.errWord = backstop_word(c);
     rc = size_blas_stack(c, K, 0, RZ_RAYS_WAVES_PER_CU, E.grid, c->dRayOvf);
     if (rc != RZ_OK) return rc;
     // host outputs are staged through one buffer of the context: hits, then rgb32f, then rgba8 (each 16-byte aligned)
-    const size_t oHits = 0, oRgb = hits ? (bHits + 15) & ~size_t(15) : 0, oRgba = oRgb + (rgb32f ? (bRgb + 15) & ~size_t(15) : 0);
-    const size_t staged = oRgba + (rgba8 ? bRgba : 0);
-    if (host && staged) {
-        rc = ensure(c, c->dRayOut, staged);
-        if (rc != RZ_OK) return rc;
-        char* base = static_cast<char*>(c->dRayOut.p);
-        E.hits = hits ? reinterpret_cast<float4*>(base + oHits) : nullptr;
-        E.rgb32f = rgb32f ? reinterpret_cast<float*>(base + oRgb) : nullptr;
-        E.rgba8 = rgba8 ? reinterpret_cast<uchar4*>(base + oRgba) : nullptr;
-    } else if (!host) {
-        E.hits = reinterpret_cast<float4*>(hits);
-        E.rgb32f = rgb32f;
-        E.rgba8 = reinterpret_cast<uchar4*>(rgba8);
-    }
+    HostStage stage(c, host);
+    const int sHits = stage.add(hits, bHits), sRgb = stage.add(rgb32f, bRgb), sRgba = stage.add(rgba8, bRgba);
+    rc = stage.place();
+    if (rc != RZ_OK) return rc;
+    E.hits = stage.dev<float4>(sHits);
+    E.rgb32f = stage.dev<float>(sRgb);
+    E.rgba8 = stage.dev<uchar4>(sRgba);
     launch_editor(K, E, c->stream);
     RZ_HIP(c, hipGetLastError());
     if (!host) return RZ_OK;
-    const char* base = static_cast<const char*>(c->dRayOut.p);
-    if (hits) RZ_HIP(c, hipMemcpyAsync(hits, base + oHits, bHits, hipMemcpyDeviceToHost, c->stream));
-    if (rgb32f) RZ_HIP(c, hipMemcpyAsync(rgb32f, base + oRgb, bRgb, hipMemcpyDeviceToHost, c->stream));
-    if (rgba8) RZ_HIP(c, hipMemcpyAsync(rgba8, base + oRgba, bRgba, hipMemcpyDeviceToHost, c->stream));
-    RZ_HIP(c, hipStreamSynchronize(c->stream));
-    unsigned bits = 0;
-    unsigned* w = static_cast<unsigned*>(c->dGroupCtr.p) + RZ_ERRWORD;
-    RZ_HIP(c, hipMemcpy(&bits, w, sizeof bits, hipMemcpyDeviceToHost));
-    if (bits != 0u) {
-        RZ_HIP(c, hipMemset(w, 0, sizeof bits));
-        return fail(c, RZ_ERR_INTERNAL, "%s: a kernel reached a backstop (bits 0x%x): pixels may be wrong", what, bits);
-    }
-    return RZ_OK;
+    rc = stage.fetch();
+    if (rc != RZ_OK) return rc;
+    return report_backstop(c, what, "pixels may be wrong");
 }
 
 // rz_denoise / rz_present_denoised (rz_denoise.hip).  Like the ray queries they read the device scene as finalize left it;
@@ -2579,10 +2684,8 @@ static int denoise_check(rz_ctx* c, const char* what, const rz_denoise_params& P
     if (P.demodulate != 0 && P.demodulate != 1) return fail(c, RZ_ERR_INVALID_ARG, "%s: demodulate %d (0 or 1)", what, P.demodulate);
     if (P.reserved[0] || P.reserved[1] || P.reserved[2]) return fail(c, RZ_ERR_INVALID_ARG, "%s: reserved words must be 0", what);
     if (!c->haveFrame) return fail(c, RZ_ERR_NOT_READY, "%s: rz_set_frame has not been called", what);
-    for (int b : {RZ_BIND_TRIANGLES, RZ_BIND_MATERIALS, RZ_BIND_LIGHTS, RZ_BIND_TLAS_NODES, RZ_BIND_TLAS_INDICES,
-                  RZ_BIND_BLAS_NODES, RZ_BIND_BLAS_INDICES, RZ_BIND_INSTANCES})
-        if (!c->present[b]) return fail(c, RZ_ERR_NOT_READY, "%s: no scene (binding %d has not been uploaded)", what, b);
-    if (hostCount<rz_material>(c, RZ_BIND_MATERIALS) == 0) return fail(c, RZ_ERR_NOT_READY, "%s: no materials", what);
+    const int rc = scene_ready(c, what, true);
+    if (rc != RZ_OK) return rc;
     if (c->frame.tile_nranks > 1)
         return fail(c, RZ_ERR_INVALID_ARG, "%s: the frame is tile %d of %d; the filter needs the whole frame", what, c->frame.tile_rank, c->frame.tile_nranks);
     return RZ_OK;
@@ -2608,30 +2711,13 @@ static int denoise_run(rz_ctx* c, const rz_denoise_params& P, const float4* in, 
         RZ_HIP(c, hipGetLastError());
         if (!hits) return RZ_OK;
     }
-    KParams K{};
-    scene_kparams(c, K);
-    K.width = f.width; K.height = f.height;
-    std::memcpy(K.invView, f.inv_view, 64);
-    std::memcpy(K.invProj, f.inv_proj, 64);
-    std::memcpy(K.camPos, f.cam_pos, 12);
-    rc = ensure_group_counter(c);           // (only its backstop word: the claim counter is the render's)
-    if (rc != RZ_OK) return rc;
-    rc = ensure_ray_inst_off(c);
+    rc = cast_ready(c);
     if (rc != RZ_OK) return rc;
     rc = ensure(c, c->dDnGuide, np * 32);
     if (rc != RZ_OK) return rc;
-    DenoiseGuideLaunch G{};
-    G.unitsX = (f.width + 63) / 64;
-    G.units = (long long)G.unitsX * f.height;
-    G.grid = rays_grid(G.units * 64);
-    G.guide = static_cast<float4*>(c->dDnGuide.p);
-    G.hits = hits;
-    G.instTriOff = static_cast<const int32_t*>(c->dRayInstOff.p);
-    G.errWord = static_cast<unsigned*>(c->dGroupCtr.p) + RZ_ERRWORD;
-    rc = size_blas_stack(c, K, 0, RZ_RAYS_WAVES_PER_CU, G.grid, c->dRayOvf);
+    float4* guide = static_cast<float4*>(c->dDnGuide.p);
+    rc = guide_cast(c, f.width, f.height, guide, hits);
     if (rc != RZ_OK) return rc;
-    launch_denoise_guides(K, G, c->stream);
-    RZ_HIP(c, hipGetLastError());
     if ((!rgb && !out4) || P.iterations == 0) return RZ_OK;
     if (P.iterations > 1) {
         rc = ensure(c, c->dDnPing, np * 16);
@@ -2641,7 +2727,7 @@ static int denoise_run(rz_ctx* c, const rz_denoise_params& P, const float4* in, 
         rc = ensure(c, c->dDnPong, np * 16);
         if (rc != RZ_OK) return rc;
     }
-    D.guide = G.guide;
+    D.guide = guide;
     const double fpx = 2.0 * std::fabs((double)f.inv_proj[5]) / (double)f.height;     // world size of a pixel at unit distance
     float4* ping = static_cast<float4*>(c->dDnPing.p);
     float4* pong = static_cast<float4*>(c->dDnPong.p);
@@ -2661,19 +2747,6 @@ static int denoise_run(rz_ctx* c, const rz_denoise_params& P, const float4* in, 
     return RZ_OK;
 }
 
-// a host-path call reads (and clears) the backstop word its launches may have set
-static int denoise_backstop(rz_ctx* c, const char* what) {
-    if (!c->dGroupCtr.p) return RZ_OK;          // (nothing that can set it has run yet)
-    unsigned bits = 0;
-    unsigned* w = static_cast<unsigned*>(c->dGroupCtr.p) + RZ_ERRWORD;
-    RZ_HIP(c, hipMemcpy(&bits, w, sizeof bits, hipMemcpyDeviceToHost));
-    if (bits != 0u) {
-        RZ_HIP(c, hipMemset(w, 0, sizeof bits));
-        return fail(c, RZ_ERR_INTERNAL, "%s: a kernel reached a backstop (bits 0x%x): the guide may be wrong", what, bits);
-    }
-    return RZ_OK;
-}
-
 static int denoise_impl(rz_ctx* c, const rz_denoise_params* pp, const float* rgba_in, size_t rgba_in_bytes, float* rgb32f,
                         size_t rgb32f_bytes, rz_hit* guides, size_t guides_bytes, unsigned flags) {
     const char* what = "rz_denoise";
@@ -2688,38 +2761,26 @@ static int denoise_impl(rz_ctx* c, const rz_denoise_params* pp, const float* rgb
     const size_t np = (size_t)c->frame.width * c->frame.height;
     const size_t bIn = np * 16, bRgb = np * 3 * sizeof(float), bHits = np * sizeof(rz_hit);
     if (rgba_in && rgba_in_bytes < bIn) return fail(c, RZ_ERR_BUFFER_SIZE, "%s: rgba_in needs %zu bytes, got %zu", what, bIn, rgba_in_bytes);
-    if (!rgba_in && c->extAccum && c->extAccumBytes < bIn)
-        return fail(c, RZ_ERR_BUFFER_SIZE, "%s: bound accumulation buffer holds %zu bytes, frame needs %zu", what, c->extAccumBytes, bIn);
+    if (!rgba_in) {
+        rc = accum_fits(c, what);
+        if (rc != RZ_OK) return rc;
+    }
     if (rgb32f && rgb32f_bytes < bRgb) return fail(c, RZ_ERR_BUFFER_SIZE, "%s: rgb32f needs %zu bytes, got %zu", what, bRgb, rgb32f_bytes);
     if (guides && guides_bytes < bHits) return fail(c, RZ_ERR_BUFFER_SIZE, "%s: guides needs %zu bytes, got %zu", what, bHits, guides_bytes);
     if (!rgb32f && !guides) return RZ_OK;
-    RZ_HIP(c, hipSetDevice(c->device));
     const float4* in = rgba_in ? reinterpret_cast<const float4*>(rgba_in) : static_cast<const float4*>(rz_accum_device_ptr(c));
-    float* dRgb = rgb32f;
-    float4* dHits = reinterpret_cast<float4*>(guides);
     // host buffers are staged through the ray-query buffers of the context: the input in dRayIn; hits, then rgb32f in dRayOut
-    const size_t oRgb = guides ? (bHits + 15) & ~size_t(15) : 0;
-    if (host) {
-        if (rgba_in) {
-            rc = ensure(c, c->dRayIn, bIn);
-            if (rc != RZ_OK) return rc;
-            RZ_HIP(c, hipMemcpyAsync(c->dRayIn.p, rgba_in, bIn, hipMemcpyHostToDevice, c->stream));
-            in = static_cast<const float4*>(c->dRayIn.p);
-        }
-        rc = ensure(c, c->dRayOut, oRgb + (rgb32f ? bRgb : 0));
-        if (rc != RZ_OK) return rc;
-        char* base = static_cast<char*>(c->dRayOut.p);
-        dHits = guides ? reinterpret_cast<float4*>(base) : nullptr;
-        dRgb = rgb32f ? reinterpret_cast<float*>(base + oRgb) : nullptr;
-    }
-    rc = denoise_run(c, P, in, dRgb, nullptr, dHits);
+    HostStage stage(c, host);
+    const int sHits = stage.add(guides, bHits), sRgb = stage.add(rgb32f, bRgb);
+    rc = stage.input(reinterpret_cast<const float4*>(rgba_in), bIn, in);
+    if (rc == RZ_OK) rc = stage.place();
+    if (rc != RZ_OK) return rc;
+    rc = denoise_run(c, P, in, stage.dev<float>(sRgb), nullptr, stage.dev<float4>(sHits));
     if (rc != RZ_OK) return rc;
     if (!host) return RZ_OK;
-    const char* base = static_cast<const char*>(c->dRayOut.p);
-    if (guides) RZ_HIP(c, hipMemcpyAsync(guides, base, bHits, hipMemcpyDeviceToHost, c->stream));
-    if (rgb32f) RZ_HIP(c, hipMemcpyAsync(rgb32f, base + oRgb, bRgb, hipMemcpyDeviceToHost, c->stream));
-    RZ_HIP(c, hipStreamSynchronize(c->stream));
-    return denoise_backstop(c, what);
+    rc = stage.fetch();
+    if (rc != RZ_OK) return rc;
+    return report_backstop(c, what, "the guide may be wrong");
 }
 
 static int present_denoised_impl(rz_ctx* c, const rz_present_params* pp, const rz_denoise_params* dp, uint8_t* rgba8,
@@ -2731,11 +2792,8 @@ static int present_denoised_impl(rz_ctx* c, const rz_present_params* pp, const r
     int rc = denoise_check(c, what, P);
     if (rc != RZ_OK) return rc;
     const size_t np = (size_t)c->frame.width * c->frame.height;
-    if (c->extAccum && c->extAccumBytes < np * 16)
-        return fail(c, RZ_ERR_BUFFER_SIZE, "%s: bound accumulation buffer holds %zu bytes, frame needs %zu", what, c->extAccumBytes, np * 16);
-    if (rgba8 && rgba8_bytes < np * 4) return fail(c, RZ_ERR_BUFFER_SIZE, "%s: rgba8 buffer needs %zu bytes", what, np * 4);
-    if (rgb32f && rgb32f_bytes < np * 12) return fail(c, RZ_ERR_BUFFER_SIZE, "%s: rgb32f buffer needs %zu bytes", what, np * 12);
-    RZ_HIP(c, hipSetDevice(c->device));
+    rc = present_sizes(c, what, np, rgba8, rgba8_bytes, rgb32f, rgb32f_bytes);
+    if (rc != RZ_OK) return rc;
     rc = ensure(c, c->dDnOut, np * 16);
     if (rc != RZ_OK) return rc;
     float4* out4 = static_cast<float4*>(c->dDnOut.p);
@@ -2743,7 +2801,7 @@ static int present_denoised_impl(rz_ctx* c, const rz_present_params* pp, const r
     if (rc != RZ_OK) return rc;
     rc = present_impl(c, pp, rgba8, rgba8_bytes, rgb32f, rgb32f_bytes, out4);
     if (rc != RZ_OK) return rc;
-    return denoise_backstop(c, what);
+    return report_backstop(c, what, "the guide may be wrong");
 }
 
 // rz_denoise_temporal / rz_present_temporal (rz_temporal.hip).  They read what rz_denoise reads and touch no render state; the
@@ -2784,38 +2842,25 @@ static int temporal_run(rz_ctx* c, const rz_temporal_params& P, const float4* in
     const bool filter = (rgb || out4) && P.iterations > 0;
     if (rc == RZ_OK && filter) rc = ensure(c, c->dDnPong, np * 16);
     if (rc == RZ_OK && filter && P.iterations > 1) rc = ensure(c, c->dDnPing, np * 16);
-    if (rc == RZ_OK) rc = ensure_group_counter(c);          // (only its backstop word)
-    if (rc == RZ_OK) rc = ensure_ray_inst_off(c);
+    if (rc == RZ_OK) rc = cast_ready(c);
     if (rc != RZ_OK) return rc;
     // the guide: rz_denoise's kernel, its rz_hit records straight into the history being written
-    KParams K{};
-    scene_kparams(c, K);
-    K.width = f.width; K.height = f.height;
-    std::memcpy(K.invView, f.inv_view, 64);
-    std::memcpy(K.invProj, f.inv_proj, 64);
-    std::memcpy(K.camPos, f.cam_pos, 12);
-    DenoiseGuideLaunch G{};
-    G.unitsX = (f.width + 63) / 64;
-    G.units = (long long)G.unitsX * f.height;
-    G.grid = rays_grid(G.units * 64);
-    G.guide = static_cast<float4*>(c->dDnGuide.p);
-    G.hits = static_cast<float4*>(c->dTmpHits[nxt].p);
-    G.instTriOff = static_cast<const int32_t*>(c->dRayInstOff.p);
-    G.errWord = static_cast<unsigned*>(c->dGroupCtr.p) + RZ_ERRWORD;
-    rc = size_blas_stack(c, K, 0, RZ_RAYS_WAVES_PER_CU, G.grid, c->dRayOvf);
+    float4* guide = static_cast<float4*>(c->dDnGuide.p);
+    float4* hitsNext = static_cast<float4*>(c->dTmpHits[nxt].p);
+    rc = guide_cast(c, f.width, f.height, guide, hitsNext);
     if (rc != RZ_OK) return rc;
-    launch_denoise_guides(K, G, c->stream);
-    RZ_HIP(c, hipGetLastError());
-    if (hits) RZ_HIP(c, hipMemcpyAsync(hits, G.hits, np * sizeof(rz_hit), hipMemcpyDeviceToDevice, c->stream));
-    launch_temporal_instances(K.instances, static_cast<const float*>(c->dTmpInst[cur].p), static_cast<float*>(c->dTmpInst[nxt].p),
+    const DevInstance* instances = static_cast<const DevInstance*>(c->dInst.p);
+    const DevMaterial* materials = static_cast<const DevMaterial*>(c->dMat.p);
+    if (hits) RZ_HIP(c, hipMemcpyAsync(hits, hitsNext, np * sizeof(rz_hit), hipMemcpyDeviceToDevice, c->stream));
+    launch_temporal_instances(instances, static_cast<const float*>(c->dTmpInst[cur].p), static_cast<float*>(c->dTmpInst[nxt].p),
                               static_cast<int*>(c->dTmpSame.p), (int)nInst, havePrev, c->stream);
     RZ_HIP(c, hipGetLastError());
     const double fpx = 2.0 * std::fabs((double)f.inv_proj[5]) / (double)f.height;
     TemporalLaunch T{};
     T.accum = in;
-    T.hits = G.hits;
-    T.materials = K.materials;
-    T.instances = K.instances;
+    T.hits = hitsNext;
+    T.materials = materials;
+    T.instances = instances;
     T.colPrev = static_cast<const float4*>(c->dTmpCol[cur].p);
     T.momPrev = static_cast<const float2*>(c->dTmpMom[cur].p);
     T.hitsPrev = static_cast<const float4*>(c->dTmpHits[cur].p);
@@ -2826,7 +2871,7 @@ static int temporal_run(rz_ctx* c, const rz_temporal_params& P, const float4* in
     T.dst = P.iterations == 0 ? out4 : nullptr;
     T.rgb = P.iterations == 0 ? rgb : nullptr;
     T.width = f.width; T.height = f.height;
-    T.nMaterials = K.nMaterials;
+    T.nMaterials = (int)hostCount<rz_material>(c, RZ_BIND_MATERIALS);
     T.demodulate = P.demodulate;
     T.havePrev = havePrev ? 1 : 0;
     T.cameraSame = havePrev && std::memcmp(c->tmpView, f.view, 64) == 0 && std::memcmp(c->tmpProj, f.proj, 64) == 0;
@@ -2844,7 +2889,7 @@ static int temporal_run(rz_ctx* c, const rz_temporal_params& P, const float4* in
         TemporalVarLaunch V{};
         V.col = T.colNext;
         V.mom = T.momNext;
-        V.guide = G.guide;
+        V.guide = guide;
         V.dst = filter ? static_cast<float4*>(c->dDnPong.p) : nullptr;
         V.stats = stats;
         V.width = f.width; V.height = f.height;
@@ -2855,8 +2900,8 @@ static int temporal_run(rz_ctx* c, const rz_temporal_params& P, const float4* in
     }
     if (filter) {
         TemporalFilterLaunch F{};
-        F.guide = G.guide;
-        F.materials = K.materials;
+        F.guide = guide;
+        F.materials = materials;
         F.width = f.width; F.height = f.height;
         F.sigmaL = P.sigma_l;
         F.sigmaNormal = P.sigma_normal;
@@ -2901,42 +2946,27 @@ static int temporal_impl(rz_ctx* c, const rz_temporal_params* pp, const float* r
     const size_t np = (size_t)c->frame.width * c->frame.height;
     const size_t bIn = np * 16, bRgb = np * 3 * sizeof(float), bHits = np * sizeof(rz_hit), bStats = np * 2 * sizeof(float);
     if (rgba_in && rgba_in_bytes < bIn) return fail(c, RZ_ERR_BUFFER_SIZE, "%s: rgba_in needs %zu bytes, got %zu", what, bIn, rgba_in_bytes);
-    if (!rgba_in && c->extAccum && c->extAccumBytes < bIn)
-        return fail(c, RZ_ERR_BUFFER_SIZE, "%s: bound accumulation buffer holds %zu bytes, frame needs %zu", what, c->extAccumBytes, bIn);
+    if (!rgba_in) {
+        rc = accum_fits(c, what);
+        if (rc != RZ_OK) return rc;
+    }
     if (rgb32f && rgb32f_bytes < bRgb) return fail(c, RZ_ERR_BUFFER_SIZE, "%s: rgb32f needs %zu bytes, got %zu", what, bRgb, rgb32f_bytes);
     if (guides && guides_bytes < bHits) return fail(c, RZ_ERR_BUFFER_SIZE, "%s: guides needs %zu bytes, got %zu", what, bHits, guides_bytes);
     if (stats && stats_bytes < bStats) return fail(c, RZ_ERR_BUFFER_SIZE, "%s: stats needs %zu bytes, got %zu", what, bStats, stats_bytes);
-    RZ_HIP(c, hipSetDevice(c->device));
     const float4* in = rgba_in ? reinterpret_cast<const float4*>(rgba_in) : static_cast<const float4*>(rz_accum_device_ptr(c));
-    float* dRgb = rgb32f;
-    float* dStats = stats;
-    float4* dHits = reinterpret_cast<float4*>(guides);
     // host buffers are staged as rz_denoise stages them: the input in dRayIn; hits, rgb32f, then stats in dRayOut
-    const size_t oRgb = guides ? (bHits + 15) & ~size_t(15) : 0;
-    const size_t oStats = oRgb + (rgb32f ? (bRgb + 15) & ~size_t(15) : 0);
-    if (host) {
-        if (rgba_in) {
-            rc = ensure(c, c->dRayIn, bIn);
-            if (rc != RZ_OK) return rc;
-            RZ_HIP(c, hipMemcpyAsync(c->dRayIn.p, rgba_in, bIn, hipMemcpyHostToDevice, c->stream));
-            in = static_cast<const float4*>(c->dRayIn.p);
-        }
-        rc = ensure(c, c->dRayOut, oStats + (stats ? bStats : 0));
-        if (rc != RZ_OK) return rc;
-        char* base = static_cast<char*>(c->dRayOut.p);
-        dHits = guides ? reinterpret_cast<float4*>(base) : nullptr;
-        dRgb = rgb32f ? reinterpret_cast<float*>(base + oRgb) : nullptr;
-        dStats = stats ? reinterpret_cast<float*>(base + oStats) : nullptr;
-    }
-    rc = temporal_run(c, P, in, dRgb, nullptr, dHits, dStats, (flags & RZ_TEMPORAL_KEEP) != 0);
+    HostStage stage(c, host);
+    const int sHits = stage.add(guides, bHits), sRgb = stage.add(rgb32f, bRgb), sStats = stage.add(stats, bStats);
+    rc = stage.input(reinterpret_cast<const float4*>(rgba_in), bIn, in);
+    if (rc == RZ_OK) rc = stage.place();
+    if (rc != RZ_OK) return rc;
+    rc = temporal_run(c, P, in, stage.dev<float>(sRgb), nullptr, stage.dev<float4>(sHits), stage.dev<float>(sStats),
+                      (flags & RZ_TEMPORAL_KEEP) != 0);
     if (rc != RZ_OK) return rc;
     if (!host) return RZ_OK;
-    const char* base = static_cast<const char*>(c->dRayOut.p);
-    if (guides) RZ_HIP(c, hipMemcpyAsync(guides, base, bHits, hipMemcpyDeviceToHost, c->stream));
-    if (rgb32f) RZ_HIP(c, hipMemcpyAsync(rgb32f, base + oRgb, bRgb, hipMemcpyDeviceToHost, c->stream));
-    if (stats) RZ_HIP(c, hipMemcpyAsync(stats, base + oStats, bStats, hipMemcpyDeviceToHost, c->stream));
-    RZ_HIP(c, hipStreamSynchronize(c->stream));
-    return denoise_backstop(c, what);
+    rc = stage.fetch();
+    if (rc != RZ_OK) return rc;
+    return report_backstop(c, what, "the guide may be wrong");
 }
 
 static int present_temporal_impl(rz_ctx* c, const rz_present_params* pp, const rz_temporal_params* tp, uint8_t* rgba8,
@@ -2948,11 +2978,8 @@ static int present_temporal_impl(rz_ctx* c, const rz_present_params* pp, const r
     int rc = temporal_check(c, what, P);
     if (rc != RZ_OK) return rc;
     const size_t np = (size_t)c->frame.width * c->frame.height;
-    if (c->extAccum && c->extAccumBytes < np * 16)
-        return fail(c, RZ_ERR_BUFFER_SIZE, "%s: bound accumulation buffer holds %zu bytes, frame needs %zu", what, c->extAccumBytes, np * 16);
-    if (rgba8 && rgba8_bytes < np * 4) return fail(c, RZ_ERR_BUFFER_SIZE, "%s: rgba8 buffer needs %zu bytes", what, np * 4);
-    if (rgb32f && rgb32f_bytes < np * 12) return fail(c, RZ_ERR_BUFFER_SIZE, "%s: rgb32f buffer needs %zu bytes", what, np * 12);
-    RZ_HIP(c, hipSetDevice(c->device));
+    rc = present_sizes(c, what, np, rgba8, rgba8_bytes, rgb32f, rgb32f_bytes);
+    if (rc != RZ_OK) return rc;
     rc = ensure(c, c->dDnOut, np * 16);
     if (rc != RZ_OK) return rc;
     float4* out4 = static_cast<float4*>(c->dDnOut.p);
@@ -2960,7 +2987,7 @@ static int present_temporal_impl(rz_ctx* c, const rz_present_params* pp, const r
     if (rc != RZ_OK) return rc;
     rc = present_impl(c, pp, rgba8, rgba8_bytes, rgb32f, rgb32f_bytes, out4);
     if (rc != RZ_OK) return rc;
-    return denoise_backstop(c, what);
+    return report_backstop(c, what, "the guide may be wrong");
 }
 
 // rz_display / rz_present_display (rz_display.hip).  Of the frame they read the size only; they need no scene (rz_present_display
@@ -3054,37 +3081,51 @@ static int display_impl(rz_ctx* c, const rz_display_params* pp, const float* rgb
     const size_t np = (size_t)c->frame.width * c->frame.height;
     const size_t bRgb = np * 3 * sizeof(float), bRgba8 = np * 4;
     if (rgb_in && rgb_in_bytes < bRgb) return fail(c, RZ_ERR_BUFFER_SIZE, "%s: rgb_in needs %zu bytes, got %zu", what, bRgb, rgb_in_bytes);
-    if (!rgb_in && c->extAccum && c->extAccumBytes < np * 16)
-        return fail(c, RZ_ERR_BUFFER_SIZE, "%s: bound accumulation buffer holds %zu bytes, frame needs %zu", what, c->extAccumBytes, np * 16);
+    if (!rgb_in) {
+        rc = accum_fits(c, what);
+        if (rc != RZ_OK) return rc;
+    }
     if (rgb32f && rgb32f_bytes < bRgb) return fail(c, RZ_ERR_BUFFER_SIZE, "%s: rgb32f needs %zu bytes, got %zu", what, bRgb, rgb32f_bytes);
     if (rgba8 && rgba8_bytes < bRgba8) return fail(c, RZ_ERR_BUFFER_SIZE, "%s: rgba8 needs %zu bytes, got %zu", what, bRgba8, rgba8_bytes);
-    RZ_HIP(c, hipSetDevice(c->device));
     const float* in = rgb_in;
     const float4* in4 = rgb_in ? nullptr : static_cast<const float4*>(rz_accum_device_ptr(c));
-    float* dRgb = rgb32f;
-    uchar4* dRgba8 = reinterpret_cast<uchar4*>(rgba8);
     // host buffers are staged as rz_denoise stages them: the input in dRayIn; rgb32f, then rgba8 in dRayOut
-    const size_t oRgba8 = rgb32f ? (bRgb + 15) & ~size_t(15) : 0;
-    if (host) {
-        if (rgb_in) {
-            rc = ensure(c, c->dRayIn, bRgb);
-            if (rc != RZ_OK) return rc;
-            RZ_HIP(c, hipMemcpyAsync(c->dRayIn.p, rgb_in, bRgb, hipMemcpyHostToDevice, c->stream));
-            in = static_cast<const float*>(c->dRayIn.p);
-        }
-        rc = ensure(c, c->dRayOut, oRgba8 + (rgba8 ? bRgba8 : 0));
-        if (rc != RZ_OK) return rc;
-        char* base = static_cast<char*>(c->dRayOut.p);
-        dRgb = rgb32f ? reinterpret_cast<float*>(base) : nullptr;
-        dRgba8 = rgba8 ? reinterpret_cast<uchar4*>(base + oRgba8) : nullptr;
-    }
-    rc = display_run(c, P, in, in4, dRgb, dRgba8, nullptr, (flags & RZ_DISPLAY_KEEP) != 0);
+    HostStage stage(c, host);
+    const int sRgb = stage.add(rgb32f, bRgb), sRgba8 = stage.add(rgba8, bRgba8);
+    rc = stage.input(rgb_in, bRgb, in);
+    if (rc == RZ_OK) rc = stage.place();
+    if (rc != RZ_OK) return rc;
+    rc = display_run(c, P, in, in4, stage.dev<float>(sRgb), stage.dev<uchar4>(sRgba8), nullptr, (flags & RZ_DISPLAY_KEEP) != 0);
     if (rc != RZ_OK) return rc;
     if (!host) return RZ_OK;
-    const char* base = static_cast<const char*>(c->dRayOut.p);
-    if (rgb32f) RZ_HIP(c, hipMemcpyAsync(rgb32f, base, bRgb, hipMemcpyDeviceToHost, c->stream));
-    if (rgba8) RZ_HIP(c, hipMemcpyAsync(rgba8, base + oRgba8, bRgba8, hipMemcpyDeviceToHost, c->stream));
-    RZ_HIP(c, hipStreamSynchronize(c->stream));
+    return stage.fetch();
+}
+
+// What rz_present_display and rz_present_upscaled tone: (source, filter_params) as given, the filter's defaults filled in.
+struct FilterSource {
+    int source = 0;         // 0 accumulation, 1 rz_denoise, 2 rz_denoise_temporal
+    rz_denoise_params P1 = kDenoiseDefaults;
+    rz_temporal_params P2 = kTemporalDefaults;
+};
+
+// The checks both calls open with, in the order their header documents: the source, the display parameters, the filter's own.
+static int source_check(rz_ctx* c, const char* what, int source, const void* filter_params, const rz_display_params& D, FilterSource& F) {
+    if (source < 0 || source > 2) return fail(c, RZ_ERR_INVALID_ARG, "%s: source %d (0 accumulation, 1 rz_denoise, 2 rz_denoise_temporal)", what, source);
+    if (source == 0 && filter_params) return fail(c, RZ_ERR_INVALID_ARG, "%s: filter_params must be NULL for source 0", what);
+    int rc = display_check(c, what, D);
+    if (rc != RZ_OK) return rc;
+    F.source = source;
+    if (source == 1 && filter_params) F.P1 = *static_cast<const rz_denoise_params*>(filter_params);
+    if (source == 2 && filter_params) F.P2 = *static_cast<const rz_temporal_params*>(filter_params);
+    if (source == 1) rc = denoise_check(c, what, F.P1);
+    if (source == 2) rc = temporal_check(c, what, F.P2);
+    return rc;
+}
+
+// Sources 1 and 2 filter `accum` (at the frame's size) into out4 as (colour, 1); source 0 runs nothing.
+static int source_run(rz_ctx* c, const FilterSource& F, const float4* accum, float4* out4) {
+    if (F.source == 1) return denoise_run(c, F.P1, accum, nullptr, out4, nullptr);
+    if (F.source == 2) return temporal_run(c, F.P2, accum, nullptr, out4, nullptr, nullptr, false);
     return RZ_OK;
 }
 
@@ -3093,37 +3134,27 @@ static int present_display_impl(rz_ctx* c, const rz_present_params* pp, const rz
     const char* what = "rz_present_display";
     if (!c) return fail(nullptr, RZ_ERR_INVALID_ARG, "%s: null context", what);
     if (!pp) return fail(c, RZ_ERR_INVALID_ARG, "%s: null present params", what);
-    if (source < 0 || source > 2) return fail(c, RZ_ERR_INVALID_ARG, "%s: source %d (0 accumulation, 1 rz_denoise, 2 rz_denoise_temporal)", what, source);
-    if (source == 0 && filter_params) return fail(c, RZ_ERR_INVALID_ARG, "%s: filter_params must be NULL for source 0", what);
     const rz_display_params& D = dp ? *dp : kDisplayDefaults;
-    int rc = display_check(c, what, D);
-    if (rc != RZ_OK) return rc;
-    const rz_denoise_params& P1 = (source == 1 && filter_params) ? *static_cast<const rz_denoise_params*>(filter_params) : kDenoiseDefaults;
-    const rz_temporal_params& P2 = (source == 2 && filter_params) ? *static_cast<const rz_temporal_params*>(filter_params) : kTemporalDefaults;
-    if (source == 1) rc = denoise_check(c, what, P1);
-    if (source == 2) rc = temporal_check(c, what, P2);
+    FilterSource F;
+    int rc = source_check(c, what, source, filter_params, D, F);
     if (rc != RZ_OK) return rc;
     if (source == 0 && D.exposure_mode == 1 && c->frame.tile_nranks > 1)
         return fail(c, RZ_ERR_INVALID_ARG, "%s: the frame is tile %d of %d; metering needs the whole frame", what, c->frame.tile_rank, c->frame.tile_nranks);
     const size_t np = (size_t)c->frame.width * c->frame.height;
-    if (c->extAccum && c->extAccumBytes < np * 16)
-        return fail(c, RZ_ERR_BUFFER_SIZE, "%s: bound accumulation buffer holds %zu bytes, frame needs %zu", what, c->extAccumBytes, np * 16);
-    if (rgba8 && rgba8_bytes < np * 4) return fail(c, RZ_ERR_BUFFER_SIZE, "%s: rgba8 buffer needs %zu bytes", what, np * 4);
-    if (rgb32f && rgb32f_bytes < np * 12) return fail(c, RZ_ERR_BUFFER_SIZE, "%s: rgb32f buffer needs %zu bytes", what, np * 12);
-    RZ_HIP(c, hipSetDevice(c->device));
+    rc = present_sizes(c, what, np, rgba8, rgba8_bytes, rgb32f, rgb32f_bytes);
+    if (rc != RZ_OK) return rc;
     rc = ensure(c, c->dDnOut, np * 16);
     if (rc != RZ_OK) return rc;
     float4* out4 = static_cast<float4*>(c->dDnOut.p);
     const float4* accum = static_cast<const float4*>(rz_accum_device_ptr(c));
     // sources 1 and 2 leave (colour, 1) in out4, which the tone kernel then rewrites in place: (colour, 1) resolves to colour
-    if (source == 1) rc = denoise_run(c, P1, accum, nullptr, out4, nullptr);
-    if (source == 2) rc = temporal_run(c, P2, accum, nullptr, out4, nullptr, nullptr, false);
+    rc = source_run(c, F, accum, out4);
     if (rc != RZ_OK) return rc;
     rc = display_run(c, D, nullptr, source == 0 ? accum : out4, nullptr, nullptr, out4, false);
     if (rc != RZ_OK) return rc;
     rc = present_impl(c, pp, rgba8, rgba8_bytes, rgb32f, rgb32f_bytes, out4);
     if (rc != RZ_OK) return rc;
-    return source == 0 ? RZ_OK : denoise_backstop(c, what);
+    return source == 0 ? RZ_OK : report_backstop(c, what, "the guide may be wrong");
 }
 
 // rz_upscale / rz_present_upscaled (rz_upscale.hip).  The frame rz_set_frame set is the LOW one; they read its size and camera,
@@ -3142,31 +3173,6 @@ static int upscale_check(rz_ctx* c, const char* what, const rz_upscale_params& P
     return RZ_OK;
 }
 
-// One launch of rz_denoise's guide kernel at width x height with the frame's camera: the guide records, and the rz_hit records
-// when asked.
-static int upscale_cast(rz_ctx* c, int width, int height, float4* guide, float4* hits) {
-    const rz_frame_params& f = c->frame;
-    KParams K{};
-    scene_kparams(c, K);
-    K.width = width; K.height = height;
-    std::memcpy(K.invView, f.inv_view, 64);
-    std::memcpy(K.invProj, f.inv_proj, 64);
-    std::memcpy(K.camPos, f.cam_pos, 12);
-    DenoiseGuideLaunch G{};
-    G.unitsX = (width + 63) / 64;
-    G.units = (long long)G.unitsX * height;
-    G.grid = rays_grid(G.units * 64);
-    G.guide = guide;
-    G.hits = hits;
-    G.instTriOff = static_cast<const int32_t*>(c->dRayInstOff.p);
-    G.errWord = static_cast<unsigned*>(c->dGroupCtr.p) + RZ_ERRWORD;
-    const int rc = size_blas_stack(c, K, 0, RZ_RAYS_WAVES_PER_CU, G.grid, c->dRayOvf);
-    if (rc != RZ_OK) return rc;
-    launch_denoise_guides(K, G, c->stream);
-    RZ_HIP(c, hipGetLastError());
-    return RZ_OK;
-}
-
 // rz_upscale_seethrough / rz_present_upscaled_seethrough (rz_seethrough.hip): the same calls with the guide cast along the
 // pixel's deterministic chain.  `st` below is null for the first-hit entry points, whose launches and buffers are unchanged.
 static const rz_seethrough_params kSeethroughDefaults = {8, {0, 0, 0, 0, 0, 0, 0}};
@@ -3181,25 +3187,14 @@ static int seethrough_check(rz_ctx* c, const char* what, const rz_seethrough_par
 // One launch of rz_seethrough_guides at width x height with the frame's camera: the 48-B records, and the rz_hit and rz_chain
 // records when asked.
 static int seethrough_cast(rz_ctx* c, int width, int height, int maxDepth, float4* rec, float4* hits, float4* chains) {
-    const rz_frame_params& f = c->frame;
     KParams K{};
-    scene_kparams(c, K);
-    K.width = width; K.height = height;
-    std::memcpy(K.invView, f.inv_view, 64);
-    std::memcpy(K.invProj, f.inv_proj, 64);
-    std::memcpy(K.camPos, f.cam_pos, 12);
     SeethroughGuideLaunch G{};
-    G.unitsX = (width + 63) / 64;
-    G.units = (long long)G.unitsX * height;
-    G.grid = rays_grid(G.units * 64);
+    const int rc = cast_wiring(c, width, height, K, G);
+    if (rc != RZ_OK) return rc;
     G.maxDepth = maxDepth;
     G.rec = rec;
     G.hits = hits;
     G.chains = chains;
-    G.instTriOff = static_cast<const int32_t*>(c->dRayInstOff.p);
-    G.errWord = static_cast<unsigned*>(c->dGroupCtr.p) + RZ_ERRWORD;
-    const int rc = size_blas_stack(c, K, 0, RZ_RAYS_WAVES_PER_CU, G.grid, c->dRayOvf);
-    if (rc != RZ_OK) return rc;
     launch_seethrough_guides(K, G, c->stream);
     RZ_HIP(c, hipGetLastError());
     return RZ_OK;
@@ -3214,9 +3209,7 @@ static int upscale_run(rz_ctx* c, const rz_upscale_params& P, const float* in3, 
     const int W = f.width * P.factor, H = f.height * P.factor;
     int rc = finalize(c);
     if (rc != RZ_OK) return rc;
-    rc = ensure_group_counter(c);           // (only its backstop word: the claim counter is the render's)
-    if (rc != RZ_OK) return rc;
-    rc = ensure_ray_inst_off(c);
+    rc = cast_ready(c);
     if (rc != RZ_OK) return rc;
     DevBuf& bufHi = st ? c->dStGuideHi : c->dUpGuideHi;
     DevBuf& bufLo = st ? c->dStGuideLo : c->dUpGuideLo;
@@ -3229,11 +3222,11 @@ static int upscale_run(rz_ctx* c, const rz_upscale_params& P, const float* in3, 
     }
     // the high cast first: its overflow columns (size_blas_stack) are the larger ones, so the low cast finds them in place
     rc = st ? seethrough_cast(c, W, H, st->max_depth, static_cast<float4*>(bufHi.p), hits, chains)
-            : upscale_cast(c, W, H, static_cast<float4*>(bufHi.p), hits);
+            : guide_cast(c, W, H, static_cast<float4*>(bufHi.p), hits);
     if (rc != RZ_OK) return rc;
     if (!rgb && !out4) return RZ_OK;
     rc = st ? seethrough_cast(c, f.width, f.height, st->max_depth, static_cast<float4*>(bufLo.p), nullptr, nullptr)
-            : upscale_cast(c, f.width, f.height, static_cast<float4*>(bufLo.p), nullptr);
+            : guide_cast(c, f.width, f.height, static_cast<float4*>(bufLo.p), nullptr);
     if (rc != RZ_OK) return rc;
     UpscaleLaunch U{};
     U.in3 = in4 ? nullptr : in3;
@@ -3276,35 +3269,25 @@ static int upscale_impl(rz_ctx* c, const rz_upscale_params* pp, const float* rgb
     const size_t np = (size_t)c->frame.width * c->frame.height, nP = np * P.factor * P.factor;
     const size_t bIn = np * 3 * sizeof(float), bRgb = nP * 3 * sizeof(float), bHits = nP * sizeof(rz_hit), bChains = nP * sizeof(rz_chain);
     if (rgb_in && rgb_in_bytes < bIn) return fail(c, RZ_ERR_BUFFER_SIZE, "%s: rgb_in needs %zu bytes, got %zu", what, bIn, rgb_in_bytes);
-    if (!rgb_in && c->extAccum && c->extAccumBytes < np * 16)
-        return fail(c, RZ_ERR_BUFFER_SIZE, "%s: bound accumulation buffer holds %zu bytes, frame needs %zu", what, c->extAccumBytes, np * 16);
+    if (!rgb_in) {
+        rc = accum_fits(c, what);
+        if (rc != RZ_OK) return rc;
+    }
     if (rgb32f && rgb32f_bytes < bRgb) return fail(c, RZ_ERR_BUFFER_SIZE, "%s: rgb32f needs %zu bytes, got %zu", what, bRgb, rgb32f_bytes);
     if (guides && guides_bytes < bHits) return fail(c, RZ_ERR_BUFFER_SIZE, "%s: guides needs %zu bytes, got %zu", what, bHits, guides_bytes);
     if (chains && chains_bytes < bChains) return fail(c, RZ_ERR_BUFFER_SIZE, "%s: chains needs %zu bytes, got %zu", what, bChains, chains_bytes);
     if (!rgb32f && !guides && !chains) return RZ_OK;
-    RZ_HIP(c, hipSetDevice(c->device));
     const float* in3 = rgb_in;
     const float4* in4 = rgb_in ? nullptr : static_cast<const float4*>(rz_accum_device_ptr(c));
-    float* dRgb = rgb32f;
-    float4* dHits = reinterpret_cast<float4*>(guides);
-    float4* dChains = reinterpret_cast<float4*>(chains);
     // host buffers are staged as rz_denoise stages them: the input in dRayIn; hits, then chains, then rgb32f in dRayOut
-    const size_t oChains = guides ? (bHits + 15) & ~size_t(15) : 0;
-    const size_t oRgb = oChains + (chains ? bChains : 0);
-    if (host) {
-        if (rgb_in) {
-            rc = ensure(c, c->dRayIn, bIn);
-            if (rc != RZ_OK) return rc;
-            RZ_HIP(c, hipMemcpyAsync(c->dRayIn.p, rgb_in, bIn, hipMemcpyHostToDevice, c->stream));
-            in3 = static_cast<const float*>(c->dRayIn.p);
-        }
-        rc = ensure(c, c->dRayOut, oRgb + (rgb32f ? bRgb : 0));
-        if (rc != RZ_OK) return rc;
-        char* base = static_cast<char*>(c->dRayOut.p);
-        dHits = guides ? reinterpret_cast<float4*>(base) : nullptr;
-        dChains = chains ? reinterpret_cast<float4*>(base + oChains) : nullptr;
-        dRgb = rgb32f ? reinterpret_cast<float*>(base + oRgb) : nullptr;
-    }
+    HostStage stage(c, host);
+    const int sHits = stage.add(guides, bHits), sChains = stage.add(chains, bChains), sRgb = stage.add(rgb32f, bRgb);
+    rc = stage.input(rgb_in, bIn, in3);
+    if (rc == RZ_OK) rc = stage.place();
+    if (rc != RZ_OK) return rc;
+    float* dRgb = stage.dev<float>(sRgb);
+    float4* dHits = stage.dev<float4>(sHits);
+    float4* dChains = stage.dev<float4>(sChains);
     if (P.factor == 1) {                    // c_p itself, and nothing is cast unless the guide is asked for
         if (dRgb && in4) {
             DenoiseLaunch D{};
@@ -3318,24 +3301,20 @@ static int upscale_impl(rz_ctx* c, const rz_upscale_params* pp, const float* rgb
         }
         if (dHits || dChains) {
             rc = finalize(c);
-            if (rc == RZ_OK) rc = ensure_group_counter(c);
-            if (rc == RZ_OK) rc = ensure_ray_inst_off(c);
+            if (rc == RZ_OK) rc = cast_ready(c);
             if (rc == RZ_OK) rc = ensure(c, st ? c->dStGuideHi : c->dUpGuideHi, np * (st ? 48 : 32));
             if (rc == RZ_OK)
                 rc = st ? seethrough_cast(c, c->frame.width, c->frame.height, st->max_depth, static_cast<float4*>(c->dStGuideHi.p), dHits, dChains)
-                        : upscale_cast(c, c->frame.width, c->frame.height, static_cast<float4*>(c->dUpGuideHi.p), dHits);
+                        : guide_cast(c, c->frame.width, c->frame.height, static_cast<float4*>(c->dUpGuideHi.p), dHits);
         }
     } else {
         rc = upscale_run(c, P, in3, in4, dRgb, nullptr, dHits, st, dChains);
     }
     if (rc != RZ_OK) return rc;
     if (!host) return RZ_OK;
-    const char* base = static_cast<const char*>(c->dRayOut.p);
-    if (guides) RZ_HIP(c, hipMemcpyAsync(guides, base, bHits, hipMemcpyDeviceToHost, c->stream));
-    if (chains) RZ_HIP(c, hipMemcpyAsync(chains, base + oChains, bChains, hipMemcpyDeviceToHost, c->stream));
-    if (rgb32f) RZ_HIP(c, hipMemcpyAsync(rgb32f, base + oRgb, bRgb, hipMemcpyDeviceToHost, c->stream));
-    RZ_HIP(c, hipStreamSynchronize(c->stream));
-    return denoise_backstop(c, what);
+    rc = stage.fetch();
+    if (rc != RZ_OK) return rc;
+    return report_backstop(c, what, "the guide may be wrong");
 }
 
 static int present_upscaled_impl(rz_ctx* c, const rz_present_params* pp, const rz_upscale_params* up, const rz_display_params* dp,
@@ -3344,16 +3323,10 @@ static int present_upscaled_impl(rz_ctx* c, const rz_present_params* pp, const r
     const char* what = st ? "rz_present_upscaled_seethrough" : "rz_present_upscaled";
     if (!c) return fail(nullptr, RZ_ERR_INVALID_ARG, "%s: null context", what);
     if (!pp) return fail(c, RZ_ERR_INVALID_ARG, "%s: null present params", what);
-    if (source < 0 || source > 2) return fail(c, RZ_ERR_INVALID_ARG, "%s: source %d (0 accumulation, 1 rz_denoise, 2 rz_denoise_temporal)", what, source);
-    if (source == 0 && filter_params) return fail(c, RZ_ERR_INVALID_ARG, "%s: filter_params must be NULL for source 0", what);
     const rz_upscale_params& U = up ? *up : kUpscaleDefaults;
     const rz_display_params& D = dp ? *dp : kDisplayDefaults;
-    int rc = display_check(c, what, D);
-    if (rc != RZ_OK) return rc;
-    const rz_denoise_params& P1 = (source == 1 && filter_params) ? *static_cast<const rz_denoise_params*>(filter_params) : kDenoiseDefaults;
-    const rz_temporal_params& P2 = (source == 2 && filter_params) ? *static_cast<const rz_temporal_params*>(filter_params) : kTemporalDefaults;
-    if (source == 1) rc = denoise_check(c, what, P1);
-    if (source == 2) rc = temporal_check(c, what, P2);
+    FilterSource F;
+    int rc = source_check(c, what, source, filter_params, D, F);
     if (rc != RZ_OK) return rc;
     rc = upscale_check(c, what, U);
     if (rc != RZ_OK) return rc;
@@ -3365,11 +3338,8 @@ static int present_upscaled_impl(rz_ctx* c, const rz_present_params* pp, const r
     if (U.factor == 1) return present_display_impl(c, pp, dp, source, filter_params, rgba8, rgba8_bytes, rgb32f, rgb32f_bytes);
     const int W = c->frame.width * U.factor, H = c->frame.height * U.factor;
     const size_t np = (size_t)c->frame.width * c->frame.height, nP = (size_t)W * H;
-    if (c->extAccum && c->extAccumBytes < np * 16)
-        return fail(c, RZ_ERR_BUFFER_SIZE, "%s: bound accumulation buffer holds %zu bytes, frame needs %zu", what, c->extAccumBytes, np * 16);
-    if (rgba8 && rgba8_bytes < nP * 4) return fail(c, RZ_ERR_BUFFER_SIZE, "%s: rgba8 buffer needs %zu bytes", what, nP * 4);
-    if (rgb32f && rgb32f_bytes < nP * 12) return fail(c, RZ_ERR_BUFFER_SIZE, "%s: rgb32f buffer needs %zu bytes", what, nP * 12);
-    RZ_HIP(c, hipSetDevice(c->device));
+    rc = present_sizes(c, what, nP, rgba8, rgba8_bytes, rgb32f, rgb32f_bytes);
+    if (rc != RZ_OK) return rc;
     rc = ensure(c, c->dUpOut, nP * 16);
     if (rc != RZ_OK) return rc;
     float4* hi4 = static_cast<float4*>(c->dUpOut.p);
@@ -3378,8 +3348,7 @@ static int present_upscaled_impl(rz_ctx* c, const rz_present_params* pp, const r
         rc = ensure(c, c->dDnOut, np * 16);
         if (rc != RZ_OK) return rc;
         float4* out4 = static_cast<float4*>(c->dDnOut.p);
-        if (source == 1) rc = denoise_run(c, P1, low4, nullptr, out4, nullptr);
-        else rc = temporal_run(c, P2, low4, nullptr, out4, nullptr, nullptr, false);
+        rc = source_run(c, F, low4, out4);
         if (rc != RZ_OK) return rc;
         low4 = out4;
     }
@@ -3389,13 +3358,12 @@ static int present_upscaled_impl(rz_ctx* c, const rz_present_params* pp, const r
     if (rc != RZ_OK) return rc;
     rc = present_impl(c, pp, rgba8, rgba8_bytes, rgb32f, rgb32f_bytes, hi4, W, H);
     if (rc != RZ_OK) return rc;
-    return denoise_backstop(c, what);
+    return report_backstop(c, what, "the guide may be wrong");
 }
 
 static int display_reset_impl(rz_ctx* c) {
     if (!c) return fail(nullptr, RZ_ERR_INVALID_ARG, "rz_display_reset: null context");
     if (!c->dDisplay.p) return RZ_OK;       // (nothing to drop)
-    RZ_HIP(c, hipSetDevice(c->device));
     RZ_HIP(c, hipMemsetAsync(c->dDisplay.p, 0, sizeof(DisplayState), c->stream));
     return RZ_OK;
 }
@@ -3406,7 +3374,6 @@ static int display_state_impl(rz_ctx* c, rz_display_info* out) {
     std::memset(out, 0, sizeof *out);
     out->exposure = out->target = 1.0f;     // a fresh state
     if (!c->dDisplay.p) return RZ_OK;
-    RZ_HIP(c, hipSetDevice(c->device));
     RZ_HIP(c, hipStreamSynchronize(c->stream));
     struct { float exposure; unsigned have; float call; unsigned pad; rz_display_info info; } head;
     static_assert(sizeof head == offsetof(DisplayState, work), "the head of DisplayState");
@@ -3418,7 +3385,6 @@ static int display_state_impl(rz_ctx* c, rz_display_info* out) {
 static int debug_read_temporal_impl(rz_ctx* c, int which, void* out, size_t bytes, size_t* needed) {
     if (!c) return fail(nullptr, RZ_ERR_INVALID_ARG, "null context");
     if (which < 0 || which > 4) return fail(c, RZ_ERR_INVALID_ARG, "which = %d", which);
-    RZ_HIP(c, hipSetDevice(c->device));
     const size_t np = c->tmpValid ? (size_t)c->tmpW * c->tmpH : 0;
     const int cur = c->tmpCur;
     float cam[51];

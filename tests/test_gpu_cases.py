@@ -464,3 +464,77 @@ def test_a_kernel_backstop_is_reported_by_rz_sync():
     r.sync()                                             # reported once, then clear
     assert (hip_render(sc, 64, 40, 64, 4, renderer=r).view(np.uint32) == img.view(np.uint32)).all()
     r.close()
+
+
+def _flat_bytes(x):
+    """Every array of a call's result (an array, a tuple of them, a dict of them), as bytes, in order."""
+    if isinstance(x, dict):
+        return [b for k in sorted(x) for b in _flat_bytes(x[k])]
+    if isinstance(x, (tuple, list)):
+        return [b for v in x for b in _flat_bytes(v)]
+    return [] if x is None else [np.ascontiguousarray(x).tobytes()]
+
+
+def _query_rays(sc):
+    from rayzen_amd.renderer import editor_rays
+    rays = editor_rays(sc.camera, 16, 8)
+    return rays["origin"].copy(), rays["dir"].copy()
+
+
+# name: (the C entry point that reports the backstop word itself, or None where the call leaves it to the next rz_sync; the call)
+_BACKSTOP_CALLS = {
+    "trace_rays": ("rz_trace_rays", lambda r, sc: r.trace_rays(*_query_rays(sc))),
+    "shadow_rays": ("rz_shadow_rays", lambda r, sc: r.shadow_rays(*_query_rays(sc), 1e30)),
+    "render_editor": ("rz_render_editor", lambda r, sc: r.render_editor(sc.camera, 16, 8, rgb32f=True, hits=True)),
+    "denoise": ("rz_denoise", lambda r, sc: r.denoise(guides=True)),
+    "denoise_temporal": ("rz_denoise_temporal", lambda r, sc: r.denoise_temporal(guides=True, stats=True)),
+    "upscale": ("rz_upscale", lambda r, sc: r.upscale(factor=2, guides=True)),
+    "upscale_seethrough": ("rz_upscale_seethrough", lambda r, sc: r.upscale(factor=2, guides=True, see_through=True, chains=True)),
+    "present_denoised": ("rz_present_denoised", lambda r, sc: r.present_denoised()),
+    "present_temporal": ("rz_present_temporal", lambda r, sc: r.present_temporal()),
+    "present_display_denoise": ("rz_present_display", lambda r, sc: r.present_display(source="denoise")),
+    "present_display_temporal": ("rz_present_display", lambda r, sc: r.present_display(source="temporal")),
+    "present_upscaled_accum": ("rz_present_upscaled", lambda r, sc: r.present_upscaled(source="accum", factor=2)),
+    # these two cast no ray
+    "display_host": (None, lambda r, sc: r.display()),
+    "present_display_accum": (None, lambda r, sc: r.present_display(source="accum")),
+}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", list(_BACKSTOP_CALLS))
+def test_which_host_path_calls_report_the_backstop_word_themselves(name):
+    """Every host-path call that casts rays reads the backstop word after its own synchronise: with the word set (the hook
+    writes it as a kernel would, RZ_BACKSTOP_RAYS = 8) the call returns RZ_ERR_INTERNAL under its own name with the bits and
+    clears the word, and the same call then gives the bytes it gave before (temporal_reset before every call: the history
+    plays no part).  rz_display and rz_present_display on the accumulation launch nothing that can set the word and do not
+    read it: they succeed, and the next rz_sync reports it, once."""
+    from rayzen_amd import _lib
+    from rayzen_amd.renderer import Renderer, RayZenError
+    L = _lib.hip()
+    entry, call = _BACKSTOP_CALLS[name]
+    sc = S.cornell_scene()
+    r = Renderer(0)
+    hip_render(sc, 16, 8, 1, 3, renderer=r)
+    r.temporal_reset()
+    before = _flat_bytes(call(r, sc))
+    assert before and all(before)
+    r.sync()
+    assert L.rz_debug_poke_backstop(r._c, 8) == 0
+    r.temporal_reset()
+    if entry is None:
+        assert _flat_bytes(call(r, sc)) == before
+        with pytest.raises(RayZenError) as e:
+            r.sync()
+        assert e.value.code == -9 and "a ray query's walk was cut short" in str(e.value), str(e.value)
+        r.sync()
+        r.close()
+        return
+    with pytest.raises(RayZenError) as e:
+        call(r, sc)
+    message = str(e.value).split("): ", 1)[1]            # (RayZenError: "<what> failed (<code>): <the library's text>")
+    assert e.value.code == -9 and message.startswith(entry + ": ") and "0x8" in message, str(e.value)
+    r.sync()                                             # reported once, then clear
+    r.temporal_reset()
+    assert _flat_bytes(call(r, sc)) == before
+    r.close()
