@@ -1021,6 +1021,65 @@ int rz_present_upscaled_seethrough(rz_ctx* ctx, const rz_present_params* present
                                    const void* filter_params, uint8_t* rgba8, size_t rgba8_bytes,
                                    float* rgb32f, size_t rgb32f_bytes);
 
+/* ------------------------------------------------------------------------ */
+/* Anti-aliased edges from sub-pixel guides (new: the reference has none)   */
+/* ------------------------------------------------------------------------ */
+/* The path loop's camera jitter is rand * 2e-5 in uv (about 0.04 pixel at 1080p), so a frame converges to its pixel-centre sample
+ * and its silhouettes stay stair-stepped at any sample count; the denoisers and the upsampler preserve edges, aliased ones
+ * included.  This stage shades once per pixel and takes geometry at s x s sub-pixel positions, on the pixels that have an edge
+ * only, then averages (sub-pixel reconstruction anti-aliasing; rz_antialias.hip).  The render path does not change.
+ * The frame of the last rz_set_frame is the frame that was rendered, w x h, and the output has its size.  c_p is its colour:
+ * rgb_in, or the accumulation as rgb / n as in rz_upscale.  g_p = (hit_p, x_p, n_p, t_p, m_p) is rz_denoise's guide record of pixel
+ * p (m the clamped material word).  f = 2 |inv_proj[5]| / h.  Row 0 = the bottom row.
+ *  DIFFERENT a neighbour q is DIFFERENT from p when any of these holds: hit_q != hit_p; both are hits and m_q != m_p; both are
+ *            hits and nd < edge_normal, nd = (n_p.x n_q.x + n_p.y n_q.y) + n_p.z n_q.z; both are hits and pd > k_e * t_p, where
+ *            pd = |dot(n_p, x_q - x_p)| in the same operand order and k_e = (float)(edge_plane * f), formed in binary64 on the
+ *            host.  Binary32, one rounding per operation, no fused multiply-add: every decision is a function of exact data
+ *            and tests/antialias_ref.py reproduces it bit for bit.
+ *  EDGE      p is an EDGE pixel iff c_p is bad (rz_denoise's bit-pattern rule) or one of its up to eight neighbours inside the
+ *            image is DIFFERENT from it.  Neighbours outside the image do not count; a 1 x 1 frame is flat unless it is bad.
+ *  flat      out = c_p exactly.
+ *  edge      out = (((u_0 + u_1) + ...) + u_{s^2 - 1}) / (float)(s s) per channel, binary32, b outer and a inner, where u_(a, b)
+ *            is what rz_upscale defines for high pixel (s x + a, s y + b) of an s w x s h output of THIS frame at factor s: the
+ *            high guide is the closest hit of the ray through that high pixel's centre, uv = ((float)X + 0.5f) / (float)(s w),
+ *            from cam_pos -- bit for bit what rz_upscale casts -- and the footprint, admissibility, W_geom, the 1e-4 floor,
+ *            stages 1 to 3, demodulation and re-modulation are rz_upscale's with this call's sigma_normal, sigma_plane and
+ *            demodulate.  A bad pixel is an edge pixel; its sub-samples find no tap in it and stage 3 reads it as black, so the
+ *            output is finite for s >= 2 whatever the input.
+ *  s = 1     out = c_p exactly and nothing is cast unless guides or edges is asked for; rz_present_antialiased then gives
+ *            rz_present_display's bytes for every source.
+ * LIMITS.  Classification sees pixel centres only: geometry that lies between the centres of a flat neighbourhood is missed.
+ * Guides are first hits, so edges behind glass and in mirrors stay aliased (the reserved words leave room for a see-through
+ * variant).  The average is taken in linear HDR, before the tone curve.
+ * Defaults (params NULL): factor 2, sigma_normal 128, sigma_plane 1, demodulate 1, edge_normal 0.9, edge_plane 1.
+ * rz_antialias.  rgb_in as rz_upscale's.  Outputs, each optional:
+ *   rgb32f   w*h*3 floats: the anti-aliased linear colour, unclamped
+ *   guides   w*h rz_hit: the frame-size guide, as rz_denoise returns it
+ *   edges    w*h bytes, 1 = edge; classified for factor 1 too
+ * Pointer, alignment, staging (RZ_ANTIALIAS_HOST), stream, backstop and error conventions are rz_upscale's; edges needs no
+ * alignment.  RZ_ERR_INVALID_ARG also covers: edge_normal outside -1..1 or not finite, edge_plane negative or not finite, non-zero
+ * reserved words, rgb32f == rgb_in on the device path (an edge pixel reads its neighbours).  A failing call launches nothing.
+ * The calls touch no render, temporal or display state; the frame-size guide lives in the upsampler's low-guide buffer.
+ * rz_present_antialiased is rz_present_display with the pass between the source and the display stage: source 0 the
+ * accumulation, 1 rz_denoise, 2 rz_denoise_temporal (the filter runs first and the history advances as in rz_present_temporal);
+ * the overlays are drawn after it.  It commits its exposure as rz_present_display does.
+ * (Additive: RZ_ABI_VERSION stays 5.) */
+typedef struct rz_antialias_params {    /* NULL = defaults */
+    int32_t factor;                     /* s: s x s sub-samples per edge pixel, 1..4 (default 2) */
+    float   sigma_normal, sigma_plane;  /* rz_upscale's (128, 1) */
+    int32_t demodulate;                 /* rz_upscale's (1) */
+    float   edge_normal;                /* default 0.9: finite, -1..1 */
+    float   edge_plane;                 /* default 1.0: finite, >= 0 */
+    int32_t reserved[2];                /* must be 0 */
+} rz_antialias_params;                  /* 32 B; rz_sizeof(26) -- 25 stays unassigned, tests probe it */
+#define RZ_ANTIALIAS_HOST 1u            /* pointers are host memory: staged, returns when written */
+int rz_antialias(rz_ctx* ctx, const rz_antialias_params* params, const float* rgb_in, size_t rgb_in_bytes,
+                 float* rgb32f, size_t rgb32f_bytes, rz_hit* guides, size_t guides_bytes,
+                 uint8_t* edges, size_t edges_bytes, unsigned flags);
+int rz_present_antialiased(rz_ctx* ctx, const rz_present_params* present, const rz_antialias_params* antialias,
+                           const rz_display_params* display, int source, const void* filter_params,
+                           uint8_t* rgba8, size_t rgba8_bytes, float* rgb32f, size_t rgb32f_bytes);
+
 /* Number of HIP devices visible to the process (0 without a GPU). */
 int rz_device_count(void);
 
@@ -1045,8 +1104,8 @@ const char* rz_source_hash(void);
  * 3 material, 4 light, 5 frame_params, 6 counters, 7 ray, 8 hit,
  * 9 visibility, 10 editor_params, 11 denoise_params, 12 temporal_params,
  * 14 display_params, 15 display_info, 17 skin_triangle, 18 morph_triangle, 20 mesh_quality,
- * 21 upscale_params, 23 seethrough_params, 24 chain (13, 16, 19 and 22 are unassigned and return 0, as every unknown index
- * does). */
+ * 21 upscale_params, 23 seethrough_params, 24 chain, 26 antialias_params (13, 16, 19, 22 and 25 are unassigned and return 0, as
+ * every unknown index does). */
 size_t rz_sizeof(int which);
 
 #ifdef __cplusplus

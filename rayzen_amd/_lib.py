@@ -29,6 +29,7 @@ HIP_SYMBOLS = (
     "rz_skin_create", "rz_skin_pose", "rz_skin_destroy", "rz_skin_last_kernel_ms",
     "rz_geometry_quality", "rz_rebuild_geometry",
     "rz_upscale", "rz_present_upscaled", "rz_upscale_seethrough", "rz_present_upscaled_seethrough",
+    "rz_antialias", "rz_present_antialiased",
 )
 ABI_VERSION = 5         # RZ_ABI_VERSION of the include/rayzen_hip.h this file mirrors
 # the symbols include/rayzen_host.h declares
@@ -179,6 +180,17 @@ SEETHROUGH_MAX_DEPTH = 8
 SIZEOF_SEETHROUGH_PARAMS, SIZEOF_CHAIN = 23, 24     # their rz_sizeof indices
 
 
+class AntialiasParams(C.Structure):
+    """rz_antialias_params of include/rayzen_hip.h (32 B)."""
+    _fields_ = [("factor", C.c_int32), ("sigma_normal", C.c_float), ("sigma_plane", C.c_float), ("demodulate", C.c_int32),
+                ("edge_normal", C.c_float), ("edge_plane", C.c_float), ("reserved", C.c_int32 * 2)]
+
+
+ANTIALIAS_DEFAULTS = dict(factor=2, sigma_normal=128.0, sigma_plane=1.0, demodulate=1, edge_normal=0.9, edge_plane=1.0)
+ANTIALIAS_HOST = 1                      # RZ_ANTIALIAS_HOST
+SIZEOF_ANTIALIAS_PARAMS = 26            # its rz_sizeof index
+
+
 class SkinTriangle(C.Structure):
     """rz_skin_triangle of include/rayzen_hip.h (64 B)."""
     _fields_ = [("bones", C.c_uint32 * 3), ("pad", C.c_uint32), ("weights", (C.c_float * 4) * 3)]
@@ -299,7 +311,9 @@ def hip():
                                 ("rz_upscale", i, [vp, vp, vp, sz, vp, sz, vp, sz, C.c_uint]),
                                 ("rz_present_upscaled", i, [vp, C.POINTER(PresentParams), vp, vp, i, vp, vp, sz, vp, sz]),
                                 ("rz_upscale_seethrough", i, [vp, vp, vp, vp, sz, vp, sz, vp, sz, vp, sz, C.c_uint]),
-                                ("rz_present_upscaled_seethrough", i, [vp, C.POINTER(PresentParams), vp, vp, vp, i, vp, vp, sz, vp, sz])):
+                                ("rz_present_upscaled_seethrough", i, [vp, C.POINTER(PresentParams), vp, vp, vp, i, vp, vp, sz, vp, sz]),
+                                ("rz_antialias", i, [vp, vp, vp, sz, vp, sz, vp, sz, vp, sz, C.c_uint]),
+                                ("rz_present_antialiased", i, [vp, C.POINTER(PresentParams), vp, vp, i, vp, vp, sz, vp, sz])):
             try:
                 fn = getattr(L, name)
                 fn.restype, fn.argtypes = res, args

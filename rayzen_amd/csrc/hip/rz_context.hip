@@ -838,9 +838,9 @@ void camera_kparams(const rz_ctx* c, KParams& K, int width, int height, const fl
 }
 
 // What the guide casts share: the frame's camera at width x height, a wave per 64-pixel run of a row, the offsets and the word
-// cast_ready made, and the BLAS stack of the launch.
+// cast_ready made, and the BLAS stack of the launch (fixedLds: what the kernel keeps in LDS per wave beside the stack).
 template <class Launch>
-int cast_wiring(rz_ctx* c, int width, int height, KParams& K, Launch& G) {
+int cast_wiring(rz_ctx* c, int width, int height, KParams& K, Launch& G, size_t fixedLds = 0) {
     const rz_frame_params& f = c->frame;
     camera_kparams(c, K, width, height, f.inv_view, f.inv_proj, f.cam_pos);
     G.unitsX = (width + 63) / 64;
@@ -848,7 +848,7 @@ int cast_wiring(rz_ctx* c, int width, int height, KParams& K, Launch& G) {
     G.grid = rays_grid(G.units * 64);
     G.instTriOff = static_cast<const int32_t*>(c->dRayInstOff.p);
     G.errWord = backstop_word(c);
-    return size_blas_stack(c, K, 0, RZ_RAYS_WAVES_PER_CU, G.grid, c->dRayOvf);
+    return size_blas_stack(c, K, fixedLds, RZ_RAYS_WAVES_PER_CU, G.grid, c->dRayOvf);
 }
 
 // Where a pass reads its input and writes its outputs.  On the device path the caller's pointers are device pointers: nothing
@@ -1141,6 +1141,7 @@ size_t rz_sizeof(int which) {
         case 21: return sizeof(rz_upscale_params);
         case 23: return sizeof(rz_seethrough_params);    // (22 stays unassigned: probed as an unknown index)
         case 24: return sizeof(rz_chain);
+        case 26: return sizeof(rz_antialias_params);     // (25 stays unassigned: probed as an unknown index)
         default: return 0;
     }
 }
@@ -3361,6 +3362,160 @@ static int present_upscaled_impl(rz_ctx* c, const rz_present_params* pp, const r
     return report_backstop(c, what, "the guide may be wrong");
 }
 
+// rz_antialias / rz_present_antialiased (rz_antialias.hip).  The frame rz_set_frame set is the frame that was rendered; they
+// read its size and camera, the device scene as finalize left it, and touch no render state.  The frame-size guide lives in the
+// upsampler's low-guide buffer, which every call that reads it casts anew.
+static const rz_antialias_params kAntialiasDefaults = {2, 128.0f, 1.0f, 1, 0.9f, 1.0f, {0, 0}};
+
+static int antialias_check(rz_ctx* c, const char* what, const rz_antialias_params& P) {
+    // the factor, the sigmas, demodulate, the frame, the scene, the whole frame: rz_upscale's
+    const rz_upscale_params U = {P.factor, P.sigma_normal, P.sigma_plane, P.demodulate, {0, 0, 0, 0}};
+    const int rc = upscale_check(c, what, U);
+    if (rc != RZ_OK) return rc;
+    if (!(P.edge_normal >= -1.0f && P.edge_normal <= 1.0f))
+        return fail(c, RZ_ERR_INVALID_ARG, "%s: edge_normal %g outside -1..1", what, (double)P.edge_normal);
+    if (!(P.edge_plane >= 0.0f && P.edge_plane < INFINITY))
+        return fail(c, RZ_ERR_INVALID_ARG, "%s: edge_plane %g (finite, >= 0)", what, (double)P.edge_plane);
+    if (P.reserved[0] || P.reserved[1]) return fail(c, RZ_ERR_INVALID_ARG, "%s: reserved words of rz_antialias_params must be 0", what);
+    return RZ_OK;
+}
+
+// Casts the frame-size guide, classifies and anti-aliases, on the stream.  The frame (device) is in3 (3 floats per pixel) or in4
+// (RGBA32F sum and count); outputs (device, frame size, each optional): rgb (3 floats per pixel), out4 ((colour, 1)), hits
+// (rz_hit), edges (a byte per pixel).  Factor 1 without `edges` casts nothing unless hits are asked for.
+static int antialias_run(rz_ctx* c, const rz_antialias_params& P, const float* in3, const float4* in4, float* rgb, float4* out4,
+                         float4* hits, uint8_t* edges) {
+    if (!rgb && !out4 && !hits && !edges) return RZ_OK;
+    const rz_frame_params& f = c->frame;
+    const size_t np = (size_t)f.width * f.height;
+    int rc = finalize(c);
+    if (rc != RZ_OK) return rc;
+    const bool kernel = edges || ((rgb || out4) && P.factor > 1);
+    if (!kernel && (rgb || out4)) {         // factor 1: c_p itself
+        if (in4) {
+            DenoiseLaunch D{};
+            D.accum = in4;
+            D.dst = out4;
+            D.rgb = rgb;
+            D.width = f.width; D.height = f.height;
+            launch_denoise_resolve(D, c->stream);
+            RZ_HIP(c, hipGetLastError());
+        } else if (rgb) {
+            RZ_HIP(c, hipMemcpyAsync(rgb, in3, np * 12, hipMemcpyDeviceToDevice, c->stream));
+        }
+    }
+    if (!kernel && !hits) return RZ_OK;
+    rc = cast_ready(c);
+    if (rc != RZ_OK) return rc;
+    rc = ensure(c, c->dUpGuideLo, np * 32);
+    if (rc != RZ_OK) return rc;
+    float4* guide = static_cast<float4*>(c->dUpGuideLo.p);
+    rc = guide_cast(c, f.width, f.height, guide, hits);
+    if (rc != RZ_OK || !kernel) return rc;
+    KParams K{};
+    AntialiasLaunch A{};
+    rc = cast_wiring(c, f.width, f.height, K, A, RZ_AA_QUEUE * sizeof(int));
+    if (rc != RZ_OK) return rc;
+    A.U.in3 = in4 ? nullptr : in3;
+    A.U.in4 = in4;
+    A.U.guideLo = guide;
+    A.U.materials = static_cast<const DevMaterial*>(c->dMat.p);
+    A.U.dst = out4;
+    A.U.rgb = rgb;
+    A.U.w = f.width; A.U.h = f.height;
+    A.U.s = P.factor;
+    A.U.sigmaNormal = P.sigma_normal;
+    const double fpx = 2.0 * std::fabs((double)f.inv_proj[5]) / (double)f.height;     // world size of a pixel at unit distance
+    A.U.planeScale = (float)(1.0 / ((double)P.sigma_plane * fpx));
+    A.U.demodulate = P.demodulate;
+    A.edges = edges;
+    A.edgeNormal = P.edge_normal;
+    A.edgePlane = (float)((double)P.edge_plane * fpx);
+    launch_antialias(K, A, c->stream);
+    RZ_HIP(c, hipGetLastError());
+    return RZ_OK;
+}
+
+static int antialias_impl(rz_ctx* c, const rz_antialias_params* pp, const float* rgb_in, size_t rgb_in_bytes, float* rgb32f,
+                          size_t rgb32f_bytes, rz_hit* guides, size_t guides_bytes, uint8_t* edges, size_t edges_bytes, unsigned flags) {
+    const char* what = "rz_antialias";
+    if (!c) return fail(nullptr, RZ_ERR_INVALID_ARG, "%s: null context", what);
+    if (flags & ~RZ_ANTIALIAS_HOST) return fail(c, RZ_ERR_INVALID_ARG, "%s: unknown flags 0x%x", what, flags);
+    const rz_antialias_params& P = pp ? *pp : kAntialiasDefaults;
+    int rc = antialias_check(c, what, P);
+    if (rc != RZ_OK) return rc;
+    const bool host = (flags & RZ_ANTIALIAS_HOST) != 0;
+    if (!host && ((reinterpret_cast<uintptr_t>(guides) & 15u) ||
+                  ((reinterpret_cast<uintptr_t>(rgb_in) | reinterpret_cast<uintptr_t>(rgb32f)) & 3u)))
+        return fail(c, RZ_ERR_INVALID_ARG, "%s: device pointers must be 16-byte (guides) or 4-byte (rgb_in, rgb32f) aligned", what);
+    if (!host && rgb32f && rgb32f == rgb_in)
+        return fail(c, RZ_ERR_INVALID_ARG, "%s: rgb32f must not be rgb_in (an edge pixel reads its neighbours)", what);
+    const size_t np = (size_t)c->frame.width * c->frame.height;
+    const size_t bRgb = np * 3 * sizeof(float), bHits = np * sizeof(rz_hit);
+    if (rgb_in && rgb_in_bytes < bRgb) return fail(c, RZ_ERR_BUFFER_SIZE, "%s: rgb_in needs %zu bytes, got %zu", what, bRgb, rgb_in_bytes);
+    if (!rgb_in) {
+        rc = accum_fits(c, what);
+        if (rc != RZ_OK) return rc;
+    }
+    if (rgb32f && rgb32f_bytes < bRgb) return fail(c, RZ_ERR_BUFFER_SIZE, "%s: rgb32f needs %zu bytes, got %zu", what, bRgb, rgb32f_bytes);
+    if (guides && guides_bytes < bHits) return fail(c, RZ_ERR_BUFFER_SIZE, "%s: guides needs %zu bytes, got %zu", what, bHits, guides_bytes);
+    if (edges && edges_bytes < np) return fail(c, RZ_ERR_BUFFER_SIZE, "%s: edges needs %zu bytes, got %zu", what, np, edges_bytes);
+    if (!rgb32f && !guides && !edges) return RZ_OK;
+    const float* in3 = rgb_in;
+    const float4* in4 = rgb_in ? nullptr : static_cast<const float4*>(rz_accum_device_ptr(c));
+    // host buffers are staged as rz_upscale stages them: the input in dRayIn; guides, then rgb32f, then edges in dRayOut
+    HostStage stage(c, host);
+    const int sHits = stage.add(guides, bHits), sRgb = stage.add(rgb32f, bRgb), sEdges = stage.add(edges, np);
+    rc = stage.input(rgb_in, bRgb, in3);
+    if (rc == RZ_OK) rc = stage.place();
+    if (rc != RZ_OK) return rc;
+    rc = antialias_run(c, P, in3, in4, stage.dev<float>(sRgb), nullptr, stage.dev<float4>(sHits), stage.dev<uint8_t>(sEdges));
+    if (rc != RZ_OK) return rc;
+    if (!host) return RZ_OK;
+    rc = stage.fetch();
+    if (rc != RZ_OK) return rc;
+    return report_backstop(c, what, "the guide may be wrong");
+}
+
+static int present_antialiased_impl(rz_ctx* c, const rz_present_params* pp, const rz_antialias_params* ap, const rz_display_params* dp,
+                                    int source, const void* filter_params, uint8_t* rgba8, size_t rgba8_bytes, float* rgb32f,
+                                    size_t rgb32f_bytes) {
+    const char* what = "rz_present_antialiased";
+    if (!c) return fail(nullptr, RZ_ERR_INVALID_ARG, "%s: null context", what);
+    if (!pp) return fail(c, RZ_ERR_INVALID_ARG, "%s: null present params", what);
+    const rz_antialias_params& A = ap ? *ap : kAntialiasDefaults;
+    const rz_display_params& D = dp ? *dp : kDisplayDefaults;
+    FilterSource F;
+    int rc = source_check(c, what, source, filter_params, D, F);
+    if (rc != RZ_OK) return rc;
+    rc = antialias_check(c, what, A);
+    if (rc != RZ_OK) return rc;
+    // factor 1: nothing to average, the call IS rz_present_display (its bytes exactly, for every source)
+    if (A.factor == 1) return present_display_impl(c, pp, dp, source, filter_params, rgba8, rgba8_bytes, rgb32f, rgb32f_bytes);
+    const size_t np = (size_t)c->frame.width * c->frame.height;
+    rc = present_sizes(c, what, np, rgba8, rgba8_bytes, rgb32f, rgb32f_bytes);
+    if (rc != RZ_OK) return rc;
+    rc = ensure(c, c->dUpOut, np * 16);
+    if (rc != RZ_OK) return rc;
+    float4* aa4 = static_cast<float4*>(c->dUpOut.p);
+    const float4* in4 = static_cast<const float4*>(rz_accum_device_ptr(c));
+    if (source != 0) {                      // the denoisers leave (colour, 1), which resolves to the colour
+        rc = ensure(c, c->dDnOut, np * 16);
+        if (rc != RZ_OK) return rc;
+        float4* out4 = static_cast<float4*>(c->dDnOut.p);
+        rc = source_run(c, F, in4, out4);
+        if (rc != RZ_OK) return rc;
+        in4 = out4;
+    }
+    rc = antialias_run(c, A, nullptr, in4, nullptr, aa4, nullptr, nullptr);
+    if (rc != RZ_OK) return rc;
+    rc = display_run(c, D, nullptr, aa4, nullptr, nullptr, aa4, false);
+    if (rc != RZ_OK) return rc;
+    rc = present_impl(c, pp, rgba8, rgba8_bytes, rgb32f, rgb32f_bytes, aa4);
+    if (rc != RZ_OK) return rc;
+    return report_backstop(c, what, "the guide may be wrong");
+}
+
 static int display_reset_impl(rz_ctx* c) {
     if (!c) return fail(nullptr, RZ_ERR_INVALID_ARG, "rz_display_reset: null context");
     if (!c->dDisplay.p) return RZ_OK;       // (nothing to drop)
@@ -3588,6 +3743,19 @@ int rz_present_upscaled_seethrough(rz_ctx* c, const rz_present_params* present, 
     return guarded(c, "rz_present_upscaled_seethrough", [&] {
         return present_upscaled_impl(c, present, upscale, display, source, filter_params, rgba8, rgba8_bytes, rgb32f, rgb32f_bytes,
                                      seethrough ? seethrough : &kSeethroughDefaults);
+    });
+}
+int rz_antialias(rz_ctx* c, const rz_antialias_params* params, const float* rgb_in, size_t rgb_in_bytes, float* rgb32f, size_t rgb32f_bytes,
+                 rz_hit* guides, size_t guides_bytes, uint8_t* edges, size_t edges_bytes, unsigned flags) {
+    return guarded(c, "rz_antialias", [&] {
+        return antialias_impl(c, params, rgb_in, rgb_in_bytes, rgb32f, rgb32f_bytes, guides, guides_bytes, edges, edges_bytes, flags);
+    });
+}
+int rz_present_antialiased(rz_ctx* c, const rz_present_params* present, const rz_antialias_params* antialias,
+                           const rz_display_params* display, int source, const void* filter_params, uint8_t* rgba8, size_t rgba8_bytes,
+                           float* rgb32f, size_t rgb32f_bytes) {
+    return guarded(c, "rz_present_antialiased", [&] {
+        return present_antialiased_impl(c, present, antialias, display, source, filter_params, rgba8, rgba8_bytes, rgb32f, rgb32f_bytes);
     });
 }
 int rz_display_reset(rz_ctx* c) {

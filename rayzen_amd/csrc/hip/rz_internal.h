@@ -101,6 +101,22 @@ struct UpscaleLaunch {          // rz_upscale_gather
 };
 void launch_upscale_gather(const UpscaleLaunch& U, hipStream_t stream);
 
+// ---- rz_antialias.hip
+constexpr int RZ_AA_QUEUE = 128;        // entries of a wave's edge queue in LDS: fewer than 64 / s^2 left over plus one unit's 64
+struct AntialiasLaunch {        // rz_antialias_edges: DenoiseGuideLaunch's shape at the frame's size
+    long long units;            // 64-pixel runs of a row
+    int unitsX;                 // runs per row
+    long long grid;             // rays_grid(units * 64)
+    const int32_t* instTriOff;  // (cast_wiring's; the kernel writes no rz_hit)
+    unsigned* errWord;          // the context's backstop word
+    UpscaleLaunch U;            // the frame (in3 / in4, w, h), its guide (guideLo), s = the factor (1: classify only), the
+                                // sigmas; dst / rgb: the w x h outputs, each optional; guideHi is unused
+    uint8_t* edges;             // w x h bytes, 1 = edge, optional
+    float edgeNormal;           // rz_antialias_params.edge_normal
+    float edgePlane;            // k_e = (float)(edge_plane * f)
+};
+void launch_antialias(const KParams& K, const AntialiasLaunch& A, hipStream_t stream);
+
 // ---- rz_seethrough.hip
 struct SeethroughGuideLaunch {  // rz_seethrough_guides: DenoiseGuideLaunch with the chain's bound and outputs
     long long units;            // 64-pixel runs of a row

@@ -4,6 +4,7 @@
 // The filter is the one stated at the head of rz_upscale.hip.  With CHAIN the guide is the final hit of the pixel's chain,
 // alpha is T * albedo (T alone for a final miss: a miss is demodulated too), and a tap is admissible only if its class equals
 // the pixel's.  Everything that differs sits behind `if constexpr (CHAIN)`: the first-hit instantiation is the code it was.
+// rz_antialias_edges (rz_antialias.hip) evaluates the same reconstruction (upscale_pixel<false>) on guides it casts itself.
 #pragma once
 #include "rz_internal.h"
 #include "rz_device_math.h"
@@ -70,17 +71,10 @@ __device__ __forceinline__ bool upscale_tap(const UpscaleLaunch& U, int qx, int 
     return true;
 }
 
-// The body of both gather kernels: one lane per HIGH pixel, launched as 64 x 4 pixels per workgroup.
+// The reconstruction of one HIGH pixel (X, Y) from its guide record held in registers (g2: CHAIN only): stages 1 to 3.  The
+// gather kernels read the record from U.guideHi; rz_antialias_edges (rz_antialias.hip) has just cast it.
 template <bool CHAIN>
-__device__ __forceinline__ void upscale_gather_body(const UpscaleLaunch& U) {
-    constexpr int REC = CHAIN ? 3 : 2;
-    const int W = U.w * U.s, H = U.h * U.s;
-    const int X = blockIdx.x * 64 + threadIdx.x, Y = blockIdx.y * 4 + threadIdx.y;
-    if (X >= W || Y >= H) return;
-    const size_t P = (size_t)Y * W + X;
-    const float4 g0 = U.guideHi[REC * P], g1 = U.guideHi[REC * P + 1];
-    float4 g2 = make_float4(1.0f, 1.0f, 1.0f, 0.0f);
-    if constexpr (CHAIN) g2 = U.guideHi[REC * P + 2];
+__device__ __forceinline__ v3 upscale_pixel(const UpscaleLaunch& U, int X, int Y, const float4 g0, const float4 g1, const float4 g2) {
     const int wordP = __float_as_int(g1.w), clsP = __float_as_int(g2.w);
     const bool hitP = wordP >= 0;
     const v3 nP = mk3(g0.x, g0.y, g0.z), xP = mk3(g1.x, g1.y, g1.z);
@@ -128,6 +122,21 @@ __device__ __forceinline__ void upscale_gather_body(const UpscaleLaunch& U) {
         out = upscale_colour(U, (size_t)(Y / U.s) * U.w + X / U.s);
         if (nonfinite_(out)) out = mk3(0.0f, 0.0f, 0.0f);
     }
+    return out;
+}
+
+// The body of both gather kernels: one lane per HIGH pixel, launched as 64 x 4 pixels per workgroup.
+template <bool CHAIN>
+__device__ __forceinline__ void upscale_gather_body(const UpscaleLaunch& U) {
+    constexpr int REC = CHAIN ? 3 : 2;
+    const int W = U.w * U.s, H = U.h * U.s;
+    const int X = blockIdx.x * 64 + threadIdx.x, Y = blockIdx.y * 4 + threadIdx.y;
+    if (X >= W || Y >= H) return;
+    const size_t P = (size_t)Y * W + X;
+    const float4 g0 = U.guideHi[REC * P], g1 = U.guideHi[REC * P + 1];
+    float4 g2 = make_float4(1.0f, 1.0f, 1.0f, 0.0f);
+    if constexpr (CHAIN) g2 = U.guideHi[REC * P + 2];
+    const v3 out = upscale_pixel<CHAIN>(U, X, Y, g0, g1, g2);
     if (U.dst) U.dst[P] = make_float4(out.x, out.y, out.z, 1.0f);
     if (U.rgb) {
         U.rgb[3 * P] = out.x;

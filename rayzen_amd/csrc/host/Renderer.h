@@ -13,7 +13,8 @@
 //                                      <- new: temporal accumulation + the variance-guided filter (rz_denoise_temporal)
 //   presentUpscaled()                  <- new: render below display size, reconstruct at display size (rz_present_upscaled,
 //                                         and rz_present_upscaled_seethrough: guides that follow glass and mirrors)
-//   presentDisplay() / resetDisplay()  <- new: exposure, tone curve and sRGB encode in front of present (rz_present_display)
+//   presentDisplay() / resetDisplay()  <- new: exposure, tone curve and sRGB encode in front of present (rz_present_display;
+//                                         with an rz_antialias_params: rz_present_antialiased, anti-aliased edges)
 // Unlike the reference's per-frame path, updateDynamicBVHAndSSBOs re-uploads
 // only what changed (instances + TLAS, a few KB), not all geometry.
 //
@@ -35,12 +36,16 @@
 #include "RayZenScene.h"
 #include "rayzen_hip.h"
 
-// The one entry point of the front end that is referenced WEAKLY: a program linked against a library from before it, or against
+// The first of the two entry points of the front end that are referenced WEAKLY: a program linked against a library from before it, or against
 // a stand-in that defines only what it exercises, still links, and presentUpscaled(..., &seeThrough) throws there.
 extern "C" int rz_present_upscaled_seethrough(rz_ctx* ctx, const rz_present_params* present, const rz_upscale_params* upscale,
                                               const rz_seethrough_params* seethrough, const rz_display_params* display, int source,
                                               const void* filter_params, uint8_t* rgba8, size_t rgba8_bytes, float* rgb32f,
                                               size_t rgb32f_bytes) __attribute__((weak));
+// ... and rz_present_antialiased, on the same terms: presentDisplay(..., &antialias) throws where it is absent.
+extern "C" int rz_present_antialiased(rz_ctx* ctx, const rz_present_params* present, const rz_antialias_params* antialias,
+                                      const rz_display_params* display, int source, const void* filter_params, uint8_t* rgba8,
+                                      size_t rgba8_bytes, float* rgb32f, size_t rgb32f_bytes) __attribute__((weak));
 
 namespace rayzen {
 
@@ -325,10 +330,17 @@ public:
     // present() behind the display stage: exposure (manual, or metered from the frame and adapted from call to call), tone
     // curve, transfer.  source 0: the accumulation; 1: rz_denoise's output (filter: an rz_denoise_params* or null); 2:
     // rz_denoise_temporal's (an rz_temporal_params* or null; the history advances).  display null: present()'s bytes.
+    // antialias non-null: rz_present_antialiased, which averages factor x factor sub-pixel reconstructions on the pixels that
+    // have a geometric edge, between the source and the display stage (factor 1: the bytes without it); null: rz_present_display.
     std::vector<uint8_t> presentDisplay(const rz_present_params& present, const rz_display_params* display = nullptr, int source = 0,
-                                        const void* filter = nullptr) {
+                                        const void* filter = nullptr, const rz_antialias_params* antialias = nullptr) {
         std::vector<uint8_t> out((size_t)width_ * (size_t)height_ * 4);
-        check(rz_present_display(ctx_, &present, display, source, filter, out.data(), out.size(), nullptr, 0), "rz_present_display");
+        if (antialias) {
+            if (&rz_present_antialiased == nullptr) throw std::runtime_error("rz_present_antialiased: the linked library does not have it");
+            check(rz_present_antialiased(ctx_, &present, antialias, display, source, filter, out.data(), out.size(), nullptr, 0),
+                  "rz_present_antialiased");
+        } else
+            check(rz_present_display(ctx_, &present, display, source, filter, out.data(), out.size(), nullptr, 0), "rz_present_display");
         return out;
     }
     // presentDisplay() at display size for a frame rendered below it: the frame last set is the LOW one (width x height), the

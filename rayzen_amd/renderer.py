@@ -835,6 +835,82 @@ class Renderer:
                                                 rgba8.ctypes.data, rgba8.nbytes, rgb.ctypes.data, rgb.nbytes), "rz_present_upscaled")
         return rgb, rgba8
 
+    # -- anti-aliased edges (rz_antialias / rz_present_antialiased) -------------------
+    @staticmethod
+    def _antialias_params(factor, sigma_normal, sigma_plane, demodulate, edge_normal, edge_plane):
+        # all None: the library's defaults (params NULL)
+        given = dict(factor=factor, sigma_normal=sigma_normal, sigma_plane=sigma_plane, demodulate=demodulate,
+                     edge_normal=edge_normal, edge_plane=edge_plane)
+        if all(v is None for v in given.values()):
+            return None
+        p = _lib.AntialiasParams()
+        for k, v in given.items():
+            d = _lib.ANTIALIAS_DEFAULTS[k]
+            setattr(p, k, d if v is None else (int(bool(v)) if k == "demodulate" else type(d)(v)))
+        return p
+
+    def antialias(self, rgb=None, factor=None, sigma_normal=None, sigma_plane=None, demodulate=None, edge_normal=None,
+                  edge_plane=None, guides=False, edges=False):
+        """Edge anti-aliasing (include/rayzen_hip.h: rz_antialias) of rgb ((h, w, 3) float32 linear colour) or, with rgb None, of
+        the accumulation, at the size of the last set_frame: a pixel with a geometric edge in its 3 x 3 neighbourhood becomes the
+        mean of factor x factor sub-pixel reconstructions, every other pixel keeps its colour bit for bit (host memory; returns
+        when done).  guides=True appends the frame-size G-buffer as (h, w) HIT_DTYPE records, edges=True the (h, w) bool edge
+        mask; row 0 = bottom row.  Parameters left None take the library's defaults (factor 2, sigma_normal 128, sigma_plane 1,
+        demodulate on, edge_normal 0.9, edge_plane 1)."""
+        ap = self._antialias_params(factor, sigma_normal, sigma_plane, demodulate, edge_normal, edge_plane)
+        src = None if rgb is None else np.ascontiguousarray(rgb, np.float32)
+        out = np.empty((self.height, self.width, 3), np.float32)
+        hh = np.empty(out.shape[:2], HIT_DTYPE) if guides else None
+        ee = np.empty(out.shape[:2], np.uint8) if edges else None
+        self._check(self._L.rz_antialias(self._c, None if ap is None else C.byref(ap), None if src is None else src.ctypes.data,
+                                         0 if src is None else src.nbytes, out.ctypes.data, out.nbytes,
+                                         None if hh is None else hh.ctypes.data, 0 if hh is None else hh.nbytes,
+                                         None if ee is None else ee.ctypes.data, 0 if ee is None else ee.nbytes,
+                                         _lib.ANTIALIAS_HOST), "rz_antialias")
+        res = (out,) + ((hh,) if guides else ()) + ((ee.astype(bool),) if edges else ())
+        return res if len(res) > 1 else out
+
+    def antialias_device(self, rgb_in_ptr=None, rgb32f_ptr=None, guides_ptr=None, edges_ptr=None, factor=None, sigma_normal=None,
+                         sigma_plane=None, demodulate=None, edge_normal=None, edge_plane=None):
+        """rz_antialias on device memory (guides 16-B aligned, rgb_in and rgb32f 4-B and distinct; each optional): enqueued on
+        the context's stream, asynchronous.  Sizes: rgb_in and rgb32f w*h*12 B, guides w*h*48 B, edges w*h B."""
+        ap = self._antialias_params(factor, sigma_normal, sigma_plane, demodulate, edge_normal, edge_plane)
+        n = self.width * self.height
+        self._check(self._L.rz_antialias(self._c, None if ap is None else C.byref(ap), C.c_void_p(rgb_in_ptr),
+                                         n * 12 if rgb_in_ptr else 0, C.c_void_p(rgb32f_ptr), n * 12 if rgb32f_ptr else 0,
+                                         C.c_void_p(guides_ptr), n * 48 if guides_ptr else 0, C.c_void_p(edges_ptr),
+                                         n if edges_ptr else 0, 0), "rz_antialias")
+
+    def present_antialiased(self, source="accum", factor=None, sigma_normal=None, sigma_plane=None, demodulate=None,
+                            edge_normal=None, edge_plane=None, fps=0.0, show_fps=True, show_lights=False, show_bvh=False,
+                            bvh_mode=0, selected_blas=0, selected_tri=0, filter=None, **params):
+        """present_display() with the anti-aliasing pass between the source and the display stage: the colour of `source` (as
+        present_display) is anti-aliased, then exposed, toned and encoded (params: as display()), and the overlays are drawn on
+        top.  Returns (rgb float32 (H,W,3), rgba8 uint8 (H,W,4)); factor=1 gives present_display()'s bytes."""
+        if source not in _lib.DISPLAY_SOURCES:
+            raise ValueError(f"source = {source!r}: one of {sorted(_lib.DISPLAY_SOURCES)}")
+        if source == "accum" and filter:
+            raise ValueError("filter parameters need source 'denoise' or 'temporal'")
+        p = _lib.PresentParams(float(fps), int(bool(show_fps)), int(bool(show_lights)), int(bool(show_bvh)),
+                               int(bvh_mode), int(selected_blas), int(selected_tri))
+        ap = self._antialias_params(factor, sigma_normal, sigma_plane, demodulate, edge_normal, edge_plane)
+        dp = self._display_params(**params)
+        fp = None
+        if source == "denoise":
+            f = dict(filter or {})
+            fp = self._denoise_params(*(f.pop(k, None) for k in ("iterations", "sigma_color", "sigma_normal", "sigma_plane", "demodulate")))
+            if f:
+                raise TypeError(f"unknown denoise parameter(s): {sorted(f)}")
+        elif source == "temporal":
+            fp = self._temporal_params(dict(filter or {}))
+        rgb = np.empty((self.height, self.width, 3), np.float32)
+        rgba8 = np.empty((self.height, self.width, 4), np.uint8)
+        self._check(self._L.rz_present_antialiased(self._c, C.byref(p), None if ap is None else C.byref(ap),
+                                                   None if dp is None else C.byref(dp), _lib.DISPLAY_SOURCES[source], fp,
+                                                   rgba8.ctypes.data, rgba8.nbytes, rgb.ctypes.data, rgb.nbytes),
+                    "rz_present_antialiased")
+        return rgb, rgba8
+
     # -- convenience -----------------------------------------------------------
     def render_scene(self, scene, width, height, spp, bounce_budget, num_lights=None, tile_rank=0, tile_nranks=1,
                      chunk=None):
