@@ -447,7 +447,10 @@ int rz_resolve_rgba8(rz_ctx* ctx, uint8_t* rgba8, size_t bytes);
  * the reference always draws them) -- and 8-bit quantisation.  rgba8 (width*height*4 bytes) and rgb32f
  * (width*height*3 floats: the colour before quantisation) may each be NULL.  Row 0 = bottom row.  Synchronises. */
 typedef struct rz_present_params {
-    float   fps;            /* uniformFps */
+    float   fps;            /* uniformFps.  The digits are (int)fps and (int)(fract(fps) * 10), as the shader spells them;
+                             * where that conversion is undefined -- fps non-finite (1 / dt with dt == 0) or
+                             * |fps| >= 2^31 -- the value is taken as 0 and the digits read 000.0.  Every finite
+                             * value below 2^31 in magnitude, negative ones included, is drawn as the shader would. */
     int32_t show_fps;       /* 1 = as the reference */
     int32_t show_lights;    /* debugShowLights */
     int32_t show_bvh;       /* debugShowBVH */

@@ -119,6 +119,9 @@ typedef struct {
 /* accum: width*height*4 floats (rgb sums, a = sample count).  rgb_out (3 floats per pixel) and rgba8_out may be NULL. */
 int rzo_present(const rzo_scene* scene, const rzo_present_params* pp, const float* accum, float* rgb_out,
                 unsigned char* rgba8_out);
+/* The branch rzo_present draws in bvh_mode 1 (findBVHBranchIterative, FS:257-307, with the nodeCount of FS:341-349): node
+ * indices relative to the instance's root in path[0 .. return value), the shader's nodeCount in *node_count (may be NULL). */
+int rzo_bvh_branch(const rzo_scene* scene, int selected_blas, int selected_tri, int path[32], int* node_count);
 
 /* Which sin / cos / acos the oracle evaluates (rz_oracle_math.h): 1 = Mesa llvmpipe's (the default, and what the product is
  * compiled with: rz_math_flavour()), with which frames of RayZen's own shader rendered by oracle/glref agree pixel by pixel at any

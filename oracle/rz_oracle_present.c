@@ -140,6 +140,9 @@ static float draw_font_char(int charIdx, p2 frag, p2 pos, float scale) {
 
 /* FS:164-183 */
 static p3 draw_fps_string(p2 frag, p2 pos, float scale, float fps, p3 fg, p3 bg) {
+    /* int(fps) is undefined in GLSL and in C for a non-finite fps and for |fps| >= 2^31: such a value is taken as 0 and
+     * reads 000.0 (include/rayzen_hip.h, rz_present_params.fps).  Every other value converts as the shader spells it. */
+    if (!(fabsf(fps) < 2147483648.0f)) fps = 0.0f;
     int fpsInt = (int)fps;
     int tenths = (int)(rzo_fract(fps) * 10.0f);
     int chars[5] = {(fpsInt / 100) % 10, (fpsInt / 10) % 10, fpsInt % 10, 10, tenths};
@@ -155,6 +158,21 @@ static p3 draw_fps_string(p2 frag, p2 pos, float scale, float fps, p3 fg, p3 bg)
     return col;
 }
 
+/* FS:341-349: the branch of debugSelectedBLAS / debugSelectedTri.  nodeCount is the shader's: the next instance's node
+ * offset minus this one's (0 or negative when that instance shares the mesh or its mesh lies earlier), and for the last
+ * instance the rest of the node array.  Returns the path length (0: instance out of range, or triangle not found). */
+int rzo_bvh_branch(const rzo_scene* sc, int selected_blas, int selected_tri, int path[32], int* node_count) {
+    if (node_count) *node_count = 0;
+    if (selected_blas < 0 || (size_t)selected_blas >= sc->n_instances) return 0;
+    const rzo_instance* selInst = &sc->instances[selected_blas];
+    const int selNodeOffset = selInst->blasNodeOffset;
+    int nodeCount = ((size_t)selected_blas + 1 < sc->n_instances)
+                        ? sc->instances[selected_blas + 1].blasNodeOffset - selNodeOffset
+                        : (int)sc->n_blas_nodes - selNodeOffset;
+    if (node_count) *node_count = nodeCount;
+    return find_bvh_branch(sc, selNodeOffset, selInst->blasTriOffset, nodeCount, selected_tri, path);
+}
+
 int rzo_present(const rzo_scene* sc, const rzo_present_params* pp, const float* accum, float* rgb_out, unsigned char* rgba8_out) {
     const int W = pp->width, H = pp->height;
     const float resx = (float)W, resy = (float)H;
@@ -165,10 +183,7 @@ int rzo_present(const rzo_scene* sc, const rzo_present_params* pp, const float* 
     if (pp->show_bvh && pp->bvh_mode == 1 && pp->selected_blas >= 0 && (size_t)pp->selected_blas < sc->n_instances) {
         selInst = &sc->instances[pp->selected_blas];
         selNodeOffset = selInst->blasNodeOffset;
-        int nodeCount = ((size_t)pp->selected_blas + 1 < sc->n_instances)
-                            ? sc->instances[pp->selected_blas + 1].blasNodeOffset - selNodeOffset
-                            : (int)sc->n_blas_nodes - selNodeOffset;
-        pathLen = find_bvh_branch(sc, selNodeOffset, selInst->blasTriOffset, nodeCount, pp->selected_tri, path);
+        pathLen = rzo_bvh_branch(sc, pp->selected_blas, pp->selected_tri, path, NULL);
     }
     for (int py = 0; py < H; ++py)
         for (int px = 0; px < W; ++px) {

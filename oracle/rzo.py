@@ -85,6 +85,8 @@ def lib():
         L.rzo_last_threads_busy.argtypes = []
         L.rzo_present.restype = C.c_int
         L.rzo_present.argtypes = [C.POINTER(_Scene), C.POINTER(_Present), C.c_void_p, C.c_void_p, C.c_void_p]
+        L.rzo_bvh_branch.restype = C.c_int
+        L.rzo_bvh_branch.argtypes = [C.POINTER(_Scene), C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_int)]
         L.rzo_trace.restype = C.c_int
         L.rzo_trace.argtypes = [C.POINTER(_Scene), C.c_void_p, C.c_void_p, C.c_void_p]
         L.rzo_shadow.restype = C.c_int
@@ -207,6 +209,15 @@ def present(scene, accum, view, proj, num_lights, fps=0.0, show_fps=True, show_l
     if rc != 0:
         raise RuntimeError("rzo_present failed")
     return rgb, rgba8
+
+
+def bvh_branch(scene, selected_blas, selected_tri):
+    """The branch present(bvh_mode=1) draws: (path, node_count) -- node indices relative to the instance's root, and the
+    shader's nodeCount for that instance (0 or negative when the next instance shares the mesh or its mesh lies earlier)."""
+    path = np.zeros(32, np.int32)
+    nc = C.c_int(0)
+    n = lib().rzo_bvh_branch(C.byref(scene.c), int(selected_blas), int(selected_tri), path.ctypes.data, C.byref(nc))
+    return path[:n].tolist(), nc.value
 
 
 def algorithmic_bytes(c):

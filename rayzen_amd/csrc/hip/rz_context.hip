@@ -2426,7 +2426,9 @@ static int present_impl(rz_ctx* c, const rz_present_params* pp, uint8_t* rgba8, 
         for (int row = 0; row < 4; ++row)
             P.viewProj[col * 4 + row] = ((A[0 * 4 + row] * B[col * 4 + 0] + A[1 * 4 + row] * B[col * 4 + 1]) +
                                          A[2 * 4 + row] * B[col * 4 + 2]) + A[3 * 4 + row] * B[col * 4 + 3];
-    P.fps = pp->fps; P.showFps = pp->show_fps; P.showLights = pp->show_lights; P.showBvh = pp->show_bvh; P.bvhMode = pp->bvh_mode;
+    // rz_present_params.fps: a value whose conversion to int is undefined (non-finite, |fps| >= 2^31) draws 000.0
+    P.fps = (std::isfinite(pp->fps) && std::fabs(pp->fps) < 2147483648.0f) ? pp->fps : 0.0f;
+    P.showFps = pp->show_fps; P.showLights = pp->show_lights; P.showBvh = pp->show_bvh; P.bvhMode = pp->bvh_mode;
     P.pathLen = 0;
     if (pp->show_bvh && pp->bvh_mode == 1 && pp->selected_blas >= 0 && pp->selected_blas < P.nInstances) {
         // findBVHBranchIterative (glsl:257-307) does not depend on the pixel: walk it once here

@@ -14,8 +14,25 @@ namespace rz {
 
 // The 8 projected corners of one box (FS:243-249 for both endpoints of every edge) do not depend on the pixel:
 // rz_project_boxes computes them once per frame with the very same operations, plus a conservative screen-space
-// bounding rectangle (valid corners only, grown by the line thickness and a 1-px guard against rounding) that lets a
-// pixel skip a box none of whose edges can come within `thickness` of it.
+// bounding rectangle that lets a pixel skip a box none of whose edges can come within `thickness` of it.
+//
+// The rectangle, per axis: [lo - g, hi + g], lo / hi = the least / greatest coordinate of the VALID corners (w > 0: an
+// edge is drawn only between two of them), M = max(|lo|, |hi|), the greatest magnitude among those coordinates, and
+//     g = (thickness + 1) + M * 2^-21          (binary32, evaluated as written; lo - g and hi + g likewise).
+// A box without a valid corner has the empty rectangle; one with an infinite valid coordinate has the whole plane.  A
+// NaN coordinate takes no part in lo and hi (minNum / maxNum drop it): an edge that ends there has a NaN distance,
+// which the minimum over the edges drops as well, so it draws nothing (the same holds for an edge that ends at infinity).
+// Why M enters: seg_dist measures the pixel against the point c = RN(a + RN(t * RN(b - a))), t in [0, 1], not against the
+// exact segment.  In one axis, with |a|, |b| <= M and u = 2M * 2^-23 (an ulp in the binade of 2M, which bounds |b - a|):
+// RN(b - a) is off by at most u/2 and t <= 1 passes that on undiminished; the product is at most 2M, its rounding adds
+// at most u/2; the sum ends between the endpoints (up to these errors), its rounding adds at most u/2 again.  So c lies
+// within 3u/2 = 3M * 2^-23 of a point of the exact segment, which lies inside [lo, hi]; a pixel with dist < thickness is
+// within `thickness` of c in either axis, hence within thickness + 3M * 2^-23 of [lo, hi].  (M is taken over the whole
+// box, not per edge: it is at least the M of every edge's own two endpoints, so the bound holds edge by edge.)  The fourth
+// M * 2^-23 pays for the rounding of g and of lo - g, hi + g; the 1 px pays for the roundings after c (the two
+// differences, the squares, their sum, the root: a few 2^-24 relative to a distance below 2).  With every corner on a
+// screen of 4096 px the term is below 0.002 px; with a corner 2^27 px away (a box corner just in front of the camera
+// plane) it is 64 px, where the drawn segment can miss the corner at its near end by up to 3u/2 = 48 px.
 struct ProjBox { float sx[8], sy[8], sw[8]; float lox, loy, hix, hiy; };
 
 __constant__ int kFontRows[11][8] = {
@@ -65,11 +82,12 @@ __device__ void project_box(const float* mn, const float* mx, const float* vp, f
             loy = fmin_(loy, B.sy[c]); hiy = fmax_(hiy, B.sy[c]);
         }
     }
-    // NaN/inf corners: keep the box (rectangle = everything)
+    // inf corners: keep the box (rectangle = everything)
     const bool finite = (lox - lox == 0.0f) && (hix - hix == 0.0f) && (loy - loy == 0.0f) && (hiy - hiy == 0.0f);
-    const float g = thickness + 1.0f;
-    B.lox = finite ? lox - g : -3.0e38f; B.hix = finite ? hix + g : 3.0e38f;
-    B.loy = finite ? loy - g : -3.0e38f; B.hiy = finite ? hiy + g : 3.0e38f;
+    const float gx = (thickness + 1.0f) + fmax_(__builtin_fabsf(lox), __builtin_fabsf(hix)) * 0x1p-21f;
+    const float gy = (thickness + 1.0f) + fmax_(__builtin_fabsf(loy), __builtin_fabsf(hiy)) * 0x1p-21f;
+    B.lox = finite ? lox - gx : -3.0e38f; B.hix = finite ? hix + gx : 3.0e38f;
+    B.loy = finite ? loy - gy : -3.0e38f; B.hiy = finite ? hiy + gy : 3.0e38f;
 }
 // FS:229-254, second half: distance of this pixel to the 12 edges
 __device__ __forceinline__ float box_wire(const ProjBox& B, float fx, float fy, float thickness) {
