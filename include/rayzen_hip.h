@@ -1083,6 +1083,53 @@ int rz_present_antialiased(rz_ctx* ctx, const rz_present_params* present, const 
                            const rz_display_params* display, int source, const void* filter_params,
                            uint8_t* rgba8, size_t rgba8_bytes, float* rgb32f, size_t rgb32f_bytes);
 
+/* ------------------------------------------------------------------------ */
+/* Anti-aliased edges seen through glass and in mirrors (new)               */
+/* ------------------------------------------------------------------------ */
+/* rz_antialias' guides are first hits (its LIMITS): a pixel in the middle of a pane is flat to its classifier, so the silhouette
+ * of what stands behind the pane stays stair-stepped, and a pixel on the pane's border is reconstructed with first-hit
+ * admissibility, which mixes colour across the edge seen through it.  These entry points classify and reconstruct on the
+ * see-through records of rz_upscale_seethrough (rz_antialias_seethrough.hip).  Everything of rz_antialias stands as written
+ * except the guide, the DIFFERENT rule and which upsampler defines a sub-pixel.
+ *  record    of pixel p: rz_upscale_seethrough's chain record at the frame's own size w x h for this call's max_depth.
+ *            G_p = (hit or miss of the FINAL query; x, n and clamped material m of the final hit; t = L), T_p the throughput,
+ *            cls_p = 0 if k == 0, else m_first + 1 -- bit for bit what rz_upscale_seethrough at factor 1 returns in guides and
+ *            chains.
+ *  DIFFERENT q is DIFFERENT from p when rz_antialias' rule holds on these FINAL records (hit status, material, edge_normal,
+ *            edge_plane with t_p = L_p, k_e unchanged) or cls_q != cls_p.  Binary32, one rounding per operation, no fused
+ *            multiply-add; tests/antialias_seethrough_ref.py reproduces it bit for bit.
+ *  EDGE      as in rz_antialias: c_p bad, or any of the up to eight neighbours inside the image DIFFERENT.
+ *  flat      out = c_p exactly.
+ *  edge      out = the binary32 mean, b outer and a inner, of u_(a, b), where u_(a, b) is what rz_upscale_seethrough defines for
+ *            high pixel (s x + a, s y + b) of an s w x s h output of THIS frame at factor s with this call's max_depth, sigmas
+ *            and demodulate: the chain of that high pixel, alpha = T * albedo, the class term in admissibility and stages 1 to 3
+ *            are stated there.
+ * So max_depth = 0, or a scene in which no pixel's chain moves, gives rz_antialias' bytes exactly (colour, edges, guides);
+ * factor 1 gives c exactly; rz_present_antialiased_seethrough at factor 1 gives rz_present_display's bytes.
+ * LIMITS.  Surfaces with 0 < reflectivity < 1 are not followed.  Classification still sees pixel centres only.  On curved glass
+ * neighbouring final hits jump, so much of a glass blob classifies as edge: this is correct, and costs s^2 chains per pixel there.
+ * Measured with the restatement on the CPU oracle's frames (tests/test_antialias_seethrough_abi.py; 80 x 60 at 8 spp, 5 bounces,
+ * s = 2, against the oracle's frame at twice the size and 64 spp, box-averaged): the mean squared error on the edge pixels whose
+ * chain moves drops 18 x (RayZen's own scene) and 2.4 x (bunny_scene with its glass blob and mirror cube) against rz_antialias,
+ * and over the whole frame 1.10 x and 1.47 x.  Cost at 1080p, s = 2 (profiles/antialias_seethrough/README.md): 0.40 ms where
+ * nothing is specular, 1.4 ms with a glass blob and a mirror cube in view (rz_upscale_seethrough at factor 2: 0.77 and 2.0 ms).
+ * rz_antialias_seethrough is rz_antialias with: seethrough (NULL: max_depth 8); guides = the rz_hit of the FINAL hit with t = L;
+ * chains, optional, w*h rz_chain, 16-byte aligned on the device path.  Pointers, alignment, RZ_ANTIALIAS_HOST, stream, backstop
+ * and "a failing call launches nothing" are rz_antialias'; in addition a max_depth outside 0..8 or a non-zero reserved word of
+ * rz_seethrough_params is RZ_ERR_INVALID_ARG and a chains buffer that is too small RZ_ERR_BUFFER_SIZE.  rz_antialias_params.reserved
+ * stays must-be-zero.  The calls touch no render, temporal or display state; the frame-size chain records live in the
+ * see-through low-guide buffer, and the list of edge pixels between the pass's two kernels in a
+ * buffer of its own.  rz_present_antialiased_seethrough is rz_present_antialiased with this pass.
+ * (Additive: RZ_ABI_VERSION stays 5; no new struct, rz_sizeof(25) and rz_sizeof(27) stay 0.) */
+int rz_antialias_seethrough(rz_ctx* ctx, const rz_antialias_params* params, const rz_seethrough_params* seethrough,
+                            const float* rgb_in, size_t rgb_in_bytes, float* rgb32f, size_t rgb32f_bytes,
+                            rz_hit* guides, size_t guides_bytes, rz_chain* chains, size_t chains_bytes,
+                            uint8_t* edges, size_t edges_bytes, unsigned flags);
+int rz_present_antialiased_seethrough(rz_ctx* ctx, const rz_present_params* present, const rz_antialias_params* antialias,
+                                      const rz_seethrough_params* seethrough, const rz_display_params* display, int source,
+                                      const void* filter_params, uint8_t* rgba8, size_t rgba8_bytes,
+                                      float* rgb32f, size_t rgb32f_bytes);
+
 /* Number of HIP devices visible to the process (0 without a GPU). */
 int rz_device_count(void);
 

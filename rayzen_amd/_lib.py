@@ -29,7 +29,7 @@ HIP_SYMBOLS = (
     "rz_skin_create", "rz_skin_pose", "rz_skin_destroy", "rz_skin_last_kernel_ms",
     "rz_geometry_quality", "rz_rebuild_geometry",
     "rz_upscale", "rz_present_upscaled", "rz_upscale_seethrough", "rz_present_upscaled_seethrough",
-    "rz_antialias", "rz_present_antialiased",
+    "rz_antialias", "rz_present_antialiased", "rz_antialias_seethrough", "rz_present_antialiased_seethrough",
 )
 ABI_VERSION = 5         # RZ_ABI_VERSION of the include/rayzen_hip.h this file mirrors
 # the symbols include/rayzen_host.h declares
@@ -313,7 +313,9 @@ def hip():
                                 ("rz_upscale_seethrough", i, [vp, vp, vp, vp, sz, vp, sz, vp, sz, vp, sz, C.c_uint]),
                                 ("rz_present_upscaled_seethrough", i, [vp, C.POINTER(PresentParams), vp, vp, vp, i, vp, vp, sz, vp, sz]),
                                 ("rz_antialias", i, [vp, vp, vp, sz, vp, sz, vp, sz, vp, sz, C.c_uint]),
-                                ("rz_present_antialiased", i, [vp, C.POINTER(PresentParams), vp, vp, i, vp, vp, sz, vp, sz])):
+                                ("rz_present_antialiased", i, [vp, C.POINTER(PresentParams), vp, vp, i, vp, vp, sz, vp, sz]),
+                                ("rz_antialias_seethrough", i, [vp, vp, vp, vp, sz, vp, sz, vp, sz, vp, sz, vp, sz, C.c_uint]),
+                                ("rz_present_antialiased_seethrough", i, [vp, C.POINTER(PresentParams), vp, vp, vp, i, vp, vp, sz, vp, sz])):
             try:
                 fn = getattr(L, name)
                 fn.restype, fn.argtypes = res, args

@@ -176,6 +176,9 @@ struct rz_ctx {
     // rz_upscale_seethrough / rz_present_upscaled_seethrough (rz_seethrough.hip): the chain guides at both sizes (3 float4 per
     // pixel each); allocated on first use and kept.  The first-hit buffers above are not touched by those calls.
     DevBuf dStGuideLo, dStGuideHi;
+    // rz_antialias_seethrough (rz_antialias_seethrough.hip): the edge pixels its classifying waves found, a segment per wave,
+    // and the segments' counts; allocated on first use and kept
+    DevBuf dAasList, dAasCounts;
     // rz_refit_geometry (rz_refit.hip)
     bool trisHostStale = false;         // binding 0 on the device (dRawTris) is newer than the host copy: fetched on demand (sync_tris_host)
     unsigned long long layoutGen = 0;   // counts the times the views / instances were laid out
@@ -1187,7 +1190,7 @@ void rz_destroy(rz_ctx* c) {
                       &c->dTmpCol[0], &c->dTmpCol[1], &c->dTmpMom[0], &c->dTmpMom[1], &c->dTmpHits[0], &c->dTmpHits[1],
                       &c->dTmpInst[0], &c->dTmpInst[1], &c->dTmpSame, &c->dDisplay, &c->dSkinOut, &c->dSkinBones, &c->dSkinWeights,
                       &c->dQualViews, &c->dQualPartials, &c->dQualCost, &c->dUpGuideLo, &c->dUpGuideHi, &c->dUpOut,
-                      &c->dStGuideLo, &c->dStGuideHi})
+                      &c->dStGuideLo, &c->dStGuideHi, &c->dAasList, &c->dAasCounts})
         b->release();
     for (auto& kv : c->rigs) kv.second.release();
     for (hipEvent_t e : c->evSkin) if (e) (void)hipEventDestroy(e);
@@ -3385,9 +3388,12 @@ static int antialias_check(rz_ctx* c, const char* what, const rz_antialias_param
 // Casts the frame-size guide, classifies and anti-aliases, on the stream.  The frame (device) is in3 (3 floats per pixel) or in4
 // (RGBA32F sum and count); outputs (device, frame size, each optional): rgb (3 floats per pixel), out4 ((colour, 1)), hits
 // (rz_hit), edges (a byte per pixel).  Factor 1 without `edges` casts nothing unless hits are asked for.
+// rz_antialias_seethrough / rz_present_antialiased_seethrough (rz_antialias_seethrough.hip) pass `st`: the frame-size records are
+// then the chain records (48 B, in the see-through low-guide buffer), `chains` (rz_chain) is one more optional output, and the
+// kernel is the one that follows the chains.  With `st` null every launch and buffer is the first-hit call's, unchanged.
 static int antialias_run(rz_ctx* c, const rz_antialias_params& P, const float* in3, const float4* in4, float* rgb, float4* out4,
-                         float4* hits, uint8_t* edges) {
-    if (!rgb && !out4 && !hits && !edges) return RZ_OK;
+                         float4* hits, uint8_t* edges, const rz_seethrough_params* st = nullptr, float4* chains = nullptr) {
+    if (!rgb && !out4 && !hits && !edges && !chains) return RZ_OK;
     const rz_frame_params& f = c->frame;
     const size_t np = (size_t)f.width * f.height;
     int rc = finalize(c);
@@ -3406,17 +3412,18 @@ static int antialias_run(rz_ctx* c, const rz_antialias_params& P, const float* i
             RZ_HIP(c, hipMemcpyAsync(rgb, in3, np * 12, hipMemcpyDeviceToDevice, c->stream));
         }
     }
-    if (!kernel && !hits) return RZ_OK;
+    if (!kernel && !hits && !chains) return RZ_OK;
     rc = cast_ready(c);
     if (rc != RZ_OK) return rc;
-    rc = ensure(c, c->dUpGuideLo, np * 32);
+    DevBuf& bufLo = st ? c->dStGuideLo : c->dUpGuideLo;
+    rc = ensure(c, bufLo, np * (st ? 48 : 32));
     if (rc != RZ_OK) return rc;
-    float4* guide = static_cast<float4*>(c->dUpGuideLo.p);
-    rc = guide_cast(c, f.width, f.height, guide, hits);
+    float4* guide = static_cast<float4*>(bufLo.p);
+    rc = st ? seethrough_cast(c, f.width, f.height, st->max_depth, guide, hits, chains) : guide_cast(c, f.width, f.height, guide, hits);
     if (rc != RZ_OK || !kernel) return rc;
     KParams K{};
-    AntialiasLaunch A{};
-    rc = cast_wiring(c, f.width, f.height, K, A, RZ_AA_QUEUE * sizeof(int));
+    AntialiasSeethroughLaunch A{};          // (AntialiasLaunch and the chain's bound; the first-hit kernel takes the base)
+    rc = cast_wiring(c, f.width, f.height, K, A, st ? 0 : RZ_AA_QUEUE * sizeof(int));
     if (rc != RZ_OK) return rc;
     A.U.in3 = in4 ? nullptr : in3;
     A.U.in4 = in4;
@@ -3433,27 +3440,43 @@ static int antialias_run(rz_ctx* c, const rz_antialias_params& P, const float* i
     A.edges = edges;
     A.edgeNormal = P.edge_normal;
     A.edgePlane = (float)((double)P.edge_plane * fpx);
-    launch_antialias(K, A, c->stream);
+    A.maxDepth = st ? st->max_depth : 0;
+    if (st) {                               // the list between the two kernels: a segment per wave of the grid
+        A.segCap = (int)((A.units + A.grid - 1) / A.grid) * 64;
+        rc = ensure(c, c->dAasList, (size_t)A.grid * A.segCap * sizeof(int));
+        if (rc == RZ_OK) rc = ensure(c, c->dAasCounts, (size_t)A.grid * sizeof(int));
+        if (rc != RZ_OK) return rc;
+        A.list = static_cast<int*>(c->dAasList.p);
+        A.counts = static_cast<int*>(c->dAasCounts.p);
+    }
+    if (st) launch_antialias_seethrough(K, A, c->stream);
+    else launch_antialias(K, A, c->stream);
     RZ_HIP(c, hipGetLastError());
     return RZ_OK;
 }
 
 static int antialias_impl(rz_ctx* c, const rz_antialias_params* pp, const float* rgb_in, size_t rgb_in_bytes, float* rgb32f,
-                          size_t rgb32f_bytes, rz_hit* guides, size_t guides_bytes, uint8_t* edges, size_t edges_bytes, unsigned flags) {
-    const char* what = "rz_antialias";
+                          size_t rgb32f_bytes, rz_hit* guides, size_t guides_bytes, uint8_t* edges, size_t edges_bytes, unsigned flags,
+                          const rz_seethrough_params* st = nullptr, rz_chain* chains = nullptr, size_t chains_bytes = 0) {
+    const char* what = st ? "rz_antialias_seethrough" : "rz_antialias";
     if (!c) return fail(nullptr, RZ_ERR_INVALID_ARG, "%s: null context", what);
     if (flags & ~RZ_ANTIALIAS_HOST) return fail(c, RZ_ERR_INVALID_ARG, "%s: unknown flags 0x%x", what, flags);
     const rz_antialias_params& P = pp ? *pp : kAntialiasDefaults;
     int rc = antialias_check(c, what, P);
     if (rc != RZ_OK) return rc;
+    if (st) {
+        rc = seethrough_check(c, what, *st);
+        if (rc != RZ_OK) return rc;
+    }
     const bool host = (flags & RZ_ANTIALIAS_HOST) != 0;
-    if (!host && ((reinterpret_cast<uintptr_t>(guides) & 15u) ||
+    if (!host && (((reinterpret_cast<uintptr_t>(guides) | reinterpret_cast<uintptr_t>(chains)) & 15u) ||
                   ((reinterpret_cast<uintptr_t>(rgb_in) | reinterpret_cast<uintptr_t>(rgb32f)) & 3u)))
-        return fail(c, RZ_ERR_INVALID_ARG, "%s: device pointers must be 16-byte (guides) or 4-byte (rgb_in, rgb32f) aligned", what);
+        return fail(c, RZ_ERR_INVALID_ARG, "%s: device pointers must be 16-byte (guides%s) or 4-byte (rgb_in, rgb32f) aligned", what,
+                    st ? ", chains" : "");
     if (!host && rgb32f && rgb32f == rgb_in)
         return fail(c, RZ_ERR_INVALID_ARG, "%s: rgb32f must not be rgb_in (an edge pixel reads its neighbours)", what);
     const size_t np = (size_t)c->frame.width * c->frame.height;
-    const size_t bRgb = np * 3 * sizeof(float), bHits = np * sizeof(rz_hit);
+    const size_t bRgb = np * 3 * sizeof(float), bHits = np * sizeof(rz_hit), bChains = np * sizeof(rz_chain);
     if (rgb_in && rgb_in_bytes < bRgb) return fail(c, RZ_ERR_BUFFER_SIZE, "%s: rgb_in needs %zu bytes, got %zu", what, bRgb, rgb_in_bytes);
     if (!rgb_in) {
         rc = accum_fits(c, what);
@@ -3462,16 +3485,19 @@ static int antialias_impl(rz_ctx* c, const rz_antialias_params* pp, const float*
     if (rgb32f && rgb32f_bytes < bRgb) return fail(c, RZ_ERR_BUFFER_SIZE, "%s: rgb32f needs %zu bytes, got %zu", what, bRgb, rgb32f_bytes);
     if (guides && guides_bytes < bHits) return fail(c, RZ_ERR_BUFFER_SIZE, "%s: guides needs %zu bytes, got %zu", what, bHits, guides_bytes);
     if (edges && edges_bytes < np) return fail(c, RZ_ERR_BUFFER_SIZE, "%s: edges needs %zu bytes, got %zu", what, np, edges_bytes);
-    if (!rgb32f && !guides && !edges) return RZ_OK;
+    if (chains && chains_bytes < bChains) return fail(c, RZ_ERR_BUFFER_SIZE, "%s: chains needs %zu bytes, got %zu", what, bChains, chains_bytes);
+    if (!rgb32f && !guides && !edges && !chains) return RZ_OK;
     const float* in3 = rgb_in;
     const float4* in4 = rgb_in ? nullptr : static_cast<const float4*>(rz_accum_device_ptr(c));
-    // host buffers are staged as rz_upscale stages them: the input in dRayIn; guides, then rgb32f, then edges in dRayOut
+    // host buffers are staged as rz_upscale stages them: the input in dRayIn; guides, then rgb32f, then edges, then chains in dRayOut
     HostStage stage(c, host);
     const int sHits = stage.add(guides, bHits), sRgb = stage.add(rgb32f, bRgb), sEdges = stage.add(edges, np);
+    const int sChains = stage.add(chains, bChains);
     rc = stage.input(rgb_in, bRgb, in3);
     if (rc == RZ_OK) rc = stage.place();
     if (rc != RZ_OK) return rc;
-    rc = antialias_run(c, P, in3, in4, stage.dev<float>(sRgb), nullptr, stage.dev<float4>(sHits), stage.dev<uint8_t>(sEdges));
+    rc = antialias_run(c, P, in3, in4, stage.dev<float>(sRgb), nullptr, stage.dev<float4>(sHits), stage.dev<uint8_t>(sEdges), st,
+                       stage.dev<float4>(sChains));
     if (rc != RZ_OK) return rc;
     if (!host) return RZ_OK;
     rc = stage.fetch();
@@ -3481,8 +3507,8 @@ static int antialias_impl(rz_ctx* c, const rz_antialias_params* pp, const float*
 
 static int present_antialiased_impl(rz_ctx* c, const rz_present_params* pp, const rz_antialias_params* ap, const rz_display_params* dp,
                                     int source, const void* filter_params, uint8_t* rgba8, size_t rgba8_bytes, float* rgb32f,
-                                    size_t rgb32f_bytes) {
-    const char* what = "rz_present_antialiased";
+                                    size_t rgb32f_bytes, const rz_seethrough_params* st = nullptr) {
+    const char* what = st ? "rz_present_antialiased_seethrough" : "rz_present_antialiased";
     if (!c) return fail(nullptr, RZ_ERR_INVALID_ARG, "%s: null context", what);
     if (!pp) return fail(c, RZ_ERR_INVALID_ARG, "%s: null present params", what);
     const rz_antialias_params& A = ap ? *ap : kAntialiasDefaults;
@@ -3492,6 +3518,10 @@ static int present_antialiased_impl(rz_ctx* c, const rz_present_params* pp, cons
     if (rc != RZ_OK) return rc;
     rc = antialias_check(c, what, A);
     if (rc != RZ_OK) return rc;
+    if (st) {
+        rc = seethrough_check(c, what, *st);
+        if (rc != RZ_OK) return rc;
+    }
     // factor 1: nothing to average, the call IS rz_present_display (its bytes exactly, for every source)
     if (A.factor == 1) return present_display_impl(c, pp, dp, source, filter_params, rgba8, rgba8_bytes, rgb32f, rgb32f_bytes);
     const size_t np = (size_t)c->frame.width * c->frame.height;
@@ -3509,7 +3539,7 @@ static int present_antialiased_impl(rz_ctx* c, const rz_present_params* pp, cons
         if (rc != RZ_OK) return rc;
         in4 = out4;
     }
-    rc = antialias_run(c, A, nullptr, in4, nullptr, aa4, nullptr, nullptr);
+    rc = antialias_run(c, A, nullptr, in4, nullptr, aa4, nullptr, nullptr, st);
     if (rc != RZ_OK) return rc;
     rc = display_run(c, D, nullptr, aa4, nullptr, nullptr, aa4, false);
     if (rc != RZ_OK) return rc;
@@ -3758,6 +3788,22 @@ int rz_present_antialiased(rz_ctx* c, const rz_present_params* present, const rz
                            float* rgb32f, size_t rgb32f_bytes) {
     return guarded(c, "rz_present_antialiased", [&] {
         return present_antialiased_impl(c, present, antialias, display, source, filter_params, rgba8, rgba8_bytes, rgb32f, rgb32f_bytes);
+    });
+}
+int rz_antialias_seethrough(rz_ctx* c, const rz_antialias_params* params, const rz_seethrough_params* seethrough, const float* rgb_in,
+                            size_t rgb_in_bytes, float* rgb32f, size_t rgb32f_bytes, rz_hit* guides, size_t guides_bytes, rz_chain* chains,
+                            size_t chains_bytes, uint8_t* edges, size_t edges_bytes, unsigned flags) {
+    return guarded(c, "rz_antialias_seethrough", [&] {
+        return antialias_impl(c, params, rgb_in, rgb_in_bytes, rgb32f, rgb32f_bytes, guides, guides_bytes, edges, edges_bytes, flags,
+                              seethrough ? seethrough : &kSeethroughDefaults, chains, chains_bytes);
+    });
+}
+int rz_present_antialiased_seethrough(rz_ctx* c, const rz_present_params* present, const rz_antialias_params* antialias,
+                                      const rz_seethrough_params* seethrough, const rz_display_params* display, int source,
+                                      const void* filter_params, uint8_t* rgba8, size_t rgba8_bytes, float* rgb32f, size_t rgb32f_bytes) {
+    return guarded(c, "rz_present_antialiased_seethrough", [&] {
+        return present_antialiased_impl(c, present, antialias, display, source, filter_params, rgba8, rgba8_bytes, rgb32f, rgb32f_bytes,
+                                        seethrough ? seethrough : &kSeethroughDefaults);
     });
 }
 int rz_display_reset(rz_ctx* c) {

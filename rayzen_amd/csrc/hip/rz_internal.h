@@ -132,6 +132,15 @@ struct SeethroughGuideLaunch {  // rz_seethrough_guides: DenoiseGuideLaunch with
 void launch_seethrough_guides(const KParams& K, const SeethroughGuideLaunch& G, hipStream_t stream);
 void launch_seethrough_gather(const UpscaleLaunch& U, hipStream_t stream);     // guideLo / guideHi: SeethroughGuideLaunch::rec
 
+// ---- rz_antialias_seethrough.hip
+struct AntialiasSeethroughLaunch : AntialiasLaunch {    // both kernels: U.guideLo = SeethroughGuideLaunch::rec at w x h
+    int maxDepth;               // rz_seethrough_params.max_depth, 0..8
+    int segCap;                 // entries of a wave's segment of `list`: 64 x ceil(units / grid)
+    int* list;                  // grid x segCap pixel indices: the edge pixels each classifying wave found
+    int* counts;                // grid: how many
+};
+void launch_antialias_seethrough(const KParams& K, const AntialiasSeethroughLaunch& A, hipStream_t stream);
+
 // ---- rz_temporal.hip
 struct TemporalLaunch {         // rz_temporal_accumulate
     const float4* accum;        // RGBA32F sum and count

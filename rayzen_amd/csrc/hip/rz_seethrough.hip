@@ -21,6 +21,7 @@
 #include "rz_upscale_body.h"
 #include "rz_query.h"
 #include "rz_path.h"
+#include "rz_chain_step.h"
 
 namespace rz {
 
@@ -57,47 +58,7 @@ __global__ __launch_bounds__(64, RZ_RAYS_MIN_WAVES) void rz_seethrough_guides(co
                 if (found) {
                     h = hq;
                     tri = x.tri;
-                    L = L + hq.t;
-                    const int m = min(max(hq.mat, 0), K.nMaterials - 1);
-                    if (k == 0) first = m;
-                    const DevMaterial M = K.materials[m];
-                    const v3 hitNormal = hq.n;
-                    v3 dir = d;
-                    if (k == G.maxDepth) {
-                        // the chain is exhausted on this surface, specular or not
-                    } else if (M.transparency > 0.0f) {     // scatter(): FS:723-746
-                        const bool entering = dot(-dir, hitNormal) > 0.0f;
-                        const v3 N = entering ? hitNormal : -hitNormal;
-                        const float extIor = ior;
-                        const float nextIor = entering ? M.ior : 1.0f;
-                        const float eta = extIor / nextIor;
-                        const float cosi = clamp_(dot(-dir, N), 0.0f, 1.0f);
-                        const float F0 = pow2_((extIor - nextIor) / (extIor + nextIor));
-                        const float fresnel = F0 + (1.0f - F0) * pow5_(1.0f - cosi);
-                        v3 refr;
-                        if (!refract_dir(dir, N, eta, refr)) {
-                            dir = reflect_ray(dir, N);
-                            T = T * 0.98f;
-                        } else {
-                            dir = refr;
-                            ior = nextIor;
-                            const float tr = M.transparency;
-                            const v3 tint = mk3(mix_(1.0f, M.albedo[0], tr), mix_(1.0f, M.albedo[1], tr), mix_(1.0f, M.albedo[2], tr));
-                            const v3 tw = (tint * tr) * (1.0f - fresnel);
-                            T = T * mk3(clamp_(tw.x, 0.0f, 1.0f), clamp_(tw.y, 0.0f, 1.0f), clamp_(tw.z, 0.0f, 1.0f));
-                        }
-                        run = true;
-                    } else if (M.reflectivity >= 1.0f) {    // scatter(): randVal < reflectivity holds for every randVal in [0, 1)
-                        dir = reflect_ray(dir, hitNormal);
-                        T = T * 0.95f;
-                        run = true;
-                    }
-                    if (run) {
-                        const float pushDir = dot(dir, hitNormal) > 0.0f ? 1.0f : -1.0f;
-                        o = hq.p + (hitNormal * pushDir) * 0.003f;
-                        d = dir;
-                        k += 1;
-                    }
+                    run = chain_step(K, G.maxDepth, hq, o, d, T, ior, L, k, first);     // rz_chain_step.h
                 }
             }
         }

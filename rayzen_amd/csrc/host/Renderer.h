@@ -14,7 +14,8 @@
 //   presentUpscaled()                  <- new: render below display size, reconstruct at display size (rz_present_upscaled,
 //                                         and rz_present_upscaled_seethrough: guides that follow glass and mirrors)
 //   presentDisplay() / resetDisplay()  <- new: exposure, tone curve and sRGB encode in front of present (rz_present_display;
-//                                         with an rz_antialias_params: rz_present_antialiased, anti-aliased edges)
+//                                         with an rz_antialias_params: rz_present_antialiased, anti-aliased edges; with an
+//                                         rz_seethrough_params too: rz_present_antialiased_seethrough)
 // Unlike the reference's per-frame path, updateDynamicBVHAndSSBOs re-uploads
 // only what changed (instances + TLAS, a few KB), not all geometry.
 //
@@ -36,7 +37,7 @@
 #include "RayZenScene.h"
 #include "rayzen_hip.h"
 
-// The first of the two entry points of the front end that are referenced WEAKLY: a program linked against a library from before it, or against
+// The first of the three entry points of the front end that are referenced WEAKLY: a program linked against a library from before it, or against
 // a stand-in that defines only what it exercises, still links, and presentUpscaled(..., &seeThrough) throws there.
 extern "C" int rz_present_upscaled_seethrough(rz_ctx* ctx, const rz_present_params* present, const rz_upscale_params* upscale,
                                               const rz_seethrough_params* seethrough, const rz_display_params* display, int source,
@@ -46,6 +47,11 @@ extern "C" int rz_present_upscaled_seethrough(rz_ctx* ctx, const rz_present_para
 extern "C" int rz_present_antialiased(rz_ctx* ctx, const rz_present_params* present, const rz_antialias_params* antialias,
                                       const rz_display_params* display, int source, const void* filter_params, uint8_t* rgba8,
                                       size_t rgba8_bytes, float* rgb32f, size_t rgb32f_bytes) __attribute__((weak));
+// ... and rz_present_antialiased_seethrough: presentDisplay(..., &antialias, &seeThrough) throws where it is absent.
+extern "C" int rz_present_antialiased_seethrough(rz_ctx* ctx, const rz_present_params* present, const rz_antialias_params* antialias,
+                                                 const rz_seethrough_params* seethrough, const rz_display_params* display, int source,
+                                                 const void* filter_params, uint8_t* rgba8, size_t rgba8_bytes, float* rgb32f,
+                                                 size_t rgb32f_bytes) __attribute__((weak));
 
 namespace rayzen {
 
@@ -332,10 +338,19 @@ public:
     // rz_denoise_temporal's (an rz_temporal_params* or null; the history advances).  display null: present()'s bytes.
     // antialias non-null: rz_present_antialiased, which averages factor x factor sub-pixel reconstructions on the pixels that
     // have a geometric edge, between the source and the display stage (factor 1: the bytes without it); null: rz_present_display.
+    // seeThrough non-null: rz_present_antialiased_seethrough, the same pass on guides that follow glass and perfect mirrors for
+    // at most max_depth steps, so that edges seen through them are smoothed too (antialias null: its defaults).
     std::vector<uint8_t> presentDisplay(const rz_present_params& present, const rz_display_params* display = nullptr, int source = 0,
-                                        const void* filter = nullptr, const rz_antialias_params* antialias = nullptr) {
+                                        const void* filter = nullptr, const rz_antialias_params* antialias = nullptr,
+                                        const rz_seethrough_params* seeThrough = nullptr) {
         std::vector<uint8_t> out((size_t)width_ * (size_t)height_ * 4);
-        if (antialias) {
+        if (seeThrough) {
+            if (&rz_present_antialiased_seethrough == nullptr)
+                throw std::runtime_error("rz_present_antialiased_seethrough: the linked library does not have it");
+            check(rz_present_antialiased_seethrough(ctx_, &present, antialias, seeThrough, display, source, filter, out.data(), out.size(),
+                                                    nullptr, 0),
+                  "rz_present_antialiased_seethrough");
+        } else if (antialias) {
             if (&rz_present_antialiased == nullptr) throw std::runtime_error("rz_present_antialiased: the linked library does not have it");
             check(rz_present_antialiased(ctx_, &present, antialias, display, source, filter, out.data(), out.size(), nullptr, 0),
                   "rz_present_antialiased");

@@ -850,18 +850,34 @@ class Renderer:
         return p
 
     def antialias(self, rgb=None, factor=None, sigma_normal=None, sigma_plane=None, demodulate=None, edge_normal=None,
-                  edge_plane=None, guides=False, edges=False):
+                  edge_plane=None, guides=False, edges=False, see_through=None, chains=False):
         """Edge anti-aliasing (include/rayzen_hip.h: rz_antialias) of rgb ((h, w, 3) float32 linear colour) or, with rgb None, of
         the accumulation, at the size of the last set_frame: a pixel with a geometric edge in its 3 x 3 neighbourhood becomes the
         mean of factor x factor sub-pixel reconstructions, every other pixel keeps its colour bit for bit (host memory; returns
         when done).  guides=True appends the frame-size G-buffer as (h, w) HIT_DTYPE records, edges=True the (h, w) bool edge
         mask; row 0 = bottom row.  Parameters left None take the library's defaults (factor 2, sigma_normal 128, sigma_plane 1,
-        demodulate on, edge_normal 0.9, edge_plane 1)."""
+        demodulate on, edge_normal 0.9, edge_plane 1).
+        see_through = 0..8 (or True: 8) takes rz_antialias_seethrough instead: the pass classifies and reconstructs on guides
+        that follow glass and perfect mirrors for at most that many steps, so edges seen through them are smoothed too; the
+        guides are then the FINAL hits with t = the length of the chain, and chains=True appends the (h, w) CHAIN_DTYPE records
+        after the guides.  None is rz_antialias."""
         ap = self._antialias_params(factor, sigma_normal, sigma_plane, demodulate, edge_normal, edge_plane)
         src = None if rgb is None else np.ascontiguousarray(rgb, np.float32)
         out = np.empty((self.height, self.width, 3), np.float32)
         hh = np.empty(out.shape[:2], HIT_DTYPE) if guides else None
         ee = np.empty(out.shape[:2], np.uint8) if edges else None
+        if see_through is not None:
+            st = self._seethrough_params(see_through)
+            ch = np.empty(out.shape[:2], CHAIN_DTYPE) if chains else None
+            self._check(self._L.rz_antialias_seethrough(
+                self._c, None if ap is None else C.byref(ap), C.byref(st), None if src is None else src.ctypes.data,
+                0 if src is None else src.nbytes, out.ctypes.data, out.nbytes, None if hh is None else hh.ctypes.data,
+                0 if hh is None else hh.nbytes, None if ch is None else ch.ctypes.data, 0 if ch is None else ch.nbytes,
+                None if ee is None else ee.ctypes.data, 0 if ee is None else ee.nbytes, _lib.ANTIALIAS_HOST), "rz_antialias_seethrough")
+            res = (out,) + ((hh,) if guides else ()) + ((ch,) if chains else ()) + ((ee.astype(bool),) if edges else ())
+            return res if len(res) > 1 else out
+        if chains:
+            raise ValueError("chains=True needs see_through")
         self._check(self._L.rz_antialias(self._c, None if ap is None else C.byref(ap), None if src is None else src.ctypes.data,
                                          0 if src is None else src.nbytes, out.ctypes.data, out.nbytes,
                                          None if hh is None else hh.ctypes.data, 0 if hh is None else hh.nbytes,
@@ -871,11 +887,22 @@ class Renderer:
         return res if len(res) > 1 else out
 
     def antialias_device(self, rgb_in_ptr=None, rgb32f_ptr=None, guides_ptr=None, edges_ptr=None, factor=None, sigma_normal=None,
-                         sigma_plane=None, demodulate=None, edge_normal=None, edge_plane=None):
+                         sigma_plane=None, demodulate=None, edge_normal=None, edge_plane=None, see_through=None, chains_ptr=None):
         """rz_antialias on device memory (guides 16-B aligned, rgb_in and rgb32f 4-B and distinct; each optional): enqueued on
-        the context's stream, asynchronous.  Sizes: rgb_in and rgb32f w*h*12 B, guides w*h*48 B, edges w*h B."""
+        the context's stream, asynchronous.  Sizes: rgb_in and rgb32f w*h*12 B, guides w*h*48 B, edges w*h B.
+        see_through = 0..8 (or True): rz_antialias_seethrough, with chains_ptr (w*h*16 B, 16-B aligned) optional."""
         ap = self._antialias_params(factor, sigma_normal, sigma_plane, demodulate, edge_normal, edge_plane)
         n = self.width * self.height
+        if see_through is not None:
+            st = self._seethrough_params(see_through)
+            self._check(self._L.rz_antialias_seethrough(
+                self._c, None if ap is None else C.byref(ap), C.byref(st), C.c_void_p(rgb_in_ptr), n * 12 if rgb_in_ptr else 0,
+                C.c_void_p(rgb32f_ptr), n * 12 if rgb32f_ptr else 0, C.c_void_p(guides_ptr), n * 48 if guides_ptr else 0,
+                C.c_void_p(chains_ptr), n * 16 if chains_ptr else 0, C.c_void_p(edges_ptr), n if edges_ptr else 0, 0),
+                "rz_antialias_seethrough")
+            return
+        if chains_ptr:
+            raise ValueError("chains_ptr needs see_through")
         self._check(self._L.rz_antialias(self._c, None if ap is None else C.byref(ap), C.c_void_p(rgb_in_ptr),
                                          n * 12 if rgb_in_ptr else 0, C.c_void_p(rgb32f_ptr), n * 12 if rgb32f_ptr else 0,
                                          C.c_void_p(guides_ptr), n * 48 if guides_ptr else 0, C.c_void_p(edges_ptr),
@@ -883,10 +910,12 @@ class Renderer:
 
     def present_antialiased(self, source="accum", factor=None, sigma_normal=None, sigma_plane=None, demodulate=None,
                             edge_normal=None, edge_plane=None, fps=0.0, show_fps=True, show_lights=False, show_bvh=False,
-                            bvh_mode=0, selected_blas=0, selected_tri=0, filter=None, **params):
+                            bvh_mode=0, selected_blas=0, selected_tri=0, filter=None, see_through=None, **params):
         """present_display() with the anti-aliasing pass between the source and the display stage: the colour of `source` (as
         present_display) is anti-aliased, then exposed, toned and encoded (params: as display()), and the overlays are drawn on
-        top.  Returns (rgb float32 (H,W,3), rgba8 uint8 (H,W,4)); factor=1 gives present_display()'s bytes."""
+        top.  Returns (rgb float32 (H,W,3), rgba8 uint8 (H,W,4)); factor=1 gives present_display()'s bytes.  see_through = 0..8
+        (or True): rz_present_antialiased_seethrough, the pass on guides that follow glass and perfect mirrors (the denoisers
+        keep their first-hit guides)."""
         if source not in _lib.DISPLAY_SOURCES:
             raise ValueError(f"source = {source!r}: one of {sorted(_lib.DISPLAY_SOURCES)}")
         if source == "accum" and filter:
@@ -905,6 +934,13 @@ class Renderer:
             fp = self._temporal_params(dict(filter or {}))
         rgb = np.empty((self.height, self.width, 3), np.float32)
         rgba8 = np.empty((self.height, self.width, 4), np.uint8)
+        if see_through is not None:
+            st = self._seethrough_params(see_through)
+            self._check(self._L.rz_present_antialiased_seethrough(
+                self._c, C.byref(p), None if ap is None else C.byref(ap), C.byref(st), None if dp is None else C.byref(dp),
+                _lib.DISPLAY_SOURCES[source], fp, rgba8.ctypes.data, rgba8.nbytes, rgb.ctypes.data, rgb.nbytes),
+                "rz_present_antialiased_seethrough")
+            return rgb, rgba8
         self._check(self._L.rz_present_antialiased(self._c, C.byref(p), None if ap is None else C.byref(ap),
                                                    None if dp is None else C.byref(dp), _lib.DISPLAY_SOURCES[source], fp,
                                                    rgba8.ctypes.data, rgba8.nbytes, rgb.ctypes.data, rgb.nbytes),
