@@ -16,10 +16,10 @@ want = sys.argv[2:] or ["rz_render_samplesILb0ELb0ELb0ELi8E", "rz_render_samples
 with tempfile.TemporaryDirectory() as tmp:
     c = shutil.copy(so, os.path.join(tmp, "lib.so"))
     subprocess.run([f"{LLVM}/llvm-objdump", "--offloading", c], cwd=tmp, check=True, capture_output=True)
-    cos = sorted((p for p in os.listdir(tmp) if "gfx950" in p), key=lambda p: -os.path.getsize(os.path.join(tmp, p)))
-    co = os.path.join(tmp, cos[0])
-    notes = subprocess.run([f"{LLVM}/llvm-readelf", "--notes", co], capture_output=True, text=True).stdout
-    dis = subprocess.run([f"{LLVM}/llvm-objdump", "-d", "--no-show-raw-insn", co], capture_output=True, text=True).stdout
+    # one code object per source file of the library: read them all
+    cos = [os.path.join(tmp, p) for p in sorted(os.listdir(tmp)) if "gfx950" in p]
+    notes = "".join(subprocess.run([f"{LLVM}/llvm-readelf", "--notes", co], capture_output=True, text=True).stdout for co in cos)
+    dis = "".join(subprocess.run([f"{LLVM}/llvm-objdump", "-d", "--no-show-raw-insn", co], capture_output=True, text=True).stdout for co in cos)
 kern = {}
 for blk in notes.split("- .agpr_count")[1:]:
     g = lambda k: (re.search(rf"\.{k}:\s*(\S+)", blk) or [None, "?"])[1]

@@ -16,24 +16,12 @@
 //                          writes the pixel.  No global atomics, no second colour buffer; no result depends on the grouping.
 //
 // DIFFERENT (q from p), EDGE and the edge pixel's mean are stated in the header; the classification is binary32, one rounding per
-// operation (tests/antialias_ref.py restates it bit for bit).
-#include "rz_upscale_body.h"
-#include "rz_query.h"
-#include "rz_path.h"
+// operation (tests/antialias_ref.py restates it bit for bit).  The steps themselves -- DIFFERENT, the append, a sub-pixel's ray,
+// the group's mean -- are rz_antialias_body.h's (CHAIN = false), shared with rz_antialias_seethrough.hip; the sub-pixel's guide
+// record is rz_pixel_cast.h's, as rz_denoise_guides writes it.  This file is the schedule and the 3 x 3 loop.
+#include "rz_antialias_body.h"
 
 namespace rz {
-
-// is the neighbour q DIFFERENT from p?  (n_p, x_p, t_p, m_p: p's record; ke = (float)(edge_plane f))
-// Written without a branch, both records fetched whatever they hold: the eight neighbours' sixteen loads are then in flight
-// together, where a test after every load would make them eight round trips to L2 one after the other.
-__device__ __forceinline__ bool aa_different(const AntialiasLaunch& A, size_t q, bool hitP, int wordP, const v3 nP, const v3 xP, float tP) {
-    const float4 h0 = A.U.guideLo[2 * q], h1 = A.U.guideLo[2 * q + 1];
-    const int wordQ = __float_as_int(h1.w);
-    const bool hitQ = wordQ >= 0;
-    const bool crease = dot(nP, mk3(h0.x, h0.y, h0.z)) < A.edgeNormal;
-    const bool step = __builtin_fabsf(dot(nP, mk3(h1.x, h1.y, h1.z) - xP)) > A.edgePlane * tP;
-    return (hitQ != hitP) | (hitP & hitQ & ((wordQ != wordP) | crease | step));
-}
 
 template <bool OVF>
 __global__ __launch_bounds__(64, RZ_RAYS_MIN_WAVES) void rz_antialias_edges(const KParams K, const AntialiasLaunch A) {
@@ -70,26 +58,15 @@ __global__ __launch_bounds__(64, RZ_RAYS_MIN_WAVES) void rz_antialias_edges(cons
                         const bool inside = qx >= 0 && qx < U.w && qy >= 0 && qy < U.h;
                         // (a neighbour outside the image does not count: its lane reads p's own record and drops the answer)
                         const size_t q = inside ? (size_t)qy * U.w + qx : p;
-                        edge = edge | (inside & aa_different(A, q, wordP >= 0, wordP, nP, xP, g0.w));
+                        edge = edge | (inside & aa_different<false>(A, q, wordP >= 0, wordP, 0, nP, xP, g0.w));
                     }
                 }
                 if (A.edges) A.edges[p] = edge ? 1 : 0;
-                if (!edge || s == 1) {          // out = c_p exactly
-                    if (U.dst) U.dst[p] = make_float4(c.x, c.y, c.z, 1.0f);
-                    if (U.rgb) {
-                        U.rgb[3 * p] = c.x;
-                        U.rgb[3 * p + 1] = c.y;
-                        U.rgb[3 * p + 2] = c.z;
-                    }
-                }
+                if (!edge || s == 1) store_colour(U.dst, U.rgb, p, c, 1.0f);        // out = c_p exactly
             }
-            u += gridDim.x;         // (strided, not consecutive units: measured, profiles/antialias/README.md)
+            u += gridDim.x;        // (strided, not consecutive units: measured, profiles/antialias/README.md)
             if (s == 1) continue;
-            const unsigned long long m = rz_ballot(edge);
-            // (the prefix count: the edge lanes below this one; count <= take - 1 here, so the index stays below RZ_AA_QUEUE)
-            const int before = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
-            if (edge) queue[count + before] = (int)p;
-            count += mask_count(m);
+            aa_append(queue, count, edge, p);       // (count <= take - 1 here, so the index stays below RZ_AA_QUEUE)
             __syncthreads();    // (one wave: orders the queue's writes before the reads below)
         }
         // cast and gather: full batches while there are any, and whatever is left after the last unit
@@ -100,39 +77,17 @@ __global__ __launch_bounds__(64, RZ_RAYS_MIN_WAVES) void rz_antialias_edges(cons
             int pix = 0;
             if (act) {
                 pix = queue[count - n + grp];
-                const int y = pix / U.w, x = pix - y * U.w;
-                const int X = s * x + sa, Y = s * y + sb;
-                v2 uv;
-                uv.x = ((float)X + 0.5f) / (float)(U.w * s);
-                uv.y = ((float)Y + 0.5f) / (float)(U.h * s);
-                const v3 d = camera_ray_centre(K.invProj, K.invView, uv);
+                int X, Y;
+                const v3 d = aa_sub_pixel(K, U, pix, sa, sb, X, Y);
                 HitRec h;
                 TraceExtra tx;
                 const bool found = ray_query<OVF, false>(K, cam, d, h, bstk, tx);
                 cut = cut || tx.cut;
-                // rz_denoise_guides' record of the high pixel
-                const int word = found ? min(max(h.mat, 0), K.nMaterials - 1) : -1;
-                const float4 g0 = found ? make_float4(h.n.x, h.n.y, h.n.z, h.t) : make_float4(0.0f, 0.0f, 0.0f, 1e30f);
-                const float4 g1 = found ? make_float4(h.p.x, h.p.y, h.p.z, __int_as_float(word))
-                                        : make_float4(0.0f, 0.0f, 0.0f, __int_as_float(-1));
+                float4 g0, g1;          // rz_denoise_guides' record of the high pixel
+                guide_record(K, found, h, h.t, g0, g1);
                 uo = upscale_pixel<false>(U, X, Y, g0, g1, make_float4(1.0f, 1.0f, 1.0f, 0.0f));
             }
-            v3 sum = uo;        // (((u_0 + u_1) + ...) + u_{s^2 - 1}), b outer and a inner: the group's lanes in order
-            for (int j = 1; j < ss; ++j) {
-                sum.x = sum.x + __shfl(uo.x, lane + j);
-                sum.y = sum.y + __shfl(uo.y, lane + j);
-                sum.z = sum.z + __shfl(uo.z, lane + j);
-            }
-            if (act && sub == 0) {
-                const float inv = (float)ss;
-                const v3 out = mk3(sum.x / inv, sum.y / inv, sum.z / inv);
-                if (U.dst) U.dst[pix] = make_float4(out.x, out.y, out.z, 1.0f);
-                if (U.rgb) {
-                    U.rgb[3 * (size_t)pix] = out.x;
-                    U.rgb[3 * (size_t)pix + 1] = out.y;
-                    U.rgb[3 * (size_t)pix + 2] = out.z;
-                }
-            }
+            aa_store_mean(U, uo, lane, ss, act && sub == 0, pix);
             count -= n;
         }
         if (!more) break;

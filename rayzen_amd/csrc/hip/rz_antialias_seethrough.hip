@@ -29,25 +29,12 @@
 // a wave was built for that form and was slower still (same README, "Stage B").
 //
 // With max_depth = 0 every chain is its first query, L = 0 + t = t, T = (1, 1, 1) and cls = 0: rz_antialias' bytes exactly.
-#include "rz_upscale_body.h"
-#include "rz_query.h"
-#include "rz_path.h"
-#include "rz_chain_step.h"
+// That holds by construction: both files run the steps of rz_antialias_body.h (here CHAIN = true: rz_antialias' rule on the
+// FINAL records, t_p = L_p, or another class), and the chain and its record are rz_pixel_cast.h's, which rz_seethrough_guides
+// runs too.  This file is the schedule and the 3 x 3 loop.
+#include "rz_antialias_body.h"
 
 namespace rz {
-
-// is the neighbour q DIFFERENT from p?  rz_antialias' rule (rz_antialias.hip: aa_different) on the FINAL records, t_p = L_p, or
-// another class.  Branch-free for the same reason: the eight neighbours' loads are in flight together.
-__device__ __forceinline__ bool aas_different(const AntialiasLaunch& A, size_t q, bool hitP, int wordP, int clsP, const v3 nP, const v3 xP,
-                                              float tP) {
-    const float4 h0 = A.U.guideLo[3 * q], h1 = A.U.guideLo[3 * q + 1];
-    const int clsQ = __float_as_int(A.U.guideLo[3 * q + 2].w);
-    const int wordQ = __float_as_int(h1.w);
-    const bool hitQ = wordQ >= 0;
-    const bool crease = dot(nP, mk3(h0.x, h0.y, h0.z)) < A.edgeNormal;
-    const bool step = __builtin_fabsf(dot(nP, mk3(h1.x, h1.y, h1.z) - xP)) > A.edgePlane * tP;
-    return (hitQ != hitP) | (clsQ != clsP) | (hitP & hitQ & ((wordQ != wordP) | crease | step));
-}
 
 __global__ __launch_bounds__(64) void rz_antialias_seethrough_classify(const AntialiasSeethroughLaunch A) {
     const UpscaleLaunch& U = A.U;
@@ -74,25 +61,14 @@ __global__ __launch_bounds__(64) void rz_antialias_seethrough_classify(const Ant
                     const bool inside = qx >= 0 && qx < U.w && qy >= 0 && qy < U.h;
                     // (a neighbour outside the image does not count: its lane reads p's own record and drops the answer)
                     const size_t q = inside ? (size_t)qy * U.w + qx : p;
-                    edge = edge | (inside & aas_different(A, q, wordP >= 0, wordP, clsP, nP, xP, g0.w));
+                    edge = edge | (inside & aa_different<true>(A, q, wordP >= 0, wordP, clsP, nP, xP, g0.w));
                 }
             }
             if (A.edges) A.edges[p] = edge ? 1 : 0;
-            if (!edge || s == 1) {          // out = c_p exactly
-                if (U.dst) U.dst[p] = make_float4(c.x, c.y, c.z, 1.0f);
-                if (U.rgb) {
-                    U.rgb[3 * p] = c.x;
-                    U.rgb[3 * p + 1] = c.y;
-                    U.rgb[3 * p + 2] = c.z;
-                }
-            }
+            if (!edge || s == 1) store_colour(U.dst, U.rgb, p, c, 1.0f);        // out = c_p exactly
         }
         if (s == 1) continue;
-        const unsigned long long m = rz_ballot(edge);
-        // (the prefix count: the edge lanes below this one; a unit adds at most 64, so the index stays below segCap)
-        const int before = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
-        if (edge) seg[count + before] = (int)p;
-        count += mask_count(m);
+        aa_append(seg, count, edge, p);         // (a unit adds at most 64, so the index stays below segCap)
     }
     if (lane == 0) A.counts[blockIdx.x] = count;
 }
@@ -146,62 +122,20 @@ __global__ __launch_bounds__(64, RZ_RAYS_MIN_WAVES) void rz_antialias_seethrough
         segi = min(segi, G - 1);                // (p < total, so the walk ends inside the grid; the clamp keeps a wrong count in bounds)
         const int at = min(max(p - base, 0), A.segCap - 1);
         int pix = 0, X = 0, Y = 0;
-        v3 o = cam, d = mk3(0.0f, 0.0f, 0.0f);
+        v3 d = mk3(0.0f, 0.0f, 0.0f);
         if (act) {
             pix = A.list[(size_t)segi * A.segCap + at];
-            const int y = pix / U.w, x = pix - y * U.w;
-            X = s * x + sa;
-            Y = s * y + sb;
-            v2 uv;
-            uv.x = ((float)X + 0.5f) / (float)(U.w * s);
-            uv.y = ((float)Y + 0.5f) / (float)(U.h * s);
-            d = camera_ray_centre(K.invProj, K.invView, uv);
+            d = aa_sub_pixel(K, U, pix, sa, sb, X, Y);
         }
         // the chain of the high pixel (X, Y): rz_seethrough_guides' loop, bit for bit what it casts at s w x s h
-        float ior = 1.0f, L = 0.0f;
-        v3 T = mk3(1.0f, 1.0f, 1.0f);
-        int k = 0, first = -1;
-        bool found = false;
-        HitRec h = {};
-        bool run = act;
-        while (rz_ballot(run) != 0ull) {    // at most max_depth + 1 trips: a lane with k == max_depth ends at its hit
-            if (run) {
-                HitRec hq;
-                TraceExtra tx;
-                found = ray_query<OVF, false>(K, o, d, hq, bstk, tx);
-                cut = cut || tx.cut;
-                run = false;
-                if (found) {
-                    h = hq;
-                    run = chain_step(K, A.maxDepth, hq, o, d, T, ior, L, k, first);     // rz_chain_step.h
-                }
-            }
-        }
+        const ChainEnd e = cast_chain<OVF>(K, A.maxDepth, cam, d, act, bstk, cut);
         v3 uo = mk3(0.0f, 0.0f, 0.0f);
         if (act) {          // rz_seethrough_guides' record of the high pixel
-            const int word = found ? min(max(h.mat, 0), K.nMaterials - 1) : -1;
-            const int cls = k == 0 ? 0 : first + 1;
-            const float4 g0 = found ? make_float4(h.n.x, h.n.y, h.n.z, L) : make_float4(0.0f, 0.0f, 0.0f, 1e30f);
-            const float4 g1 = found ? make_float4(h.p.x, h.p.y, h.p.z, __int_as_float(word))
-                                    : make_float4(0.0f, 0.0f, 0.0f, __int_as_float(-1));
-            uo = upscale_pixel<true>(U, X, Y, g0, g1, make_float4(T.x, T.y, T.z, __int_as_float(cls)));
+            float4 g0, g1;
+            guide_record(K, e.found, e.h, e.L, g0, g1);
+            uo = upscale_pixel<true>(U, X, Y, g0, g1, make_float4(e.T.x, e.T.y, e.T.z, __int_as_float(e.cls())));
         }
-        v3 sum = uo;        // (((u_0 + u_1) + ...) + u_{s^2 - 1}), b outer and a inner: the group's lanes in order
-        for (int j = 1; j < ss; ++j) {
-            sum.x = sum.x + __shfl(uo.x, lane + j);
-            sum.y = sum.y + __shfl(uo.y, lane + j);
-            sum.z = sum.z + __shfl(uo.z, lane + j);
-        }
-        if (act && sub == 0) {
-            const float inv = (float)ss;
-            const v3 out = mk3(sum.x / inv, sum.y / inv, sum.z / inv);
-            if (U.dst) U.dst[pix] = make_float4(out.x, out.y, out.z, 1.0f);
-            if (U.rgb) {
-                U.rgb[3 * (size_t)pix] = out.x;
-                U.rgb[3 * (size_t)pix + 1] = out.y;
-                U.rgb[3 * (size_t)pix + 2] = out.z;
-            }
-        }
+        aa_store_mean(U, uo, lane, ss, act && sub == 0, pix);
     }
     rays_backstop(A.errWord, cut);
 }

@@ -3206,6 +3206,59 @@ static int seethrough_cast(rz_ctx* c, int width, int height, int maxDepth, float
     return RZ_OK;
 }
 
+// Casts a guide of either kind at width x height into the buffer that kind keeps, which it sizes first: the chain records (48 B,
+// seethrough_cast) into the see-through pair with `st`, rz_denoise's (32 B, guide_cast; `chains` is then null) into the
+// upsampler's pair without.  hi: the pair's high-size buffer.  `guide` receives the records' address.
+static int either_cast(rz_ctx* c, const rz_seethrough_params* st, bool hi, int width, int height, float4* hits, float4* chains,
+                       const float4*& guide) {
+    DevBuf& buf = st ? (hi ? c->dStGuideHi : c->dStGuideLo) : (hi ? c->dUpGuideHi : c->dUpGuideLo);
+    const int rc = ensure(c, buf, (size_t)width * height * (st ? 48 : 32));
+    if (rc != RZ_OK) return rc;
+    float4* rec = static_cast<float4*>(buf.p);
+    guide = rec;
+    return st ? seethrough_cast(c, width, height, st->max_depth, rec, hits, chains) : guide_cast(c, width, height, rec, hits);
+}
+
+// The world size of a frame pixel at unit distance.
+static double frame_fpx(const rz_frame_params& f) { return 2.0 * std::fabs((double)f.inv_proj[5]) / (double)f.height; }
+
+// What rz_upscale_gather and the antialias kernels read and write, at the frame rz_set_frame set (the upsampler's LOW frame): the
+// colour in3 or in4, the guides, the outputs and the filter's terms.
+static UpscaleLaunch upscale_wiring(rz_ctx* c, const rz_upscale_params& P, const float* in3, const float4* in4, const float4* guideLo,
+                                    const float4* guideHi, float* rgb, float4* out4) {
+    const rz_frame_params& f = c->frame;
+    UpscaleLaunch U{};
+    U.in3 = in4 ? nullptr : in3;
+    U.in4 = in4;
+    U.guideLo = guideLo;
+    U.guideHi = guideHi;
+    U.materials = static_cast<const DevMaterial*>(c->dMat.p);
+    U.dst = out4;
+    U.rgb = rgb;
+    U.w = f.width; U.h = f.height;
+    U.s = P.factor;
+    U.sigmaNormal = P.sigma_normal;
+    U.planeScale = (float)(1.0 / ((double)P.sigma_plane * frame_fpx(f)));
+    U.demodulate = P.demodulate;
+    return U;
+}
+
+// Factor 1 of rz_upscale and rz_antialias, c_p itself: in4 resolved into out4 and rgb, or in3 copied to rgb unless it is rgb.
+static int colour_itself(rz_ctx* c, const float* in3, const float4* in4, float* rgb, float4* out4) {
+    if (in4) {
+        DenoiseLaunch D{};
+        D.accum = in4;
+        D.dst = out4;
+        D.rgb = rgb;
+        D.width = c->frame.width; D.height = c->frame.height;
+        launch_denoise_resolve(D, c->stream);
+        RZ_HIP(c, hipGetLastError());
+    } else if (rgb && rgb != in3) {
+        RZ_HIP(c, hipMemcpyAsync(rgb, in3, (size_t)c->frame.width * c->frame.height * 12, hipMemcpyDeviceToDevice, c->stream));
+    }
+    return RZ_OK;
+}
+
 // Casts both guides and gathers, on the stream; factor >= 2.  The low frame (device) is in3 (3 floats per pixel) or in4 (RGBA32F
 // sum and count); outputs (device, high size, each optional): rgb (3 floats per pixel), out4 ((colour, 1)), hits (rz_hit).
 static int upscale_run(rz_ctx* c, const rz_upscale_params& P, const float* in3, const float4* in4, float* rgb, float4* out4, float4* hits,
@@ -3217,37 +3270,14 @@ static int upscale_run(rz_ctx* c, const rz_upscale_params& P, const float* in3, 
     if (rc != RZ_OK) return rc;
     rc = cast_ready(c);
     if (rc != RZ_OK) return rc;
-    DevBuf& bufHi = st ? c->dStGuideHi : c->dUpGuideHi;
-    DevBuf& bufLo = st ? c->dStGuideLo : c->dUpGuideLo;
-    const size_t rec = st ? 48 : 32;
-    rc = ensure(c, bufHi, (size_t)W * H * rec);
-    if (rc != RZ_OK) return rc;
-    if (rgb || out4) {
-        rc = ensure(c, bufLo, (size_t)f.width * f.height * rec);
-        if (rc != RZ_OK) return rc;
-    }
     // the high cast first: its overflow columns (size_blas_stack) are the larger ones, so the low cast finds them in place
-    rc = st ? seethrough_cast(c, W, H, st->max_depth, static_cast<float4*>(bufHi.p), hits, chains)
-            : guide_cast(c, W, H, static_cast<float4*>(bufHi.p), hits);
+    const float4 *guideHi = nullptr, *guideLo = nullptr;
+    rc = either_cast(c, st, true, W, H, hits, chains, guideHi);
     if (rc != RZ_OK) return rc;
     if (!rgb && !out4) return RZ_OK;
-    rc = st ? seethrough_cast(c, f.width, f.height, st->max_depth, static_cast<float4*>(bufLo.p), nullptr, nullptr)
-            : guide_cast(c, f.width, f.height, static_cast<float4*>(bufLo.p), nullptr);
+    rc = either_cast(c, st, false, f.width, f.height, nullptr, nullptr, guideLo);
     if (rc != RZ_OK) return rc;
-    UpscaleLaunch U{};
-    U.in3 = in4 ? nullptr : in3;
-    U.in4 = in4;
-    U.guideLo = static_cast<const float4*>(bufLo.p);
-    U.guideHi = static_cast<const float4*>(bufHi.p);
-    U.materials = static_cast<const DevMaterial*>(c->dMat.p);
-    U.dst = out4;
-    U.rgb = rgb;
-    U.w = f.width; U.h = f.height;
-    U.s = P.factor;
-    U.sigmaNormal = P.sigma_normal;
-    const double fpx = 2.0 * std::fabs((double)f.inv_proj[5]) / (double)f.height;     // world size of a LOW pixel at unit distance
-    U.planeScale = (float)(1.0 / ((double)P.sigma_plane * fpx));
-    U.demodulate = P.demodulate;
+    const UpscaleLaunch U = upscale_wiring(c, P, in3, in4, guideLo, guideHi, rgb, out4);
     if (st) launch_seethrough_gather(U, c->stream);
     else launch_upscale_gather(U, c->stream);
     RZ_HIP(c, hipGetLastError());
@@ -3295,23 +3325,12 @@ static int upscale_impl(rz_ctx* c, const rz_upscale_params* pp, const float* rgb
     float4* dHits = stage.dev<float4>(sHits);
     float4* dChains = stage.dev<float4>(sChains);
     if (P.factor == 1) {                    // c_p itself, and nothing is cast unless the guide is asked for
-        if (dRgb && in4) {
-            DenoiseLaunch D{};
-            D.accum = in4;
-            D.rgb = dRgb;
-            D.width = c->frame.width; D.height = c->frame.height;
-            launch_denoise_resolve(D, c->stream);
-            RZ_HIP(c, hipGetLastError());
-        } else if (dRgb && dRgb != in3) {
-            RZ_HIP(c, hipMemcpyAsync(dRgb, in3, bIn, hipMemcpyDeviceToDevice, c->stream));
-        }
-        if (dHits || dChains) {
+        if (dRgb) rc = colour_itself(c, in3, in4, dRgb, nullptr);
+        if (rc == RZ_OK && (dHits || dChains)) {
+            const float4* guide = nullptr;
             rc = finalize(c);
             if (rc == RZ_OK) rc = cast_ready(c);
-            if (rc == RZ_OK) rc = ensure(c, st ? c->dStGuideHi : c->dUpGuideHi, np * (st ? 48 : 32));
-            if (rc == RZ_OK)
-                rc = st ? seethrough_cast(c, c->frame.width, c->frame.height, st->max_depth, static_cast<float4*>(c->dStGuideHi.p), dHits, dChains)
-                        : guide_cast(c, c->frame.width, c->frame.height, static_cast<float4*>(c->dUpGuideHi.p), dHits);
+            if (rc == RZ_OK) rc = either_cast(c, st, true, c->frame.width, c->frame.height, dHits, dChains, guide);
         }
     } else {
         rc = upscale_run(c, P, in3, in4, dRgb, nullptr, dHits, st, dChains);
@@ -3395,51 +3414,27 @@ static int antialias_run(rz_ctx* c, const rz_antialias_params& P, const float* i
                          float4* hits, uint8_t* edges, const rz_seethrough_params* st = nullptr, float4* chains = nullptr) {
     if (!rgb && !out4 && !hits && !edges && !chains) return RZ_OK;
     const rz_frame_params& f = c->frame;
-    const size_t np = (size_t)f.width * f.height;
     int rc = finalize(c);
     if (rc != RZ_OK) return rc;
     const bool kernel = edges || ((rgb || out4) && P.factor > 1);
     if (!kernel && (rgb || out4)) {         // factor 1: c_p itself
-        if (in4) {
-            DenoiseLaunch D{};
-            D.accum = in4;
-            D.dst = out4;
-            D.rgb = rgb;
-            D.width = f.width; D.height = f.height;
-            launch_denoise_resolve(D, c->stream);
-            RZ_HIP(c, hipGetLastError());
-        } else if (rgb) {
-            RZ_HIP(c, hipMemcpyAsync(rgb, in3, np * 12, hipMemcpyDeviceToDevice, c->stream));
-        }
+        rc = colour_itself(c, in3, in4, rgb, out4);
+        if (rc != RZ_OK) return rc;
     }
     if (!kernel && !hits && !chains) return RZ_OK;
     rc = cast_ready(c);
     if (rc != RZ_OK) return rc;
-    DevBuf& bufLo = st ? c->dStGuideLo : c->dUpGuideLo;
-    rc = ensure(c, bufLo, np * (st ? 48 : 32));
-    if (rc != RZ_OK) return rc;
-    float4* guide = static_cast<float4*>(bufLo.p);
-    rc = st ? seethrough_cast(c, f.width, f.height, st->max_depth, guide, hits, chains) : guide_cast(c, f.width, f.height, guide, hits);
+    const float4* guide = nullptr;
+    rc = either_cast(c, st, false, f.width, f.height, hits, chains, guide);
     if (rc != RZ_OK || !kernel) return rc;
     KParams K{};
     AntialiasSeethroughLaunch A{};          // (AntialiasLaunch and the chain's bound; the first-hit kernel takes the base)
     rc = cast_wiring(c, f.width, f.height, K, A, st ? 0 : RZ_AA_QUEUE * sizeof(int));
     if (rc != RZ_OK) return rc;
-    A.U.in3 = in4 ? nullptr : in3;
-    A.U.in4 = in4;
-    A.U.guideLo = guide;
-    A.U.materials = static_cast<const DevMaterial*>(c->dMat.p);
-    A.U.dst = out4;
-    A.U.rgb = rgb;
-    A.U.w = f.width; A.U.h = f.height;
-    A.U.s = P.factor;
-    A.U.sigmaNormal = P.sigma_normal;
-    const double fpx = 2.0 * std::fabs((double)f.inv_proj[5]) / (double)f.height;     // world size of a pixel at unit distance
-    A.U.planeScale = (float)(1.0 / ((double)P.sigma_plane * fpx));
-    A.U.demodulate = P.demodulate;
+    A.U = upscale_wiring(c, {P.factor, P.sigma_normal, P.sigma_plane, P.demodulate, {0, 0, 0, 0}}, in3, in4, guide, nullptr, rgb, out4);
     A.edges = edges;
     A.edgeNormal = P.edge_normal;
-    A.edgePlane = (float)((double)P.edge_plane * fpx);
+    A.edgePlane = (float)((double)P.edge_plane * frame_fpx(f));
     A.maxDepth = st ? st->max_depth : 0;
     if (st) {                               // the list between the two kernels: a segment per wave of the grid
         A.segCap = (int)((A.units + A.grid - 1) / A.grid) * 64;

@@ -27,9 +27,10 @@
 // it drops its own term, takes every remaining tap at colour weight 1 and becomes num / den, or (0, 0, 0) when no tap is left.  So
 // pass 0's output is finite and the later passes need no test (include/rayzen_hip.h states the rule).
 // Arithmetic is binary32 (tests/denoise_ref.py restates it in binary64; tests/test_denoise_gpu.py states the tolerance).
+// rz_denoise_guides is made of shared pieces: the pixel's ray and the guide record are rz_pixel_cast.h's, the rz_hit record
+// rz_query.h's (store_hit); the colour outputs go through store_colour (rz_internal.h).
 #include "rz_internal.h"
-#include "rz_query.h"
-#include "rz_path.h"
+#include "rz_pixel_cast.h"
 
 namespace rz {
 
@@ -43,34 +44,17 @@ __global__ __launch_bounds__(64, RZ_RAYS_MIN_WAVES) void rz_denoise_guides(const
     for (long long u = blockIdx.x; u < G.units; u += gridDim.x) {
         const int py = (int)(u / G.unitsX), px = (int)(u - (long long)py * G.unitsX) * 64 + lane;
         if (px >= K.width) continue;
-        v2 uv;
-        uv.x = ((float)px + 0.5f) / (float)K.width;
-        uv.y = ((float)py + 0.5f) / (float)K.height;
-        const v3 d = camera_ray_centre(K.invProj, K.invView, uv);
+        const v3 d = pixel_centre_dir(K, px, py, K.width, K.height);
         HitRec h;
         TraceExtra x;
         const bool found = ray_query<OVF, false>(K, cam, d, h, bstk, x);
         cut = cut || x.cut;
         const size_t pix = (size_t)py * K.width + px;
-        // the guide: (n, t) | (x, hit word = the clamped material index, -1 for a miss)
-        const int word = found ? min(max(h.mat, 0), K.nMaterials - 1) : -1;
-        G.guide[2 * pix] = found ? make_float4(h.n.x, h.n.y, h.n.z, h.t) : make_float4(0.0f, 0.0f, 0.0f, 1e30f);
-        G.guide[2 * pix + 1] = found ? make_float4(h.p.x, h.p.y, h.p.z, __int_as_float(word))
-                                     : make_float4(0.0f, 0.0f, 0.0f, __int_as_float(-1));
-        if (G.hits) {           // rz_trace_rays_kernel's record, miss included
-            float4 r0 = make_float4(1e30f, 0.0f, 0.0f, 0.0f);
-            float4 r1 = make_float4(0.0f, 0.0f, 0.0f, __int_as_float(-1));
-            float4 r2 = make_float4(__int_as_float(-1), __int_as_float(-1), __int_as_float(-1), 0.0f);
-            if (found) {
-                const int prim = K.tris[x.tri].src;
-                r0 = make_float4(h.t, h.p.x, h.p.y, h.p.z);
-                r1 = make_float4(h.n.x, h.n.y, h.n.z, __int_as_float(h.mat));
-                r2 = make_float4(__int_as_float(h.inst), __int_as_float(prim - G.instTriOff[h.inst]), __int_as_float(prim), 0.0f);
-            }
-            G.hits[3 * pix] = r0;
-            G.hits[3 * pix + 1] = r1;
-            G.hits[3 * pix + 2] = r2;
-        }
+        float4 g0, g1;
+        guide_record(K, found, h, h.t, g0, g1);
+        G.guide[2 * pix] = g0;
+        G.guide[2 * pix + 1] = g1;
+        if (G.hits) store_hit(K, G.instTriOff, G.hits, pix, found, h, x.tri, h.t);      // rz_trace_rays_kernel's record, miss included
     }
     rays_backstop(G.errWord, cut);
 }
@@ -164,12 +148,7 @@ __global__ __launch_bounds__(256) void rz_denoise_atrous(const DenoiseLaunch D) 
         const v3 al = albedo_of(D, wordP);
         out = mk3(out.x * al.x, out.y * al.y, out.z * al.z);
     }
-    if (D.dst) D.dst[p] = make_float4(out.x, out.y, out.z, LAST ? 1.0f : 0.0f);
-    if (LAST && D.rgb) {
-        D.rgb[3 * p] = out.x;
-        D.rgb[3 * p + 1] = out.y;
-        D.rgb[3 * p + 2] = out.z;
-    }
+    store_colour(D.dst, LAST ? D.rgb : nullptr, p, out, LAST ? 1.0f : 0.0f);
 }
 
 __global__ __launch_bounds__(256) void rz_denoise_resolve(const DenoiseLaunch D) {
@@ -177,12 +156,7 @@ __global__ __launch_bounds__(256) void rz_denoise_resolve(const DenoiseLaunch D)
     if (px >= D.width || py >= D.height) return;
     const size_t p = (size_t)py * D.width + px;
     const v3 c = resolve_px(D.accum[p]);
-    if (D.dst) D.dst[p] = make_float4(c.x, c.y, c.z, 1.0f);
-    if (D.rgb) {
-        D.rgb[3 * p] = c.x;
-        D.rgb[3 * p + 1] = c.y;
-        D.rgb[3 * p + 2] = c.z;
-    }
+    store_colour(D.dst, D.rgb, p, c, 1.0f);
 }
 
 void launch_denoise_guides(const KParams& K, const DenoiseGuideLaunch& G, hipStream_t stream) {

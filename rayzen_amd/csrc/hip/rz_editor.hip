@@ -16,9 +16,10 @@
 // rz_rays.hip (or one 8 x 8 tile, RZ_TILE_W x RZ_TILE_H, under RZ_EDITOR_TILES=1: the rows measured faster on C2, C4 and C5,
 // the tiles on c2close and RayZen's own scene -- profiles/editor/README.md).  Nothing of the render state is touched (accumulation, currentIor, pools, the claim counter,
 // the frame of rz_set_frame); a walk stopped at its backstop sets RZ_BACKSTOP_RAYS, as the ray queries do.
+// Shared with the other off-frame passes: the pixel's ray (rz_pixel_cast.h: pixel_centre_dir) and the rz_hit record (rz_query.h:
+// store_hit).
 #include "rz_internal.h"
-#include "rz_query.h"
-#include "rz_path.h"
+#include "rz_pixel_cast.h"
 
 namespace rz {
 
@@ -136,12 +137,7 @@ __global__ __launch_bounds__(64, RZ_RAYS_MIN_WAVES) void rz_editor_kernel(const 
         const int py = E.rows ? uy : uy * RZ_TILE_H + (lane >> 3);
         const bool inside = px < K.width && py < K.height;
         v3 d = mk3(0.0f, 0.0f, 0.0f);
-        if (inside) {
-            v2 uv;
-            uv.x = ((float)px + 0.5f) / (float)K.width;         // gl_FragCoord.xy / resolution (FS:669)
-            uv.y = ((float)py + 0.5f) / (float)K.height;
-            d = camera_ray_centre(K.invProj, K.invView, uv);
-        }
+        if (inside) d = pixel_centre_dir(K, px, py, K.width, K.height);
         // the closest hit, and past the near plane when it lies in front of it
         HitRec h;
         int tri = -1, restarts = 0;
@@ -172,20 +168,8 @@ __global__ __launch_bounds__(64, RZ_RAYS_MIN_WAVES) void rz_editor_kernel(const 
         }
         if (!inside) continue;
         const size_t pix = (size_t)py * K.width + px;
-        if (E.hits) {           // (written before the shading, which then has the registers of the record to itself)
-            float4 r0 = make_float4(1e30f, 0.0f, 0.0f, 0.0f);      // the miss record of rz_trace_rays
-            float4 r1 = make_float4(0.0f, 0.0f, 0.0f, __int_as_float(-1));
-            float4 r2 = make_float4(__int_as_float(-1), __int_as_float(-1), __int_as_float(-1), 0.0f);
-            if (visible) {
-                const int prim = K.tris[tri].src;
-                r0 = make_float4(start > 0.0f ? start + h.t : h.t, h.p.x, h.p.y, h.p.z);
-                r1 = make_float4(h.n.x, h.n.y, h.n.z, __int_as_float(h.mat));
-                r2 = make_float4(__int_as_float(h.inst), __int_as_float(prim - E.instTriOff[h.inst]), __int_as_float(prim), 0.0f);
-            }
-            E.hits[3 * pix] = r0;
-            E.hits[3 * pix + 1] = r1;
-            E.hits[3 * pix + 2] = r2;
-        }
+        // rz_trace_rays' record, t from the camera (written before the shading, which then has the record's registers to itself)
+        if (E.hits) store_hit(K, E.instTriOff, E.hits, pix, visible, h, tri, start > 0.0f ? start + h.t : h.t);
         if (!E.rgb32f && !E.rgba8) continue;
         const v3 color = visible ? editor_shade(K, E, h.p, h.n, h.mat) : mk3(E.clear[0], E.clear[1], E.clear[2]);
         if (E.rgb32f) {

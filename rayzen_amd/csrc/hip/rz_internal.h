@@ -10,6 +10,18 @@
 
 namespace rz {
 
+// ---- the colour outputs of the passes that run outside a frame (rz_denoise.hip, rz_temporal.hip, rz_upscale_body.h,
+// rz_antialias_body.h): pixel p as (c, w) in `dst` and as three floats in `rgb`, each optional.  C: a colour with x, y, z (v3).
+template <class C>
+__device__ __forceinline__ void store_colour(float4* dst, float* rgb, size_t p, const C& c, float w) {
+    if (dst) dst[p] = make_float4(c.x, c.y, c.z, w);
+    if (rgb) {
+        rgb[3 * p] = c.x;
+        rgb[3 * p + 1] = c.y;
+        rgb[3 * p + 2] = c.z;
+    }
+}
+
 // ---- rz_kernels.hip
 void launch_render_pixels(const KParams& K, bool counted, hipStream_t stream);
 SamplesPlan plan_render_samples(int spp, int nSlots, bool glass);

@@ -1,6 +1,6 @@
 // rz_query.h -- what the kernels that query the device scene outside a frame share (rz_rays.hip: rz_trace_rays /
-// rz_shadow_rays; rz_editor.hip: rz_render_editor): their occupancy, the closest-hit query they run, their BLAS stack and
-// the way a walk cut short at its backstop is reported.
+// rz_shadow_rays; rz_editor.hip: rz_render_editor; the guide and antialias casts through rz_pixel_cast.h): their occupancy, the
+// closest-hit query they run, their BLAS stack, the way a walk cut short at its backstop is reported and the rz_hit record.
 #pragma once
 #include "rz_trace.h"
 
@@ -20,6 +20,26 @@ template <bool OVF, bool SPREAD>
 __device__ __forceinline__ bool ray_query(const KParams& K, v3 o, v3 d, HitRec& h, const BlasStackT<OVF>& bstk, TraceExtra& x) {
     Tally c = {};
     return SPREAD ? trace_spread<false, OVF, true>(K, o, d, h, bstk, c, &x) : trace_closest<false, OVF, true>(K, o, d, h, bstk, c, &x);
+}
+
+// The rz_hit of a query, three 16-B stores at hits[3 i ..]: (t, point | normal, material | instance, triangle, prim, reserved).
+// tri: the winner (TraceExtra::tri); t: the distance the record states -- h.t, or what the caller measured along its own ray
+// (rz_editor_kernel past the near plane, the length of a see-through chain).  A miss: the shader's initial tHit (FS:459), ids
+// -1, point and normal zero.
+__device__ __forceinline__ void store_hit(const KParams& K, const int32_t* instTriOff, float4* hits, size_t i, bool found,
+                                          const HitRec& h, int tri, float t) {
+    float4 r0 = make_float4(1e30f, 0.0f, 0.0f, 0.0f);
+    float4 r1 = make_float4(0.0f, 0.0f, 0.0f, __int_as_float(-1));
+    float4 r2 = make_float4(__int_as_float(-1), __int_as_float(-1), __int_as_float(-1), 0.0f);
+    if (found) {
+        const int prim = K.tris[tri].src;           // the winner's index in binding 0
+        r0 = make_float4(t, h.p.x, h.p.y, h.p.z);
+        r1 = make_float4(h.n.x, h.n.y, h.n.z, __int_as_float(h.mat));
+        r2 = make_float4(__int_as_float(h.inst), __int_as_float(prim - instTriOff[h.inst]), __int_as_float(prim), 0.0f);
+    }
+    hits[3 * i] = r0;
+    hits[3 * i + 1] = r1;
+    hits[3 * i + 2] = r2;
 }
 
 template <bool OVF>

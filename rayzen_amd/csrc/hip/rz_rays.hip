@@ -10,6 +10,7 @@
 // visibility).  The BLAS stack is an LDS window plus per-resident-wave overflow columns, sized by the render's rule
 // (rz_context.hip: size_blas_stack).  Nothing of the render state -- accumulation, currentIor, pools, the claim counter -- is
 // touched; a walk that stops at its backstop sets RZ_BACKSTOP_RAYS in the context's backstop word, as the render kernels do.
+// The rz_hit record is store_hit of rz_query.h, which every pass that returns one calls.
 #include <algorithm>
 
 #include "rz_internal.h"
@@ -35,19 +36,7 @@ __global__ __launch_bounds__(64, RZ_RAYS_MIN_WAVES) void rz_trace_rays_kernel(co
             TraceExtra x;
             const bool found = ray_query<OVF, SPREAD>(K, mk3(a.x, a.y, a.z), mk3(b.x, b.y, b.z), h, bstk, x);
             cut = cut || x.cut;
-            // a miss: the shader's initial tHit (FS:459), ids -1, point and normal zero
-            float4 r0 = make_float4(1e30f, 0.0f, 0.0f, 0.0f);
-            float4 r1 = make_float4(0.0f, 0.0f, 0.0f, __int_as_float(-1));
-            float4 r2 = make_float4(__int_as_float(-1), __int_as_float(-1), __int_as_float(-1), 0.0f);
-            if (found) {
-                const int prim = K.tris[x.tri].src;         // the winner's index in binding 0
-                r0 = make_float4(h.t, h.p.x, h.p.y, h.p.z);
-                r1 = make_float4(h.n.x, h.n.y, h.n.z, __int_as_float(h.mat));
-                r2 = make_float4(__int_as_float(h.inst), __int_as_float(prim - instTriOff[h.inst]), __int_as_float(prim), 0.0f);
-            }
-            hits[3 * i] = r0;
-            hits[3 * i + 1] = r1;
-            hits[3 * i + 2] = r2;
+            store_hit(K, instTriOff, hits, (size_t)i, found, h, x.tri, h.t);
         }
     }
     rays_backstop(errWord, cut);

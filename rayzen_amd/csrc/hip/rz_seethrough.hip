@@ -18,10 +18,10 @@
 //   miss ends the chain (final = miss); L += t; M = materials[clamp(h.material)]; if k == max_depth the chain ends at h; else
 //   if M.transparency > 0 the dielectric step of scatter(); else if M.reflectivity >= 1 d = reflect(d, n), T *= 0.95; else the
 //   chain ends at h.  After a step o = hp + (hn * pushDir) * 0.003 and k += 1.  cls = 0 if k == 0, else m_first + 1.
+// The pixel's ray, the chain loop and the (n, L | x, word) part of the record are rz_pixel_cast.h's, the step rz_chain_step.h's,
+// the rz_hit rz_query.h's (store_hit), the gather rz_upscale_body.h's.
 #include "rz_upscale_body.h"
-#include "rz_query.h"
-#include "rz_path.h"
-#include "rz_chain_step.h"
+#include "rz_pixel_cast.h"
 
 namespace rz {
 
@@ -36,55 +36,18 @@ __global__ __launch_bounds__(64, RZ_RAYS_MIN_WAVES) void rz_seethrough_guides(co
         const int py = (int)(u / G.unitsX), px = (int)(u - (long long)py * G.unitsX) * 64 + lane;
         const bool inside = px < K.width;
         v3 o = cam, d = mk3(0.0f, 0.0f, 0.0f);
-        if (inside) {
-            v2 uv;
-            uv.x = ((float)px + 0.5f) / (float)K.width;
-            uv.y = ((float)py + 0.5f) / (float)K.height;
-            d = camera_ray_centre(K.invProj, K.invView, uv);
-        }
-        float ior = 1.0f, L = 0.0f;
-        v3 T = mk3(1.0f, 1.0f, 1.0f);
-        int k = 0, first = -1, tri = 0;
-        bool found = false;
-        HitRec h = {};
-        bool run = inside;
-        while (rz_ballot(run) != 0ull) {        // at most max_depth + 1 trips: a lane with k == max_depth ends at its hit
-            if (run) {
-                HitRec hq;
-                TraceExtra x;
-                found = ray_query<OVF, false>(K, o, d, hq, bstk, x);
-                cut = cut || x.cut;
-                run = false;
-                if (found) {
-                    h = hq;
-                    tri = x.tri;
-                    run = chain_step(K, G.maxDepth, hq, o, d, T, ior, L, k, first);     // rz_chain_step.h
-                }
-            }
-        }
+        if (inside) d = pixel_centre_dir(K, px, py, K.width, K.height);
+        const ChainEnd e = cast_chain<OVF>(K, G.maxDepth, o, d, inside, bstk, cut);
         if (!inside) continue;
         const size_t pix = (size_t)py * K.width + px;
-        const int word = found ? min(max(h.mat, 0), K.nMaterials - 1) : -1;
-        const int cls = k == 0 ? 0 : first + 1;
-        G.rec[3 * pix] = found ? make_float4(h.n.x, h.n.y, h.n.z, L) : make_float4(0.0f, 0.0f, 0.0f, 1e30f);
-        G.rec[3 * pix + 1] = found ? make_float4(h.p.x, h.p.y, h.p.z, __int_as_float(word))
-                                   : make_float4(0.0f, 0.0f, 0.0f, __int_as_float(-1));
-        G.rec[3 * pix + 2] = make_float4(T.x, T.y, T.z, __int_as_float(cls));
-        if (G.hits) {           // rz_trace_rays_kernel's record of the final query, with t = L
-            float4 r0 = make_float4(1e30f, 0.0f, 0.0f, 0.0f);
-            float4 r1 = make_float4(0.0f, 0.0f, 0.0f, __int_as_float(-1));
-            float4 r2 = make_float4(__int_as_float(-1), __int_as_float(-1), __int_as_float(-1), 0.0f);
-            if (found) {
-                const int prim = K.tris[tri].src;
-                r0 = make_float4(L, h.p.x, h.p.y, h.p.z);
-                r1 = make_float4(h.n.x, h.n.y, h.n.z, __int_as_float(h.mat));
-                r2 = make_float4(__int_as_float(h.inst), __int_as_float(prim - G.instTriOff[h.inst]), __int_as_float(prim), 0.0f);
-            }
-            G.hits[3 * pix] = r0;
-            G.hits[3 * pix + 1] = r1;
-            G.hits[3 * pix + 2] = r2;
-        }
-        if (G.chains) G.chains[pix] = make_float4(T.x, T.y, T.z, __int_as_float(k | ((first + 1) << 8)));
+        float4 g0, g1;
+        guide_record(K, e.found, e.h, e.L, g0, g1);
+        G.rec[3 * pix] = g0;
+        G.rec[3 * pix + 1] = g1;
+        G.rec[3 * pix + 2] = make_float4(e.T.x, e.T.y, e.T.z, __int_as_float(e.cls()));
+        // rz_trace_rays_kernel's record of the final query, with t = L
+        if (G.hits) store_hit(K, G.instTriOff, G.hits, pix, e.found, e.h, e.tri, e.L);
+        if (G.chains) G.chains[pix] = make_float4(e.T.x, e.T.y, e.T.z, __int_as_float(e.k | ((e.first + 1) << 8)));
     }
     rays_backstop(G.errWord, cut);
 }

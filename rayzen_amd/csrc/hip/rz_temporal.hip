@@ -164,12 +164,7 @@ __global__ __launch_bounds__(256) void rz_temporal_accumulate(const TemporalLaun
     if (T.dst || T.rgb) {       // K = 0: D alpha; a pixel without history returns c_p itself (rz_denoise's K = 0)
         v3 out = c;
         if (accepted) out = (T.demodulate && hit) ? mk3(D.x * al.x, D.y * al.y, D.z * al.z) : D;
-        if (T.dst) T.dst[p] = make_float4(out.x, out.y, out.z, 1.0f);
-        if (T.rgb) {
-            T.rgb[3 * p] = out.x;
-            T.rgb[3 * p + 1] = out.y;
-            T.rgb[3 * p + 2] = out.z;
-        }
+        store_colour(T.dst, T.rgb, p, out, 1.0f);
     }
 }
 
@@ -293,12 +288,7 @@ __global__ __launch_bounds__(256) void rz_temporal_atrous(const TemporalFilterLa
         const DevMaterial& m = F.materials[wordP];
         out = mk3(out.x * m.albedo[0], out.y * m.albedo[1], out.z * m.albedo[2]);
     }
-    if (F.dst) F.dst[p] = make_float4(out.x, out.y, out.z, LAST ? 1.0f : var);
-    if (LAST && F.rgb) {
-        F.rgb[3 * p] = out.x;
-        F.rgb[3 * p + 1] = out.y;
-        F.rgb[3 * p + 2] = out.z;
-    }
+    store_colour(F.dst, LAST ? F.rgb : nullptr, p, out, LAST ? 1.0f : var);
 }
 
 static dim3 pixel_grid(int w, int h) { return dim3((unsigned)((w + 63) / 64), (unsigned)((h + 3) / 4)); }

@@ -137,12 +137,7 @@ __device__ __forceinline__ void upscale_gather_body(const UpscaleLaunch& U) {
     float4 g2 = make_float4(1.0f, 1.0f, 1.0f, 0.0f);
     if constexpr (CHAIN) g2 = U.guideHi[REC * P + 2];
     const v3 out = upscale_pixel<CHAIN>(U, X, Y, g0, g1, g2);
-    if (U.dst) U.dst[P] = make_float4(out.x, out.y, out.z, 1.0f);
-    if (U.rgb) {
-        U.rgb[3 * P] = out.x;
-        U.rgb[3 * P + 1] = out.y;
-        U.rgb[3 * P + 2] = out.z;
-    }
+    store_colour(U.dst, U.rgb, P, out, 1.0f);
 }
 
 }  // namespace rz
