@@ -602,7 +602,9 @@ int finalize_body(rz_ctx* c) {
                 if (c->layoutOnDevice) {
                     rc = device_view(c, inst[i].blasNodeOffset, inst[i].blasTriOffset, inst[i].globalTriOffset, V);
                     if (rc == 1) {          // start over on the host
-                        if (keepTris) { const int src = sync_tris_host(c); if (src != RZ_OK) return src; }     // (the host layout reads the host copy)
+                        // (the host layout reads the host copy: stale after a rebuild that kept binding 0 on the device, and, with
+                        //  no geometry upload pending, after a device-pointer refit)
+                        { const int src = sync_tris_host(c); if (src != RZ_OK) return src; }
                         c->layoutOnDevice = false;
                         c->views.clear(); c->hPairs.clear(); c->hTris.clear(); c->triNValid = -1;
                         redo = true;

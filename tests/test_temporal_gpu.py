@@ -271,8 +271,11 @@ def test_what_drops_the_history_and_what_keeps_it():
     assert length() == 1 and length() == 2 and length() == 3
     tris = sc.arrays[S.BIND_TRIANGLES]
     xf = np.asarray(sc.arrays[S.BIND_INSTANCES]["transform"], F32).reshape(-1, 16)
+    edited = sc.arrays[S.BIND_MATERIALS][:1].copy()
+    edited["roughness"] = 0.5                                    # (a real edit: rz_update drops a patch that changes nothing)
+    assert edited.tobytes() != sc.arrays[S.BIND_MATERIALS][:1].tobytes()
     keeps = {
-        "rz_update": lambda: r.update(S.BIND_MATERIALS, sc.arrays[S.BIND_MATERIALS][:1]),
+        "rz_update": lambda: r.update(S.BIND_MATERIALS, edited),
         "rz_update_transforms": lambda: r.update_transforms(xf),
         "rz_refit_geometry": lambda: r.refit_geometry(),
         "rz_upload of materials": lambda: r.upload(S.BIND_MATERIALS, sc.arrays[S.BIND_MATERIALS]),
