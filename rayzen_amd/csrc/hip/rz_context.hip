@@ -40,6 +40,13 @@ struct DevBuf {
     void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
 };
 
+// Where a group of the caller's arrays is current (DESIGN.md 4.3 has the table).  The context keeps a host copy and a device
+// copy of each group, several calls write only one of the two, and at least one of them always holds the bytes in force.
+//   kTris: host[0] | dRawTris.   kBlas: host[7], [8] | dRawNodes, dRawIdx, described by devNodes, devIdx, devRoots.
+//   kTlas: host[9], [5], [6] | dInstRef, dTlasNodes, dTlasIdx, described by tlasHostCounts, devTlasNodes; dXforms holds the transforms in force.
+struct Residency { bool host = true, dev = false; };
+enum Group { kTris, kBlas, kTlas, kNumGroups, kNoGroup = -1 };
+
 // One BLAS as seen from an instance: RayZen lets every instance name its own
 // node / index / triangle offsets (include/BVH.h:14-21); distinct triples are
 // laid out once each.
@@ -85,6 +92,15 @@ size_t elem_size(int b) {
         default: return 0;
     }
 }
+// (materials and lights have a host copy only: finalize uploads it whenever it has changed)
+int group_of(int b) {
+    switch (b) {
+        case RZ_BIND_TRIANGLES: return kTris;
+        case RZ_BIND_BLAS_NODES: case RZ_BIND_BLAS_INDICES: return kBlas;
+        case RZ_BIND_INSTANCES: case RZ_BIND_TLAS_NODES: case RZ_BIND_TLAS_INDICES: return kTlas;
+        default: return kNoGroup;
+    }
+}
 
 }  // namespace
 
@@ -112,6 +128,7 @@ struct rz_ctx {
     // host copies of the caller's arrays (the re-layout needs them; rz_update patches them)
     std::vector<unsigned char> host[kNumBindings];
     bool present[kNumBindings] = {};
+    Residency where[kNumGroups];    // triangles, BLAS nodes + indices, instances + TLAS: which copy is current
     bool geomDirty = true, instDirty = true, tlasDirty = true, matDirty = true, lightDirty = true;
 
     // device scene
@@ -129,7 +146,6 @@ struct rz_ctx {
     DevBuf dXforms, dInstRef, dTlasScratch, dProjBoxes, dBuildWs, dTlasDfs, dTriN;
     int nTlasDfs = 0;               // pop positions of the TLAS (rz_trace.h: trace_closest)
     int* tlasHostCounts = nullptr;      // pinned: node count, index count, depth
-    bool deviceOwnsTlas = false;        // instances + TLAS on the device are newer than the host copies
     int devTlasNodes = 0;
     bool sceneHasTransparency = true;   // some triangle uses a material with transparency > 0
     const char* lastKernel = "";
@@ -147,8 +163,7 @@ struct rz_ctx {
     bool matChangedSinceLayout = false; // materials were uploaded after the BLAS views were laid out: their per-view transparency hints are stale
     unsigned devTransparent = 0;       // device re-layout: bit 0 a transparent material is in use, bit 1 an irregular child box
     bool irregularBoxes = false;       // some BLAS child box has min > max or a NaN plane: the traversal keeps the generic slab test
-    // rz_build_geometry: BLAS nodes / indices live in dRawNodes / dRawIdx; the host copies are fetched on demand
-    bool geomOnDevice = false, geomHostFresh = false;
+    // what describes dRawNodes / dRawIdx while only they are current (rz_build_geometry, a device refit, rz_rebuild_geometry)
     size_t devNodes = 0, devIdx = 0;
     std::map<int, rz_bvh_node> devRoots;    // node offset of a mesh -> its root node
     // ray queries (rz_trace_rays / rz_shadow_rays, rz_rays.hip): their own BLAS overflow columns, the staging buffers of
@@ -180,7 +195,6 @@ struct rz_ctx {
     // and the segments' counts; allocated on first use and kept
     DevBuf dAasList, dAasCounts;
     // rz_refit_geometry (rz_refit.hip)
-    bool trisHostStale = false;         // binding 0 on the device (dRawTris) is newer than the host copy: fetched on demand (sync_tris_host)
     unsigned long long layoutGen = 0;   // counts the times the views / instances were laid out
     unsigned long long refitGen = ~0ull; // the layout the refit topology below was derived from
     std::vector<RefitView> refitViews;  // in the order of `views`
@@ -201,7 +215,6 @@ struct rz_ctx {
     int qualBlocks = 0;
     std::map<std::tuple<int, int, int>, double> costBuilt;
     unsigned long long costGen = ~0ull;  // the layout whose views all have their entry in costBuilt
-    bool keepDevTris = false;           // rz_rebuild_geometry's re-layout: dRawTris is binding 0 as it stands, neither fetched nor uploaded again
 };
 
 namespace {
@@ -283,16 +296,64 @@ int upload_vec(rz_ctx* c, DevBuf& b, const void* src, size_t bytes) {
 
 template <class T> const T* hostArr(const rz_ctx* c, int b) { return reinterpret_cast<const T*>(c->host[b].data()); }
 template <class T> size_t hostCount(const rz_ctx* c, int b) { return c->host[b].size() / sizeof(T); }
-size_t blasNodeCount(const rz_ctx* c) { return c->geomOnDevice ? c->devNodes : hostCount<rz_bvh_node>(c, RZ_BIND_BLAS_NODES); }
-size_t blasIdxCount(const rz_ctx* c) { return c->geomOnDevice ? c->devIdx : hostCount<int32_t>(c, RZ_BIND_BLAS_INDICES); }
+size_t blasNodeCount(const rz_ctx* c) { return c->where[kBlas].host ? hostCount<rz_bvh_node>(c, RZ_BIND_BLAS_NODES) : c->devNodes; }
+size_t blasIdxCount(const rz_ctx* c) { return c->where[kBlas].host ? hostCount<int32_t>(c, RZ_BIND_BLAS_INDICES) : c->devIdx; }
 
-int sync_geom_host(rz_ctx* c);
-int sync_tris_host(rz_ctx* c);
+// ---- the four operations on a group's Residency (nothing else writes one) and the fetch they share ----------------------
+// The device copy of a group brought to its host copy: one stream synchronisation, then the copies.  `skip`: a binding the
+// caller is about to replace whole (rz_upload), which is not fetched; the others of its group must survive on the host.
+int fetch_host(rz_ctx* c, int g, int skip) {
+    struct Part { int binding; const DevBuf* src; size_t bytes; } parts[3];
+    int n = 0;
+    if (g == kTris) {
+        parts[n++] = {RZ_BIND_TRIANGLES, &c->dRawTris, c->host[RZ_BIND_TRIANGLES].size()};
+    } else if (g == kBlas) {
+        parts[n++] = {RZ_BIND_BLAS_NODES, &c->dRawNodes, c->devNodes * sizeof(rz_bvh_node)};
+        parts[n++] = {RZ_BIND_BLAS_INDICES, &c->dRawIdx, c->devIdx * sizeof(int32_t)};
+        alloc_point(c);
+    } else {        // (3.4 KB at 16 instances)
+        parts[n++] = {RZ_BIND_INSTANCES, &c->dInstRef, c->host[RZ_BIND_INSTANCES].size()};
+        parts[n++] = {RZ_BIND_TLAS_NODES, &c->dTlasNodes, (size_t)c->tlasHostCounts[0] * sizeof(rz_bvh_node)};
+        parts[n++] = {RZ_BIND_TLAS_INDICES, &c->dTlasIdx, (size_t)c->tlasHostCounts[1] * sizeof(int32_t)};
+    }
+    if (n == 1 && parts[0].binding == skip) return RZ_OK;
+    for (int k = 0; k < n; ++k)
+        if (parts[k].binding != skip) c->host[parts[k].binding].resize(parts[k].bytes);
+    RZ_HIP(c, hipStreamSynchronize(c->stream));
+    for (int k = 0; k < n; ++k)
+        if (parts[k].binding != skip && parts[k].bytes)
+            RZ_HIP(c, hipMemcpy(c->host[parts[k].binding].data(), parts[k].src->p, parts[k].bytes, hipMemcpyDeviceToHost));
+    return RZ_OK;
+}
+
+// Need host: whoever reads the host copy asks first.  A look: the device side stays as it was.
+int need_host(rz_ctx* c, int g, int skip = -1) {
+    if (c->where[g].host) return RZ_OK;
+    const int rc = fetch_host(c, g, skip);
+    if (rc == RZ_OK) c->where[g].host = true;
+    return rc;
+}
+
+// Host changed: whoever writes the host copy, or lays the device scene out from it, takes the group to the host.
+int host_changed(rz_ctx* c, int g, int skip = -1) {
+    const int rc = need_host(c, g, skip);
+    if (rc != RZ_OK) return rc;
+    c->where[g].dev = false;
+    if (g == kBlas) c->devRoots.clear();        // (they described the device copy)
+    return RZ_OK;
+}
+
+// Device changed: a kernel or a device-to-device copy wrote the device copy.  Device mirrors host: the host copy was uploaded as it stands.
+void device_changed(rz_ctx* c, int g) { c->where[g].host = false; c->where[g].dev = true; }
+void device_mirrors_host(rz_ctx* c, int g) { c->where[g].host = c->where[g].dev = true; }
+
+void drop_layout(rz_ctx* c) { c->views.clear(); c->hPairs.clear(); c->hTris.clear(); c->triNValid = -1; }
+void drop_built_costs(rz_ctx* c) { c->costBuilt.clear(); c->costGen = ~0ull; }    // new trees: their "built" costs are measured again
 
 // Lay out one BLAS: breadth-first walk from its root, one DevPair per internal
 // node (so the hot top levels are contiguous), triangles gathered to leaf order.
 int build_view(rz_ctx* c, int nodeOff, int triOff, int gTriOff, BlasView& V) {
-    { int rc = sync_geom_host(c); if (rc != RZ_OK) return rc; }
+    for (int g : {kBlas, kTris}) { const int rc = need_host(c, g); if (rc != RZ_OK) return rc; }
     const rz_bvh_node* nodes = hostArr<rz_bvh_node>(c, RZ_BIND_BLAS_NODES);
     const int32_t* idx = hostArr<int32_t>(c, RZ_BIND_BLAS_INDICES);
     const rz_triangle* tris = hostArr<rz_triangle>(c, RZ_BIND_TRIANGLES);
@@ -392,47 +453,6 @@ int build_view(rz_ctx* c, int nodeOff, int triOff, int gTriOff, BlasView& V) {
     return RZ_OK;
 }
 
-// After rz_update_transforms the device holds newer instances / TLAS than the host copies: bring them back
-// (3.4 KB at 16 instances) before anything reads or patches those copies.
-// After rz_build_geometry the BLAS nodes / indices exist only on the device: bring them to the host copies before
-// anything reads or patches those (rz_read_binding, rz_update, the host re-layout, the wireframe's path walk).
-int sync_geom_host(rz_ctx* c) {
-    if (!c->geomOnDevice || c->geomHostFresh) return RZ_OK;
-    alloc_point(c);
-    c->host[RZ_BIND_BLAS_NODES].resize(c->devNodes * sizeof(rz_bvh_node));
-    c->host[RZ_BIND_BLAS_INDICES].resize(c->devIdx * sizeof(int32_t));
-    RZ_HIP(c, hipStreamSynchronize(c->stream));
-    if (c->devNodes) RZ_HIP(c, hipMemcpy(c->host[RZ_BIND_BLAS_NODES].data(), c->dRawNodes.p, c->devNodes * sizeof(rz_bvh_node), hipMemcpyDeviceToHost));
-    if (c->devIdx) RZ_HIP(c, hipMemcpy(c->host[RZ_BIND_BLAS_INDICES].data(), c->dRawIdx.p, c->devIdx * sizeof(int32_t), hipMemcpyDeviceToHost));
-    c->geomHostFresh = true;
-    return RZ_OK;
-}
-
-// After a device-pointer rz_refit_geometry the triangles exist only in dRawTris: bring them to the host copy before
-// anything reads, patches or re-uploads that (rz_read_binding, rz_update, either re-layout).
-int sync_tris_host(rz_ctx* c) {
-    if (!c->trisHostStale) return RZ_OK;
-    RZ_HIP(c, hipStreamSynchronize(c->stream));
-    const size_t bytes = c->host[RZ_BIND_TRIANGLES].size();
-    if (bytes) RZ_HIP(c, hipMemcpy(c->host[RZ_BIND_TRIANGLES].data(), c->dRawTris.p, bytes, hipMemcpyDeviceToHost));
-    c->trisHostStale = false;
-    return RZ_OK;
-}
-
-int sync_host_from_device(rz_ctx* c) {
-    if (!c->deviceOwnsTlas) return RZ_OK;
-    const size_t nInst = hostCount<rz_bvh_instance>(c, RZ_BIND_INSTANCES);
-    RZ_HIP(c, hipStreamSynchronize(c->stream));
-    const int nn = c->tlasHostCounts[0], ni = c->tlasHostCounts[1];
-    c->host[RZ_BIND_TLAS_NODES].resize((size_t)nn * sizeof(rz_bvh_node));
-    c->host[RZ_BIND_TLAS_INDICES].resize((size_t)ni * sizeof(int32_t));
-    if (nInst) RZ_HIP(c, hipMemcpy(c->host[RZ_BIND_INSTANCES].data(), c->dInstRef.p, nInst * sizeof(rz_bvh_instance), hipMemcpyDeviceToHost));
-    if (nn) RZ_HIP(c, hipMemcpy(c->host[RZ_BIND_TLAS_NODES].data(), c->dTlasNodes.p, (size_t)nn * sizeof(rz_bvh_node), hipMemcpyDeviceToHost));
-    if (ni) RZ_HIP(c, hipMemcpy(c->host[RZ_BIND_TLAS_INDICES].data(), c->dTlasIdx.p, (size_t)ni * sizeof(int32_t), hipMemcpyDeviceToHost));
-    c->deviceOwnsTlas = false;
-    return RZ_OK;
-}
-
 // The TLAS as the list of its nodes in the order FS:464-501 pops them (right child first), with the position that follows
 // each subtree (TlasDfs, rz_scene_dev.h).  `below` is the number of stack entries under a node when it is popped: the
 // shader's stack[64] holds no more, and the oracle drops a push that would not fit -- such a node never expands (count 0).
@@ -497,18 +517,21 @@ bool host_relayout_forced(const rz_ctx* c) {
     return e && *e && *e != '0';
 }
 
-int prepare_device_relayout(rz_ctx* c, bool keepTris) {       // raw arrays + materials on the device, output buffers sized, scratch
+int prepare_device_relayout(rz_ctx* c) {       // raw arrays + materials on the device, output buffers sized, scratch
     const size_t nNodes = blasNodeCount(c), nIdx = blasIdxCount(c);
     int rc;
-    if (!c->geomOnDevice) {                    // (rz_build_geometry left nodes and indices there already)
+    // a group goes up exactly when its device copy is not current (rz_build_geometry, a device refit, rz_rebuild_geometry left theirs there)
+    if (!c->where[kBlas].dev) {
         rc = upload_vec(c, c->dRawNodes, c->host[RZ_BIND_BLAS_NODES].data(), c->host[RZ_BIND_BLAS_NODES].size());
         if (rc != RZ_OK) return rc;
         rc = upload_vec(c, c->dRawIdx, c->host[RZ_BIND_BLAS_INDICES].data(), c->host[RZ_BIND_BLAS_INDICES].size());
         if (rc != RZ_OK) return rc;
+        device_mirrors_host(c, kBlas);
     }
-    if (!keepTris) {                           // (rz_rebuild_geometry: dRawTris holds binding 0 as it stands, possibly newer than the host copy)
+    if (!c->where[kTris].dev) {
         rc = upload_vec(c, c->dRawTris, c->host[RZ_BIND_TRIANGLES].data(), c->host[RZ_BIND_TRIANGLES].size());
         if (rc != RZ_OK) return rc;
+        device_mirrors_host(c, kTris);
     }
     rc = ensure(c, c->dPairs, std::max<size_t>(nNodes, 1) * sizeof(DevPair));
     if (rc != RZ_OK) return rc;
@@ -526,7 +549,7 @@ int device_view(rz_ctx* c, int nodeOff, int triOff, int gTriOff, BlasView& V) {
     const long long nTris = (long long)hostCount<rz_triangle>(c, RZ_BIND_TRIANGLES);
     if (nodeOff < 0 || nodeOff >= nNodes) return 1;
     rz_bvh_node root;
-    if (c->geomOnDevice) {
+    if (!c->where[kBlas].host) {
         auto it = c->devRoots.find(nodeOff);
         if (it == c->devRoots.end()) return 1;      // an instance that does not start at a mesh's root: let the host path look at it
         root = it->second;
@@ -562,9 +585,6 @@ int finalize_body(rz_ctx* c) {
         if (!c->present[b]) return fail(c, RZ_ERR_NOT_READY, "binding %d has not been uploaded", b);
 
     // (the per-view "may hold transparent triangles" hints were taken from the materials of the moment the views were laid out)
-    // (after a rebuild of meshes on the device the device layout reads binding 0 where it is: posed triangles stay there)
-    const bool keepTris = c->geomDirty && c->keepDevTris && !host_relayout_forced(c);
-    if (c->geomDirty && !keepTris) { int rc = sync_tris_host(c); if (rc != RZ_OK) return rc; }
     if (c->geomDirty) c->matChangedSinceLayout = false;
     else if (c->matDirty && !c->matChangedSinceLayout) { c->matChangedSinceLayout = true; c->instDirty = true; }
     // materials first: the device re-layout checks triangle material indices against them
@@ -574,15 +594,17 @@ int finalize_body(rz_ctx* c) {
     }
     if (c->geomDirty) {
         // the traversal addresses a BLAS's pairs with a 32-bit byte offset (rz_trace.h: sload16_off): < 2^26 pairs per BLAS
-        const size_t nodesNow = c->geomOnDevice ? c->devNodes : hostCount<rz_bvh_node>(c, RZ_BIND_BLAS_NODES);
+        const size_t nodesNow = blasNodeCount(c);
         if (nodesNow >= ((size_t)1 << 27))
             return fail(c, RZ_ERR_BAD_SCENE, "BLAS node array holds %zu nodes; the limit is %zu", nodesNow, ((size_t)1 << 27) - 1);
-        c->views.clear(); c->hPairs.clear(); c->hTris.clear(); c->instDirty = true;
-        c->triNValid = -1;
+        drop_layout(c);
+        c->instDirty = true;
         c->devPairsUsed = c->devTrisUsed = 0; c->devTransparent = 0; c->irregularBoxes = false;
         c->layoutOnDevice = !host_relayout_forced(c);
-        if (c->layoutOnDevice) { int rc = prepare_device_relayout(c, keepTris); if (rc != RZ_OK) return rc; }
+        if (c->layoutOnDevice) { int rc = prepare_device_relayout(c); if (rc != RZ_OK) return rc; }
     }
+    // instances and TLAS are laid out from their host copies: what rz_update_transforms left on the device is no longer in force
+    if (c->instDirty || c->tlasDirty) { int rc = host_changed(c, kTlas); if (rc != RZ_OK) return rc; }
     if (c->instDirty) {
         const rz_bvh_instance* inst = hostArr<rz_bvh_instance>(c, RZ_BIND_INSTANCES);
         const size_t nInst = hostCount<rz_bvh_instance>(c, RZ_BIND_INSTANCES);
@@ -601,19 +623,16 @@ int finalize_body(rz_ctx* c) {
                 int rc;
                 if (c->layoutOnDevice) {
                     rc = device_view(c, inst[i].blasNodeOffset, inst[i].blasTriOffset, inst[i].globalTriOffset, V);
-                    if (rc == 1) {          // start over on the host
-                        // (the host layout reads the host copy: stale after a rebuild that kept binding 0 on the device, and, with
-                        //  no geometry upload pending, after a device-pointer refit)
-                        { const int src = sync_tris_host(c); if (src != RZ_OK) return src; }
+                    if (rc == 1) {          // start over on the host (build_view asks for the host copies it reads)
                         c->layoutOnDevice = false;
-                        c->views.clear(); c->hPairs.clear(); c->hTris.clear(); c->triNValid = -1;
+                        drop_layout(c);
                         redo = true;
                         break;
                     }
                 } else {
                     rc = build_view(c, inst[i].blasNodeOffset, inst[i].blasTriOffset, inst[i].globalTriOffset, V);
                 }
-                if (rc != RZ_OK) { c->views.clear(); c->hPairs.clear(); c->hTris.clear(); c->triNValid = -1; c->geomDirty = true; return rc; }
+                if (rc != RZ_OK) { drop_layout(c); c->geomDirty = true; return rc; }
                 c->views.emplace(key, V);
                 grew = true;
             }
@@ -736,7 +755,7 @@ int finalize(rz_ctx* c) {
     try {
         return finalize_body(c);
     } catch (...) {
-        c->views.clear(); c->hPairs.clear(); c->hTris.clear(); c->triNValid = -1;
+        drop_layout(c);
         c->geomDirty = true;
         throw;
     }
@@ -753,7 +772,7 @@ int finalize(rz_ctx* c) {
 #endif
 
 long long tlas_index_count(const rz_ctx* c) {
-    return c->deviceOwnsTlas ? (long long)c->tlasHostCounts[1] : (long long)hostCount<int32_t>(c, RZ_BIND_TLAS_INDICES);
+    return c->where[kTlas].host ? (long long)hostCount<int32_t>(c, RZ_BIND_TLAS_INDICES) : (long long)c->tlasHostCounts[1];
 }
 
 // One lane per sample: independent samples when no triangle is transparent, speculated currentIor otherwise
@@ -1207,25 +1226,14 @@ void rz_destroy(rz_ctx* c) {
     delete c;
 }
 
-static int upload_impl(rz_ctx* c, rz_binding binding, const void* data, size_t bytes) {
-    if (!c) return fail(nullptr, RZ_ERR_INVALID_ARG, "null context");
-    const size_t es = elem_size((int)binding);
-    if (es == 0) return fail(c, RZ_ERR_INVALID_ARG, "unknown binding %d", (int)binding);
-    if (bytes % es) return fail(c, RZ_ERR_INVALID_ARG, "binding %d: %zu bytes is not a multiple of the %zu-byte element", (int)binding, bytes, es);
-    if (bytes && !data) return fail(c, RZ_ERR_INVALID_ARG, "null data");
-    if (c->deviceOwnsTlas) { int rc = sync_host_from_device(c); if (rc != RZ_OK) return rc; }
-    if (c->geomOnDevice && (binding == RZ_BIND_BLAS_NODES || binding == RZ_BIND_BLAS_INDICES)) {
-        int rc = sync_geom_host(c);         // the other of the two arrays must survive on the host
-        if (rc != RZ_OK) return rc;
-        c->geomOnDevice = false;
-    }
-    alloc_point(c);
-    c->host[binding].assign(static_cast<const unsigned char*>(data), static_cast<const unsigned char*>(data) + bytes);
-    if (binding == RZ_BIND_TRIANGLES) c->trisHostStale = false;
-    if (binding == RZ_BIND_BLAS_NODES || binding == RZ_BIND_BLAS_INDICES) { c->costBuilt.clear(); c->costGen = ~0ull; }   // trees handed over
-    if (binding == RZ_BIND_TRIANGLES || binding == RZ_BIND_BLAS_NODES || binding == RZ_BIND_BLAS_INDICES || binding == RZ_BIND_INSTANCES)
-        c->tmpValid = false;                // new geometry or instances: rz_denoise_temporal's history describes another scene
-    c->present[binding] = true;
+// What rz_upload, rz_update and rz_read_binding share.  Before the call touches a binding's host copy: its group's, current
+// (`replacing`: all of the group but the binding itself, which the call overwrites whole).  After the call has changed it:
+// the device copy is not current any more, and finalize has the matching part of the device scene to redo.
+static int host_copy_for(rz_ctx* c, int binding, bool replacing = false) {
+    const int g = group_of(binding);
+    return g == kNoGroup ? RZ_OK : need_host(c, g, replacing ? binding : -1);
+}
+static void mark_dirty(rz_ctx* c, int binding) {
     switch (binding) {
         case RZ_BIND_MATERIALS: c->matDirty = true; break;
         case RZ_BIND_LIGHTS: c->lightDirty = true; break;
@@ -1233,7 +1241,29 @@ static int upload_impl(rz_ctx* c, rz_binding binding, const void* data, size_t b
         case RZ_BIND_INSTANCES: c->instDirty = true; break;
         default: c->geomDirty = true; break;
     }
+}
+static int host_copy_changed(rz_ctx* c, int binding) {
+    const int g = group_of(binding);
+    if (g != kNoGroup) { const int rc = host_changed(c, g); if (rc != RZ_OK) return rc; }
+    if (g == kBlas) drop_built_costs(c);        // trees handed over
+    mark_dirty(c, binding);
     return RZ_OK;
+}
+
+static int upload_impl(rz_ctx* c, rz_binding binding, const void* data, size_t bytes) {
+    if (!c) return fail(nullptr, RZ_ERR_INVALID_ARG, "null context");
+    const size_t es = elem_size((int)binding);
+    if (es == 0) return fail(c, RZ_ERR_INVALID_ARG, "unknown binding %d", (int)binding);
+    if (bytes % es) return fail(c, RZ_ERR_INVALID_ARG, "binding %d: %zu bytes is not a multiple of the %zu-byte element", (int)binding, bytes, es);
+    if (bytes && !data) return fail(c, RZ_ERR_INVALID_ARG, "null data");
+    alloc_point(c);
+    c->host[binding].reserve(bytes);        // (the allocation that can fail, before the group is touched: assign() below cannot throw)
+    { const int rc = host_copy_for(c, binding, true); if (rc != RZ_OK) return rc; }
+    c->host[binding].assign(static_cast<const unsigned char*>(data), static_cast<const unsigned char*>(data) + bytes);
+    if (binding == RZ_BIND_TRIANGLES || binding == RZ_BIND_BLAS_NODES || binding == RZ_BIND_BLAS_INDICES || binding == RZ_BIND_INSTANCES)
+        c->tmpValid = false;                // new geometry or instances: rz_denoise_temporal's history describes another scene
+    c->present[binding] = true;
+    return host_copy_changed(c, binding);
 }
 
 static int update_impl(rz_ctx* c, rz_binding binding, size_t offset, const void* data, size_t bytes) {
@@ -1241,27 +1271,13 @@ static int update_impl(rz_ctx* c, rz_binding binding, size_t offset, const void*
     if (elem_size((int)binding) == 0) return fail(c, RZ_ERR_INVALID_ARG, "unknown binding %d", (int)binding);
     if (!c->present[binding]) return fail(c, RZ_ERR_NOT_READY, "binding %d has not been uploaded", (int)binding);
     if (bytes && !data) return fail(c, RZ_ERR_INVALID_ARG, "null data");
-    if (c->deviceOwnsTlas) { int rc = sync_host_from_device(c); if (rc != RZ_OK) return rc; }
-    if (c->geomOnDevice && (binding == RZ_BIND_BLAS_NODES || binding == RZ_BIND_BLAS_INDICES)) {
-        int rc = sync_geom_host(c);
-        if (rc != RZ_OK) return rc;
-        c->geomOnDevice = false;            // the host copies are the truth again
-    }
-    if (binding == RZ_BIND_TRIANGLES) { int rc = sync_tris_host(c); if (rc != RZ_OK) return rc; }
+    { const int rc = host_copy_for(c, binding); if (rc != RZ_OK) return rc; }
     if (offset > c->host[binding].size() || bytes > c->host[binding].size() - offset)
         return fail(c, RZ_ERR_OUT_OF_RANGE, "binding %d: update [%zu,+%zu) past its %zu bytes", (int)binding, offset, bytes, c->host[binding].size());
     if (bytes == 0) return RZ_OK;
     if (std::memcmp(c->host[binding].data() + offset, data, bytes) == 0) return RZ_OK;   // unchanged: nothing to redo
     std::memcpy(c->host[binding].data() + offset, data, bytes);
-    if (binding == RZ_BIND_BLAS_NODES || binding == RZ_BIND_BLAS_INDICES) { c->costBuilt.clear(); c->costGen = ~0ull; }   // trees handed over
-    switch (binding) {
-        case RZ_BIND_MATERIALS: c->matDirty = true; break;
-        case RZ_BIND_LIGHTS: c->lightDirty = true; break;
-        case RZ_BIND_TLAS_NODES: case RZ_BIND_TLAS_INDICES: c->tlasDirty = true; break;
-        case RZ_BIND_INSTANCES: c->instDirty = true; break;
-        default: c->geomDirty = true; break;
-    }
-    return RZ_OK;
+    return host_copy_changed(c, binding);
 }
 
 static int tlas_rebuild(rz_ctx* c, const float* transforms, size_t n);
@@ -1324,7 +1340,7 @@ static int tlas_rebuild(rz_ctx* c, const float* transforms, size_t n) {
     c->devTlasNodes = c->tlasHostCounts[0];
     c->nTlasDfs = c->tlasHostCounts[0];
     c->tlasDepth = std::max(1, c->tlasHostCounts[2]);
-    c->deviceOwnsTlas = true;
+    device_changed(c, kTlas);
     return RZ_OK;
 }
 
@@ -1335,9 +1351,8 @@ static int tlas_rebuild(rz_ctx* c, const float* transforms, size_t n) {
 // if it lives on the device), uploaded, and kept until the views are laid out again.
 static int refit_topology(rz_ctx* c) {
     if (c->refitGen == c->layoutGen) return RZ_OK;
-    int rc = sync_geom_host(c);
-    if (rc != RZ_OK) return rc;
-    if (c->deviceOwnsTlas) { rc = sync_host_from_device(c); if (rc != RZ_OK) return rc; c->deviceOwnsTlas = true; }
+    int rc;
+    for (int g : {kBlas, kTlas}) if ((rc = need_host(c, g)) != RZ_OK) return rc;
     const rz_bvh_node* nodes = hostArr<rz_bvh_node>(c, RZ_BIND_BLAS_NODES);
     const long long nNodes = (long long)hostCount<rz_bvh_node>(c, RZ_BIND_BLAS_NODES);
     alloc_point(c);
@@ -1477,7 +1492,7 @@ static bool host_refit_mesh(rz_ctx* c, rz_bvh_node* nodes, long long nNodes, con
 static int refit_tlas_step(rz_ctx* c) {
     const size_t nInst = hostCount<rz_bvh_instance>(c, RZ_BIND_INSTANCES);
     if (nInst == 0) return RZ_OK;
-    if (c->deviceOwnsTlas) return tlas_rebuild(c, nullptr, nInst);
+    if (c->where[kTlas].dev) return tlas_rebuild(c, nullptr, nInst);
     const rz_bvh_instance* inst = hostArr<rz_bvh_instance>(c, RZ_BIND_INSTANCES);
     alloc_point(c);
     std::vector<float> xf(nInst * 16);
@@ -1538,7 +1553,7 @@ static int measure_costs(rz_ctx* c, std::vector<double>& costs) {
         if (nViews) std::memcpy(costs.data(), h, nViews * sizeof(double));
         return RZ_OK;
     }
-    if ((rc = sync_geom_host(c)) != RZ_OK) return rc;
+    if ((rc = need_host(c, kBlas)) != RZ_OK) return rc;
     size_t v = 0;
     for (const auto& kv : c->views) {
         if (!host_sah_cost(c, hostArr<rz_bvh_node>(c, RZ_BIND_BLAS_NODES), (long long)hostCount<rz_bvh_node>(c, RZ_BIND_BLAS_NODES),
@@ -1572,23 +1587,25 @@ static int note_built_costs(rz_ctx* c, const std::vector<double>* measured) {
     return RZ_OK;
 }
 
+// n triangles from a host or a device pointer into the host copy of binding 0, from triangle `first` on
+static int patch_host_triangles(rz_ctx* c, const rz_triangle* triangles, size_t first, size_t n, bool hostPtr) {
+    unsigned char* dst = c->host[RZ_BIND_TRIANGLES].data() + first * sizeof(rz_triangle);
+    if (hostPtr) std::memcpy(dst, triangles, n * sizeof(rz_triangle));
+    else {
+        RZ_HIP(c, hipStreamSynchronize(c->stream));
+        RZ_HIP(c, hipMemcpy(dst, triangles, n * sizeof(rz_triangle), hipMemcpyDeviceToHost));
+    }
+    return RZ_OK;
+}
+
 // The host route: patch the host copies, refit there, and let the re-layout run (RZ_FLAG_HOST_RELAYOUT; a layout that
 // fell back to the host; materials changed since the views were laid out).  Same bytes as the device route.
 static int refit_on_host(rz_ctx* c, const rz_triangle* triangles, size_t first, size_t n, bool hostPtr) {
-    int rc = sync_host_from_device(c);
-    if (rc != RZ_OK) return rc;
-    if ((rc = sync_tris_host(c)) != RZ_OK) return rc;
-    if ((rc = sync_geom_host(c)) != RZ_OK) return rc;
+    int rc;
+    for (int g : {kTlas, kTris, kBlas}) if ((rc = need_host(c, g)) != RZ_OK) return rc;
     if ((rc = note_built_costs(c, nullptr)) != RZ_OK) return rc;       // (before a box moves: rz_geometry_quality's sah_cost_built)
-    c->geomOnDevice = false;            // the host copies are the truth again
-    if (n) {
-        unsigned char* dst = c->host[RZ_BIND_TRIANGLES].data() + first * sizeof(rz_triangle);
-        if (hostPtr) std::memcpy(dst, triangles, n * sizeof(rz_triangle));
-        else {
-            RZ_HIP(c, hipStreamSynchronize(c->stream));
-            RZ_HIP(c, hipMemcpy(dst, triangles, n * sizeof(rz_triangle), hipMemcpyDeviceToHost));
-        }
-    }
+    for (int g : {kTlas, kTris, kBlas}) if ((rc = host_changed(c, g)) != RZ_OK) return rc;     // the host copies are the truth again
+    if (n && (rc = patch_host_triangles(c, triangles, first, n, hostPtr)) != RZ_OK) return rc;
     rz_bvh_node* nodes = reinterpret_cast<rz_bvh_node*>(c->host[RZ_BIND_BLAS_NODES].data());
     const long long nNodes = (long long)hostCount<rz_bvh_node>(c, RZ_BIND_BLAS_NODES), nIdx = (long long)hostCount<int32_t>(c, RZ_BIND_BLAS_INDICES);
     const long long nTris = (long long)hostCount<rz_triangle>(c, RZ_BIND_TRIANGLES);
@@ -1638,13 +1655,8 @@ static int refit_geometry_impl(rz_ctx* c, const rz_triangle* triangles, size_t f
     if (c->geomDirty && n) {
         // a re-layout is pending anyway (the geometry was uploaded or patched since the last launch -- or an earlier refit left a
         // bad materialIndex behind): the new triangles go into the host copy first, so that it is their layout that is checked
-        if ((rc = sync_tris_host(c)) != RZ_OK) return rc;
-        unsigned char* dst = c->host[RZ_BIND_TRIANGLES].data() + first * sizeof(rz_triangle);
-        if (hostPtr) std::memcpy(dst, triangles, n * sizeof(rz_triangle));
-        else {
-            RZ_HIP(c, hipStreamSynchronize(c->stream));
-            RZ_HIP(c, hipMemcpy(dst, triangles, n * sizeof(rz_triangle), hipMemcpyDeviceToHost));
-        }
+        if ((rc = host_changed(c, kTris)) != RZ_OK) return rc;
+        if ((rc = patch_host_triangles(c, triangles, first, n, hostPtr)) != RZ_OK) return rc;
         copied = true;                  // (the re-layout below uploads them with the rest)
     }
     rc = finalize(c);                   // the device scene must exist: the refit patches it
@@ -1656,7 +1668,8 @@ static int refit_geometry_impl(rz_ctx* c, const rz_triangle* triangles, size_t f
     const size_t nInst = hostCount<rz_bvh_instance>(c, RZ_BIND_INSTANCES);
     alloc_point(c);
     std::vector<float> xf;              // the transforms in force, unless dXforms holds them (rz_update_transforms wrote the current ones)
-    if (!c->deviceOwnsTlas) {
+    const bool devXforms = c->where[kTlas].dev;
+    if (!devXforms) {
         const rz_bvh_instance* inst = hostArr<rz_bvh_instance>(c, RZ_BIND_INSTANCES);
         xf.resize(nInst * 16);
         for (size_t i = 0; i < nInst; ++i) std::memcpy(&xf[i * 16], inst[i].transform, 64);
@@ -1666,12 +1679,12 @@ static int refit_geometry_impl(rz_ctx* c, const rz_triangle* triangles, size_t f
     // binding 0 first (every triangle of the interval, whether a mesh names it or not) ...
     if (n && !copied) {
         void* dst = static_cast<rz_triangle*>(c->dRawTris.p) + first;
-        if (hostPtr) {
+        if (hostPtr) {      // both copies get the interval: each stays as current as it was (the device's is: the layout lives there)
             RZ_HIP(c, hipMemcpyAsync(dst, triangles, n * sizeof(rz_triangle), hipMemcpyHostToDevice, c->stream));
             std::memcpy(c->host[RZ_BIND_TRIANGLES].data() + first * sizeof(rz_triangle), triangles, n * sizeof(rz_triangle));
         } else {
             RZ_HIP(c, hipMemcpyAsync(dst, triangles, n * sizeof(rz_triangle), hipMemcpyDeviceToDevice, c->stream));
-            c->trisHostStale = true;
+            device_changed(c, kTris);
         }
     }
     // ... then every view whose triangle range meets the interval
@@ -1715,17 +1728,16 @@ static int refit_geometry_impl(rz_ctx* c, const rz_triangle* triangles, size_t f
         if (e != 0) return fail(c, RZ_ERR_HIP, "%s: %s", what, hipGetErrorString((hipError_t)(-e)));
         RZ_HIP(c, hipMemcpyAsync(hFlags, dFlags, (size_t)nViews * 16, hipMemcpyDeviceToHost, c->stream));
         RZ_HIP(c, hipMemcpyAsync(hRoots, c->dRefitRoots.p, (size_t)nViews * sizeof(rz_bvh_node), hipMemcpyDeviceToHost, c->stream));
-        // the node array on the device is the truth from here on, as after rz_build_geometry (the host copy is fetched on demand)
-        if (!c->geomOnDevice) {
+        // the node array on the device is the truth from here on, as after rz_build_geometry: seed what describes it from the host
+        // copy, if that is current (devRoots: emptied when the host copy last changed; the roots of the views follow below)
+        if (c->where[kBlas].host) {
             c->devNodes = hostCount<rz_bvh_node>(c, RZ_BIND_BLAS_NODES);
             c->devIdx = hostCount<int32_t>(c, RZ_BIND_BLAS_INDICES);
-            c->devRoots.clear();
-            c->geomOnDevice = true;
         }
-        c->geomHostFresh = false;
+        device_changed(c, kBlas);
     }
     // world boxes and the TLAS with the transforms in force; its synchronisation is this call's (host-pointer copies have left `triangles`)
-    rc = tlas_rebuild(c, c->deviceOwnsTlas ? nullptr : xf.data(), nInst);
+    rc = tlas_rebuild(c, devXforms ? nullptr : xf.data(), nInst);
     if (rc != RZ_OK) return rc;
     if (nInst == 0) RZ_HIP(c, hipStreamSynchronize(c->stream));
     if (!nTouched) return RZ_OK;
@@ -1784,7 +1796,7 @@ static int skin_create_impl(rz_ctx* c, size_t first, size_t n, const rz_triangle
                 }
     }
     if (!rest) {        // binding 0 as it stands (after a device-pointer refit only the device holds it: fetched first)
-        const int rc = sync_tris_host(c);
+        const int rc = need_host(c, kTris);
         if (rc != RZ_OK) return rc;
         rest = hostArr<rz_triangle>(c, RZ_BIND_TRIANGLES) + first;
     }
@@ -1978,7 +1990,8 @@ struct RebuildSaved {
     std::vector<unsigned char> host7, host8, host9;
     std::map<int, rz_bvh_node> devRoots;
     std::map<std::tuple<int, int, int>, double> costBuilt;
-    bool geomOnDevice = false, geomHostFresh = false, tmpValid = false;
+    Residency blas, tlas;           // of the arrays above (instances and TLAS: on the host, on either side of the swap)
+    bool tmpValid = false;
     size_t devNodes = 0, devIdx = 0;
     ~RebuildSaved() { nodes.release(); idx.release(); }
 };
@@ -1991,13 +2004,12 @@ static void rebuild_swap(rz_ctx* c, RebuildSaved& S) {
     c->host[RZ_BIND_INSTANCES].swap(S.host9);
     c->devRoots.swap(S.devRoots);
     c->costBuilt.swap(S.costBuilt);
-    std::swap(c->geomOnDevice, S.geomOnDevice);
-    std::swap(c->geomHostFresh, S.geomHostFresh);
+    std::swap(c->where[kBlas], S.blas);
+    std::swap(c->where[kTlas], S.tlas);
     std::swap(c->tmpValid, S.tmpValid);
     std::swap(c->devNodes, S.devNodes);
     std::swap(c->devIdx, S.devIdx);
     c->costGen = ~0ull;
-    c->deviceOwnsTlas = false;      // (the host copies of instances and TLAS were brought up to date before the first swap)
     c->geomDirty = true;            // the views are laid out again from whichever arrays are in place now
 }
 
@@ -2054,12 +2066,11 @@ static int rebuild_geometry_impl(rz_ctx* c, double maxRatio, rz_mesh_quality* ou
         if (idxExtents[k].first < idxExtents[k - 1].second)
             return fail(c, RZ_ERR_INVALID_ARG, "%s: two meshes share the index extent at %lld", what, idxExtents[k].first);
     // 4. new bindings 7 and 8 in fresh buffers (as rz_build_geometry: the context's arrays are never written to)
-    if (c->deviceOwnsTlas) { rc = sync_host_from_device(c); if (rc != RZ_OK) return rc; }      // the instances with the transforms in force
-    if (!c->layoutOnDevice) { rc = sync_tris_host(c); if (rc != RZ_OK) return rc; }
-    const bool devGeom = c->geomOnDevice || c->layoutOnDevice;         // (a device layout keeps a current copy of host-owned arrays)
+    if ((rc = host_changed(c, kTlas)) != RZ_OK) return rc;      // the instances with the transforms in force: their node offsets are patched below
+    const bool devGeom = c->where[kBlas].dev, devTris = c->where[kTris].dev;    // read where they are current (a device layout keeps a copy)
     const rz_bvh_node* srcNodes = devGeom ? static_cast<const rz_bvh_node*>(c->dRawNodes.p) : hostArr<rz_bvh_node>(c, RZ_BIND_BLAS_NODES);
     const int32_t* srcIdx = devGeom ? static_cast<const int32_t*>(c->dRawIdx.p) : hostArr<int32_t>(c, RZ_BIND_BLAS_INDICES);
-    const rz_triangle* srcTris = c->layoutOnDevice ? static_cast<const rz_triangle*>(c->dRawTris.p) : hostArr<rz_triangle>(c, RZ_BIND_TRIANGLES);
+    const rz_triangle* srcTris = devTris ? static_cast<const rz_triangle*>(c->dRawTris.p) : hostArr<rz_triangle>(c, RZ_BIND_TRIANGLES);
     const long long lead = M.empty() ? nNodes : std::get<0>(M[0].key);  // (nodes in front of the first mesh stay)
     size_t capNodes = (size_t)lead, maxN = 0;
     for (size_t k = 0; k < M.size(); ++k) {
@@ -2115,20 +2126,17 @@ static int rebuild_geometry_impl(rz_ctx* c, double maxRatio, rz_mesh_quality* ou
         S.devRoots[newOff[k]] = root;
         if (!sel[k]) S.costBuilt[std::make_tuple(newOff[k], std::get<1>(M[k].key), std::get<2>(M[k].key))] = c->costBuilt.at(M[k].key);
     }
-    S.geomOnDevice = true; S.geomHostFresh = false; S.tmpValid = false;
+    S.blas.host = false; S.blas.dev = true; S.tmpValid = false;
     S.devNodes = at; S.devIdx = (size_t)nIdx;
     // the swap, then the re-layout and world boxes + TLAS with the transforms in force, exactly as rz_refit_geometry's host route
     rebuild_swap(c, S);
     std::vector<QualityMesh> After;
-    c->keepDevTris = c->layoutOnDevice;     // (a device layout's dRawTris is binding 0 as it stands: the builder above read it too)
     try {
-        rc = finalize(c);
-        c->keepDevTris = false;
+        rc = finalize(c);               // (binding 0 is laid out from where it is current: posed triangles stay on the device)
         if (rc == RZ_OK) rc = refit_tlas_step(c);
         if (rc == RZ_OK) { named_meshes(c, named); rc = measure_meshes(c, named, After); }
         if (rc == RZ_OK && After.size() != M.size()) rc = fail(c, RZ_ERR_INTERNAL, "%s: the rebuilt scene has %zu meshes, not %zu", what, After.size(), M.size());
     } catch (...) {
-        c->keepDevTris = false;
         rebuild_swap(c, S);
         throw;
     }
@@ -2158,10 +2166,9 @@ static int build_geometry_impl(rz_ctx* c, const rz_triangle* triangles, size_t n
     }
     if (capNodes > ((size_t)1 << 30)) return fail(c, RZ_ERR_INVALID_ARG, "too many nodes");
     RZ_HIP(c, hipSetDevice(c->device));
-    if (c->deviceOwnsTlas) { int rc = sync_host_from_device(c); if (rc != RZ_OK) return rc; }
     // The build goes into FRESH buffers that replace the context's node / index arrays only when every mesh has been built:
     // a call that fails half-way (HIP error, internal limit, out of host memory) leaves the context exactly as it was -- the
-    // arrays of an earlier rz_build_geometry, which devRoots / devNodes / geomOnDevice still describe, are never written to.
+    // arrays of an earlier rz_build_geometry, which devRoots / devNodes / the BLAS group's record still describe, are never written to.
     struct Fresh { DevBuf nodes, idx; ~Fresh() { nodes.release(); idx.release(); } } fresh;
     int rc = ensure(c, fresh.nodes, std::max<size_t>(capNodes, 1) * sizeof(rz_bvh_node));
     if (rc != RZ_OK) return rc;
@@ -2200,19 +2207,19 @@ static int build_geometry_impl(rz_ctx* c, const rz_triangle* triangles, size_t n
     {   // (the last allocation that can fail: a copy first, then nothing below throws)
         std::vector<unsigned char> tcopy(reinterpret_cast<const unsigned char*>(triangles), reinterpret_cast<const unsigned char*>(triangles) + nTris * sizeof(rz_triangle));
         c->host[RZ_BIND_TRIANGLES].swap(tcopy);
-        c->trisHostStale = false;
     }
+    if ((rc = host_changed(c, kTris, RZ_BIND_TRIANGLES)) != RZ_OK) return rc;     // (replaced whole, as by rz_upload: nothing is fetched)
     RZ_HIP(c, hipStreamSynchronize(c->stream));        // nothing in flight reads the old arrays
     std::swap(c->dRawNodes, fresh.nodes);               // (the old ones are released with `fresh`)
     std::swap(c->dRawIdx, fresh.idx);
     c->host[RZ_BIND_BLAS_NODES].clear();
     c->host[RZ_BIND_BLAS_INDICES].clear();
     c->present[RZ_BIND_TRIANGLES] = c->present[RZ_BIND_BLAS_NODES] = c->present[RZ_BIND_BLAS_INDICES] = true;
-    c->geomOnDevice = true; c->geomHostFresh = false;
+    device_changed(c, kBlas);
     c->tmpValid = false;                    // (rz_denoise_temporal's history)
     c->devNodes = nodeOff; c->devIdx = idxOff;
     c->devRoots.swap(roots);
-    c->costBuilt.clear(); c->costGen = ~0ull;   // new trees: rz_geometry_quality's "built" costs are measured again
+    drop_built_costs(c);
     c->geomDirty = true;
     return RZ_OK;
 }
@@ -2257,9 +2264,7 @@ static int read_binding_impl(rz_ctx* c, rz_binding binding, void* out, size_t by
     if (!c) return fail(nullptr, RZ_ERR_INVALID_ARG, "null context");
     if (elem_size((int)binding) == 0) return fail(c, RZ_ERR_INVALID_ARG, "unknown binding %d", (int)binding);
     if (!c->present[binding]) return fail(c, RZ_ERR_NOT_READY, "binding %d has not been uploaded", (int)binding);
-    if (c->deviceOwnsTlas) { int rc = sync_host_from_device(c); if (rc != RZ_OK) return rc; c->deviceOwnsTlas = true; }
-    if (c->geomOnDevice && (binding == RZ_BIND_BLAS_NODES || binding == RZ_BIND_BLAS_INDICES)) { int rc = sync_geom_host(c); if (rc != RZ_OK) return rc; }
-    if (binding == RZ_BIND_TRIANGLES) { int rc = sync_tris_host(c); if (rc != RZ_OK) return rc; }
+    { const int rc = host_copy_for(c, binding); if (rc != RZ_OK) return rc; }
     const size_t have = c->host[binding].size();
     if (needed) *needed = have;
     if (!out) return RZ_OK;
@@ -2422,7 +2427,7 @@ static int present_impl(rz_ctx* c, const rz_present_params* pp, uint8_t* rgba8, 
     P.instances = static_cast<const DevInstance*>(c->dInst.p);
     P.lights = static_cast<const DevLight*>(c->dLight.p);
     P.width = width; P.height = height;
-    P.nTlasNodes = c->deviceOwnsTlas ? c->devTlasNodes : (int)hostCount<rz_bvh_node>(c, RZ_BIND_TLAS_NODES);
+    P.nTlasNodes = c->where[kTlas].host ? (int)hostCount<rz_bvh_node>(c, RZ_BIND_TLAS_NODES) : c->devTlasNodes;
     P.nInstances = (int)hostCount<rz_bvh_instance>(c, RZ_BIND_INSTANCES);
     P.nLights = std::max(0, std::min<int>(c->frame.num_lights, (int)hostCount<rz_light>(c, RZ_BIND_LIGHTS)));
     // camera.projectionMatrix * camera.viewMatrix, terms summed left to right (glsl:321)
@@ -2437,9 +2442,7 @@ static int present_impl(rz_ctx* c, const rz_present_params* pp, uint8_t* rgba8, 
     P.pathLen = 0;
     if (pp->show_bvh && pp->bvh_mode == 1 && pp->selected_blas >= 0 && pp->selected_blas < P.nInstances) {
         // findBVHBranchIterative (glsl:257-307) does not depend on the pixel: walk it once here
-        if (c->deviceOwnsTlas) { rc = sync_host_from_device(c); if (rc != RZ_OK) return rc; c->deviceOwnsTlas = true; }
-        rc = sync_geom_host(c);
-        if (rc != RZ_OK) return rc;
+        for (int g : {kTlas, kBlas}) if ((rc = need_host(c, g)) != RZ_OK) return rc;
         const rz_bvh_instance* inst = hostArr<rz_bvh_instance>(c, RZ_BIND_INSTANCES);
         const rz_bvh_node* nodes = hostArr<rz_bvh_node>(c, RZ_BIND_BLAS_NODES);
         const int32_t* idx = hostArr<int32_t>(c, RZ_BIND_BLAS_INDICES);

@@ -280,6 +280,7 @@ MAX_UNCHANGED = 3           # cases whose final frame equals the base's: M7a, I4
 # what also runs in the prior states S1 .. S5 of tests/test_scene_edits_gpu.py, and what a geometry call follows
 IN_PRIOR_STATES = ("M1", "M2", "L1", "I1", "I3")
 BEFORE_GEOMETRY_CALLS = ("M2", "M4", "I3")
+AFTER_A_READ_BACK = ("M1", "I1", "I3")          # in S1 .. S4, once rz_read_binding has refreshed every host copy
 
 
 def case_arrays(name, arrays=None):
@@ -301,25 +302,27 @@ def num_lights(name, before):
 AMPLITUDE = 0.1             # of refit_ref.wobble, on meshes 1.4 to 2.8 units in radius
 
 
-def moved_transforms(b):
-    """The transforms S1 hands to rz_update_transforms: every object but the floor moves a little, away from the camera."""
+def moved_transforms(b, again=False):
+    """The transforms S1 hands to rz_update_transforms: every object but the floor moves a little, away from the camera.
+    `again`: other ones, for a second rz_update_transforms (the objects move the other way, and further)."""
+    d = (-0.5, 0.25, -0.4) if again else (0.3, 0.1, 0.2)
     out = []
     for k, (_, xf) in enumerate(b.objects):
-        out.append(np.asarray(xf, F32) if k == 0 else S.translate(xf, (0.3, 0.1 + 0.02 * k, 0.2)))
+        out.append(np.asarray(xf, F32) if k == 0 else S.translate(xf, (d[0], d[1] + 0.02 * k, d[2])))
     return np.stack(out)
 
 
-def moved_arrays(b):
+def moved_arrays(b, again=False):
     """Scene.set_transform of every object and Scene.update_dynamic, on arrays."""
     out = copy_arrays(b.arrays)
-    for k, xf in enumerate(moved_transforms(b)):
+    for k, xf in enumerate(moved_transforms(b, again)):
         out[INST]["transform"][k], out[INST]["inverseTransform"][k] = xf, S.inverse(xf)
     return with_tlas(out)
 
 
-def deformed(b):
-    """(first triangle, moved triangles) of the mesh S3 and S4 refit."""
-    return b.ranges[b.deform][0], R.wobble(b.meshes[b.deform], AMPLITUDE)
+def deformed(b, again=False):
+    """(first triangle, moved triangles) of the mesh S3 and S4 refit.  `again`: another deformation of it, for a second refit."""
+    return b.ranges[b.deform][0], R.wobble(b.meshes[b.deform], -1.5 * AMPLITUDE if again else AMPLITUDE)
 
 
 # ---- the host partners of the geometry calls, on arrays ------------------------------------------------------------------

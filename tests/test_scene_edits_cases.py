@@ -85,6 +85,24 @@ def test_the_edit_bites_in_the_prior_states_too(state, name):
     assert moved >= FLOOR
 
 
+@pytest.mark.parametrize("name", E.AFTER_A_READ_BACK)
+@pytest.mark.parametrize("state", ["S1", "S3"])
+def test_a_second_device_call_bites(state, name):
+    """What test_a_device_call_after_a_read_back runs with no edit: a second rz_update_transforms with other transforms (S1), a
+    second device-pointer refit with another deformation (S3).  The frame moves from the state's to the step's."""
+    assert set(E.AFTER_A_READ_BACK) <= set(E.IN_PRIOR_STATES)         # (their edits bite in S1, S3 and S4: the test above)
+    b = E.base(E.CASES[name].base)
+    if state == "S1":
+        current, final = E.moved_arrays(b), E.moved_arrays(b, again=True)
+    else:
+        current = E.refit_arrays(b.arrays, *E.deformed(b))
+        final = E.refit_arrays(current, *E.deformed(b, again=True))
+    nl = len(current[E.LIGHT])
+    moved = _changed(_oracle(b, current, nl), _oracle(b, final, nl))
+    print(f"{name}'s base in {state}, the second call: {moved} pixels")
+    assert moved >= FLOOR
+
+
 def test_the_bases_are_the_scenes_they_name():
     ref = E.base("reference")
     assert len(ref.arrays[S.BIND_TRIANGLES]) == 4872 and len(ref.arrays[E.INST]) == 7

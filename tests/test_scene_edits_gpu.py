@@ -10,6 +10,9 @@ geometry built on the device; S3: after a device-pointer refit (binding 0's host
 rz_rebuild_geometry (bindings 7 and 8 live on the device, the layout read binding 0 where it was); S5: a context that lays
 out on the host.  In S1, S3 and S4 the arrays in force are read from a twin context brought to the same state, so that
 reading them does not disturb the state under test; on the context under test the frame comes before any rz_read_binding.
+The other order has its own tests: in S1 .. S4 every binding is read back (twice) BEFORE the edit, so that both copies of every
+array are current when it comes, and in S1 and S3 a second device call follows the read-back with no edit at all -- a look at
+the host copies must leave the device's in force.
 
 The row this table found: I3 in S3.  After a device-pointer refit the roots of meshes no instance names are unknown to the
 device layout, so the spare glass view sends finalize to the host layout -- which read binding 0's stale host copy and laid
@@ -232,6 +235,83 @@ def test_edit_in_a_prior_state(state, name):
     # F1 first: rz_read_binding brings the host copies up to date (binding 0 after a device-pointer refit, 7 and 8 of geometry
     # on the device), so the finalize that digests the edit must run before anything is read back
     _check_frame(name, r, fresh, b, final, nl, oracle, what)
+    _check_bindings(r, final, what)
+    r.close(); fresh.close()
+    hip.close()
+
+
+# ---- S1 .. S4 once every host copy has been refreshed: the order the tests above avoid ---------------------------------------
+
+def _bring_and_read_back(state, b, hip, what):
+    """The context in the state with a frame rendered and every binding read back twice, and the arrays in force (the twin's)."""
+    r = _bring(state, b, hip)
+    if state == "S2":
+        current = b.arrays
+    else:
+        twin = _bring(state, b, hip)
+        current = _read_all(twin)
+        twin.close()
+    _render(r, b, current, len(current[E.LIGHT]))
+    first, second = _read_all(r), _read_all(r)
+    for k in S.BINDING_DTYPES:
+        assert first[k].tobytes() == second[k].tobytes(), f"{what}: binding {k}, read twice"
+        assert first[k].tobytes() == current[k].tobytes(), f"{what}: binding {k} against the twin's"
+    return r, current
+
+
+def _check_against_fresh(name, r, b, current, final, nl, what):
+    """The FLOOR condition on the oracle's frames, then F1 and F4 against a fresh context on `final`."""
+    fresh = _upload(final)
+    oracle = _oracle(b, final, nl)
+    moved = int((oracle.view(np.uint32) != _oracle(b, current, len(current[E.LIGHT])).view(np.uint32)).any(axis=-1).sum())
+    assert moved >= FLOOR, f"{what}: the step moves {moved} pixels of the oracle's frame in this state"
+    _check_frame(name, r, fresh, b, final, nl, oracle, what)
+    _check_bindings(r, final, what)
+    fresh.close()
+
+
+@pytest.mark.parametrize("name", E.AFTER_A_READ_BACK)
+@pytest.mark.parametrize("state", ("S1", "S2", "S3", "S4"))
+def test_edit_after_a_read_back(state, name):
+    """test_edit_in_a_prior_state with the host copies refreshed first: both sides of every group are current when the edit comes."""
+    case = E.CASES[name]
+    b = E.base(case.base)
+    what = f"{name} in {state} after a read-back"
+    hip = Hip()
+    r, current = _bring_and_read_back(state, b, hip, what)
+    calls = case.edit(current)
+    _apply(r, calls)
+    _check_against_fresh(name, r, b, current, E.apply(calls, current), E.num_lights(name, current), what)
+    r.close()
+    hip.close()
+
+
+@pytest.mark.parametrize("name", E.AFTER_A_READ_BACK)
+@pytest.mark.parametrize("state", ("S1", "S3"))
+def test_a_device_call_after_a_read_back(state, name):
+    """A look leaves the device side in force: with no edit, a second rz_update_transforms (S1) or a second device-pointer refit
+    (S3) follows the read-back, and the context answers as a fresh one on the arrays the host partners give."""
+    b = E.base(E.CASES[name].base)
+    what = f"{name}'s base in {state}, a device call after a read-back"
+    hip = Hip()
+    r, current = _bring_and_read_back(state, b, hip, what)
+    if state == "S1":
+        r.update_transforms(E.moved_transforms(b, again=True))
+        final = E.moved_arrays(b, again=True)
+    else:
+        first, moved = E.deformed(b, again=True)
+        r.refit_geometry_device(hip.upload(moved), first, len(moved))
+        final = E.refit_arrays(current, first, moved)
+    # (the materials are the base's: the kernel variant and the plan are the fresh context's, whatever the case says of its edit)
+    fresh = _upload(final)
+    nl = len(final[E.LIGHT])
+    oracle = _oracle(b, final, nl)
+    moved_px = int((oracle.view(np.uint32) != _oracle(b, current, nl).view(np.uint32)).any(axis=-1).sum())
+    assert moved_px >= FLOOR, f"{what}: the call moves {moved_px} pixels of the oracle's frame"
+    got, want = _render(r, b, final, nl), _render(fresh, b, final, nl)
+    assert _bits_equal(got, want), f"{what} vs the fresh context: " + mismatch_report(got, want)
+    assert _bits_equal(got, oracle), f"{what} vs the oracle: " + mismatch_report(got, oracle)
+    assert r.last_kernel_name() == fresh.last_kernel_name(), what
     _check_bindings(r, final, what)
     r.close(); fresh.close()
     hip.close()
