@@ -558,8 +558,11 @@ void* rz_group_frame_device_ptr(rz_group* g);
  * rz_sync returns RZ_ERR_INTERNAL naming them and clears the word. */
 int rz_debug_poke_backstop(rz_ctx* ctx, unsigned bits);
 
-/* TEST HOOK: the device-side scene layout as built (which = 0: DevPair[] 64 B each, 1: DevTri[] 48 B each;
- * rayzen_amd/csrc/hip/rz_scene_dev.h).  out NULL: only *needed is set.  Runs the pending re-layout first. */
+/* TEST HOOK: the device-side scene layout as built (which = 0: DevPair[] 64 B each, 1: DevTri[] 48 B each, 2: TlasDfs[] 64 B
+ * each -- the TLAS in the order the shader's loop pops it, the list every traversal walks, whether the host route made it
+ * from bindings 10 / 11 or the device rebuild of rz_update_transforms / rz_refit_geometry / rz_rebuild_geometry /
+ * rz_skin_pose did; rayzen_amd/csrc/hip/rz_scene_dev.h).  out NULL: only *needed is set.  Runs the pending re-layout first.
+ * RZ_ERR_BUFFER_SIZE: `bytes` is less than the view holds; RZ_ERR_INVALID_ARG: which is not 0, 1 or 2. */
 int rz_debug_read_layout(rz_ctx* ctx, int which, void* out, size_t bytes, size_t* needed);
 
 /* TEST HOOK: how the last rz_render / rz_render_counted of this context was launched (rz_kernels.hip:

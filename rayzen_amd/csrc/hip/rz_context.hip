@@ -3815,14 +3815,15 @@ int rz_display_state(rz_ctx* c, rz_display_info* out) {
 int rz_debug_read_layout(rz_ctx* c, int which, void* out, size_t bytes, size_t* needed) {
     return guarded(c, "rz_debug_read_layout", [&]() -> int {
         if (!c) return fail(nullptr, RZ_ERR_INVALID_ARG, "null context");
-        if (which != 0 && which != 1) return fail(c, RZ_ERR_INVALID_ARG, "which = %d", which);
+        if (which < 0 || which > 2) return fail(c, RZ_ERR_INVALID_ARG, "which = %d", which);
         RZ_HIP(c, hipSetDevice(c->device));
         int rc = finalize(c);
         if (rc != RZ_OK) return rc;
         size_t have;
         const void* src;
         if (which == 0) { have = (c->layoutOnDevice ? (size_t)c->devPairsUsed : c->hPairs.size()) * sizeof(DevPair); src = c->dPairs.p; }
-        else { have = (c->layoutOnDevice ? (size_t)c->devTrisUsed : c->hTris.size()) * sizeof(DevTri); src = c->dTris.p; }
+        else if (which == 1) { have = (c->layoutOnDevice ? (size_t)c->devTrisUsed : c->hTris.size()) * sizeof(DevTri); src = c->dTris.p; }
+        else { have = (size_t)c->nTlasDfs * sizeof(TlasDfs); src = c->dTlasDfs.p; }     // whoever made it: finalize's upload or rz_tlas_refit
         if (needed) *needed = have;
         if (!out) return RZ_OK;
         if (bytes < have) return fail(c, RZ_ERR_BUFFER_SIZE, "layout %d holds %zu bytes, buffer has %zu", which, have, bytes);

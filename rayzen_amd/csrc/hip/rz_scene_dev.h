@@ -30,6 +30,7 @@
 //  * TLAS nodes and indices keep RayZen's 32-B node layout: a TLAS has a
 //    handful of nodes and is traversed literally (FS:457-503).
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 
 namespace rz {
@@ -81,6 +82,10 @@ struct alignas(64) TlasDfs {
     int32_t pad[6];
 };
 static_assert(sizeof(TlasDfs) == 64, "TlasDfs is one scalar fetch");
+// (the offsets rz_debug_read_layout's view 2 is read with: tests/tlas_shapes.py, TLAS_DFS)
+static_assert(offsetof(TlasDfs, bmin) == 0 && offsetof(TlasDfs, first) == 12 && offsetof(TlasDfs, bmax) == 16 &&
+              offsetof(TlasDfs, count) == 28 && offsetof(TlasDfs, skip) == 32 && offsetof(TlasDfs, inst0) == 36 &&
+              offsetof(TlasDfs, pad) == 40, "TlasDfs field offsets");
 
 struct DevMaterial { float albedo[3], metallic, roughness, reflectivity, transparency, ior; };
 struct DevLight { float posdir[4], color[3], power; };

@@ -379,7 +379,7 @@ class Renderer:
         return {n: int(getattr(lp, n)) for n, _ in _lib.LaunchPlan._fields_}
 
     def debug_read_layout(self, which):
-        """Test hook: the device scene layout as raw bytes (0: DevPair[], 1: DevTri[])."""
+        """Test hook: the device scene layout as raw bytes (0: DevPair[], 1: DevTri[], 2: TlasDfs[], the TLAS in pop order)."""
         need = C.c_size_t(0)
         self._check(self._L.rz_debug_read_layout(self._c, int(which), None, 0, C.byref(need)), "rz_debug_read_layout")
         out = np.zeros(need.value, np.uint8)

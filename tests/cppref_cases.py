@@ -5,7 +5,8 @@ Every BLAS case is (name, constructor).  The inputs tests/test_bvh.py and tests/
 THOSE modules' constructors (imported, not restated); the adversarial ones are defined here.  Only finite vertices: a NaN
 centroid breaks std::sort's ordering contract inside the reference, whose output is then undefined.
 Fixture files (tests/golden/cppref_<group>.npz) hold, per case, `<case>__tris / __nodes / __idx / __oob` (whole cases) or
-`<case>__digest` (large cases: SHA-256 of the input, then SHA-256 / length of the reference's nodes and indices, and the depth).
+`<case>__digest` (large cases: SHA-256 of the input, then SHA-256 / length of the reference's nodes and indices, and the depth;
+in cppref_tlas.npz `<case>__roots / __nodes / __idx`, or `<case>__digest` for the cases of TLAS_BY_DIGEST).
 """
 import hashlib
 import os
@@ -309,7 +310,51 @@ def tlas_cases():
         return leaf_boxes(sc.arrays[S.BIND_TLAS_NODES], sc.arrays[S.BIND_TLAS_INDICES], 7)
 
     cases.append(("rayzen_main_scene", rayzen_main))
+
+    # tests/tlas_shapes.py: the world boxes SceneBuffers::updateDynamic gives every shape of the table (chains deeper than the
+    # shader's stack, equal centres, chosen partitions, lattices, signed zeros)
+    import tlas_shapes
+    for name in tlas_shapes.NAMES:
+        def make(name=name):
+            sh = tlas_shapes.get(name)
+            sc, _ = sh.host_scene()
+            return leaf_boxes(sc.arrays[S.BIND_TLAS_NODES], sc.arrays[S.BIND_TLAS_INDICES], sh.n)
+        cases.append((shape_case(name), make))
     return cases
+
+
+def shape_case(name):
+    return f"shape_{name}"
+
+
+TLAS_BY_DIGEST = ("shape_random_3000",)         # 3 000 x (32 + 64 + 4) B: recorded as the large BLAS cases are
+
+
+def tlas_digest(roots, nodes, idx):
+    return np.array([sha(roots), sha(nodes), sha(idx), str(len(roots)), str(len(nodes))])
+
+
+def tlas_names(fix):
+    """(whole cases, cases by digest) of a loaded cppref_tlas.npz."""
+    return (sorted(k[:-len("__roots")] for k in fix if k.endswith("__roots")),
+            sorted(k[:-len("__digest")] for k in fix if k.endswith("__digest")))
+
+
+def tlas_matches(fix, name, nodes, idx, roots=None):
+    """None, or what differs between a TLAS (and optionally its input boxes) and the fixture's record of RayZen's build."""
+    nodes, idx = np.ascontiguousarray(nodes), np.ascontiguousarray(idx)
+    if f"{name}__digest" in fix:
+        want = [str(x) for x in fix[f"{name}__digest"]]
+        if roots is not None and (sha(roots), str(len(roots))) != (want[0], want[3]):
+            return "root boxes"
+        if str(len(nodes)) != want[4] or sha(nodes) != want[1]:
+            return "nodes"
+        return None if sha(idx) == want[2] else "indices"
+    if roots is not None and np.ascontiguousarray(roots).tobytes() != fix[f"{name}__roots"].tobytes():
+        return "root boxes"
+    if nodes.tobytes() != fix[f"{name}__nodes"].tobytes():
+        return "nodes"
+    return None if idx.tobytes() == fix[f"{name}__idx"].tobytes() else "indices"
 
 
 # ---- OBJ ------------------------------------------------------------------------------------------------------------------------

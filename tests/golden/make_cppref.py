@@ -1,11 +1,12 @@
 """Writes tests/golden/cppref_*.npz: what RayZen's own BVH.cpp and Mesh.cpp (compiled by oracle/cppref) compute for the
 inputs of tests/cppref_cases.py.  Needs the reference checkout (oracle/cppref/README.md); run from the repository root:
 
-    python tests/golden/make_cppref.py [--skip-slow]
+    python tests/golden/make_cppref.py [--skip-slow] [--only-tlas]
 
 Files: cppref_suite / cppref_adversarial / cppref_sizes (BLAS: input, nodes, indices, count of axis == -1 reads), cppref_large
 (digests of the big blobs), cppref_tlas (root boxes, nodes, indices), cppref_obj (texts, the reader's output, which components
-may be asserted).  Each file stays under 1 MB.  --skip-slow keeps the 1 M-triangle entry of an existing cppref_large.npz.
+may be asserted).  Each file stays under 1 MB.  --skip-slow keeps the 1 M-triangle entry of an existing cppref_large.npz;
+--only-tlas rewrites cppref_tlas.npz alone (a new TLAS case leaves the other files as they are).
 """
 import os
 import sys
@@ -30,10 +31,25 @@ def save(group, arrays):
     return size
 
 
+def tlas_fixture():
+    tlas = {}
+    for name, ctor in K.tlas_cases():
+        roots = np.ascontiguousarray(ctor())
+        nodes, idx = cppref.build_tlas(roots)
+        if name in K.TLAS_BY_DIGEST:
+            tlas[f"{name}__digest"] = K.tlas_digest(roots, nodes, idx)
+        else:
+            tlas[f"{name}__roots"], tlas[f"{name}__nodes"], tlas[f"{name}__idx"] = roots.view(np.uint8), nodes.view(np.uint8), idx
+    return save("tlas", tlas)
+
+
 def main():
     assert cppref.available(), "the reference's sources are not here"
     cppref.build()
     total = 0
+    if "--only-tlas" in sys.argv:
+        tlas_fixture()
+        return
     for group, make in K.BLAS_GROUPS.items():
         out, flagged = {}, []
         for name, ctor in make():
@@ -65,12 +81,7 @@ def main():
         print(f"large {name}: {len(tris)} triangles, {len(nodes)} nodes, reference build {dt:.2f} s")
     total += save("large", large)
 
-    tlas = {}
-    for name, ctor in K.tlas_cases():
-        roots = np.ascontiguousarray(ctor())
-        nodes, idx = cppref.build_tlas(roots)
-        tlas[f"{name}__roots"], tlas[f"{name}__nodes"], tlas[f"{name}__idx"] = roots.view(np.uint8), nodes.view(np.uint8), idx
-    total += save("tlas", tlas)
+    total += tlas_fixture()
 
     obj = {}
     for mesh in K.OBJ_MESHES:

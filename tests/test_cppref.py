@@ -22,7 +22,7 @@ with np.load(K.fixture("tlas")) as _z:
     TLAS = {k: _z[k] for k in _z.files}
 with np.load(K.fixture("obj")) as _z:
     OBJ = {k: _z[k] for k in _z.files}
-TLAS_NAMES = sorted(k[:-len("__roots")] for k in TLAS if k.endswith("__roots"))
+TLAS_NAMES, TLAS_DIGESTS = K.tlas_names(TLAS)
 OBJ_TEXTS = sorted(k[len("text__"):-len("__bytes")] for k in OBJ if k.endswith("__bytes"))
 
 live = pytest.mark.skipif(not cppref.built(), reason="oracle/_ref/cppref is not built (the reference's sources are not here)")
@@ -42,7 +42,8 @@ def _same(got, want, what):
 def test_the_fixture_holds_every_case_of_the_list():
     want = [(g, n) for g, make in K.BLAS_GROUPS.items() for n, _ in make()]
     assert sorted(BLAS) == sorted(want)
-    assert sorted(TLAS_NAMES) == sorted(n for n, _ in K.tlas_cases())
+    assert sorted(TLAS_NAMES + TLAS_DIGESTS) == sorted(n for n, _ in K.tlas_cases())
+    assert TLAS_DIGESTS == sorted(K.TLAS_BY_DIGEST)
     assert sorted(OBJ_TEXTS) == sorted(K.obj_texts())
     assert sorted(k[:-len("__digest")] for k in LARGE if k.endswith("__digest")) == sorted(n for n, _, _ in K.LARGE)
 
@@ -76,7 +77,11 @@ def test_the_inputs_are_what_the_constructors_build_today():
         for name, ctor in make():
             assert np.ascontiguousarray(ctor()).tobytes() == K.load_blas(g, name)[0].tobytes(), (g, name)
     for name, ctor in K.tlas_cases():
-        assert np.ascontiguousarray(ctor()).tobytes() == TLAS[f"{name}__roots"].tobytes(), name
+        roots = np.ascontiguousarray(ctor())
+        if name in TLAS_DIGESTS:
+            assert [K.sha(roots), str(len(roots))] == [str(x) for x in TLAS[f"{name}__digest"][[0, 3]]], name
+        else:
+            assert roots.tobytes() == TLAS[f"{name}__roots"].tobytes(), name
     for name, (text, asserted) in K.obj_texts().items():
         assert text == OBJ[f"text__{name}__bytes"].tobytes(), name
         assert (K.obj_asserted_mask(text, asserted) == OBJ[f"text__{name}__mask"]).all(), name
@@ -128,6 +133,14 @@ def test_tlas_host_and_oracle_equal_rayzens_build(name):
     on, oi = rzo.build_tlas(roots)
     _same(on.view(S.BVH_NODE), nodes, "oracle TLAS nodes")
     _same(oi, idx, "oracle TLAS indices")
+
+
+@pytest.mark.parametrize("name", TLAS_DIGESTS)
+def test_tlas_by_digest_host_and_oracle_equal_rayzens_build(name):
+    roots = dict(K.tlas_cases())[name]()
+    assert K.tlas_matches(TLAS, name, *S.build_tlas(roots), roots=roots) is None
+    on, oi = rzo.build_tlas(roots)
+    assert K.tlas_matches(TLAS, name, on.view(S.BVH_NODE), oi) is None
 
 
 @pytest.mark.parametrize("mesh", K.OBJ_MESHES)
@@ -201,6 +214,9 @@ def test_live_fixtures_are_current():
     for name in TLAS_NAMES:
         rn, ri = cppref.build_tlas(TLAS[f"{name}__roots"].view(S.BVH_NODE).reshape(-1))
         assert rn.tobytes() == TLAS[f"{name}__nodes"].tobytes() and ri.tobytes() == TLAS[f"{name}__idx"].tobytes(), name
+    for name in TLAS_DIGESTS:
+        roots = dict(K.tlas_cases())[name]()
+        assert K.tlas_matches(TLAS, name, *cppref.build_tlas(roots), roots=roots) is None, name
     for name in OBJ_TEXTS:
         t = cppref.load_obj_text(OBJ[f"text__{name}__bytes"].tobytes(), 2)
         assert t.tobytes() == OBJ[f"text__{name}__tris"].tobytes(), name

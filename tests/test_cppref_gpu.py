@@ -87,9 +87,13 @@ def test_build_geometry_slices_equal_rayzens_per_mesh_builds(r, names):
 
 
 def _check_tlas(r, name, n):
-    roots = TLAS[f"{name}__roots"].view(S.BVH_NODE).reshape(-1)
     tn, ti = r.read_binding(S.BIND_TLAS_NODES), r.read_binding(S.BIND_TLAS_INDICES)
     boxes = K.leaf_boxes(tn, ti, n)
+    if f"{name}__digest" in TLAS:                        # (a case recorded by digest: cppref_cases.TLAS_BY_DIGEST)
+        differs = K.tlas_matches(TLAS, name, tn, ti, roots=boxes)
+        assert differs is None, f"{name}: the device's {differs} differ from RayZen's build"
+        return
+    roots = TLAS[f"{name}__roots"].view(S.BVH_NODE).reshape(-1)
     # first the world boxes: a difference here is a difference in the transform arithmetic, not in the TLAS builder
     diff = [i for i in range(n) if boxes[i].tobytes() != roots[i].tobytes()]
     assert not diff, (f"{name}: world boxes of instances {diff} differ from the fixture's: device "

@@ -1,7 +1,10 @@
 """The TLAS walk of rz_trace.h keeps no stack: it follows the list of nodes in the order the shader's loop pops them
-(FS:464-501, right child first), with skip positions.  These scenes give it TLAS shapes RayZen's own builder
-(BVH.cpp:178-240: one instance per leaf, balanced) never produces -- the C-ABI takes any node array -- and compare with
-the oracle's literal stack loop, bit for bit, tallies included."""
+(FS:464-501, right child first), with skip positions.  These scenes give it hand-uploaded TLAS node arrays -- the C-ABI
+takes any -- and compare with the oracle's literal stack loop, bit for bit, tallies included: leaves that hold several
+instances, which RayZen's own builder (BVH.cpp:178-240: one instance per leaf) never makes, and chains of 70 links with
+repeated instances.  Chains deeper than the shader's stack the builder DOES produce -- its midpoint split peels one instance
+per level off instances spread over many octaves -- and the ones it produces, built by the device kernel, are covered by
+tests/test_tlas_shapes_gpu.py."""
 import numpy as np
 import pytest
 
