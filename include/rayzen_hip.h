@@ -1133,6 +1133,77 @@ int rz_present_antialiased_seethrough(rz_ctx* ctx, const rz_present_params* pres
                                       const void* filter_params, uint8_t* rgba8, size_t rgba8_bytes,
                                       float* rgb32f, size_t rgb32f_bytes);
 
+/* ------------------------------------------------------------------------ */
+/* Where a frame is expensive: the per-pixel traversal cost map (new)       */
+/* ------------------------------------------------------------------------ */
+/* rz_render_counted prices a frame in the reference algorithm's memory touches, as totals.  rz_render_cost keeps the attribution:
+ * for every pixel, what the reference shader would touch for that pixel's samples (rz_cost.hip).
+ * rz_render_cost measures the frame of the last rz_set_frame -- size, camera, num_lights, bounce_budget -- with its own spp
+ * (rz_cost_params.spp; 0 = the frame's), always from sample 0: samples 0 .. spp-1 of every pixel, from currentIor 1, exactly the
+ * paths rz_render runs at sample_base 0.  The record of a pixel holds the eight traversal-side counts of rz_counters for those
+ * paths, so every column summed over the frame is rz_render_counted's total.  `totals` is optional HOST memory whatever the
+ * flags say: when given it receives exactly what rz_render_counted returns for the same frame at sample_base 0 (the call then
+ * waits for its kernel).  The call sees the scene as the last upload / update / refit / pose / rebuild left it.  It leaves the
+ * accumulation, currentIor, the pools, rz_debug_last_plan, rz_last_kernel_name, the ring of render times, and temporal and
+ * display state untouched.  The context keeps the last cost buffer with its size and spp; `cost` may be NULL, in which case
+ * only that copy is kept.  Row 0 of `cost` is the bottom row, as everywhere.
+ * The VALUE v of a pixel is a uint64 and depends on the metric:
+ *   0 bytes            32 tlas_nodes + 4 tlas_leaf_indices + 144 instances + 32 blas_nodes + 68 triangles + 32 materials +
+ *                      32 light_fetches + 16 (rz_counters' formula with the pixel's own 16 bytes: the frame's sum is that total)
+ *   1 node visits      tlas_nodes + blas_nodes
+ *   2 triangle tests   triangles
+ *   3 traversals       traversals
+ *   4 instances        instances
+ * rz_cost_view reduces the metric over the frame -- rz_cost_stats: the maximum, the LOWEST pixel index that attains it as
+ * (max_x, max_y), the sum; exact integers, the same on every run -- and maps every pixel to a false colour, in binary32 with one
+ * rounding per operation and no fused multiply-add:
+ *   S = scale > 0 ? scale : (float)max_value, and 1 for a frame whose maximum is 0 (scale_used reports S);
+ *   linear u = min((float)v / S, 1); logarithmic u = min(log2(1 + (float)v) / log2(1 + S), 1);
+ *   k = min((int)(u * 4), 3), w = u * 4 - (float)k, c = a_k + (a_(k+1) - a_k) * w
+ *   with the stops a_0 .. a_4 = (0,0,0), (0,0,1), (0,1,0), (1,1,0), (1,0,0): black, blue, green, yellow, red;
+ *   a pixel with (float)v > S is (1,1,1): possible only under a caller's scale, it flags saturation.
+ * With cost == NULL it views the context's last cost buffer: RZ_ERR_NOT_READY if there is none or the frame's size has changed
+ * since.  A caller's buffer holds width * height records of the frame's size.  rgb32f (width * height * 3 floats) and stats are
+ * each optional.  rz_present_cost is rz_present with that colour, as (c, 1), in place of the accumulation's divide, the way
+ * rz_present_denoised does it, from the context's last cost buffer: wireframe, light markers and FPS digits are drawn on top of
+ * the heat map.  Its buffers are host memory, as rz_present's.
+ * Conventions are rz_denoise's.  cost, rgb32f and stats are DEVICE pointers (cost 16-byte, stats 8-byte, rgb32f 4-byte aligned)
+ * and the work is queued on the context's stream, a walk cut at its backstop being left to rz_sync; with RZ_COST_HOST they are
+ * host memory, staged, the call returns when they are written and reports a cut walk itself as RZ_ERR_INTERNAL.  A failing
+ * call launches nothing and leaves its outputs untouched.
+ * Errors.  RZ_ERR_NOT_READY: no scene, no materials (rz_render_cost) or no frame.  RZ_ERR_INVALID_ARG: null context; spp outside
+ * 0..1024; unknown metric, curve or flags; scale negative or not finite; a non-zero reserved word; a misaligned device pointer;
+ * a frame with tile_nranks > 1.  RZ_ERR_BUFFER_SIZE: any buffer too small.
+ * Cost (profiles/cost/README.md): the path loop of the one-lane-per-pixel kernel plus 32 B per pixel -- a 1-spp map of a 1080p
+ * frame of a 69 k-triangle scene takes 2.3 ms, 0.65 of that kernel's counted render; rz_cost_view 0.035 ms.
+ * (Additive: RZ_ABI_VERSION stays 5; rz_sizeof(25) and rz_sizeof(27) stay 0.) */
+typedef struct rz_pixel_cost {          /* 32 B; rz_sizeof(28) */
+    uint32_t traversals, tlas_nodes, tlas_leaf_indices, instances, blas_nodes, triangles, materials, light_fetches;
+} rz_pixel_cost;
+typedef struct rz_cost_params {         /* NULL = defaults; 32 B; rz_sizeof(29) */
+    int32_t spp;                        /* 0 = the frame's spp; else 1..1024 */
+    int32_t reserved[7];                /* must be 0 */
+} rz_cost_params;
+typedef struct rz_cost_view_params {    /* NULL = defaults; 32 B; rz_sizeof(30) */
+    int32_t metric;                     /* 0 bytes (default) 1 node visits 2 triangle tests 3 traversals 4 instances entered */
+    int32_t curve;                      /* 0 linear (default), 1 logarithmic */
+    float   scale;                      /* value at the top of the ramp; 0 = this frame's maximum */
+    int32_t reserved[5];                /* must be 0 */
+} rz_cost_view_params;
+typedef struct rz_cost_stats {          /* 32 B; rz_sizeof(31) */
+    uint64_t max_value, sum_value;
+    int32_t  max_x, max_y;              /* lowest pixel index among the maxima; row 0 = bottom row */
+    float    scale_used;
+    int32_t  reserved;
+} rz_cost_stats;
+#define RZ_COST_HOST 1u                 /* pointers are host memory, as RZ_DENOISE_HOST */
+int rz_render_cost(rz_ctx* ctx, const rz_cost_params* params, rz_pixel_cost* cost, size_t cost_bytes, rz_counters* totals,
+                   unsigned flags);
+int rz_cost_view(rz_ctx* ctx, const rz_cost_view_params* params, const rz_pixel_cost* cost, size_t cost_bytes,
+                 float* rgb32f, size_t rgb32f_bytes, rz_cost_stats* stats, unsigned flags);
+int rz_present_cost(rz_ctx* ctx, const rz_present_params* present, const rz_cost_view_params* params,
+                    uint8_t* rgba8, size_t rgba8_bytes, float* rgb32f, size_t rgb32f_bytes);
+
 /* Number of HIP devices visible to the process (0 without a GPU). */
 int rz_device_count(void);
 
@@ -1157,8 +1228,8 @@ const char* rz_source_hash(void);
  * 3 material, 4 light, 5 frame_params, 6 counters, 7 ray, 8 hit,
  * 9 visibility, 10 editor_params, 11 denoise_params, 12 temporal_params,
  * 14 display_params, 15 display_info, 17 skin_triangle, 18 morph_triangle, 20 mesh_quality,
- * 21 upscale_params, 23 seethrough_params, 24 chain, 26 antialias_params (13, 16, 19, 22 and 25 are unassigned and return 0, as
- * every unknown index does). */
+ * 21 upscale_params, 23 seethrough_params, 24 chain, 26 antialias_params, 28 pixel_cost, 29 cost_params, 30 cost_view_params,
+ * 31 cost_stats (13, 16, 19, 22, 25 and 27 are unassigned and return 0, as every unknown index does). */
 size_t rz_sizeof(int which);
 
 #ifdef __cplusplus

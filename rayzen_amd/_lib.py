@@ -30,6 +30,7 @@ HIP_SYMBOLS = (
     "rz_geometry_quality", "rz_rebuild_geometry",
     "rz_upscale", "rz_present_upscaled", "rz_upscale_seethrough", "rz_present_upscaled_seethrough",
     "rz_antialias", "rz_present_antialiased", "rz_antialias_seethrough", "rz_present_antialiased_seethrough",
+    "rz_render_cost", "rz_cost_view", "rz_present_cost",
 )
 ABI_VERSION = 5         # RZ_ABI_VERSION of the include/rayzen_hip.h this file mirrors
 # the symbols include/rayzen_host.h declares
@@ -191,6 +192,38 @@ ANTIALIAS_HOST = 1                      # RZ_ANTIALIAS_HOST
 SIZEOF_ANTIALIAS_PARAMS = 26            # its rz_sizeof index
 
 
+class PixelCost(C.Structure):
+    """rz_pixel_cost of include/rayzen_hip.h (32 B)."""
+    _fields_ = [(n, C.c_uint32) for n in ("traversals", "tlas_nodes", "tlas_leaf_indices", "instances", "blas_nodes", "triangles",
+                                          "materials", "light_fetches")]
+
+
+class CostParams(C.Structure):
+    """rz_cost_params of include/rayzen_hip.h (32 B)."""
+    _fields_ = [("spp", C.c_int32), ("reserved", C.c_int32 * 7)]
+
+
+class CostViewParams(C.Structure):
+    """rz_cost_view_params of include/rayzen_hip.h (32 B)."""
+    _fields_ = [("metric", C.c_int32), ("curve", C.c_int32), ("scale", C.c_float), ("reserved", C.c_int32 * 5)]
+
+
+class CostStats(C.Structure):
+    """rz_cost_stats of include/rayzen_hip.h (32 B)."""
+    _fields_ = [("max_value", C.c_uint64), ("sum_value", C.c_uint64), ("max_x", C.c_int32), ("max_y", C.c_int32),
+                ("scale_used", C.c_float), ("reserved", C.c_int32)]
+
+
+# rz_pixel_cost as a numpy record
+PIXEL_COST_DTYPE = np.dtype([(n, np.uint32) for n, _ in PixelCost._fields_])
+COST_DEFAULTS = dict(spp=0)
+COST_VIEW_DEFAULTS = dict(metric=0, curve=0, scale=0.0)
+COST_METRICS = {"bytes": 0, "nodes": 1, "triangles": 2, "traversals": 3, "instances": 4}
+COST_CURVES = {"linear": 0, "log": 1}
+COST_HOST = 1                           # RZ_COST_HOST
+SIZEOF_PIXEL_COST, SIZEOF_COST_PARAMS, SIZEOF_COST_VIEW_PARAMS, SIZEOF_COST_STATS = 28, 29, 30, 31    # their rz_sizeof indices
+
+
 class SkinTriangle(C.Structure):
     """rz_skin_triangle of include/rayzen_hip.h (64 B)."""
     _fields_ = [("bones", C.c_uint32 * 3), ("pad", C.c_uint32), ("weights", (C.c_float * 4) * 3)]
@@ -315,7 +348,10 @@ def hip():
                                 ("rz_antialias", i, [vp, vp, vp, sz, vp, sz, vp, sz, vp, sz, C.c_uint]),
                                 ("rz_present_antialiased", i, [vp, C.POINTER(PresentParams), vp, vp, i, vp, vp, sz, vp, sz]),
                                 ("rz_antialias_seethrough", i, [vp, vp, vp, vp, sz, vp, sz, vp, sz, vp, sz, vp, sz, C.c_uint]),
-                                ("rz_present_antialiased_seethrough", i, [vp, C.POINTER(PresentParams), vp, vp, vp, i, vp, vp, sz, vp, sz])):
+                                ("rz_present_antialiased_seethrough", i, [vp, C.POINTER(PresentParams), vp, vp, vp, i, vp, vp, sz, vp, sz]),
+                                ("rz_render_cost", i, [vp, vp, vp, sz, C.POINTER(Counters), C.c_uint]),
+                                ("rz_cost_view", i, [vp, vp, vp, sz, vp, sz, vp, C.c_uint]),
+                                ("rz_present_cost", i, [vp, C.POINTER(PresentParams), vp, vp, sz, vp, sz])):
             try:
                 fn = getattr(L, name)
                 fn.restype, fn.argtypes = res, args

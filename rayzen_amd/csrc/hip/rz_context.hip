@@ -215,6 +215,12 @@ struct rz_ctx {
     int qualBlocks = 0;
     std::map<std::tuple<int, int, int>, double> costBuilt;
     unsigned long long costGen = ~0ull;  // the layout whose views all have their entry in costBuilt
+    // rz_render_cost / rz_cost_view / rz_present_cost (rz_cost.hip): the last cost buffer (rz_pixel_cost per pixel) with the size
+    // and spp it was measured at, the call's own counters, the reduction's partial records and its rz_cost_stats, and the
+    // (colour, 1) buffer rz_present_cost presents; allocated on first use and kept
+    DevBuf dCost, dCostCounters, dCostPartials, dCostStats, dCostOut;
+    bool costValid = false;
+    int costW = 0, costH = 0, costSpp = 0;
 };
 
 namespace {
@@ -1017,25 +1023,12 @@ int render_samples(rz_ctx* c, KParams K, bool counted, int evSlot) {
     return RZ_OK;
 }
 
-int do_render(rz_ctx* c, bool counted, rz_counters* out) {
-    if (!c) return fail(nullptr, RZ_ERR_INVALID_ARG, "null context");
-    if (!c->haveFrame) return fail(c, RZ_ERR_NOT_READY, "rz_set_frame has not been called");
-    RZ_HIP(c, hipSetDevice(c->device));
-    int rc = finalize(c);
-    if (rc != RZ_OK) return rc;
+// What a render launch reads of the scene and of the frame of rz_set_frame -- its tiles, camera, lights and bounce budget --
+// for `spp` samples per pixel from sample `sampleBase` (do_render: the frame's own; rz_render_cost: its own spp from sample 0),
+// and the check that the one-lane-per-pixel kernel's LDS stack fits.
+int frame_kparams(rz_ctx* c, KParams& K, int spp, int sampleBase) {
     const rz_frame_params& f = c->frame;
-    const size_t nPix = (size_t)f.width * f.height;
-    float4* accum = nullptr;
-    if (c->extAccum) {
-        if (c->extAccumBytes < nPix * 16) return fail(c, RZ_ERR_BUFFER_SIZE, "bound accumulation buffer holds %zu bytes, frame needs %zu", c->extAccumBytes, nPix * 16);
-        accum = static_cast<float4*>(c->extAccum);
-    } else {
-        accum = static_cast<float4*>(c->ownAccum.p);
-    }
-    KParams K{};
     scene_kparams(c, K);
-    K.accum = accum;
-    K.ior = static_cast<float*>(c->dIor.p);
     K.nLights = std::max(0, std::min<int>(f.num_lights, (int)hostCount<rz_light>(c, RZ_BIND_LIGHTS)));
     K.width = f.width; K.height = f.height;
     K.tilesX = (f.width + RZ_TILE_W - 1) / RZ_TILE_W;
@@ -1044,7 +1037,7 @@ int do_render(rz_ctx* c, bool counted, rz_counters* out) {
     K.tileRank = f.tile_rank; K.tileNRanks = f.tile_nranks;
     K.nLocalTiles = (nTiles - f.tile_rank + f.tile_nranks - 1) / f.tile_nranks;
     K.maxBounces = f.bounce_budget > 0 ? f.bounce_budget : 5;      // FS:673
-    K.spp = f.spp; K.sampleBase = f.sample_base;
+    K.spp = spp; K.sampleBase = sampleBase;
     std::memcpy(K.invView, f.inv_view, 64);
     std::memcpy(K.invProj, f.inv_proj, 64);
     std::memcpy(K.camPos, f.cam_pos, 12);
@@ -1061,6 +1054,29 @@ int do_render(rz_ctx* c, bool counted, rz_counters* out) {
     const size_t perWave = (size_t)K.blasStackCap * 512 + (size_t)K.tlasStackCap * 256 + 4864;
     if (perWave * 4 > 160 * 1024)   // sized for the largest (4-wave) workgroup
         return fail(c, RZ_ERR_BAD_SCENE, "BLAS depth %d needs %zu B of LDS stack per wave; the limit is %d", c->maxBlasDepth, perWave, 40 * 1024);
+    return RZ_OK;
+}
+
+int do_render(rz_ctx* c, bool counted, rz_counters* out) {
+    if (!c) return fail(nullptr, RZ_ERR_INVALID_ARG, "null context");
+    if (!c->haveFrame) return fail(c, RZ_ERR_NOT_READY, "rz_set_frame has not been called");
+    RZ_HIP(c, hipSetDevice(c->device));
+    int rc = finalize(c);
+    if (rc != RZ_OK) return rc;
+    const rz_frame_params& f = c->frame;
+    const size_t nPix = (size_t)f.width * f.height;
+    float4* accum = nullptr;
+    if (c->extAccum) {
+        if (c->extAccumBytes < nPix * 16) return fail(c, RZ_ERR_BUFFER_SIZE, "bound accumulation buffer holds %zu bytes, frame needs %zu", c->extAccumBytes, nPix * 16);
+        accum = static_cast<float4*>(c->extAccum);
+    } else {
+        accum = static_cast<float4*>(c->ownAccum.p);
+    }
+    KParams K{};
+    K.accum = accum;
+    K.ior = static_cast<float*>(c->dIor.p);
+    rc = frame_kparams(c, K, f.spp, f.sample_base);
+    if (rc != RZ_OK) return rc;
     if (counted) {
         rc = ensure(c, c->dCounters, sizeof(DevCounters) + 160 * sizeof(unsigned long long));
         if (rc != RZ_OK) return rc;
@@ -1166,6 +1182,10 @@ size_t rz_sizeof(int which) {
         case 23: return sizeof(rz_seethrough_params);    // (22 stays unassigned: probed as an unknown index)
         case 24: return sizeof(rz_chain);
         case 26: return sizeof(rz_antialias_params);     // (25 stays unassigned: probed as an unknown index)
+        case 28: return sizeof(rz_pixel_cost);           // (27 stays unassigned too)
+        case 29: return sizeof(rz_cost_params);
+        case 30: return sizeof(rz_cost_view_params);
+        case 31: return sizeof(rz_cost_stats);
         default: return 0;
     }
 }
@@ -1211,7 +1231,8 @@ void rz_destroy(rz_ctx* c) {
                       &c->dTmpCol[0], &c->dTmpCol[1], &c->dTmpMom[0], &c->dTmpMom[1], &c->dTmpHits[0], &c->dTmpHits[1],
                       &c->dTmpInst[0], &c->dTmpInst[1], &c->dTmpSame, &c->dDisplay, &c->dSkinOut, &c->dSkinBones, &c->dSkinWeights,
                       &c->dQualViews, &c->dQualPartials, &c->dQualCost, &c->dUpGuideLo, &c->dUpGuideHi, &c->dUpOut,
-                      &c->dStGuideLo, &c->dStGuideHi, &c->dAasList, &c->dAasCounts})
+                      &c->dStGuideLo, &c->dStGuideHi, &c->dAasList, &c->dAasCounts,
+                      &c->dCost, &c->dCostCounters, &c->dCostPartials, &c->dCostStats, &c->dCostOut})
         b->release();
     for (auto& kv : c->rigs) kv.second.release();
     for (hipEvent_t e : c->evSkin) if (e) (void)hipEventDestroy(e);
@@ -2815,6 +2836,167 @@ static int present_denoised_impl(rz_ctx* c, const rz_present_params* pp, const r
     return report_backstop(c, what, "the guide may be wrong");
 }
 
+// rz_render_cost / rz_cost_view / rz_present_cost (rz_cost.hip).  rz_render_cost runs the one-lane-per-pixel path loop over the
+// frame of rz_set_frame with buffers of its own: no accumulation, no currentIor, no claim scratch, no event of the ring, and
+// nothing of lastPlan / lastKernel is touched.  The other two read the frame's size only.
+static const rz_cost_params kCostDefaults = {0, {0, 0, 0, 0, 0, 0, 0}};
+static const rz_cost_view_params kCostViewDefaults = {0, 0, 0.0f, {0, 0, 0, 0, 0}};
+
+static int cost_frame_check(rz_ctx* c, const char* what) {
+    if (!c->haveFrame) return fail(c, RZ_ERR_NOT_READY, "%s: rz_set_frame has not been called", what);
+    if (c->frame.tile_nranks > 1)
+        return fail(c, RZ_ERR_INVALID_ARG, "%s: the frame is tile %d of %d; the cost map covers the whole frame", what, c->frame.tile_rank, c->frame.tile_nranks);
+    return RZ_OK;
+}
+
+static int cost_view_check(rz_ctx* c, const char* what, const rz_cost_view_params& V) {
+    if (V.metric < 0 || V.metric > 4) return fail(c, RZ_ERR_INVALID_ARG, "%s: metric %d outside 0..4", what, V.metric);
+    if (V.curve != 0 && V.curve != 1) return fail(c, RZ_ERR_INVALID_ARG, "%s: curve %d (0 linear, 1 logarithmic)", what, V.curve);
+    if (!(V.scale >= 0.0f && V.scale < INFINITY)) return fail(c, RZ_ERR_INVALID_ARG, "%s: scale %g (finite, >= 0)", what, (double)V.scale);
+    for (int r : V.reserved) if (r) return fail(c, RZ_ERR_INVALID_ARG, "%s: reserved words must be 0", what);
+    return cost_frame_check(c, what);
+}
+
+// the context's last cost buffer, if it was measured at the frame's size
+static int cost_kept(rz_ctx* c, const char* what) {
+    if (!c->costValid) return fail(c, RZ_ERR_NOT_READY, "%s: rz_render_cost has not been called", what);
+    if (c->costW != c->frame.width || c->costH != c->frame.height)
+        return fail(c, RZ_ERR_NOT_READY, "%s: the cost buffer was measured at %dx%d, the frame is %dx%d", what, c->costW, c->costH, c->frame.width, c->frame.height);
+    return RZ_OK;
+}
+
+static int render_cost_impl(rz_ctx* c, const rz_cost_params* pp, rz_pixel_cost* cost, size_t cost_bytes, rz_counters* totals, unsigned flags) {
+    const char* what = "rz_render_cost";
+    if (!c) return fail(nullptr, RZ_ERR_INVALID_ARG, "%s: null context", what);
+    if (flags & ~RZ_COST_HOST) return fail(c, RZ_ERR_INVALID_ARG, "%s: unknown flags 0x%x", what, flags);
+    const rz_cost_params& P = pp ? *pp : kCostDefaults;
+    if (P.spp < 0 || P.spp > 1024) return fail(c, RZ_ERR_INVALID_ARG, "%s: spp %d outside 0..1024", what, P.spp);
+    for (int r : P.reserved) if (r) return fail(c, RZ_ERR_INVALID_ARG, "%s: reserved words must be 0", what);
+    int rc = cost_frame_check(c, what);
+    if (rc == RZ_OK) rc = scene_ready(c, what, true);
+    if (rc != RZ_OK) return rc;
+    const bool host = (flags & RZ_COST_HOST) != 0;
+    if (!host && (reinterpret_cast<uintptr_t>(cost) & 15u)) return fail(c, RZ_ERR_INVALID_ARG, "%s: a device cost pointer must be 16-byte aligned", what);
+    const rz_frame_params& f = c->frame;
+    const size_t np = (size_t)f.width * f.height, bCost = np * sizeof(rz_pixel_cost);
+    if (cost && cost_bytes < bCost) return fail(c, RZ_ERR_BUFFER_SIZE, "%s: cost needs %zu bytes, got %zu", what, bCost, cost_bytes);
+    rc = finalize(c);
+    if (rc == RZ_OK) rc = ensure_group_counter(c);          // (only its backstop word)
+    if (rc == RZ_OK) rc = ensure(c, c->dCost, bCost);
+    if (rc == RZ_OK) rc = ensure(c, c->dCostCounters, sizeof(DevCounters));
+    if (rc != RZ_OK) return rc;
+    KParams K{};
+    const int spp = P.spp > 0 ? P.spp : f.spp;
+    rc = frame_kparams(c, K, spp, 0);
+    if (rc != RZ_OK) return rc;
+    K.counters = static_cast<DevCounters*>(c->dCostCounters.p);
+    CostLaunch C{static_cast<uint4*>(c->dCost.p), backstop_word(c)};
+    c->costValid = false;
+    RZ_HIP(c, hipMemsetAsync(c->dCostCounters.p, 0, sizeof(DevCounters), c->stream));
+    launch_cost_pixels(K, C, c->stream);
+    RZ_HIP(c, hipGetLastError());
+    c->costValid = true;
+    c->costW = f.width; c->costH = f.height; c->costSpp = spp;
+    if (cost) RZ_HIP(c, hipMemcpyAsync(cost, c->dCost.p, bCost, host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, c->stream));
+    if (totals) {
+        DevCounters h{};
+        RZ_HIP(c, hipMemcpyAsync(&h, c->dCostCounters.p, sizeof h, hipMemcpyDeviceToHost, c->stream));
+        RZ_HIP(c, hipStreamSynchronize(c->stream));
+        totals->samples = h.samples; totals->traversals = h.traversals; totals->tlas_nodes = h.tlas_nodes;
+        totals->tlas_leaf_indices = h.tlas_leaf_indices; totals->instances = h.instances; totals->blas_nodes = h.blas_nodes;
+        totals->triangles = h.triangles; totals->materials = h.materials; totals->light_fetches = h.light_fetches;
+        totals->pixels = h.pixels;
+        totals->scatters = h.scatters; totals->diffuse_scatters = h.diffuse_scatters; totals->hemi_draws = h.hemi_draws;
+        totals->lit_lights = h.lit_lights; totals->triangles_past_u = h.triangles_past_u;
+    }
+    if (!host) return RZ_OK;
+    RZ_HIP(c, hipStreamSynchronize(c->stream));
+    return report_backstop(c, what, "the cost map may be short of what the cut walks would have touched");
+}
+
+// Reduces the metric over `cost` (device) and maps it: the rz_cost_stats land in dCostStats; rgb (3 floats per pixel) and out4
+// ((colour, 1) per pixel) are device outputs, each optional.
+static int cost_view_run(rz_ctx* c, const rz_cost_view_params& V, const uint4* cost, float* rgb, float4* out4) {
+    const rz_frame_params& f = c->frame;
+    CostReduceLaunch R{};
+    R.cost = cost;
+    R.n = (long long)f.width * f.height;
+    R.width = f.width;
+    R.metric = V.metric;
+    R.scale = V.scale;
+    R.blocks = cost_reduce_blocks(R.n);
+    int rc = ensure(c, c->dCostPartials, (size_t)RZ_COST_REDUCE_BLOCKS * 3 * sizeof(unsigned long long));
+    if (rc == RZ_OK) rc = ensure(c, c->dCostStats, sizeof(rz_cost_stats));
+    if (rc != RZ_OK) return rc;
+    R.partials = static_cast<unsigned long long*>(c->dCostPartials.p);
+    R.stats = static_cast<rz_cost_stats*>(c->dCostStats.p);
+    launch_cost_reduce(R, c->stream);
+    RZ_HIP(c, hipGetLastError());
+    if (!rgb && !out4) return RZ_OK;
+    CostViewLaunch L{};
+    L.cost = cost;
+    L.stats = R.stats;
+    L.width = f.width; L.height = f.height;
+    L.metric = V.metric; L.curve = V.curve;
+    L.dst = out4;
+    L.rgb = rgb;
+    launch_cost_view(L, c->stream);
+    RZ_HIP(c, hipGetLastError());
+    return RZ_OK;
+}
+
+static int cost_view_impl(rz_ctx* c, const rz_cost_view_params* pp, const rz_pixel_cost* cost, size_t cost_bytes, float* rgb32f,
+                          size_t rgb32f_bytes, rz_cost_stats* stats, unsigned flags) {
+    const char* what = "rz_cost_view";
+    if (!c) return fail(nullptr, RZ_ERR_INVALID_ARG, "%s: null context", what);
+    if (flags & ~RZ_COST_HOST) return fail(c, RZ_ERR_INVALID_ARG, "%s: unknown flags 0x%x", what, flags);
+    const rz_cost_view_params& V = pp ? *pp : kCostViewDefaults;
+    int rc = cost_view_check(c, what, V);
+    if (rc != RZ_OK) return rc;
+    const bool host = (flags & RZ_COST_HOST) != 0;
+    if (!host && ((reinterpret_cast<uintptr_t>(cost) & 15u) || (reinterpret_cast<uintptr_t>(stats) & 7u) || (reinterpret_cast<uintptr_t>(rgb32f) & 3u)))
+        return fail(c, RZ_ERR_INVALID_ARG, "%s: device pointers must be 16-byte (cost), 8-byte (stats) or 4-byte (rgb32f) aligned", what);
+    const size_t np = (size_t)c->frame.width * c->frame.height;
+    const size_t bCost = np * sizeof(rz_pixel_cost), bRgb = np * 3 * sizeof(float);
+    if (cost && cost_bytes < bCost) return fail(c, RZ_ERR_BUFFER_SIZE, "%s: cost needs %zu bytes, got %zu", what, bCost, cost_bytes);
+    if (!cost) {
+        rc = cost_kept(c, what);
+        if (rc != RZ_OK) return rc;
+    }
+    if (rgb32f && rgb32f_bytes < bRgb) return fail(c, RZ_ERR_BUFFER_SIZE, "%s: rgb32f needs %zu bytes, got %zu", what, bRgb, rgb32f_bytes);
+    if (!rgb32f && !stats) return RZ_OK;
+    const uint4* in = cost ? reinterpret_cast<const uint4*>(cost) : static_cast<const uint4*>(c->dCost.p);
+    HostStage stage(c, host);
+    const int sRgb = stage.add(rgb32f, bRgb);
+    rc = stage.input(reinterpret_cast<const uint4*>(cost), bCost, in);
+    if (rc == RZ_OK) rc = stage.place();
+    if (rc != RZ_OK) return rc;
+    rc = cost_view_run(c, V, in, stage.dev<float>(sRgb), nullptr);
+    if (rc != RZ_OK) return rc;
+    if (stats) RZ_HIP(c, hipMemcpyAsync(stats, c->dCostStats.p, sizeof(rz_cost_stats), host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, c->stream));
+    return host ? stage.fetch() : RZ_OK;
+}
+
+static int present_cost_impl(rz_ctx* c, const rz_present_params* pp, const rz_cost_view_params* vp, uint8_t* rgba8, size_t rgba8_bytes,
+                             float* rgb32f, size_t rgb32f_bytes) {
+    const char* what = "rz_present_cost";
+    if (!c) return fail(nullptr, RZ_ERR_INVALID_ARG, "%s: null context", what);
+    if (!pp) return fail(c, RZ_ERR_INVALID_ARG, "%s: null present params", what);
+    const rz_cost_view_params& V = vp ? *vp : kCostViewDefaults;
+    int rc = cost_view_check(c, what, V);
+    if (rc == RZ_OK) rc = cost_kept(c, what);
+    if (rc != RZ_OK) return rc;
+    const size_t np = (size_t)c->frame.width * c->frame.height;
+    if (rgba8 && rgba8_bytes < np * 4) return fail(c, RZ_ERR_BUFFER_SIZE, "%s: rgba8 buffer needs %zu bytes", what, np * 4);
+    if (rgb32f && rgb32f_bytes < np * 12) return fail(c, RZ_ERR_BUFFER_SIZE, "%s: rgb32f buffer needs %zu bytes", what, np * 12);
+    rc = ensure(c, c->dCostOut, np * 16);
+    if (rc != RZ_OK) return rc;
+    float4* out4 = static_cast<float4*>(c->dCostOut.p);
+    rc = cost_view_run(c, V, static_cast<const uint4*>(c->dCost.p), nullptr, out4);
+    if (rc != RZ_OK) return rc;
+    return present_impl(c, pp, rgba8, rgba8_bytes, rgb32f, rgb32f_bytes, out4);
+}
+
 // rz_denoise_temporal / rz_present_temporal (rz_temporal.hip).  They read what rz_denoise reads and touch no render state; the
 // history they keep is the context's own (rz_ctx: dTmp*).
 static const rz_temporal_params kTemporalDefaults = {0.2f, 0.2f, 32, 0.9f, 2.0f, 5, 0.5f, 128.0f, 1.0f, 1, {0, 0, 0, 0, 0, 0}};
@@ -3805,6 +3987,17 @@ int rz_present_antialiased_seethrough(rz_ctx* c, const rz_present_params* presen
         return present_antialiased_impl(c, present, antialias, display, source, filter_params, rgba8, rgba8_bytes, rgb32f, rgb32f_bytes,
                                         seethrough ? seethrough : &kSeethroughDefaults);
     });
+}
+int rz_render_cost(rz_ctx* c, const rz_cost_params* params, rz_pixel_cost* cost, size_t cost_bytes, rz_counters* totals, unsigned flags) {
+    return guarded(c, "rz_render_cost", [&] { return render_cost_impl(c, params, cost, cost_bytes, totals, flags); });
+}
+int rz_cost_view(rz_ctx* c, const rz_cost_view_params* params, const rz_pixel_cost* cost, size_t cost_bytes, float* rgb32f,
+                 size_t rgb32f_bytes, rz_cost_stats* stats, unsigned flags) {
+    return guarded(c, "rz_cost_view", [&] { return cost_view_impl(c, params, cost, cost_bytes, rgb32f, rgb32f_bytes, stats, flags); });
+}
+int rz_present_cost(rz_ctx* c, const rz_present_params* present, const rz_cost_view_params* params, uint8_t* rgba8, size_t rgba8_bytes,
+                    float* rgb32f, size_t rgb32f_bytes) {
+    return guarded(c, "rz_present_cost", [&] { return present_cost_impl(c, present, params, rgba8, rgba8_bytes, rgb32f, rgb32f_bytes); });
 }
 int rz_display_reset(rz_ctx* c) {
     return guarded(c, "rz_display_reset", [&] { return display_reset_impl(c); });

@@ -23,6 +23,14 @@ __device__ __forceinline__ void store_colour(float4* dst, float* rgb, size_t p, 
 }
 
 // ---- rz_kernels.hip
+// The launch shape of rz_render_pixels, which rz_cost_pixels (rz_cost.hip) takes as it stands.
+#ifndef RZ_WAVES_PER_BLOCK
+#define RZ_WAVES_PER_BLOCK 1   // measured on C2: 4 -> 98.9 ms, 2 -> 88.5 ms, 1 -> 88.0 ms (a 4-wave group holds its CU slots until its slowest tile ends)
+#endif
+constexpr int WAVES_PER_BLOCK = RZ_WAVES_PER_BLOCK;
+#ifndef RZ_MIN_WAVES_PER_SIMD
+#define RZ_MIN_WAVES_PER_SIMD 2
+#endif
 void launch_render_pixels(const KParams& K, bool counted, hipStream_t stream);
 SamplesPlan plan_render_samples(int spp, int nSlots, bool glass);
 size_t samples_lds_extra(bool glass, bool compact);
@@ -310,8 +318,37 @@ struct SkinWork {               // one rig posed: every pointer is device memory
 };
 int skin_device(const SkinWork& W, hipStream_t s);
 
+// ---- rz_cost.hip
+constexpr int RZ_COST_REDUCE_BLOCKS = 1024;     // the most workgroups of rz_cost_reduce's first stage (= partial records)
+struct CostLaunch {             // rz_cost_pixels (beside the KParams of a one-lane-per-pixel render at sample 0)
+    uint4* cost;                // width x height rz_pixel_cost (2 uint4)
+    unsigned* errWord;          // the context's backstop word
+};
+struct CostReduceLaunch {       // rz_cost_reduce_partials, rz_cost_reduce_final
+    const uint4* cost;          // width x height rz_pixel_cost
+    long long n;                // pixels
+    int width;
+    int metric;                 // rz_cost_view_params.metric
+    float scale;                // rz_cost_view_params.scale
+    int blocks;                 // workgroups of the first stage, <= RZ_COST_REDUCE_BLOCKS
+    unsigned long long* partials;   // blocks x (maximum, its lowest pixel index, sum)
+    rz_cost_stats* stats;       // what the second stage writes
+};
+struct CostViewLaunch {         // rz_cost_view
+    const uint4* cost;
+    const rz_cost_stats* stats; // scale_used: the top of the ramp
+    int width, height;
+    int metric, curve;
+    float4* dst;                // (colour, 1), optional
+    float* rgb;                 // width x height x 3 floats, optional
+};
+void launch_cost_pixels(const KParams& K, const CostLaunch& C, hipStream_t stream);
+int cost_reduce_blocks(long long n);
+void launch_cost_reduce(const CostReduceLaunch& R, hipStream_t stream);
+void launch_cost_view(const CostViewLaunch& V, hipStream_t stream);
+
 // ---- rz_present.hip
-struct ProjBox;                 // screen-space corners of one box (rz_present.hip)
+struct ProjBox;                // screen-space corners of one box (rz_present.hip)
 struct PresentParams {
     const float4* accum;
     uchar4* rgba8;              // may be null

@@ -22,13 +22,7 @@
 
 namespace rz {
 
-#ifndef RZ_WAVES_PER_BLOCK
-#define RZ_WAVES_PER_BLOCK 1   // measured on C2: 4 -> 98.9 ms, 2 -> 88.5 ms, 1 -> 88.0 ms (a 4-wave group holds its CU slots until its slowest tile ends)
-#endif
-constexpr int WAVES_PER_BLOCK = RZ_WAVES_PER_BLOCK;
-#ifndef RZ_MIN_WAVES_PER_SIMD
-#define RZ_MIN_WAVES_PER_SIMD 2
-#endif
+// (WAVES_PER_BLOCK and RZ_MIN_WAVES_PER_SIMD, the launch shape of rz_render_pixels: rz_internal.h -- rz_cost.hip takes it too)
 
 #ifdef RZ_PROF
 __device__ unsigned long long rz_wave_log[1 << 17][3];     // diagnostic build: start, end (100 MHz ticks), hw id

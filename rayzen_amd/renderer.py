@@ -41,6 +41,7 @@ VISIBILITY_DTYPE = np.dtype([("visibility", "<f4"), ("lit", "<i4")])            
 MESH_QUALITY = np.dtype([("node_offset", "<i4"), ("index_offset", "<i4"), ("tri_offset", "<i4"), ("node_offset_before", "<i4"),
                          ("n_triangles", "<i4"), ("n_nodes", "<i4"), ("depth", "<i4"), ("flags", "<u4"), ("sah_cost", "<f8"),
                          ("sah_cost_built", "<f8"), ("sah_cost_before", "<f8"), ("reserved", "<f8")])        # rz_mesh_quality
+PIXEL_COST_DTYPE = _lib.PIXEL_COST_DTYPE # rz_pixel_cost (32 B): what render_cost returns
 CHAIN_DTYPE = _lib.CHAIN_DTYPE           # rz_chain (16 B): what upscale(see_through=..., chains=True) returns
 
 
@@ -945,6 +946,81 @@ class Renderer:
                                                    None if dp is None else C.byref(dp), _lib.DISPLAY_SOURCES[source], fp,
                                                    rgba8.ctypes.data, rgba8.nbytes, rgb.ctypes.data, rgb.nbytes),
                     "rz_present_antialiased")
+        return rgb, rgba8
+
+    # -- where a frame is expensive (rz_render_cost / rz_cost_view / rz_present_cost) ------
+    @staticmethod
+    def _cost_params(spp):
+        if spp is None:
+            return None
+        p = _lib.CostParams()
+        p.spp = int(spp)
+        return C.byref(p)
+
+    @staticmethod
+    def _cost_view_params(metric, curve, scale):
+        p = _lib.CostViewParams()
+        p.metric = _lib.COST_METRICS[metric] if isinstance(metric, str) else int(metric)
+        p.curve = _lib.COST_CURVES[curve] if isinstance(curve, str) else int(curve)
+        p.scale = float(scale)
+        return p
+
+    def render_cost(self, spp=None, totals=False):
+        """The per-pixel traversal cost map (include/rayzen_hip.h: rz_render_cost) of the frame of the last set_frame: (H, W)
+        PIXEL_COST_DTYPE records, row 0 = bottom row -- what the reference shader would touch for samples 0 .. spp-1 of each pixel
+        (spp None: the frame's).  Touches no render state; the context keeps the map for cost_view / present_cost.  With
+        totals=True also the frame's counters as render_counted returns them at sample_base 0."""
+        out = np.empty((self.height, self.width), PIXEL_COST_DTYPE)
+        cnt = _lib.Counters() if totals else None
+        self._check(self._L.rz_render_cost(self._c, self._cost_params(spp), out.ctypes.data, out.nbytes,
+                                           None if cnt is None else C.byref(cnt), _lib.COST_HOST), "rz_render_cost")
+        return (out, {n: int(getattr(cnt, n)) for n in _lib.COUNTER_FIELDS}) if totals else out
+
+    def render_cost_device(self, ptr=None, spp=None, totals=False):
+        """rz_render_cost on device memory (ptr: W*H*32 B, 16-B aligned, or None to keep the context's copy only): enqueued on the
+        context's stream.  totals=True waits for the kernel and returns the counters."""
+        cnt = _lib.Counters() if totals else None
+        self._check(self._L.rz_render_cost(self._c, self._cost_params(spp), C.c_void_p(ptr), self.width * self.height * 32 if ptr else 0,
+                                           None if cnt is None else C.byref(cnt), 0), "rz_render_cost")
+        return {n: int(getattr(cnt, n)) for n in _lib.COUNTER_FIELDS} if totals else None
+
+    def cost_view(self, cost=None, metric="bytes", curve="linear", scale=0.0, stats=False):
+        """A cost map as a false colour (rz_cost_view): (H, W, 3) float32, black - blue - green - yellow - red from 0 to `scale`
+        (0: the frame's maximum), white above a caller's scale.  cost None: the context's last map.  metric: "bytes", "nodes",
+        "triangles", "traversals" or "instances"; curve: "linear" or "log".  With stats=True also a dict of max_value, sum_value,
+        max_x, max_y (the lowest pixel index among the maxima; row 0 = bottom) and scale_used."""
+        vp = self._cost_view_params(metric, curve, scale)
+        src = None if cost is None else np.ascontiguousarray(cost, PIXEL_COST_DTYPE)
+        rgb = np.empty((self.height, self.width, 3), np.float32)
+        st = _lib.CostStats() if stats else None
+        self._check(self._L.rz_cost_view(self._c, C.byref(vp), None if src is None else src.ctypes.data,
+                                         0 if src is None else src.nbytes, rgb.ctypes.data, rgb.nbytes,
+                                         None if st is None else C.addressof(st), _lib.COST_HOST), "rz_cost_view")
+        if not stats:
+            return rgb
+        return rgb, dict(max_value=int(st.max_value), sum_value=int(st.sum_value), max_x=int(st.max_x), max_y=int(st.max_y),
+                         scale_used=float(st.scale_used))
+
+    def cost_view_device(self, rgb32f_ptr=None, stats_ptr=None, cost_ptr=None, metric="bytes", curve="linear", scale=0.0):
+        """rz_cost_view on device memory (cost 16-B, stats 8-B, rgb32f 4-B aligned; each optional): enqueued on the context's
+        stream.  Sizes: cost W*H*32 B, rgb32f W*H*12 B, stats 32 B."""
+        vp = self._cost_view_params(metric, curve, scale)
+        n = self.width * self.height
+        self._check(self._L.rz_cost_view(self._c, C.byref(vp), C.c_void_p(cost_ptr), n * 32 if cost_ptr else 0,
+                                         C.c_void_p(rgb32f_ptr), n * 12 if rgb32f_ptr else 0, C.c_void_p(stats_ptr), 0),
+                    "rz_cost_view")
+
+    def present_cost(self, metric="bytes", curve="linear", scale=0.0, fps=0.0, show_fps=True, show_lights=False, show_bvh=False,
+                     bvh_mode=0, selected_blas=0, selected_tri=0):
+        """present() with the heat map of the context's last cost map in place of the resolve: the overlays are drawn on top.
+        Returns (rgb float32 (H,W,3), rgba8 uint8 (H,W,4))."""
+        p = _lib.PresentParams(float(fps), int(bool(show_fps)), int(bool(show_lights)), int(bool(show_bvh)),
+                               int(bvh_mode), int(selected_blas), int(selected_tri))
+        vp = self._cost_view_params(metric, curve, scale)
+        rgb = np.empty((self.height, self.width, 3), np.float32)
+        rgba8 = np.empty((self.height, self.width, 4), np.uint8)
+        self._check(self._L.rz_present_cost(self._c, C.byref(p), C.byref(vp), rgba8.ctypes.data, rgba8.nbytes, rgb.ctypes.data,
+                                            rgb.nbytes), "rz_present_cost")
         return rgb, rgba8
 
     # -- convenience -----------------------------------------------------------
