@@ -1,5 +1,7 @@
 """One counted C2 frame with the RZ_PROF diagnostic build (RAYZEN_HIP_SO=rayzen_amd/lib/librayzen_hip_prof.so):
-prints per-site wave executions / active lanes and the wave-cycle split to stderr."""
+prints per-site wave executions / active lanes, the wave-cycle split and, per query round, what became of RZ_SHADOW_EXIT's
+eligible queries (cut short / refused by which guard / held / traced again) to stderr.  That build's counted frame skips back-face
+shadow queries and takes the shortcut as the product's uncounted frames do, so its tallies are not the oracle's."""
 import os
 import sys
 

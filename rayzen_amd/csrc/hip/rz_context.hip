@@ -1132,6 +1132,12 @@ int do_render(rz_ctx* c, bool counted, rz_counters* out) {
         fprintf(stderr, "[rz_prof] pool_trace (a claim's pooled queries traced together): %llu wave cycles = T phases %llu + B phases %llu (of which refills %llu); round 7 above = its steps\n", pr[120], pr[121], pr[122], pr[123]);
         fprintf(stderr, "[rz_prof] descend steps of the general (per-lane) walk by children entered: none %llu  one %llu  both %llu (lane-level; the scalar-unit steps are not in here); in the pools' walks: none %llu  one %llu  both %llu\n", pr[132], pr[133], pr[134], pr[136], pr[137], pr[138]);
         fprintf(stderr, "[rz_prof] wait slots: end-of-claim sections %llu wave cycles (of which the claim-end sums %llu); slot_sums inside pool_process %llu\n", pr[124], pr[126], pr[125]);
+        // (this build's counted frame takes the shortcut, as the product's uncounted one does: rz_path.h, shadow_exit)
+        for (int r = 0; r < 3; ++r) {
+            const unsigned long long* q = pr + 140 + 6 * r;
+            fprintf(stderr, "[rz_prof] shadow exit, round %d%s: eligible queries %llu | walks cut short %llu | refused: hit within 2 EPS %llu, not clearly nearer than the light %llu | held %llu | traced again %llu\n",
+                    r + 1, r == 2 ? " and later" : "", q[0], q[1], q[2], q[3], q[4], q[5]);
+        }
         fprintf(stderr, "[rz_prof] inside advance: sky %llu  hit %llu  start_light %llu  shade_light %llu  scatter %llu (hemisphere %llu)  shadow step %llu\n", pr[22], pr[23], pr[24], pr[25], pr[26], pr[27], pr[28]);
 #endif
     }

@@ -187,6 +187,11 @@ __device__ __forceinline__ void rz_prof_rounds(const Tally& c, unsigned long lon
         }
         if ((threadIdx.x & 63) == 0 && c.rt[r]) atomicAdd(&pr[32 + 11 * r + 10], c.rt[r]);
     }
+    for (int k = 0; k < 18; ++k) {      // RZ_SHADOW_EXIT: eligible / cut / refused / held / traced again, rounds 1, 2, 3+ -> pr[140 + k]
+        unsigned x = c.sx[k / 6][k % 6];
+        for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
+        if ((threadIdx.x & 63) == 0 && x) atomicAdd(&pr[140 + k], (unsigned long long)x);
+    }
 }
 #endif
 __device__ __forceinline__ void tally_add(Tally& a, const Tally& b) {
@@ -199,6 +204,7 @@ __device__ __forceinline__ void tally_add(Tally& a, const Tally& b) {
     for (int k = 0; k < 8; ++k) a.ps[k] += b.ps[k];
     for (int k = 0; k < 20; ++k) a.t[k] += b.t[k];
     for (int r = 0; r < 8; ++r) { a.rt[r] += b.rt[r]; for (int k = 0; k < 10; ++k) a.rp[r][k] += b.rp[r][k]; }
+    for (int k = 0; k < 18; ++k) a.sx[k / 6][k % 6] += b.sx[k / 6][k % 6];
 #endif
 }
 
@@ -337,14 +343,21 @@ __device__ __forceinline__ void render_samples_group(const KParams& K, const uns
                     bool found = false;
                     // (the shadow ray of a light behind the surface is not traced -- rz_path.h, RZ_BACKFACE_SKIP; a wave is a few
                     //  pixels' samples with near-identical hit points, so this is mostly one scalar branch around the whole query)
+                    // (a first-iteration shadow query may stop at a blocker, and is traced again if that is in doubt -- rz_trace.h,
+                    //  RZ_SHADOW_EXIT; a spread wave holds no shadow query)
+                    int sx = 0;
                     if (!shadow_candidate<COUNT, false>(P)) {
                         RZ_SITE(c, 6);
-                        found = spread ? trace_spread<COUNT, OVF>(K, P.o, P.d, h, bstk, c) : trace_closest<COUNT, OVF>(K, P.o, P.d, h, bstk, c);
+                        if constexpr (shadow_exit<COUNT, false>)
+                            found = spread ? trace_spread<COUNT, OVF>(K, P.o, P.d, h, bstk, c)
+                                           : trace_closest<COUNT, OVF, false, true>(K, P.o, P.d, h, bstk, c, nullptr, shadow_exit_dist<COUNT, false>(P), &sx);
+                        else
+                            found = spread ? trace_spread<COUNT, OVF>(K, P.o, P.d, h, bstk, c) : trace_closest<COUNT, OVF>(K, P.o, P.d, h, bstk, c);
                     }
 #ifdef RZ_PROF
                     t2 = __builtin_amdgcn_s_memtime();
 #endif
-                    advance<COUNT, false>(K, P, found, h, c);
+                    advance<COUNT, false>(K, P, found, h, c, sx);
                 }
 #ifdef RZ_PROF
                 tTrace += t2 - t1; tAdv += __builtin_amdgcn_s_memtime() - t2;
@@ -878,14 +891,19 @@ __device__ __forceinline__ void render_claim_compact(const KParams& K, const Cla
                     const unsigned long long tq0_ = __builtin_amdgcn_s_memtime();
 #endif
                     // (not for the shadow ray of a light behind the surface: rz_path.h, RZ_BACKFACE_SKIP)
+                    // (a first-iteration shadow query may stop at a blocker, and is traced again if that is in doubt: RZ_SHADOW_EXIT)
+                    int sx = 0;
                     if (!shadow_candidate<COUNT, GLASS>(P)) {
                         RZ_SITE(c, 6);
-                        found = trace_closest<COUNT, OVF>(K, P.o, P.d, h, bstk, tu);
+                        if constexpr (shadow_exit<COUNT, GLASS>)
+                            found = trace_closest<COUNT, OVF, false, true>(K, P.o, P.d, h, bstk, tu, nullptr, shadow_exit_dist<COUNT, GLASS>(P), &sx);
+                        else
+                            found = trace_closest<COUNT, OVF>(K, P.o, P.d, h, bstk, tu);
                     }
 #ifdef RZ_PROF
                     c.rt[c.rnd & 7] += __builtin_amdgcn_s_memtime() - tq0_;
 #endif
-                    advance<COUNT, GLASS, GLASS ? 1 : 0>(K, P, found, h, tu);
+                    advance<COUNT, GLASS, GLASS ? 1 : 0>(K, P, found, h, tu, sx);
                 }
 #ifdef RZ_PROF
                 if (c.rnd < 7) ++c.rnd;

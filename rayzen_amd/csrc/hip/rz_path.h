@@ -193,10 +193,23 @@ __device__ __forceinline__ v3 random_hemisphere_direction(const KParams& K, v3 n
 #endif
 template <bool COUNT, bool GLASS>
 constexpr bool backface_skip = RZ_BACKFACE_SKIP && !GLASS && (!COUNT || RZ_BACKFACE_COUNTED);
+// RZ_SHADOW_EXIT (rz_trace.h): the same instantiations -- opaque, not counting.  P.iter carries one more
+// mark between start_light and the end of a light's first iteration: -2, "reference only", a query whose shortcut was in doubt
+// and is traced again in full (the back-face candidate's mark is -1).
+template <bool COUNT, bool GLASS>
+constexpr bool shadow_exit = RZ_SHADOW_EXIT && !GLASS && (!COUNT || RZ_BACKFACE_COUNTED);      // (the RZ_PROF build's counted frame takes the shortcut too, as it skips back faces: its tallies are then not the oracle's)
 // The path's pending query is the shadow ray of a light behind its surface: the caller does not trace it (found = false).
 template <bool COUNT, bool GLASS>
 __device__ __forceinline__ bool shadow_candidate(const Path& P) {
+    if constexpr (shadow_exit<COUNT, GLASS>) return backface_skip<COUNT, GLASS> && P.mode == MODE_SHADOW && P.iter == -1;
     return backface_skip<COUNT, GLASS> && P.mode == MODE_SHADOW && P.iter < 0;
+}
+// The light's distance if the path's pending query may take the shortcut -- a shadow query in its first iteration that is
+// neither a back-face candidate nor sent back for the reference's answer -- and 0 ("not eligible") otherwise.
+template <bool COUNT, bool GLASS>
+__device__ __forceinline__ float shadow_exit_dist(const Path& P) {
+    if constexpr (!shadow_exit<COUNT, GLASS>) return 0.0f;
+    return (P.mode == MODE_SHADOW && P.iter == 0 && P.traveled == 0.0f) ? P.maxDist : 0.0f;
 }
 
 // Set up the shadow query of light P.li for the parked surface point
@@ -448,7 +461,7 @@ __device__ __forceinline__ void finish_lighting(const KParams& K, Path& P, Tally
 
 // Advance a path by the result of the closest-hit query of its current ray.
 template <bool COUNT, bool GLASS = true, int GMODE = 0>
-__device__ __forceinline__ void advance(const KParams& K, Path& P, bool found, const HitRec& h, Tally& c) {
+__device__ __forceinline__ void advance(const KParams& K, Path& P, bool found, const HitRec& h, Tally& c, int sx = 0) {
     if (P.mode == MODE_SEGMENT) {
         if (!found) {   // FS:705-711
             RZ_T0();
@@ -477,12 +490,21 @@ __device__ __forceinline__ void advance(const KParams& K, Path& P, bool found, c
     }
     // MODE_SHADOW: the body of one iteration of FS:511-526
     constexpr bool BFS = backface_skip<COUNT, GLASS>;
+    constexpr bool SX = shadow_exit<COUNT, GLASS>;
+    if constexpr (SX) {
+        // RZ_SHADOW_EXIT, sx as trace_closest reported it.  2: the shortcut was taken and is in doubt -- the path stays exactly as
+        // start_light left it but for the mark, and the caller's next trip traces the same query in full (one re-trace at most: a
+        // marked path is not eligible).  The mark has done its work once that answer is here.
+        if (sx == 2) { P.iter = -2; return; }
+        if (P.iter == -2) P.iter = 0;
+    }
     // a candidate of RZ_BACKFACE_SKIP: its query was not traced (the caller passed found = false, h is not read)
     bool cand = BFS && P.iter < 0;
 #pragma nounroll
     for (;;) {      // (one trip, but for RZ_BACKFACE_CHAIN: there one per light dealt with in this call, at most nLights)
         bool done = false, lit = false;
         if (cand || !found) { done = true; lit = true; }
+        else if (SX && sx == 1) { P.vis = 0.0f; done = true; lit = false; }     // the shortcut holds: an opaque blocker (FS:522-524); h was not written
         else if (h.t < 0.001f) { P.o = P.o + P.d * 0.001f; }
         else {
             P.traveled += h.t;

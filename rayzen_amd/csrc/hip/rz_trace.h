@@ -43,6 +43,14 @@ namespace rz {
 #define RZ_DESCEND_MIN_LANES 4   // leave the descend loop when fewer lanes than this still have an internal node (lane=sample kernel on C2: 1 -> 17.6 ms, 2 -> 17.4, 3..6 -> 17.15-17.2, 8 -> 17.3, 12 -> 17.4)
 #endif
 
+// RZ_SHADOW_EXIT (round 7, profiles/r07_shadow_exit/; the rule and why it is safe: DESIGN.md section 4.2).  An opaque light
+// needs "something blocks it", not which triangle: a first-iteration shadow query of the opaque, non-counting sample kernels
+// stops looking for a NEARER blocker at the end of the first leaf in which it accepted a triangle -- if the guards hold -- and
+// only rules out a hit near its origin; a query whose shortcut is in doubt at its end is traced again in full.
+// 0: the code before, instruction for instruction.
+#ifndef RZ_SHADOW_EXIT
+#define RZ_SHADOW_EXIT 1
+#endif
 struct Tally {          // per-thread counts of the REFERENCE algorithm's memory touches
     unsigned traversals, tlas_nodes, tlas_leaf_indices, instances, blas_nodes, triangles, materials, light_fetches,
         samples;
@@ -54,6 +62,7 @@ struct Tally {          // per-thread counts of the REFERENCE algorithm's memory
     unsigned ps[8];             // descend steps by lane: [0] both child boxes missed or culled, [1] one entered, [2] both (one stacked); [4..6] the same for the pool's walks (pool_trace)
     int rnd;                    // which closest-hit query of its path this lane is in (0 primary, 1-2 shadow, 3.. bounces), capped at 7
     unsigned rp[8][10];         // per query round: wave-execs / lanes of [0,1] descend steps [2,3] triangle tests [4,5] instance entries [6,7] uniform-pair steps [8,9] queries
+    unsigned sx[3][6];          // RZ_SHADOW_EXIT, per query round 1, 2, 3 and later (lanes): [0] eligible queries [1] walks cut short [2] refused: the leaf's nearest hit not beyond 2 EPS k [3] refused: not clearly nearer than the light [4] queries whose shortcut held [5] queries traced again
     unsigned long long rt[8];   // per query round: wave cycles inside trace_closest (lane 0's clock)
     unsigned long long t[20];   // ([16] the end-of-claim section of a compacting claim, [17] slot_sums inside pool_process, [18] the claim-end sums alone) ([4] / [9]: phase 1 / pool rounds of a compacting claim, [10] pool rounds, [11] paths in them)   wave cycles (s_memtime): [0] descend loops, [1] leaf phases, [2] whole BLAS walks; rz_path.h advance(): [3] sky, [4] hit bookkeeping, [5] start_light, [6] shade_light, [7] scatter, [8] of it the hemisphere direction, [9] shadow-step bookkeeping
 #endif
@@ -63,8 +72,10 @@ struct Tally {          // per-thread counts of the REFERENCE algorithm's memory
 #define RZ_SITE(c, k) do { const bool first_ = __lane_id() == (unsigned)(__ffsll((long long)rz_ballot(1)) - 1); (c).p[2 * (k) + 1] += 1u; if (first_) (c).p[2 * (k)] += 1u; \
         constexpr int rs_ = (k) == 3 ? 0 : (k) == 2 ? 1 : (k) == 5 ? 2 : (k) == 7 ? 3 : (k) == 6 ? 4 : -1; \
         if (rs_ >= 0) { (c).rp[(c).rnd & 7][2 * (rs_ < 0 ? 0 : rs_) + 1] += 1u; if (first_) (c).rp[(c).rnd & 7][2 * (rs_ < 0 ? 0 : rs_)] += 1u; } } while (0)
+#define RZ_SX_COUNT(c, k) do { (c).sx[((c).rnd < 1 ? 1 : (c).rnd > 3 ? 3 : (c).rnd) - 1][k] += 1u; } while (0)
 #else
 #define RZ_SITE(c, k) do { } while (0)
+#define RZ_SX_COUNT(c, k) do { } while (0)
 #endif
 
 // "These registers are needed now": stops hipcc from splitting a record load and sinking part of it into a later
@@ -310,9 +321,13 @@ __device__ __forceinline__ bool pop_entry(const BlasStackT<OVF>& S, int& sp, flo
 // MI ("many instances"): the lanes of the wave walk DIFFERENT instances at the same time -- `pairs` / `tris` are then the
 // scene's arrays, the lane's instance contributes its bases pbase / tbase, and a node number is only meaningful together
 // with its base.  Such waves hold incoherent rays (the late bounces), so the wave-uniform scalar fetch is not even tried.
-template <bool COUNT, bool OVF, int OCT, bool MI>
+// SX (RZ_SHADOW_EXIT): a lane with sxkIO > 0 (the scale k of this local space) carries a first-iteration shadow query to a light
+// sxMaxDist away and may cut the walk short at the end of the first leaf in which it accepted a triangle; sxkIO < 0 says it did.
+template <bool COUNT, bool OVF, int OCT, bool MI, bool SX = false>
 __device__ __forceinline__ int blas_walk(const DevPair* __restrict__ pairs, const DevTri* __restrict__ tris, v3 lo, v3 ld, v3 inv,
-                                         bool go, int cur, int pbase, int tbase, float& tLocOut, const BlasStackT<OVF>& bstk, Tally& c) {
+                                         bool go, int cur, int pbase, int tbase, float& tLocOut, const BlasStackT<OVF>& bstk, Tally& c,
+                                         float sxMaxDist, float& sxkIO) {
+    float sxk = SX ? sxkIO : 0.0f;
     float tLoc = 1e30f;
     int best = -1;
     int sp = 0;
@@ -586,6 +601,24 @@ __device__ __forceinline__ int blas_walk(const DevPair* __restrict__ pairs, cons
                 triMask = rz_ballot(i < count);
                 any = triMask != 0ull;
             }
+            if constexpr (SX) {
+                // The lane's first accepted triangle lies in the leaf just tested (an eligible lane stops being one right here, so
+                // best >= 0 is news), and the leaf was tested to its end: tLoc is the nearest of its hits.  If that is a blocker
+                // whatever else the walk may find -- clearly nearer than the light, beyond twice the restart distance -- the rest of
+                // the walk only has to rule out a hit under twice the restart distance: the lane's cull distance shrinks to it.
+                // The blocker waits in `best` as -2 - index and its distance in sxk as -t until the walk is over.
+                const bool decide = sxk > 0.0f && best >= 0;
+                if (rz_ballot(decide) != 0ull) {
+                    const float minLoc = (2.0f * 0.001f) * sxk;                          // 2 EPS, EPS as in FS:510
+                    const float maxLoc = (sxMaxDist * (1.0f - 0x1p-7f)) * sxk;
+                    const bool ok = decide && tLoc > minLoc && tLoc < maxLoc;
+#ifdef RZ_PROF
+                    if (decide) { if (ok) RZ_SX_COUNT(c, 1); else if (!(tLoc > minLoc)) RZ_SX_COUNT(c, 2); else RZ_SX_COUNT(c, 3); }
+#endif
+                    if (decide) sxk = ok ? -tLoc : 0.0f;
+                    if (ok) { tLoc = minLoc; best = -2 - best; }
+                }
+            }
             if (leaf) {
                 if (!pop_entry(bstk, sp, tLoc, cur)) cur = -1;
             }
@@ -598,6 +631,13 @@ __device__ __forceinline__ int blas_walk(const DevPair* __restrict__ pairs, cons
 #ifdef RZ_PROF
     c.t[2] += __builtin_amdgcn_s_memtime() - tw0_;
 #endif
+    if constexpr (SX) {
+        if (sxk < 0.0f) {       // the walk was cut short: the blocker, unless something nearer than twice the restart distance turned up
+            if (best < -1) { best = -2 - best; tLoc = -sxk; }
+            sxk = -1.0f;
+        }
+        sxkIO = sxk;
+    }
     tLocOut = tLoc;
     return best;
 }
@@ -607,9 +647,9 @@ __device__ __forceinline__ int blas_walk(const DevPair* __restrict__ pairs, cons
 #define RZ_OCTANT_SLAB 1
 #endif
 // The lanes of the wave enter ONE instance, `I` (wave-uniform: its record comes through the scalar cache).
-template <bool COUNT, bool OVF>
+template <bool COUNT, bool OVF, bool SX = false>
 __device__ __forceinline__ int traverse_blas(const KParams& K, const DevInstance* __restrict__ I, v3 lo, v3 ld,
-                                             float& tLocOut, const BlasStackT<OVF>& bstk, Tally& c) {
+                                             float& tLocOut, const BlasStackT<OVF>& bstk, Tally& c, float sxMaxDist, float& sxk) {
     const v3 inv = rcp3(ld);
     if (COUNT) c.blas_nodes += 1;            // the shader pops the root
     // (I is wave-uniform: the instance's root box, root reference and bases come through the scalar cache)
@@ -639,20 +679,20 @@ __device__ __forceinline__ int traverse_blas(const KParams& K, const DevInstance
             if (rz_ballot(go && (!fin || oct != first)) == 0ull) uoct = first;
         }
         switch (uoct) {
-            case 0: best = blas_walk<COUNT, OVF, 0, false>(pairs, tris, lo, ld, inv, go, cur, 0, 0, tLocOut, bstk, c); break;
-            case 1: best = blas_walk<COUNT, OVF, 1, false>(pairs, tris, lo, ld, inv, go, cur, 0, 0, tLocOut, bstk, c); break;
-            case 2: best = blas_walk<COUNT, OVF, 2, false>(pairs, tris, lo, ld, inv, go, cur, 0, 0, tLocOut, bstk, c); break;
-            case 3: best = blas_walk<COUNT, OVF, 3, false>(pairs, tris, lo, ld, inv, go, cur, 0, 0, tLocOut, bstk, c); break;
-            case 4: best = blas_walk<COUNT, OVF, 4, false>(pairs, tris, lo, ld, inv, go, cur, 0, 0, tLocOut, bstk, c); break;
-            case 5: best = blas_walk<COUNT, OVF, 5, false>(pairs, tris, lo, ld, inv, go, cur, 0, 0, tLocOut, bstk, c); break;
-            case 6: best = blas_walk<COUNT, OVF, 6, false>(pairs, tris, lo, ld, inv, go, cur, 0, 0, tLocOut, bstk, c); break;
-            case 7: best = blas_walk<COUNT, OVF, 7, false>(pairs, tris, lo, ld, inv, go, cur, 0, 0, tLocOut, bstk, c); break;
-            default: best = blas_walk<COUNT, OVF, -1, false>(pairs, tris, lo, ld, inv, go, cur, 0, 0, tLocOut, bstk, c); break;
+            case 0: best = blas_walk<COUNT, OVF, 0, false, SX>(pairs, tris, lo, ld, inv, go, cur, 0, 0, tLocOut, bstk, c, sxMaxDist, sxk); break;
+            case 1: best = blas_walk<COUNT, OVF, 1, false, SX>(pairs, tris, lo, ld, inv, go, cur, 0, 0, tLocOut, bstk, c, sxMaxDist, sxk); break;
+            case 2: best = blas_walk<COUNT, OVF, 2, false, SX>(pairs, tris, lo, ld, inv, go, cur, 0, 0, tLocOut, bstk, c, sxMaxDist, sxk); break;
+            case 3: best = blas_walk<COUNT, OVF, 3, false, SX>(pairs, tris, lo, ld, inv, go, cur, 0, 0, tLocOut, bstk, c, sxMaxDist, sxk); break;
+            case 4: best = blas_walk<COUNT, OVF, 4, false, SX>(pairs, tris, lo, ld, inv, go, cur, 0, 0, tLocOut, bstk, c, sxMaxDist, sxk); break;
+            case 5: best = blas_walk<COUNT, OVF, 5, false, SX>(pairs, tris, lo, ld, inv, go, cur, 0, 0, tLocOut, bstk, c, sxMaxDist, sxk); break;
+            case 6: best = blas_walk<COUNT, OVF, 6, false, SX>(pairs, tris, lo, ld, inv, go, cur, 0, 0, tLocOut, bstk, c, sxMaxDist, sxk); break;
+            case 7: best = blas_walk<COUNT, OVF, 7, false, SX>(pairs, tris, lo, ld, inv, go, cur, 0, 0, tLocOut, bstk, c, sxMaxDist, sxk); break;
+            default: best = blas_walk<COUNT, OVF, -1, false, SX>(pairs, tris, lo, ld, inv, go, cur, 0, 0, tLocOut, bstk, c, sxMaxDist, sxk); break;
         }
     } else
 #endif
     {
-        best = blas_walk<COUNT, OVF, -1, false>(pairs, tris, lo, ld, inv, go, cur, 0, 0, tLocOut, bstk, c);
+        best = blas_walk<COUNT, OVF, -1, false, SX>(pairs, tris, lo, ld, inv, go, cur, 0, 0, tLocOut, bstk, c, sxMaxDist, sxk);
     }
     return best < 0 ? -1 : best + triBase;
 }
@@ -669,7 +709,8 @@ __device__ __forceinline__ int traverse_blas_mi(const KParams& K, int inst, v3 l
     float tminRoot;
     bool go = slab(lo, inv, r0.x, r0.y, r0.z, r1.x, r1.y, r1.z, tminRoot);
     go = go && !(tminRoot > 1e30f) && !(r2.y & 1);
-    return blas_walk<COUNT, OVF, -1, true>(K.pairs, K.tris, lo, ld, inv, go, __float_as_int(r0.w), __float_as_int(r1.w), r2.x, tLocOut, bstk, c);
+    float sxNone = 0.0f;
+    return blas_walk<COUNT, OVF, -1, true>(K.pairs, K.tris, lo, ld, inv, go, __float_as_int(r0.w), __float_as_int(r1.w), r2.x, tLocOut, bstk, c, 0.0f, sxNone);
 }
 
 // FS:457-503 without a stack.  The shader's loop pops nodes in an order that does not depend on the ray: depth first,
@@ -687,9 +728,21 @@ __device__ __forceinline__ int traverse_blas_mi(const KParams& K, int inst, v3 l
 // (The shader's stack[64] has no overflow guard; the oracle skips a push that would not fit.  The number of entries
 //  below a node when it is popped is a property of the tree -- one per ancestor whose right subtree holds it -- so
 //  the layout marks such nodes as never expanding: count 0.)
-template <bool COUNT, bool OVF, bool EXTRA = false>
+// SX (RZ_SHADOW_EXIT): a lane with sxMaxDist > 0 carries a first-iteration shadow query to a light sxMaxDist away and may leave
+// ONE instance's walk early (blas_walk); everything after that is walked in full.  *sxOut then says what became of it:
+//   1  the shortcut holds: the query is BLOCKED -- returns true, h is not written (the winner is not the reference's);
+//   2  it is in doubt (something was delivered nearer than 2 EPS, or not clearly nearer than the light): nothing of this
+//      query may be used, the caller traces it again without the shortcut;
+//   0  the lane took no shortcut: the reference's answer, as ever.
+template <bool COUNT, bool OVF, bool EXTRA = false, bool SX = false>
 __device__ __forceinline__ bool trace_closest(const KParams& K, v3 o, v3 d, HitRec& h, const BlasStackT<OVF>& bstk, Tally& c,
-                                              TraceExtra* x = nullptr) {
+                                              TraceExtra* x = nullptr, float sxMaxDist = 0.0f, int* sxOut = nullptr) {
+    // the lane's shortcut state, one float: > 0 it may still take the shortcut (inside an instance: k = |M^-1 d|, the scale of its
+    // local space, local t = k * world t), 0 it may not, < 0 it took it
+    float sxk = (SX && sxMaxDist > 0.0f && K.regularBoxes != 0) ? 1.0f : 0.0f;
+#ifdef RZ_PROF
+    if (sxk > 0.0f) RZ_SX_COUNT(c, 0);
+#endif
     float tHit = 1e30f;
     int bestTri = -1, bestInst = -1;
     v3 bestP = mk3(0.0f, 0.0f, 0.0f);
@@ -726,9 +779,14 @@ __device__ __forceinline__ bool trace_closest(const KParams& K, v3 o, v3 d, HitR
                         sload12(I->inv, m0, m1);
                         const float mi[12] = {m0[0], m0[1], m0[2], m0[3], m0[4], m0[5], m0[6], m0[7], m1[0], m1[1], m1[2], m1[3]};
                         const v3 lo = x34_point(mi, o);
-                        const v3 ld = normalize(x34_dir(mi, d));
+                        const v3 ldRaw = x34_dir(mi, d);
+                        const v3 ld = normalize(ldRaw);
+                        if constexpr (SX) {
+                            const float k = __builtin_amdgcn_sqrtf(dot(ldRaw, ldRaw));      // to an ulp or two: a guard's scale, not a result
+                            sxk = sxk > 0.0f ? k : sxk;                                      // (a k of 0 or NaN ends the lane's eligibility)
+                        }
                         float tLoc;
-                        const int tri = traverse_blas<COUNT, OVF>(K, I, lo, ld, tLoc, bstk, c);
+                        const int tri = traverse_blas<COUNT, OVF, SX>(K, I, lo, ld, tLoc, bstk, c, sxMaxDist, sxk);
                         if (rz_ballot(tri >= 0) != 0ull) {
                             f32x8 f0;
                             f32x4s f1;
@@ -755,6 +813,16 @@ __device__ __forceinline__ bool trace_closest(const KParams& K, v3 o, v3 d, HitR
         }
     }
     if constexpr (EXTRA) { x->tri = bestTri; x->cut = pos < nDfs; }
+    if constexpr (SX) {
+        // tHit is the nearest world distance any instance delivered, those walked in full before and after the exit included.
+        // (a distance that is NaN or not < 1e30 was delivered by nobody: tHit is still 1e30 and the second test fails)
+        const bool held = tHit >= 2.0f * 0.001f && tHit < sxMaxDist * (1.0f - 0x1p-7f);
+#ifdef RZ_PROF
+        if (sxk < 0.0f) { if (held) RZ_SX_COUNT(c, 4); else RZ_SX_COUNT(c, 5); }
+#endif
+        *sxOut = sxk < 0.0f ? (held ? 1 : 2) : 0;
+        if (sxk < 0.0f) return true;         // (neither h nor the winner's normal is needed: blocked, or traced again)
+    }
     if (bestTri < 0) return false;
     // the winner's normal and material (FS:411-412, 489-491): the triangle's own normal comes precomputed (DevTriN)
     const float4 nm = *reinterpret_cast<const float4*>(K.triN + bestTri);
