@@ -31,6 +31,7 @@ HIP_SYMBOLS = (
     "rz_upscale", "rz_present_upscaled", "rz_upscale_seethrough", "rz_present_upscaled_seethrough",
     "rz_antialias", "rz_present_antialiased", "rz_antialias_seethrough", "rz_present_antialiased_seethrough",
     "rz_render_cost", "rz_cost_view", "rz_present_cost",
+    "rz_coverage", "rz_outline",
 )
 ABI_VERSION = 5         # RZ_ABI_VERSION of the include/rayzen_hip.h this file mirrors
 # the symbols include/rayzen_host.h declares
@@ -224,6 +225,30 @@ COST_HOST = 1                           # RZ_COST_HOST
 SIZEOF_PIXEL_COST, SIZEOF_COST_PARAMS, SIZEOF_COST_VIEW_PARAMS, SIZEOF_COST_STATS = 28, 29, 30, 31    # their rz_sizeof indices
 
 
+class CoverageParams(C.Structure):
+    """rz_coverage_params of include/rayzen_hip.h (32 B)."""
+    _fields_ = [("x0", C.c_int32), ("y0", C.c_int32), ("x1", C.c_int32), ("y1", C.c_int32), ("reserved", C.c_int32 * 4)]
+
+
+class InstanceCoverage(C.Structure):
+    """rz_instance_coverage of include/rayzen_hip.h (32 B)."""
+    _fields_ = [("pixels", C.c_uint32), ("x_min", C.c_int32), ("y_min", C.c_int32), ("x_max", C.c_int32), ("y_max", C.c_int32),
+                ("t_min", C.c_float), ("t_max", C.c_float), ("reserved", C.c_uint32)]
+
+
+class OutlineParams(C.Structure):
+    """rz_outline_params of include/rayzen_hip.h (32 B)."""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("radius", C.c_int32), ("color", C.c_float * 3), ("alpha", C.c_float),
+                ("reserved", C.c_int32)]
+
+
+# rz_instance_coverage as a numpy record
+INSTANCE_COVERAGE_DTYPE = np.dtype([("pixels", "<u4"), ("x_min", "<i4"), ("y_min", "<i4"), ("x_max", "<i4"), ("y_max", "<i4"),
+                                    ("t_min", "<f4"), ("t_max", "<f4"), ("reserved", "<u4")])
+COVERAGE_HOST = OUTLINE_HOST = 1        # RZ_COVERAGE_HOST, RZ_OUTLINE_HOST
+SIZEOF_COVERAGE_PARAMS, SIZEOF_INSTANCE_COVERAGE, SIZEOF_OUTLINE_PARAMS = 33, 34, 35      # their rz_sizeof indices
+
+
 class SkinTriangle(C.Structure):
     """rz_skin_triangle of include/rayzen_hip.h (64 B)."""
     _fields_ = [("bones", C.c_uint32 * 3), ("pad", C.c_uint32), ("weights", (C.c_float * 4) * 3)]
@@ -351,7 +376,9 @@ def hip():
                                 ("rz_present_antialiased_seethrough", i, [vp, C.POINTER(PresentParams), vp, vp, vp, i, vp, vp, sz, vp, sz]),
                                 ("rz_render_cost", i, [vp, vp, vp, sz, C.POINTER(Counters), C.c_uint]),
                                 ("rz_cost_view", i, [vp, vp, vp, sz, vp, sz, vp, C.c_uint]),
-                                ("rz_present_cost", i, [vp, C.POINTER(PresentParams), vp, vp, sz, vp, sz])):
+                                ("rz_present_cost", i, [vp, C.POINTER(PresentParams), vp, vp, sz, vp, sz]),
+                                ("rz_coverage", i, [vp, C.POINTER(FrameParams), vp, vp, sz, vp, sz, C.c_uint]),
+                                ("rz_outline", i, [vp, vp, vp, sz, vp, sz, vp, sz, vp, sz, C.c_uint])):
             try:
                 fn = getattr(L, name)
                 fn.restype, fn.argtypes = res, args

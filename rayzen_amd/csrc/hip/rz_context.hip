@@ -221,6 +221,11 @@ struct rz_ctx {
     DevBuf dCost, dCostCounters, dCostPartials, dCostStats, dCostOut;
     bool costValid = false;
     int costW = 0, costH = 0, costSpp = 0;
+    // rz_coverage (rz_coverage.hip): the private sets of records its workgroups merge into, and the layout (sets, stride in
+    // bytes, records per set) at which they are all empty -- rz_coverage_merge leaves them so; 0 sets: not known to be
+    DevBuf dCovSets;
+    long long covSets = 0;
+    size_t covStride = 0, covCount = 0;
 };
 
 namespace {
@@ -1192,6 +1197,9 @@ size_t rz_sizeof(int which) {
         case 29: return sizeof(rz_cost_params);
         case 30: return sizeof(rz_cost_view_params);
         case 31: return sizeof(rz_cost_stats);
+        case 33: return sizeof(rz_coverage_params);      // (32 stays unassigned: probed as an unknown index)
+        case 34: return sizeof(rz_instance_coverage);
+        case 35: return sizeof(rz_outline_params);
         default: return 0;
     }
 }
@@ -1238,7 +1246,7 @@ void rz_destroy(rz_ctx* c) {
                       &c->dTmpInst[0], &c->dTmpInst[1], &c->dTmpSame, &c->dDisplay, &c->dSkinOut, &c->dSkinBones, &c->dSkinWeights,
                       &c->dQualViews, &c->dQualPartials, &c->dQualCost, &c->dUpGuideLo, &c->dUpGuideHi, &c->dUpOut,
                       &c->dStGuideLo, &c->dStGuideHi, &c->dAasList, &c->dAasCounts,
-                      &c->dCost, &c->dCostCounters, &c->dCostPartials, &c->dCostStats, &c->dCostOut})
+                      &c->dCost, &c->dCostCounters, &c->dCostPartials, &c->dCostStats, &c->dCostOut, &c->dCovSets})
         b->release();
     for (auto& kv : c->rigs) kv.second.release();
     for (hipEvent_t e : c->evSkin) if (e) (void)hipEventDestroy(e);
@@ -3003,6 +3011,167 @@ static int present_cost_impl(rz_ctx* c, const rz_present_params* pp, const rz_co
     return present_impl(c, pp, rgba8, rgba8_bytes, rgb32f, rgb32f_bytes, out4);
 }
 
+// rz_coverage (rz_coverage.hip).  Like rz_render_editor it reads the device scene as finalize left it and, of the frame, only what
+// the call is given (width, height, inv_view, inv_proj, cam_pos); it touches no render state and not the frame of rz_set_frame.
+static int coverage_impl(rz_ctx* c, const rz_frame_params* f, const rz_coverage_params* pp, rz_instance_coverage* coverage,
+                         size_t coverage_bytes, int32_t* ids, size_t ids_bytes, unsigned flags) {
+    const char* what = "rz_coverage";
+    if (!c) return fail(nullptr, RZ_ERR_INVALID_ARG, "%s: null context", what);
+    if (!f) return fail(c, RZ_ERR_INVALID_ARG, "%s: null frame", what);
+    if (flags & ~RZ_COVERAGE_HOST) return fail(c, RZ_ERR_INVALID_ARG, "%s: unknown flags 0x%x", what, flags);
+    if (f->width <= 0 || f->height <= 0) return fail(c, RZ_ERR_INVALID_ARG, "%s: bad size %dx%d", what, f->width, f->height);
+    const size_t np = (size_t)f->width * (size_t)f->height;
+    if (np > (size_t)std::numeric_limits<int32_t>::max())
+        return fail(c, RZ_ERR_INVALID_ARG, "%s: %zu pixels, at most %d per frame", what, np, std::numeric_limits<int32_t>::max());
+    if (pp) {
+        if (pp->x1 < pp->x0 || pp->y1 < pp->y0)
+            return fail(c, RZ_ERR_INVALID_ARG, "%s: rectangle [%d, %d) x [%d, %d)", what, pp->x0, pp->x1, pp->y0, pp->y1);
+        for (int r : pp->reserved) if (r) return fail(c, RZ_ERR_INVALID_ARG, "%s: reserved words must be 0", what);
+    }
+    if (!coverage && !ids) return fail(c, RZ_ERR_INVALID_ARG, "%s: neither coverage nor ids given", what);
+    const bool host = (flags & RZ_COVERAGE_HOST) != 0;
+    if (!host && ((reinterpret_cast<uintptr_t>(coverage) & 15u) || (reinterpret_cast<uintptr_t>(ids) & 3u)))
+        return fail(c, RZ_ERR_INVALID_ARG, "%s: device pointers must be 16-byte (coverage) or 4-byte (ids) aligned", what);
+    int rc = scene_ready(c, what, false);
+    if (rc != RZ_OK) return rc;
+    const size_t nInst = hostCount<rz_bvh_instance>(c, RZ_BIND_INSTANCES);
+    const size_t bCov = (nInst + 1) * sizeof(rz_instance_coverage), bIds = np * sizeof(int32_t);
+    if (coverage && coverage_bytes < bCov)
+        return fail(c, RZ_ERR_BUFFER_SIZE, "%s: coverage needs %zu bytes (%zu instances and the misses), got %zu", what, bCov, nInst, coverage_bytes);
+    if (ids && ids_bytes < bIds) return fail(c, RZ_ERR_BUFFER_SIZE, "%s: ids needs %zu bytes, got %zu", what, bIds, ids_bytes);
+    CoverageLaunch V{};
+    V.x0 = pp ? std::max(pp->x0, 0) : 0;
+    V.y0 = pp ? std::max(pp->y0, 0) : 0;
+    V.x1 = pp ? std::min(pp->x1, f->width) : f->width;
+    V.y1 = pp ? std::min(pp->y1, f->height) : f->height;
+    const bool empty = V.x0 >= V.x1 || V.y0 >= V.y1;
+    if (empty && !coverage) return RZ_OK;               // no pixel to write an id for
+    // host outputs are staged through dRayOut: coverage, then the id image (of which only the rectangle travels back)
+    HostStage stage(c, host);
+    const int sCov = stage.add(coverage, bCov), sIds = stage.add(empty ? nullptr : ids, bIds);
+    rc = stage.place();
+    if (rc != RZ_OK) return rc;
+    unsigned* out = stage.dev<unsigned>(sCov);
+    V.ids = stage.dev<int32_t>(sIds);
+    if (!empty) {
+        rc = finalize(c);
+        if (rc == RZ_OK) rc = ensure_group_counter(c);      // (only its backstop word)
+        if (rc != RZ_OK) return rc;
+    }
+    KParams K{};
+    if (!empty) {
+        camera_kparams(c, K, f->width, f->height, f->inv_view, f->inv_proj, f->cam_pos);
+        V.unitsX = (V.x1 - V.x0 + 63) / 64;
+        V.units = (long long)V.unitsX * (V.y1 - V.y0);
+        V.grid = rays_grid(V.units * 64);
+        if (const char* e = std::getenv("RZ_COVERAGE_GRID")) V.grid = std::max<long long>(1, std::min<long long>(V.grid, std::atoi(e)));   // test aid: several runs per wave on a small frame; same bytes
+        V.nInst = (int)nInst;
+        V.errWord = backstop_word(c);
+        V.tableCap = 64;
+        if (const char* e = std::getenv("RZ_COVERAGE_TABLE")) V.tableCap = std::max(1, std::min(64, std::atoi(e)));    // test aid: same bytes
+        rc = size_blas_stack(c, K, 0, RZ_RAYS_WAVES_PER_CU, V.grid, c->dRayOvf);
+        if (rc != RZ_OK) return rc;
+    }
+    if (out) {
+        // the private sets: one per workgroup up to RZ_COVERAGE_SETS, 256 bytes apart at least, RZ_COVERAGE_SCRATCH at most
+        const size_t stride = (bCov + 255) & ~size_t(255);
+        const long long fit = std::max<long long>(1, (long long)(RZ_COVERAGE_SCRATCH / stride));
+        long long sets = empty ? 1 : std::min<long long>({V.grid, RZ_COVERAGE_SETS, fit});
+        if (const char* e = std::getenv("RZ_COVERAGE_SETS"))                    // A/B aid, same bytes: within the grid and the scratch too
+            sets = empty ? 1 : std::max<long long>(1, std::min<long long>({V.grid, fit, std::atoi(e)}));
+        const bool clean = c->dCovSets.p && c->covSets == sets && c->covStride == stride && c->covCount == nInst + 1;
+        rc = ensure(c, c->dCovSets, (size_t)sets * stride);
+        if (rc != RZ_OK) return rc;
+        V.records = static_cast<unsigned*>(c->dCovSets.p);
+        V.copies = (int)sets;
+        V.strideWords = (int)(stride / 4);
+        c->covSets = 0;                     // (until the merge below is queued)
+        if (!clean) {
+            launch_coverage_init(V.records, V.copies, V.strideWords, (int)nInst + 1, c->stream);
+            RZ_HIP(c, hipGetLastError());
+        }
+    }
+    if (!empty) {
+        launch_coverage(K, V, c->stream);
+        RZ_HIP(c, hipGetLastError());
+    }
+    if (out) {
+        launch_coverage_merge(V.records, V.copies, V.strideWords, out, (int)nInst + 1, c->stream);
+        RZ_HIP(c, hipGetLastError());
+        c->covSets = V.copies; c->covStride = (size_t)V.strideWords * 4; c->covCount = nInst + 1;
+    }
+    if (!host) return RZ_OK;
+    if (coverage) RZ_HIP(c, hipMemcpyAsync(coverage, out, bCov, hipMemcpyDeviceToHost, c->stream));
+    if (V.ids) {
+        const size_t pitch = (size_t)f->width * sizeof(int32_t), first = (size_t)V.y0 * f->width + V.x0;
+        RZ_HIP(c, hipMemcpy2DAsync(ids + first, pitch, V.ids + first, pitch, (size_t)(V.x1 - V.x0) * sizeof(int32_t), (size_t)(V.y1 - V.y0),
+                                   hipMemcpyDeviceToHost, c->stream));
+    }
+    RZ_HIP(c, hipStreamSynchronize(c->stream));
+    return empty ? RZ_OK : report_backstop(c, what, "records and ids may be wrong");
+}
+
+// rz_outline (rz_outline.hip): no scene, no frame; the images are blended in place.
+static int outline_impl(rz_ctx* c, const rz_outline_params* P, const int32_t* ids, size_t ids_bytes, const uint32_t* selected,
+                        size_t n_instances, uint8_t* rgba8, size_t rgba8_bytes, float* rgb32f, size_t rgb32f_bytes, unsigned flags) {
+    const char* what = "rz_outline";
+    if (!c) return fail(nullptr, RZ_ERR_INVALID_ARG, "%s: null context", what);
+    if (!P) return fail(c, RZ_ERR_INVALID_ARG, "%s: null params", what);
+    if (flags & ~RZ_OUTLINE_HOST) return fail(c, RZ_ERR_INVALID_ARG, "%s: unknown flags 0x%x", what, flags);
+    if (P->width <= 0 || P->height <= 0) return fail(c, RZ_ERR_INVALID_ARG, "%s: bad size %dx%d", what, P->width, P->height);
+    const size_t np = (size_t)P->width * (size_t)P->height;
+    if (np > (size_t)std::numeric_limits<int32_t>::max())
+        return fail(c, RZ_ERR_INVALID_ARG, "%s: %zu pixels, at most %d per image", what, np, std::numeric_limits<int32_t>::max());
+    if (P->radius < 1 || P->radius > RZ_OUTLINE_MAX_RADIUS)
+        return fail(c, RZ_ERR_INVALID_ARG, "%s: radius %d outside 1..%d", what, P->radius, RZ_OUTLINE_MAX_RADIUS);
+    for (float v : P->color)
+        if (!(std::fabs(v) < INFINITY)) return fail(c, RZ_ERR_INVALID_ARG, "%s: color (%g, %g, %g) is not finite", what, (double)P->color[0], (double)P->color[1], (double)P->color[2]);
+    if (!(P->alpha >= 0.0f && P->alpha <= 1.0f)) return fail(c, RZ_ERR_INVALID_ARG, "%s: alpha %g outside [0, 1]", what, (double)P->alpha);
+    if (P->reserved) return fail(c, RZ_ERR_INVALID_ARG, "%s: reserved words must be 0", what);
+    // an id is an int32: no word past the one that holds bit 2^31 - 1 can be asked for
+    const size_t nSel = std::min<size_t>(n_instances, (size_t)1 << 31), bSel = (nSel + 31) / 32 * sizeof(uint32_t);
+    if (!ids) return fail(c, RZ_ERR_INVALID_ARG, "%s: null ids", what);
+    if (!selected && nSel) return fail(c, RZ_ERR_INVALID_ARG, "%s: null selected", what);
+    if (!rgba8 && !rgb32f) return fail(c, RZ_ERR_INVALID_ARG, "%s: neither rgba8 nor rgb32f given", what);
+    const bool host = (flags & RZ_OUTLINE_HOST) != 0;
+    if (!host && ((reinterpret_cast<uintptr_t>(ids) | reinterpret_cast<uintptr_t>(selected) | reinterpret_cast<uintptr_t>(rgba8) |
+                   reinterpret_cast<uintptr_t>(rgb32f)) & 3u))
+        return fail(c, RZ_ERR_INVALID_ARG, "%s: device pointers must be 4-byte aligned", what);
+    const size_t bIds = np * sizeof(int32_t), bRgba = np * 4, bRgb = np * 3 * sizeof(float);
+    if (ids_bytes < bIds) return fail(c, RZ_ERR_BUFFER_SIZE, "%s: ids needs %zu bytes, got %zu", what, bIds, ids_bytes);
+    if (rgba8 && rgba8_bytes < bRgba) return fail(c, RZ_ERR_BUFFER_SIZE, "%s: rgba8 needs %zu bytes, got %zu", what, bRgba, rgba8_bytes);
+    if (rgb32f && rgb32f_bytes < bRgb) return fail(c, RZ_ERR_BUFFER_SIZE, "%s: rgb32f needs %zu bytes, got %zu", what, bRgb, rgb32f_bytes);
+    OutlineLaunch O{};
+    O.ids = ids;
+    O.selected = selected;
+    O.nInstances = nSel;
+    O.width = P->width; O.height = P->height; O.radius = P->radius;
+    std::memcpy(O.color, P->color, sizeof O.color);
+    O.alpha = P->alpha;
+    // host buffers: the ids, then the bit set in dRayIn; the images in dRayOut, copied in, blended there and copied back
+    HostStage stage(c, host);
+    const int sRgba = stage.add(rgba8, bRgba), sRgb = stage.add(rgb32f, bRgb);
+    int rc = stage.place();
+    if (rc != RZ_OK) return rc;
+    O.rgba8 = stage.dev<uchar4>(sRgba);
+    O.rgb = stage.dev<float>(sRgb);
+    if (host) {
+        const size_t offSel = (bIds + 15) & ~size_t(15);
+        rc = ensure(c, c->dRayIn, offSel + bSel);
+        if (rc != RZ_OK) return rc;
+        char* in = static_cast<char*>(c->dRayIn.p);
+        RZ_HIP(c, hipMemcpyAsync(in, ids, bIds, hipMemcpyHostToDevice, c->stream));
+        if (bSel) RZ_HIP(c, hipMemcpyAsync(in + offSel, selected, bSel, hipMemcpyHostToDevice, c->stream));
+        if (rgba8) RZ_HIP(c, hipMemcpyAsync(O.rgba8, rgba8, bRgba, hipMemcpyHostToDevice, c->stream));
+        if (rgb32f) RZ_HIP(c, hipMemcpyAsync(O.rgb, rgb32f, bRgb, hipMemcpyHostToDevice, c->stream));
+        O.ids = reinterpret_cast<const int32_t*>(in);
+        O.selected = reinterpret_cast<const uint32_t*>(in + offSel);
+    }
+    launch_outline(O, c->stream);
+    RZ_HIP(c, hipGetLastError());
+    return host ? stage.fetch() : RZ_OK;
+}
+
 // rz_denoise_temporal / rz_present_temporal (rz_temporal.hip).  They read what rz_denoise reads and touch no render state; the
 // history they keep is the context's own (rz_ctx: dTmp*).
 static const rz_temporal_params kTemporalDefaults = {0.2f, 0.2f, 32, 0.9f, 2.0f, 5, 0.5f, 128.0f, 1.0f, 1, {0, 0, 0, 0, 0, 0}};
@@ -4004,6 +4173,16 @@ int rz_cost_view(rz_ctx* c, const rz_cost_view_params* params, const rz_pixel_co
 int rz_present_cost(rz_ctx* c, const rz_present_params* present, const rz_cost_view_params* params, uint8_t* rgba8, size_t rgba8_bytes,
                     float* rgb32f, size_t rgb32f_bytes) {
     return guarded(c, "rz_present_cost", [&] { return present_cost_impl(c, present, params, rgba8, rgba8_bytes, rgb32f, rgb32f_bytes); });
+}
+int rz_coverage(rz_ctx* c, const rz_frame_params* frame, const rz_coverage_params* params, rz_instance_coverage* coverage,
+                size_t coverage_bytes, int32_t* ids, size_t ids_bytes, unsigned flags) {
+    return guarded(c, "rz_coverage", [&] { return coverage_impl(c, frame, params, coverage, coverage_bytes, ids, ids_bytes, flags); });
+}
+int rz_outline(rz_ctx* c, const rz_outline_params* params, const int32_t* ids, size_t ids_bytes, const uint32_t* selected,
+               size_t n_instances, uint8_t* rgba8, size_t rgba8_bytes, float* rgb32f, size_t rgb32f_bytes, unsigned flags) {
+    return guarded(c, "rz_outline", [&] {
+        return outline_impl(c, params, ids, ids_bytes, selected, n_instances, rgba8, rgba8_bytes, rgb32f, rgb32f_bytes, flags);
+    });
 }
 int rz_display_reset(rz_ctx* c) {
     return guarded(c, "rz_display_reset", [&] { return display_reset_impl(c); });

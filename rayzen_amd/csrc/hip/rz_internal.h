@@ -347,6 +347,39 @@ int cost_reduce_blocks(long long n);
 void launch_cost_reduce(const CostReduceLaunch& R, hipStream_t stream);
 void launch_cost_view(const CostViewLaunch& V, hipStream_t stream);
 
+// ---- rz_coverage.hip
+struct CoverageLaunch {         // rz_coverage_runs (beside the KParams of camera_kparams)
+    int x0, y0, x1, y1;         // the rectangle clipped to the frame, not empty
+    int unitsX;                 // 64-pixel runs per row of the rectangle
+    long long units;            // runs
+    long long grid;             // rays_grid(units * 64)
+    int nInst;                  // instances of binding 9: the key of a miss, and the record it is counted in
+    unsigned* records;          // `copies` private sets of nInst + 1 rz_instance_coverage (8 words each), strideWords apart, all
+    int copies, strideWords;    //   empty; a workgroup sends its table to set blockIdx.x % copies; optional
+    int tableCap;               // entries of a wave's table of groups, 1..64 (64; fewer: RZ_COVERAGE_TABLE, a test aid)
+    int32_t* ids;               // width x height, optional
+    unsigned* errWord;          // the context's backstop word
+};
+constexpr size_t RZ_COVERAGE_SCRATCH = (size_t)32 << 20;        // the most the private sets may take, and
+constexpr int RZ_COVERAGE_SETS = 256;                           // the most there are (measured: profiles/coverage/README.md)
+void launch_coverage_init(unsigned* sets, int copies, int strideWords, int count, hipStream_t stream);
+void launch_coverage(const KParams& K, const CoverageLaunch& V, hipStream_t stream);
+void launch_coverage_merge(unsigned* sets, int copies, int strideWords, unsigned* out, int count, hipStream_t stream);
+
+// ---- rz_outline.hip
+constexpr int RZ_OUTLINE_MAX_RADIUS = 4;        // rz_outline_params.radius: 1..4 (the halo the kernel stages)
+struct OutlineLaunch {          // rz_outline_kernel
+    const int32_t* ids;         // width x height
+    const uint32_t* selected;   // (nInstances + 31) / 32 words
+    unsigned long long nInstances;
+    int width, height, radius;
+    int tilesX;                 // (set by launch_outline)
+    float color[3], alpha;
+    uchar4* rgba8;              // images blended in place, each optional
+    float* rgb;
+};
+void launch_outline(OutlineLaunch O, hipStream_t stream);
+
 // ---- rz_present.hip
 struct ProjBox;                // screen-space corners of one box (rz_present.hip)
 struct PresentParams {

@@ -42,6 +42,7 @@ MESH_QUALITY = np.dtype([("node_offset", "<i4"), ("index_offset", "<i4"), ("tri_
                          ("n_triangles", "<i4"), ("n_nodes", "<i4"), ("depth", "<i4"), ("flags", "<u4"), ("sah_cost", "<f8"),
                          ("sah_cost_built", "<f8"), ("sah_cost_before", "<f8"), ("reserved", "<f8")])        # rz_mesh_quality
 PIXEL_COST_DTYPE = _lib.PIXEL_COST_DTYPE # rz_pixel_cost (32 B): what render_cost returns
+INSTANCE_COVERAGE_DTYPE = _lib.INSTANCE_COVERAGE_DTYPE   # rz_instance_coverage (32 B): what coverage returns
 CHAIN_DTYPE = _lib.CHAIN_DTYPE           # rz_chain (16 B): what upscale(see_through=..., chains=True) returns
 
 
@@ -109,6 +110,7 @@ class Renderer:
         if not self._c:
             raise RayZenError("rz_create", -2, self._L.rz_last_error(None).decode())
         self.width = self.height = 0
+        self._frame = None      # a copy of the last set_frame's params: what coverage(frame=None) casts through
 
     def close(self):
         c, self._c = getattr(self, "_c", None), None
@@ -310,6 +312,7 @@ class Renderer:
     def set_frame(self, params):
         self._check(self._L.rz_set_frame(self._c, C.byref(params)), "rz_set_frame")
         self.width, self.height = params.width, params.height
+        self._frame = _lib.FrameParams.from_buffer_copy(params)
 
     def set_stream(self, hip_stream):
         self._check(self._L.rz_set_stream(self._c, C.c_void_p(hip_stream)), "rz_set_stream")
@@ -1022,6 +1025,100 @@ class Renderer:
         self._check(self._L.rz_present_cost(self._c, C.byref(p), C.byref(vp), rgba8.ctypes.data, rgba8.nbytes, rgb.ctypes.data,
                                             rgb.nbytes), "rz_present_cost")
         return rgb, rgba8
+
+    # -- selecting what is on screen (rz_coverage / rz_outline) ---------------------------
+    def _coverage_args(self, frame, rect):
+        fp = self._frame if frame is None else frame
+        if fp is None:
+            raise ValueError("coverage: no frame given and set_frame has not been called")
+        if rect is None:
+            return fp, None
+        p = _lib.CoverageParams()
+        p.x0, p.y0, p.x1, p.y1 = (int(v) for v in rect)
+        return fp, C.byref(p)
+
+    def n_instances(self):
+        """How many instances binding 9 holds: coverage returns one record more."""
+        need = C.c_size_t(0)
+        self._check(self._L.rz_read_binding(self._c, int(BIND_INSTANCES), None, 0, C.byref(need)), "rz_read_binding")
+        return need.value // BINDING_DTYPES[BIND_INSTANCES].itemsize
+
+    def coverage(self, frame=None, rect=None, want_ids=False):
+        """Which instances the screen shows, where and how near (include/rayzen_hip.h: rz_coverage), for the pixel-centre rays of
+        `frame` (frame_params(...); None: the frame of the last set_frame) inside rect = (x0, y0, x1, y1), pixels [x0, x1) x
+        [y0, y1) with row 0 = the bottom row (None: the whole frame).  Returns n + 1 INSTANCE_COVERAGE_DTYPE records -- record i
+        is instance i, the last one the misses -- and with want_ids=True also the id image (H, W) int32: the instance of every
+        pixel inside the rectangle, -1 for a miss and for the pixels outside it.  Host memory; returns when done."""
+        fp, cp = self._coverage_args(frame, rect)
+        rec = np.empty(self.n_instances() + 1, INSTANCE_COVERAGE_DTYPE)
+        ids = np.full((fp.height, fp.width), -1, np.int32) if want_ids else None
+        self._check(self._L.rz_coverage(self._c, C.byref(fp), cp, rec.ctypes.data, rec.nbytes, None if ids is None else ids.ctypes.data,
+                                        0 if ids is None else ids.nbytes, _lib.COVERAGE_HOST), "rz_coverage")
+        return (rec, ids) if want_ids else rec
+
+    def coverage_device(self, coverage_ptr=None, coverage_bytes=0, ids_ptr=None, frame=None, rect=None):
+        """rz_coverage on device memory (coverage: (n + 1) * 32 B, 16-B aligned; ids: W*H*4 B, 4-B aligned; either may be None):
+        enqueued on the context's stream, asynchronous.  Pixels of ids outside the rectangle are not written."""
+        fp, cp = self._coverage_args(frame, rect)
+        self._check(self._L.rz_coverage(self._c, C.byref(fp), cp, C.c_void_p(coverage_ptr), int(coverage_bytes) if coverage_ptr else 0,
+                                        C.c_void_p(ids_ptr), fp.width * fp.height * 4 if ids_ptr else 0, 0), "rz_coverage")
+
+    def select_rect(self, rect, min_pixels=1, frame=None):
+        """The marquee: [(instance, pixels), ...] of the instances that are the closest hit of at least min_pixels pixels of rect,
+        the most pixels first, ties by the lower index."""
+        px = self.coverage(frame, rect)["pixels"][:-1]
+        hit = np.flatnonzero(px >= max(int(min_pixels), 1))
+        order = np.lexsort((hit, -px[hit].astype(np.int64)))
+        return [(int(hit[k]), int(px[hit[k]])) for k in order]
+
+    @staticmethod
+    def selection_bits(selected, n_instances=None):
+        """rz_outline's bit set of an iterable of instance indices: (words uint32, n_instances) with bit i & 31 of word i >> 5
+        set for every i; n_instances None: the largest index + 1."""
+        sel = sorted({int(i) for i in selected})
+        if sel and sel[0] < 0:
+            raise ValueError(f"selection_bits: negative instance index {sel[0]}")
+        n = (sel[-1] + 1 if sel else 0) if n_instances is None else int(n_instances)
+        words = np.zeros((n + 31) // 32, np.uint32)
+        for i in sel:
+            if i < n:
+                words[i >> 5] |= np.uint32(1 << (i & 31))
+        return words, n
+
+    @staticmethod
+    def _outline_params(width, height, radius, color, alpha):
+        p = _lib.OutlineParams()
+        p.width, p.height, p.radius = int(width), int(height), int(radius)
+        p.color[:] = [float(v) for v in color]
+        p.alpha = float(alpha)
+        return p
+
+    def outline(self, ids, selected, rgba8=None, rgb32f=None, radius=2, color=(1.0, 0.6, 0.0), alpha=1.0):
+        """Marks the instances of `selected` (an iterable of instance indices) on an image (rz_outline): the pixels within
+        `radius` of a selected pixel of ids ((H, W) int32: coverage's id image, or the instance field of a hit buffer) that are
+        not selected themselves are blended towards `color` by `alpha`.  rgba8 (H, W, 4) uint8 and rgb32f (H, W, 3) float32, each
+        optional, are not modified: returns (rgba8, rgb32f) as blended copies, None for the one not given.  Needs no scene."""
+        idm = np.ascontiguousarray(ids, np.int32)
+        h, w = idm.shape
+        words, n = self.selection_bits(selected)
+        out8 = None if rgba8 is None else np.array(rgba8, np.uint8, order="C").reshape(h, w, 4)
+        out32 = None if rgb32f is None else np.array(rgb32f, np.float32, order="C").reshape(h, w, 3)
+        p = self._outline_params(w, h, radius, color, alpha)
+        self._check(self._L.rz_outline(self._c, C.byref(p), idm.ctypes.data, idm.nbytes, words.ctypes.data if n else None, n,
+                                       None if out8 is None else out8.ctypes.data, 0 if out8 is None else out8.nbytes,
+                                       None if out32 is None else out32.ctypes.data, 0 if out32 is None else out32.nbytes,
+                                       _lib.OUTLINE_HOST), "rz_outline")
+        return out8, out32
+
+    def outline_device(self, width, height, ids_ptr, selected_ptr, n_instances, rgba8_ptr=None, rgb32f_ptr=None, radius=2,
+                       color=(1.0, 0.6, 0.0), alpha=1.0):
+        """rz_outline on device memory, in place (4-B aligned; ids W*H*4 B, selected (n_instances + 31) // 32 words, rgba8 W*H*4 B,
+        rgb32f W*H*12 B): enqueued on the context's stream, asynchronous."""
+        p = self._outline_params(width, height, radius, color, alpha)
+        n = int(width) * int(height)
+        self._check(self._L.rz_outline(self._c, C.byref(p), C.c_void_p(ids_ptr), n * 4, C.c_void_p(selected_ptr), int(n_instances),
+                                       C.c_void_p(rgba8_ptr), n * 4 if rgba8_ptr else 0, C.c_void_p(rgb32f_ptr),
+                                       n * 12 if rgb32f_ptr else 0, 0), "rz_outline")
 
     # -- convenience -----------------------------------------------------------
     def render_scene(self, scene, width, height, spp, bounce_budget, num_lights=None, tile_rank=0, tile_nranks=1,
