@@ -1264,6 +1264,55 @@ int rz_coverage(rz_ctx* ctx, const rz_frame_params* frame, const rz_coverage_par
 int rz_outline(rz_ctx* ctx, const rz_outline_params* params, const int32_t* ids, size_t ids_bytes, const uint32_t* selected,
                size_t n_instances, uint8_t* rgba8, size_t rgba8_bytes, float* rgb32f, size_t rgb32f_bytes, unsigned flags);
 
+/* ------------------------------------------------------------------------ */
+/* Ambient occlusion for previews (new)                                     */
+/* ------------------------------------------------------------------------ */
+/* rz_ambient_occlusion gives the ray-cast viewport contact and depth: distance-limited ambient occlusion, N short visibility
+ * walks per hit pixel over an interleaved 4 x 4 pattern of directions and an edge-aware 4 x 4 gather (rz_ao.hip).  All arithmetic
+ * is binary32 with one rounding per operation, no fused multiply-add; `/` and sqrt are correctly rounded.
+ * Direction table.  For candidates k = 1, 2, ...: a = (k * 3242174889u) >> 8, b = (k * 2447445414u) >> 8 (uint32, wrapping);
+ * x1 = (float)a * 2^-23 - 1, x2 = (float)b * 2^-23 - 1; S = x1*x1 + x2*x2.  The candidate is accepted iff S < 1; the j-th accepted
+ * candidate, j = 0..255, gives P_j = ((2*x1)*q, (2*x2)*q, 1 - 2*S) with q = sqrt(1 - S): Marsaglia's sphere point from an R2
+ * lattice, no trigonometry.  321 candidates yield the 256 points.  The library builds the table once on the host;
+ * rz_ao_directions copies its 256 x 3 floats to `out` and needs no GPU (RZ_ERR_INVALID_ARG: null out; RZ_ERR_BUFFER_SIZE).
+ * Per pixel (X, Y), row 0 = the bottom row.  The guide is the closest hit of the pixel-centre ray from cam_pos, unclipped: the ray
+ * and the record of rz_denoise's guide.  A miss gives raw = ao = 1.  For a hit with point x, unit normal n and ray direction d:
+ * n_f = (n.x*d.x + n.y*d.y) + n.z*d.z > 0 ? -n : n;  o = x + n_f * 0.001f per component;  c = (X & 3) + 4 * (Y & 3).  For sample
+ * i = 0..N-1: v = n_f + P[16*i + c], L2 = (v.x*v.x + v.y*v.y) + v.z*v.z.  If !(L2 >= 1e-6f), a_i = 1 and nothing is walked;
+ * otherwise v = v / sqrt(L2) and a_i is rz_shadow_rays' answer for the ray (o, v, max_dist = radius): lit ? visibility : 0.
+ * Glass attenuates, it does not block.  raw_p = tree(a) * (1.0f / N), tree the pairwise sum s[i] = s[2i] + s[2i+1] applied level
+ * by level.  The walk is the shader's: it finds the closest hit in the whole scene and only then compares its distance with radius.
+ * Smoothing (smooth = 1).  For a hit p the taps are q = (X + a, Y + b), b = -2..1 the outer loop and a = -2..1 the inner: the
+ * window holds each of the 16 patterns once.  A tap counts iff q is inside the image, q is a hit and, for (a, b) != (0, 0),
+ * dot(n_p, n_q) >= normal_cos and |dot(n_p, x_q - x_p)| <= ((plane_tol * t_p) * f) * max(|a|, |b|), with n, x, t the guide's
+ * normal, point and distance, f = 2 |inv_proj[5]| / height evaluated in binary64 and rounded to binary32, dots and sums left to
+ * right.  ao_p = (the sum of raw_q over the counted taps, in loop order) / (float)count.  With smooth = 0, ao_p = raw_p.
+ * Outputs, each optional, at least one: ao, width*height floats; rgb32f, rgb_in * m per channel with m = 1.0f - strength *
+ * (1.0f - ao_p), a NULL rgb_in standing for (1, 1, 1); rgba8, rz_present's quantisation of that colour, rint(clamp(c, 0, 1) *
+ * 255), alpha 255.
+ * Conventions are rz_coverage's.  `frame` is read for width, height, inv_view, inv_proj and cam_pos; no rz_set_frame is needed
+ * and the tile fields are ignored.  Pointers are DEVICE memory (4-byte aligned), the work is queued on the context's stream and a
+ * walk cut at its backstop is left to rz_sync; with RZ_AO_HOST they are host memory, staged, the call returns when the outputs
+ * are written and reports a cut walk itself as RZ_ERR_INTERNAL.  A failing call launches nothing and leaves its outputs
+ * untouched.  No render, temporal or display state is touched (the guide goes to the scratch rz_denoise casts its own into).
+ * Errors.  RZ_ERR_INVALID_ARG: null context or frame; unknown flags; a bad frame size; samples not 1, 2, 4, 8 or 16; radius or
+ * plane_tol not finite and > 0; smooth not 0 or 1; strength outside [0, 1]; normal_cos outside [-1, 1]; a non-zero reserved
+ * word; no output given; a misaligned device pointer.  RZ_ERR_NOT_READY: no scene, or no materials.  RZ_ERR_BUFFER_SIZE: any
+ * buffer too small.  Cost: profiles/ao/README.md.  (Additive: RZ_ABI_VERSION stays 5; rz_sizeof(36) stays 0.) */
+typedef struct rz_ao_params {            /* NULL = defaults; 32 B; rz_sizeof(37) */
+    int32_t samples;                     /* N: 1, 2, 4, 8, 16; default 4 */
+    float   radius;                      /* world units, finite, > 0; default 1 */
+    int32_t smooth;                      /* 0 / 1; default 1 */
+    float   strength;                    /* 0..1; default 1 */
+    float   normal_cos, plane_tol;       /* tap validity; defaults 0.9 and 2 */
+    int32_t reserved[2];                 /* must be 0 */
+} rz_ao_params;
+#define RZ_AO_HOST 1u                    /* pointers are host memory, as RZ_DENOISE_HOST */
+int rz_ambient_occlusion(rz_ctx* ctx, const rz_frame_params* frame, const rz_ao_params* params, const float* rgb_in,
+                         size_t rgb_in_bytes, float* ao, size_t ao_bytes, float* rgb32f, size_t rgb32f_bytes, uint8_t* rgba8,
+                         size_t rgba8_bytes, unsigned flags);
+int rz_ao_directions(float* out, size_t bytes);
+
 /* Number of HIP devices visible to the process (0 without a GPU). */
 int rz_device_count(void);
 
@@ -1289,7 +1338,7 @@ const char* rz_source_hash(void);
  * 9 visibility, 10 editor_params, 11 denoise_params, 12 temporal_params,
  * 14 display_params, 15 display_info, 17 skin_triangle, 18 morph_triangle, 20 mesh_quality,
  * 21 upscale_params, 23 seethrough_params, 24 chain, 26 antialias_params, 28 pixel_cost, 29 cost_params, 30 cost_view_params,
- * 31 cost_stats, 33 coverage_params, 34 instance_coverage, 35 outline_params (13, 16, 19, 22, 25, 27 and 32 are unassigned and
+ * 31 cost_stats, 33 coverage_params, 34 instance_coverage, 35 outline_params, 37 ao_params (13, 16, 19, 22, 25, 27, 32 and 36 are unassigned and
  * return 0, as every unknown index does). */
 size_t rz_sizeof(int which);
 

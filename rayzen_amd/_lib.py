@@ -32,6 +32,7 @@ HIP_SYMBOLS = (
     "rz_antialias", "rz_present_antialiased", "rz_antialias_seethrough", "rz_present_antialiased_seethrough",
     "rz_render_cost", "rz_cost_view", "rz_present_cost",
     "rz_coverage", "rz_outline",
+    "rz_ambient_occlusion", "rz_ao_directions",
 )
 ABI_VERSION = 5         # RZ_ABI_VERSION of the include/rayzen_hip.h this file mirrors
 # the symbols include/rayzen_host.h declares
@@ -249,6 +250,17 @@ COVERAGE_HOST = OUTLINE_HOST = 1        # RZ_COVERAGE_HOST, RZ_OUTLINE_HOST
 SIZEOF_COVERAGE_PARAMS, SIZEOF_INSTANCE_COVERAGE, SIZEOF_OUTLINE_PARAMS = 33, 34, 35      # their rz_sizeof indices
 
 
+class AoParams(C.Structure):
+    """rz_ao_params of include/rayzen_hip.h (32 B)."""
+    _fields_ = [("samples", C.c_int32), ("radius", C.c_float), ("smooth", C.c_int32), ("strength", C.c_float),
+                ("normal_cos", C.c_float), ("plane_tol", C.c_float), ("reserved", C.c_int32 * 2)]
+
+
+AO_HOST = 1                             # RZ_AO_HOST
+AO_DIRECTIONS = 256                     # points of rz_ao_directions' table
+SIZEOF_AO_PARAMS = 37                   # its rz_sizeof index (36 is unassigned)
+
+
 class SkinTriangle(C.Structure):
     """rz_skin_triangle of include/rayzen_hip.h (64 B)."""
     _fields_ = [("bones", C.c_uint32 * 3), ("pad", C.c_uint32), ("weights", (C.c_float * 4) * 3)]
@@ -378,7 +390,9 @@ def hip():
                                 ("rz_cost_view", i, [vp, vp, vp, sz, vp, sz, vp, C.c_uint]),
                                 ("rz_present_cost", i, [vp, C.POINTER(PresentParams), vp, vp, sz, vp, sz]),
                                 ("rz_coverage", i, [vp, C.POINTER(FrameParams), vp, vp, sz, vp, sz, C.c_uint]),
-                                ("rz_outline", i, [vp, vp, vp, sz, vp, sz, vp, sz, vp, sz, C.c_uint])):
+                                ("rz_outline", i, [vp, vp, vp, sz, vp, sz, vp, sz, vp, sz, C.c_uint]),
+                                ("rz_ambient_occlusion", i, [vp, C.POINTER(FrameParams), vp, vp, sz, vp, sz, vp, sz, vp, sz, C.c_uint]),
+                                ("rz_ao_directions", i, [vp, sz])):
             try:
                 fn = getattr(L, name)
                 fn.restype, fn.argtypes = res, args

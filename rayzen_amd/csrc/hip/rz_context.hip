@@ -226,6 +226,10 @@ struct rz_ctx {
     DevBuf dCovSets;
     long long covSets = 0;
     size_t covStride = 0, covCount = 0;
+    // rz_ambient_occlusion (rz_ao.hip): the direction table (uploaded by the first call), raw_p of every pixel and the counter
+    // its waves claim tiles from (zeroed by every call); the guide it casts goes to dDnGuide, which every pass that casts one
+    // rewrites before it reads it
+    DevBuf dAoDirs, dAoRaw, dAoClaim;
 };
 
 namespace {
@@ -1200,6 +1204,7 @@ size_t rz_sizeof(int which) {
         case 33: return sizeof(rz_coverage_params);      // (32 stays unassigned: probed as an unknown index)
         case 34: return sizeof(rz_instance_coverage);
         case 35: return sizeof(rz_outline_params);
+        case 37: return sizeof(rz_ao_params);            // (36 stays unassigned: probed as an unknown index)
         default: return 0;
     }
 }
@@ -1246,7 +1251,8 @@ void rz_destroy(rz_ctx* c) {
                       &c->dTmpInst[0], &c->dTmpInst[1], &c->dTmpSame, &c->dDisplay, &c->dSkinOut, &c->dSkinBones, &c->dSkinWeights,
                       &c->dQualViews, &c->dQualPartials, &c->dQualCost, &c->dUpGuideLo, &c->dUpGuideHi, &c->dUpOut,
                       &c->dStGuideLo, &c->dStGuideHi, &c->dAasList, &c->dAasCounts,
-                      &c->dCost, &c->dCostCounters, &c->dCostPartials, &c->dCostStats, &c->dCostOut, &c->dCovSets})
+                      &c->dCost, &c->dCostCounters, &c->dCostPartials, &c->dCostStats, &c->dCostOut, &c->dCovSets,
+                      &c->dAoDirs, &c->dAoRaw, &c->dAoClaim})
         b->release();
     for (auto& kv : c->rigs) kv.second.release();
     for (hipEvent_t e : c->evSkin) if (e) (void)hipEventDestroy(e);
@@ -3111,6 +3117,128 @@ static int coverage_impl(rz_ctx* c, const rz_frame_params* f, const rz_coverage_
     return empty ? RZ_OK : report_backstop(c, what, "records and ids may be wrong");
 }
 
+// rz_ambient_occlusion (rz_ao.hip).  Like rz_coverage it reads the device scene as finalize left it and, of the frame, only what
+// the call is given (width, height, inv_view, inv_proj, cam_pos); it touches no render state and not the frame of rz_set_frame.
+static const rz_ao_params kAoDefaults = {4, 1.0f, 1, 1.0f, 0.9f, 2.0f, {0, 0}};
+
+static int ao_impl(rz_ctx* c, const rz_frame_params* f, const rz_ao_params* pp, const float* rgb_in, size_t rgb_in_bytes, float* ao,
+                   size_t ao_bytes, float* rgb32f, size_t rgb32f_bytes, uint8_t* rgba8, size_t rgba8_bytes, unsigned flags) {
+    const char* what = "rz_ambient_occlusion";
+    if (!c) return fail(nullptr, RZ_ERR_INVALID_ARG, "%s: null context", what);
+    if (!f) return fail(c, RZ_ERR_INVALID_ARG, "%s: null frame", what);
+    if (flags & ~RZ_AO_HOST) return fail(c, RZ_ERR_INVALID_ARG, "%s: unknown flags 0x%x", what, flags);
+    if (f->width <= 0 || f->height <= 0) return fail(c, RZ_ERR_INVALID_ARG, "%s: bad size %dx%d", what, f->width, f->height);
+    const size_t np = (size_t)f->width * (size_t)f->height;
+    if (np > (size_t)std::numeric_limits<int32_t>::max())
+        return fail(c, RZ_ERR_INVALID_ARG, "%s: %zu pixels, at most %d per frame", what, np, std::numeric_limits<int32_t>::max());
+    const rz_ao_params& P = pp ? *pp : kAoDefaults;
+    int log2n = 0;
+    while ((1 << log2n) < P.samples && log2n < 4) ++log2n;
+    if (P.samples != (1 << log2n)) return fail(c, RZ_ERR_INVALID_ARG, "%s: samples %d (1, 2, 4, 8 or 16)", what, P.samples);
+    if (!(P.radius > 0.0f && P.radius < INFINITY)) return fail(c, RZ_ERR_INVALID_ARG, "%s: radius %g (finite, > 0)", what, (double)P.radius);
+    if (P.smooth != 0 && P.smooth != 1) return fail(c, RZ_ERR_INVALID_ARG, "%s: smooth %d (0 or 1)", what, P.smooth);
+    if (!(P.strength >= 0.0f && P.strength <= 1.0f)) return fail(c, RZ_ERR_INVALID_ARG, "%s: strength %g outside [0, 1]", what, (double)P.strength);
+    if (!(P.normal_cos >= -1.0f && P.normal_cos <= 1.0f)) return fail(c, RZ_ERR_INVALID_ARG, "%s: normal_cos %g outside [-1, 1]", what, (double)P.normal_cos);
+    if (!(P.plane_tol > 0.0f && P.plane_tol < INFINITY)) return fail(c, RZ_ERR_INVALID_ARG, "%s: plane_tol %g (finite, > 0)", what, (double)P.plane_tol);
+    if (P.reserved[0] || P.reserved[1]) return fail(c, RZ_ERR_INVALID_ARG, "%s: reserved words must be 0", what);
+    if (!ao && !rgb32f && !rgba8) return fail(c, RZ_ERR_INVALID_ARG, "%s: none of ao, rgb32f and rgba8 given", what);
+    const bool host = (flags & RZ_AO_HOST) != 0;
+    if (!host && ((reinterpret_cast<uintptr_t>(rgb_in) | reinterpret_cast<uintptr_t>(ao) | reinterpret_cast<uintptr_t>(rgb32f) |
+                   reinterpret_cast<uintptr_t>(rgba8)) & 3u))
+        return fail(c, RZ_ERR_INVALID_ARG, "%s: device pointers must be 4-byte aligned", what);
+    int rc = scene_ready(c, what, true);
+    if (rc != RZ_OK) return rc;
+    const size_t bAo = np * sizeof(float), bRgb = np * 3 * sizeof(float), bRgba = np * 4;
+    if (rgb_in && rgb_in_bytes < bRgb) return fail(c, RZ_ERR_BUFFER_SIZE, "%s: rgb_in needs %zu bytes, got %zu", what, bRgb, rgb_in_bytes);
+    if (ao && ao_bytes < bAo) return fail(c, RZ_ERR_BUFFER_SIZE, "%s: ao needs %zu bytes, got %zu", what, bAo, ao_bytes);
+    if (rgb32f && rgb32f_bytes < bRgb) return fail(c, RZ_ERR_BUFFER_SIZE, "%s: rgb32f needs %zu bytes, got %zu", what, bRgb, rgb32f_bytes);
+    if (rgba8 && rgba8_bytes < bRgba) return fail(c, RZ_ERR_BUFFER_SIZE, "%s: rgba8 needs %zu bytes, got %zu", what, bRgba, rgba8_bytes);
+    // host buffers are staged as rz_denoise stages them: the input in dRayIn; ao, then rgb32f, then rgba8 in dRayOut
+    HostStage stage(c, host);
+    const int sAo = stage.add(ao, bAo), sRgb = stage.add(rgb32f, bRgb), sRgba = stage.add(rgba8, bRgba);
+    const float* in = rgb_in;
+    rc = stage.input(rgb_in, bRgb, in);
+    if (rc == RZ_OK) rc = stage.place();
+    if (rc == RZ_OK) rc = finalize(c);
+    if (rc == RZ_OK) rc = cast_ready(c);
+    if (rc == RZ_OK) rc = ensure(c, c->dDnGuide, np * 32);
+    if (rc == RZ_OK) rc = ensure(c, c->dAoClaim, (size_t)RZ_AO_COUNTERS * 128);
+    if (rc != RZ_OK) return rc;
+    float* aoDev = stage.dev<float>(sAo);
+    const bool smooth = P.smooth != 0;
+    // without smoothing ao_p is raw_p: the walks write the caller's image, and nothing is left to resolve unless a colour is asked
+    float* raw = (!smooth && aoDev) ? aoDev : nullptr;
+    if (!raw) {
+        rc = ensure(c, c->dAoRaw, bAo);
+        if (rc != RZ_OK) return rc;
+        raw = static_cast<float*>(c->dAoRaw.p);
+    }
+    if (!c->dAoDirs.p) {
+        rc = upload_vec(c, c->dAoDirs, ao_direction_table(), RZ_AO_DIRS * 3 * sizeof(float));       // (static storage: it outlives the copy)
+        if (rc != RZ_OK) return rc;
+    }
+    // the guide cast: rz_denoise's kernel through this call's camera, a wave per 64-pixel run of a row
+    KParams KG{};
+    camera_kparams(c, KG, f->width, f->height, f->inv_view, f->inv_proj, f->cam_pos);
+    DenoiseGuideLaunch G{};
+    G.unitsX = (f->width + 63) / 64;
+    G.units = (long long)G.unitsX * f->height;
+    G.grid = rays_grid(G.units * 64);
+    G.instTriOff = static_cast<const int32_t*>(c->dRayInstOff.p);
+    G.errWord = backstop_word(c);
+    G.guide = static_cast<float4*>(c->dDnGuide.p);
+    // the walks: a wave per 8 x 8 tile, its records beside the BLAS stack
+    KParams KW = KG;
+    AoWalkLaunch A{};
+    A.guide = G.guide;
+    A.dirs = static_cast<const float*>(c->dAoDirs.p);
+    A.raw = raw;
+    A.samples = P.samples; A.log2Samples = log2n;
+    A.radius = P.radius;
+    A.tilesX = (f->width + 7) / 8;
+    A.tiles = (long long)A.tilesX * ((f->height + 7) / 8);
+    A.grid = rays_grid(A.tiles * 64);
+    A.claim = static_cast<unsigned*>(c->dAoClaim.p);
+    // 64 sequences of trips, a counter each: measured against a sequence per wave, one counter, 16 and 256, and whole tiles as
+    // units (profiles/ao/README.md)
+    A.counters = 64;
+    A.perTrip = 1;
+    if (const char* e = std::getenv("RZ_AO_COUNTERS")) A.counters = std::max(0, std::min(RZ_AO_COUNTERS, std::atoi(e)));    // A/B aids, same bytes
+    if (const char* e = std::getenv("RZ_AO_PER_TRIP")) A.perTrip = std::atoi(e) != 0;
+    A.counters = (int)std::min<long long>(A.counters, A.grid);         // (a sequence no wave serves would never be walked)
+    A.errWord = G.errWord;
+    // (one overflow buffer serves both launches: sized for the larger need before either is queued)
+    rc = size_blas_stack(c, KW, RZ_AO_WALK_LDS, RZ_RAYS_WAVES_PER_CU, A.grid, c->dRayOvf);
+    if (rc == RZ_OK && KW.blasOvfCap > 0)
+        rc = ensure(c, c->dRayOvf, (size_t)std::max(G.grid, A.grid) * KW.blasOvfCap * 64 * sizeof(uint2));
+    if (rc == RZ_OK) rc = size_blas_stack(c, KG, 0, RZ_RAYS_WAVES_PER_CU, G.grid, c->dRayOvf);
+    if (rc != RZ_OK) return rc;
+    if (KW.blasOvfCap > 0) KW.blasOvf = static_cast<uint2*>(c->dRayOvf.p);
+    launch_denoise_guides(KG, G, c->stream);
+    RZ_HIP(c, hipGetLastError());
+    if (A.counters > 0) RZ_HIP(c, hipMemsetAsync(A.claim, 0, (size_t)A.counters * 128, c->stream));
+    launch_ao_walks(KW, A, c->stream);
+    RZ_HIP(c, hipGetLastError());
+    AoResolveLaunch R{};
+    R.raw = raw;
+    R.guide = G.guide;
+    R.rgbIn = in;
+    R.width = f->width; R.height = f->height;
+    R.strength = P.strength; R.normalCos = P.normal_cos; R.planeTol = P.plane_tol;
+    R.f = (float)(2.0 * std::fabs((double)f->inv_proj[5]) / (double)f->height);
+    R.ao = raw == aoDev ? nullptr : aoDev;
+    R.rgb = stage.dev<float>(sRgb);
+    R.rgba8 = stage.dev<uchar4>(sRgba);
+    if (R.ao || R.rgb || R.rgba8) {
+        launch_ao_resolve(R, smooth, c->stream);
+        RZ_HIP(c, hipGetLastError());
+    }
+    if (!host) return RZ_OK;
+    rc = stage.fetch();
+    if (rc != RZ_OK) return rc;
+    return report_backstop(c, what, "the occlusion may be wrong");
+}
+
 // rz_outline (rz_outline.hip): no scene, no frame; the images are blended in place.
 static int outline_impl(rz_ctx* c, const rz_outline_params* P, const int32_t* ids, size_t ids_bytes, const uint32_t* selected,
                         size_t n_instances, uint8_t* rgba8, size_t rgba8_bytes, float* rgb32f, size_t rgb32f_bytes, unsigned flags) {
@@ -4177,6 +4305,19 @@ int rz_present_cost(rz_ctx* c, const rz_present_params* present, const rz_cost_v
 int rz_coverage(rz_ctx* c, const rz_frame_params* frame, const rz_coverage_params* params, rz_instance_coverage* coverage,
                 size_t coverage_bytes, int32_t* ids, size_t ids_bytes, unsigned flags) {
     return guarded(c, "rz_coverage", [&] { return coverage_impl(c, frame, params, coverage, coverage_bytes, ids, ids_bytes, flags); });
+}
+int rz_ambient_occlusion(rz_ctx* c, const rz_frame_params* frame, const rz_ao_params* params, const float* rgb_in, size_t rgb_in_bytes,
+                         float* ao, size_t ao_bytes, float* rgb32f, size_t rgb32f_bytes, uint8_t* rgba8, size_t rgba8_bytes, unsigned flags) {
+    return guarded(c, "rz_ambient_occlusion", [&] {
+        return ao_impl(c, frame, params, rgb_in, rgb_in_bytes, ao, ao_bytes, rgb32f, rgb32f_bytes, rgba8, rgba8_bytes, flags);
+    });
+}
+int rz_ao_directions(float* out, size_t bytes) {
+    const size_t need = RZ_AO_DIRS * 3 * sizeof(float);
+    if (!out) return fail(nullptr, RZ_ERR_INVALID_ARG, "rz_ao_directions: null output");
+    if (bytes < need) return fail(nullptr, RZ_ERR_BUFFER_SIZE, "rz_ao_directions: out needs %zu bytes, got %zu", need, bytes);
+    std::memcpy(out, ao_direction_table(), need);
+    return RZ_OK;
 }
 int rz_outline(rz_ctx* c, const rz_outline_params* params, const int32_t* ids, size_t ids_bytes, const uint32_t* selected,
                size_t n_instances, uint8_t* rgba8, size_t rgba8_bytes, float* rgb32f, size_t rgb32f_bytes, unsigned flags) {

@@ -380,8 +380,41 @@ struct OutlineLaunch {          // rz_outline_kernel
 };
 void launch_outline(OutlineLaunch O, hipStream_t stream);
 
+// ---- rz_ao.hip
+constexpr int RZ_AO_DIRS = 256;                 // points of the direction table (rz_ao_directions)
+constexpr int RZ_AO_COUNTERS = 256;              // the most counters rz_ao_walks' waves claim units from (128 B apart)
+constexpr size_t RZ_AO_WALK_LDS = 2048;         // what rz_ao_walks keeps in LDS per wave beside the BLAS stack: 64 records of 32 B
+const float* ao_direction_table();              // host: RZ_AO_DIRS x 3 floats, built on first use
+struct AoWalkLaunch {           // rz_ao_walks (beside the KParams of camera_kparams)
+    const float4* guide;        // DenoiseGuideLaunch::guide at the frame's size
+    const float* dirs;          // device: the direction table
+    float* raw;                 // width x height: raw_p, 1 for a miss
+    int samples, log2Samples;   // N = 1, 2, 4, 8, 16
+    float radius;
+    int tilesX;                 // 8 x 8 tiles per row of tiles
+    long long tiles;
+    long long grid;             // rays_grid(tiles * 64)
+    unsigned* claim;            // `counters` words, 32 words apart, zero when the kernel starts: the next unit of each sequence
+    int counters;               // 1..RZ_AO_COUNTERS sequences of units, each with a counter; 0: a sequence per wave, no counter
+    int perTrip;                // a unit is one trip of a tile, not a tile
+    unsigned* errWord;          // the context's backstop word
+};
+struct AoResolveLaunch {        // rz_ao_resolve
+    const float* raw;           // AoWalkLaunch::raw
+    const float4* guide;        // smooth: the guide
+    const float* rgbIn;         // width x height x 3, optional: (1, 1, 1)
+    int width, height;
+    float strength, normalCos, planeTol;
+    float f;                    // 2 |inv_proj[5]| / height, rounded to binary32
+    float* ao;                  // outputs, each optional
+    float* rgb;
+    uchar4* rgba8;
+};
+void launch_ao_walks(const KParams& K, const AoWalkLaunch& A, hipStream_t stream);
+void launch_ao_resolve(const AoResolveLaunch& R, bool smooth, hipStream_t stream);
+
 // ---- rz_present.hip
-struct ProjBox;                // screen-space corners of one box (rz_present.hip)
+struct ProjBox;               // screen-space corners of one box (rz_present.hip)
 struct PresentParams {
     const float4* accum;
     uchar4* rgba8;              // may be null

@@ -22,6 +22,46 @@ __device__ __forceinline__ bool ray_query(const KParams& K, v3 o, v3 d, HitRec& 
     return SPREAD ? trace_spread<false, OVF, true>(K, o, d, h, bstk, c, &x) : trace_closest<false, OVF, true>(K, o, d, h, bstk, c, &x);
 }
 
+// The transparency-aware visibility walk of FS:507-528 for the lanes with `run`, the whole wave in step (rz_shadow_rays_kernel,
+// rz_ao_walks): up to 32 queries a ray.  A lane whose walk has ended stays out of the wave's further queries (the wave-uniform
+// loop with a predicated body of the render's single trace call site).  Leaves (vis, lit) as rz_visibility states them; a lane
+// without `run` keeps (1, false).  A query stopped at its backstop sets `cut`.
+template <bool OVF, bool SPREAD>
+__device__ __forceinline__ void shadow_walk(const KParams& K, v3 o, v3 d, float maxDist, bool run, const BlasStackT<OVF>& bstk,
+                                            bool& cut, float& vis, bool& lit) {
+    vis = 1.0f;
+    lit = false;
+    float traveled = 0.0f;
+    int iter = 0;
+    bool anyRun = rz_ballot(run) != 0ull;
+    while (anyRun) {
+        if (run) {
+            HitRec h;
+            TraceExtra x;
+            const bool found = ray_query<OVF, SPREAD>(K, o, d, h, bstk, x);
+            cut = cut || x.cut;
+            bool done = false;
+            if (!found) { done = true; lit = true; }                        // FS:514
+            else if (h.t < 0.001f) { o = o + d * 0.001f; }                  // FS:515
+            else {
+                traveled += h.t;                                            // FS:516-517
+                if (traveled >= maxDist) { done = true; lit = true; }
+                else {
+                    const float tr = K.materials[h.mat].transparency;       // FS:518-525
+                    if (tr > 0.0f) { vis *= tr; o = h.p + d * 0.001f; }
+                    else { vis = 0.0f; done = true; lit = false; }
+                }
+            }
+            if (!done) {
+                iter += 1;
+                if (!(iter < 32 && vis > 0.05f)) { done = true; lit = vis > 0.05f; }    // FS:511, 527
+            }
+            run = !done;
+        }
+        anyRun = rz_ballot(run) != 0ull;
+    }
+}
+
 // The rz_hit of a query, three 16-B stores at hits[3 i ..]: (t, point | normal, material | instance, triangle, prim, reserved).
 // tri: the winner (TraceExtra::tri); t: the distance the record states -- h.t, or what the caller measured along its own ray
 // (rz_editor_kernel past the near plane, the length of a see-through chain).  A miss: the shader's initial tHit (FS:459), ids

@@ -42,8 +42,8 @@ __global__ __launch_bounds__(64, RZ_RAYS_MIN_WAVES) void rz_trace_rays_kernel(co
     rays_backstop(errWord, cut);
 }
 
-// FS:507-528 per ray: origin, max_dist | dir.  out: n x rz_visibility (visibility, lit).  A lane whose walk has ended stays
-// out of the wave's further queries (the wave-uniform loop with a predicated body of the render's single trace call site).
+// FS:507-528 per ray: origin, max_dist | dir.  out: n x rz_visibility (visibility, lit).  The walk is shadow_walk (rz_query.h),
+// which rz_ao_walks calls too.
 template <bool OVF, bool SPREAD>
 __global__ __launch_bounds__(64, RZ_RAYS_MIN_WAVES) void rz_shadow_rays_kernel(const KParams K, const float4* __restrict__ rays,
                                                                                 float2* __restrict__ out, const int n, unsigned* errWord) {
@@ -62,36 +62,9 @@ __global__ __launch_bounds__(64, RZ_RAYS_MIN_WAVES) void rz_shadow_rays_kernel(c
             maxDist = a.w;
             d = mk3(b.x, b.y, b.z);
         }
-        float vis = 1.0f, traveled = 0.0f;
-        int iter = 0;
-        bool lit = false;
-        bool anyRun = rz_ballot(run) != 0ull;
-        while (anyRun) {
-            if (run) {
-                HitRec h;
-                TraceExtra x;
-                const bool found = ray_query<OVF, SPREAD>(K, o, d, h, bstk, x);
-                cut = cut || x.cut;
-                bool done = false;
-                if (!found) { done = true; lit = true; }                        // FS:514
-                else if (h.t < 0.001f) { o = o + d * 0.001f; }                  // FS:515
-                else {
-                    traveled += h.t;                                            // FS:516-517
-                    if (traveled >= maxDist) { done = true; lit = true; }
-                    else {
-                        const float tr = K.materials[h.mat].transparency;       // FS:518-525
-                        if (tr > 0.0f) { vis *= tr; o = h.p + d * 0.001f; }
-                        else { vis = 0.0f; done = true; lit = false; }
-                    }
-                }
-                if (!done) {
-                    iter += 1;
-                    if (!(iter < 32 && vis > 0.05f)) { done = true; lit = vis > 0.05f; }    // FS:511, 527
-                }
-                run = !done;
-            }
-            anyRun = rz_ballot(run) != 0ull;
-        }
+        float vis;
+        bool lit;
+        shadow_walk<OVF, SPREAD>(K, o, d, maxDist, run, bstk, cut, vis, lit);
         if (i < n) out[i] = make_float2(vis, __int_as_float(lit ? 1 : 0));
     }
     rays_backstop(errWord, cut);

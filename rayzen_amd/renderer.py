@@ -103,6 +103,15 @@ def editor_rays(camera, width, height):
     return make_rays(np.broadcast_to(np.asarray(camera.position, f32), d.shape), d)
 
 
+def ao_directions():
+    """The 256 unit directions rz_ambient_occlusion samples (rz_ao_directions): (256, 3) float32.  Host-only, no GPU."""
+    out = np.empty((_lib.AO_DIRECTIONS, 3), np.float32)
+    rc = _lib.hip().rz_ao_directions(out.ctypes.data, out.nbytes)
+    if rc != 0:
+        raise RayZenError("rz_ao_directions", rc, _lib.hip().rz_last_error(None).decode())
+    return out
+
+
 class Renderer:
     def __init__(self, device=0, flags=0):
         self._L = _lib.hip()
@@ -1119,6 +1128,47 @@ class Renderer:
         self._check(self._L.rz_outline(self._c, C.byref(p), C.c_void_p(ids_ptr), n * 4, C.c_void_p(selected_ptr), int(n_instances),
                                        C.c_void_p(rgba8_ptr), n * 4 if rgba8_ptr else 0, C.c_void_p(rgb32f_ptr),
                                        n * 12 if rgb32f_ptr else 0, 0), "rz_outline")
+
+    # -- ambient occlusion for previews (rz_ambient_occlusion) ---------------------------
+    def _ao_args(self, frame, samples, radius, smooth, strength, normal_cos, plane_tol):
+        fp = self._frame if frame is None else frame
+        if fp is None:
+            raise ValueError("ambient_occlusion: no frame given and set_frame has not been called")
+        p = _lib.AoParams()
+        p.samples, p.radius, p.smooth, p.strength = int(samples), float(radius), int(smooth), float(strength)
+        p.normal_cos, p.plane_tol = float(normal_cos), float(plane_tol)
+        return fp, p
+
+    def ambient_occlusion(self, frame=None, rgb=None, samples=4, radius=1.0, smooth=True, strength=1.0, normal_cos=0.9,
+                          plane_tol=2.0, want=("ao",)):
+        """Distance-limited ambient occlusion of the pixel-centre hits of `frame` (frame_params(...); None: the frame of the last
+        set_frame), include/rayzen_hip.h: rz_ambient_occlusion.  rgb: an (H, W, 3) float32 image to darken (render_editor's
+        rgb32f), None: white.  want: which of "ao" ((H, W) float32), "rgb32f" ((H, W, 3) float32) and "rgba8" ((H, W, 4) uint8)
+        to return; a dict of them.  Host memory; returns when done."""
+        fp, p = self._ao_args(frame, samples, radius, smooth, strength, normal_cos, plane_tol)
+        h, w = fp.height, fp.width
+        src = None if rgb is None else np.ascontiguousarray(rgb, np.float32).reshape(h, w, 3)
+        shapes = {"ao": ((h, w), np.float32), "rgb32f": ((h, w, 3), np.float32), "rgba8": ((h, w, 4), np.uint8)}
+        unknown = set(want) - set(shapes)
+        if unknown:
+            raise ValueError(f"ambient_occlusion: unknown outputs {sorted(unknown)}")
+        out = {k: np.empty(*shapes[k]) for k in shapes if k in want}
+        ptr = {k: (out[k].ctypes.data, out[k].nbytes) if k in out else (None, 0) for k in shapes}
+        self._check(self._L.rz_ambient_occlusion(self._c, C.byref(fp), C.byref(p), None if src is None else src.ctypes.data,
+                                                 0 if src is None else src.nbytes, *ptr["ao"], *ptr["rgb32f"], *ptr["rgba8"],
+                                                 _lib.AO_HOST), "rz_ambient_occlusion")
+        return out
+
+    def ambient_occlusion_device(self, frame=None, rgb_in_ptr=None, ao_ptr=None, rgb32f_ptr=None, rgba8_ptr=None, samples=4,
+                                 radius=1.0, smooth=True, strength=1.0, normal_cos=0.9, plane_tol=2.0):
+        """rz_ambient_occlusion on device memory (4-B aligned; rgb_in and rgb32f W*H*12 B, ao and rgba8 W*H*4 B; each may be None,
+        not all three outputs): enqueued on the context's stream, asynchronous."""
+        fp, p = self._ao_args(frame, samples, radius, smooth, strength, normal_cos, plane_tol)
+        n = fp.width * fp.height
+        self._check(self._L.rz_ambient_occlusion(self._c, C.byref(fp), C.byref(p), C.c_void_p(rgb_in_ptr), n * 12 if rgb_in_ptr else 0,
+                                                 C.c_void_p(ao_ptr), n * 4 if ao_ptr else 0, C.c_void_p(rgb32f_ptr),
+                                                 n * 12 if rgb32f_ptr else 0, C.c_void_p(rgba8_ptr), n * 4 if rgba8_ptr else 0, 0),
+                    "rz_ambient_occlusion")
 
     # -- convenience -----------------------------------------------------------
     def render_scene(self, scene, width, height, spp, bounce_budget, num_lights=None, tile_rank=0, tile_nranks=1,
