@@ -145,7 +145,8 @@ struct rz_ctx {
     // device-side dynamic update (rz_update_transforms)
     DevBuf dXforms, dInstRef, dTlasScratch, dProjBoxes, dBuildWs, dTlasDfs, dTriN;
     int nTlasDfs = 0;               // pop positions of the TLAS (rz_trace.h: trace_closest)
-    int* tlasHostCounts = nullptr;      // pinned: node count, index count, depth
+    int tlasEntry = 0;              // the verdict of whoever made dTlasDfs: queries may enter the list behind its root (rz_scene_dev.h: tlas_entry_verdict)
+    int* tlasHostCounts = nullptr;      // pinned: node count, index count, depth, entry verdict
     int devTlasNodes = 0;
     bool sceneHasTransparency = true;   // some triangle uses a material with transparency > 0
     const char* lastKernel = "";
@@ -723,6 +724,7 @@ int finalize_body(rz_ctx* c) {
         std::vector<TlasDfs> dfs;
         tlas_pop_order(tn, nTn, ti, dfs);
         c->nTlasDfs = (int)dfs.size();
+        c->tlasEntry = tlas_entry_verdict(dfs.data(), c->nTlasDfs);
         rc = upload_vec(c, c->dTlasDfs, dfs.data(), dfs.size() * sizeof(TlasDfs));
         if (rc != RZ_OK) return rc;
         RZ_HIP(c, hipStreamSynchronize(c->stream));     // the staging vector dies at scope exit
@@ -864,6 +866,9 @@ void scene_kparams(const rz_ctx* c, KParams& K) {
     K.tlasStackCap = 0;         // the TLAS walk keeps no stack (rz_trace.h: trace_closest)
     K.traceRoundCap = (int)std::min<long long>(0x7fffffff, tlas_index_count(c) + (long long)c->nTlasDfs + 64);
     K.regularBoxes = c->irregularBoxes ? 0 : 1;
+#if RZ_TLAS_ENTRY
+    K.tlasEntry = c->tlasEntry;
+#endif
 }
 
 // ... and of the camera, for the kernels that cast one ray per pixel outside the frame loop: the scene as finalize left it,
@@ -1375,11 +1380,12 @@ static int tlas_rebuild(rz_ctx* c, const float* transforms, size_t n) {
     W.n = (int)n;
     launch_tlas_refit(W, c->stream);
     RZ_HIP(c, hipGetLastError());
-    RZ_HIP(c, hipMemcpyAsync(c->tlasHostCounts, W.outCounts, 12, hipMemcpyDeviceToHost, c->stream));
+    RZ_HIP(c, hipMemcpyAsync(c->tlasHostCounts, W.outCounts, 16, hipMemcpyDeviceToHost, c->stream));
     // the caller's transform array may die after this call returns, and the TLAS depth sizes the LDS stack
     RZ_HIP(c, hipStreamSynchronize(c->stream));
     c->devTlasNodes = c->tlasHostCounts[0];
     c->nTlasDfs = c->tlasHostCounts[0];
+    c->tlasEntry = c->tlasHostCounts[3];        // (the builder's own verdict on the list it wrote)
     c->tlasDepth = std::max(1, c->tlasHostCounts[2]);
     device_changed(c, kTlas);
     return RZ_OK;

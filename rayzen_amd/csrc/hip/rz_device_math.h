@@ -107,6 +107,15 @@ __device__ __forceinline__ v3 rcp3(v3 d) {
     if (rz_ballot(!ok) == 0ull) return mk3(rcp_mid(d.x), rcp_mid(d.y), rcp_mid(d.z));
     return rcp3_ieee(d);
 }
+// ... and which way the wave went: allMid says that every component of every active lane lies in [2^-126, 2^126] -- so that every
+// reciprocal is finite, normal and not zero (rz_trace.h: RZ_TLAS_ENTRY's guard, at the price of no further instruction)
+__device__ __forceinline__ v3 rcp3(v3 d, bool& allMid) {
+    const bool okx = rcp_mid_ok(d.x), oky = rcp_mid_ok(d.y), okz = rcp_mid_ok(d.z);
+    const bool ok = okx & oky & okz;
+    allMid = rz_ballot(!ok) == 0ull;
+    if (allMid) return mk3(rcp_mid(d.x), rcp_mid(d.y), rcp_mid(d.z));
+    return rcp3_ieee(d);
+}
 
 // ---- quotients and square roots ---------------------------------------------
 // a / b and sqrt(x) must be the correctly rounded IEEE results (pinned numerics); hipcc's expansions are 11 and 13

@@ -350,9 +350,9 @@ __device__ __forceinline__ void render_samples_group(const KParams& K, const uns
                         RZ_SITE(c, 6);
                         if constexpr (shadow_exit<COUNT, false>)
                             found = spread ? trace_spread<COUNT, OVF>(K, P.o, P.d, h, bstk, c)
-                                           : trace_closest<COUNT, OVF, false, true>(K, P.o, P.d, h, bstk, c, nullptr, shadow_exit_dist<COUNT, false>(P), &sx);
+                                           : trace_closest<COUNT, OVF, false, true, true>(K, P.o, P.d, h, bstk, c, nullptr, shadow_exit_dist<COUNT, false>(P), &sx);
                         else
-                            found = spread ? trace_spread<COUNT, OVF>(K, P.o, P.d, h, bstk, c) : trace_closest<COUNT, OVF>(K, P.o, P.d, h, bstk, c);
+                            found = spread ? trace_spread<COUNT, OVF>(K, P.o, P.d, h, bstk, c) : trace_closest<COUNT, OVF, false, false, true>(K, P.o, P.d, h, bstk, c);
                     }
 #ifdef RZ_PROF
                     t2 = __builtin_amdgcn_s_memtime();
@@ -896,9 +896,9 @@ __device__ __forceinline__ void render_claim_compact(const KParams& K, const Cla
                     if (!shadow_candidate<COUNT, GLASS>(P)) {
                         RZ_SITE(c, 6);
                         if constexpr (shadow_exit<COUNT, GLASS>)
-                            found = trace_closest<COUNT, OVF, false, true>(K, P.o, P.d, h, bstk, tu, nullptr, shadow_exit_dist<COUNT, GLASS>(P), &sx);
+                            found = trace_closest<COUNT, OVF, false, true, true>(K, P.o, P.d, h, bstk, tu, nullptr, shadow_exit_dist<COUNT, GLASS>(P), &sx);
                         else
-                            found = trace_closest<COUNT, OVF>(K, P.o, P.d, h, bstk, tu);
+                            found = trace_closest<COUNT, OVF, false, false, true>(K, P.o, P.d, h, bstk, tu);
                     }
 #ifdef RZ_PROF
                     c.rt[c.rnd & 7] += __builtin_amdgcn_s_memtime() - tq0_;

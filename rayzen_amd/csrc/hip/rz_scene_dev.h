@@ -95,6 +95,15 @@ struct DevCounters {
         materials, light_fetches, pixels, scatters, diffuse_scatters, hemi_draws, lit_lights, triangles_past_u;
 };
 
+// RZ_TLAS_ENTRY (round 8, profiles/r08_tlas_front/; why it is exact: DESIGN.md section 4.1).  A closest-hit query of the sample
+// kernels' non-counting instantiations enters the pop-order list BEHIND the root where the list's maker has found the root's box
+// to hold both its children's (KParams::tlasEntry) and no lane's reciprocal direction is zero, infinite or NaN (read off the wave
+// test rcp3 makes anyway): the root's step can only report what the two children's steps report anyway.
+// 0: the code before, instruction for instruction.
+#ifndef RZ_TLAS_ENTRY
+#define RZ_TLAS_ENTRY 1
+#endif
+
 // Everything a render kernel needs, passed by value.
 struct KParams {
     const DevPair* pairs;
@@ -147,7 +156,36 @@ struct KParams {
     //      transparent scatter (rz_path.h: snapshot_store), from which the sample's second version starts; null: re-runs start at the camera
     float* snap;            // [resident wave][snapStride] floats
     uint32_t snapStride;    // >= (RZ_SNAP_FIELDS + RZ_SNAP_TALLY + RZ_GVER_ROWS) * 64 + RZ_GLATE_FIELDS * RZ_GLATE_CAP
+    // ---- round 8 (profiles/r08_tlas_front/): in what was padding -- the struct's size is the one before -- and only with the switch
+    //      on: as a field of its own with the switch off it left the transparent claims' kernel two instructions longer
+#if RZ_TLAS_ENTRY
+    int32_t tlasEntry;      // 1: a closest-hit query of the sample kernels may enter the pop-order list behind the root (tlas_entry_verdict below; rz_trace.h: trace_closest)
+#endif
 };
+
+// RZ_TLAS_ENTRY's verdict on a pop-order list: may a query skip the root's box test and start at
+// position 1?  Only if the list has a root with two children, every plane of the three boxes is finite with min <= max, and
+// the root's box contains both children's plane by plane -- then (b - o) * inv, monotone in b for finite operands, puts each
+// child's t interval inside the root's, and a ray that fails the root's test fails both children's.  Evaluated where the
+// list is made: on the host after tlas_pop_order (rz_context.hip), on the device at the end of rz_tlas_refit.
+#ifdef __HIPCC__
+__host__ __device__
+#endif
+inline int tlas_entry_verdict(const TlasDfs* d, int n) {
+    if (n < 3 || d[0].count != -1) return 0;
+    const int l = d[1].skip;                        // the right child is popped at 1, the left one behind the right subtree
+    if (l < 2 || l >= n) return 0;
+    const TlasDfs* box[3] = {d, d + 1, d + l};
+    for (int k = 0; k < 3; ++k)
+        for (int a = 0; a < 3; ++a) {
+            const float lo = box[k]->bmin[a], hi = box[k]->bmax[a];
+            if (!(lo - lo == 0.0f) || !(hi - hi == 0.0f) || !(lo <= hi)) return 0;      // (x - x is 0 for a finite x alone)
+        }
+    for (int k = 1; k < 3; ++k)
+        for (int a = 0; a < 3; ++a)
+            if (!(d[0].bmin[a] <= box[k]->bmin[a]) || !(d[0].bmax[a] >= box[k]->bmax[a])) return 0;
+    return 1;
+}
 
 // Arguments of the device TLAS rebuild (rz_tlas_device.hip: rz_tlas_refit; filled in by rz_context.hip).
 struct TlasWork {
@@ -161,7 +199,7 @@ struct TlasWork {
     float* worldMax;                // scratch n x 3
     int32_t* order;                 // scratch n (meshIndices)
     int32_t* stack;                 // scratch 3 x (2n+8)
-    int32_t* outCounts;             // [0] = node count, [1] = index count, [2] = depth
+    int32_t* outCounts;             // [0] = node count, [1] = index count, [2] = depth, [3] = tlas_entry_verdict of dfs
     int32_t* scratch;               // 4 x n ints (ranks|flags, two pointer buffers, the permuted order) + 2 x 6 x (n + 1) (level lists)
     int n;
 };

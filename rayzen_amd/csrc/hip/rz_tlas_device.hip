@@ -250,7 +250,11 @@ __global__ __launch_bounds__(1024) void rz_tlas_refit(const TlasWork W) {
         int32_t* t = cur; cur = nxt; nxt = t;
         __syncthreads();
     }
-    if (threadIdx.x == 0) { W.outCounts[0] = n > 0 ? 2 * n - 1 : 1; W.outCounts[1] = n; W.outCounts[2] = depth; }
+    if (threadIdx.x == 0) {
+        W.outCounts[0] = n > 0 ? 2 * n - 1 : 1; W.outCounts[1] = n; W.outCounts[2] = depth;
+        // may a query enter this list behind its root?  (the records were written by this block, in front of the loop's last barrier)
+        W.outCounts[3] = tlas_entry_verdict(W.dfs, n > 0 ? 2 * n - 1 : 1);
+    }
 }
 
 void launch_tlas_refit(const TlasWork& W, hipStream_t s) {

@@ -51,6 +51,18 @@ namespace rz {
 #ifndef RZ_SHADOW_EXIT
 #define RZ_SHADOW_EXIT 1
 #endif
+// RZ_TLAS_ENTRY (rz_scene_dev.h, beside the kernel argument it adds): the sample kernels' non-counting instantiations.
+// (the RZ_PROF build's counted frame takes the entry too, as it takes the other shortcuts: its per-site lines then show the product's walk)
+#ifdef RZ_PROF
+template <bool COUNT> constexpr bool tlas_entry = RZ_TLAS_ENTRY != 0;
+#else
+template <bool COUNT> constexpr bool tlas_entry = RZ_TLAS_ENTRY != 0 && !COUNT;
+#endif
+#if RZ_TLAS_ENTRY
+__device__ __forceinline__ int tlas_entry_of(const KParams& K) { return K.tlasEntry; }
+#else
+__device__ __forceinline__ int tlas_entry_of(const KParams&) { return 0; }
+#endif
 struct Tally {          // per-thread counts of the REFERENCE algorithm's memory touches
     unsigned traversals, tlas_nodes, tlas_leaf_indices, instances, blas_nodes, triangles, materials, light_fetches,
         samples;
@@ -734,7 +746,9 @@ __device__ __forceinline__ int traverse_blas_mi(const KParams& K, int inst, v3 l
 //   2  it is in doubt (something was delivered nearer than 2 EPS, or not clearly nearer than the light): nothing of this
 //      query may be used, the caller traces it again without the shortcut;
 //   0  the lane took no shortcut: the reference's answer, as ever.
-template <bool COUNT, bool OVF, bool EXTRA = false, bool SX = false>
+// ENTRY (RZ_TLAS_ENTRY): the wave may start at position 1, behind the root, when the list's maker said so (K.tlasEntry) and
+// every reciprocal of every active lane is finite and not zero -- rcp3's own wave test; else the whole wave starts at 0 as ever.
+template <bool COUNT, bool OVF, bool EXTRA = false, bool SX = false, bool ENTRY = false>
 __device__ __forceinline__ bool trace_closest(const KParams& K, v3 o, v3 d, HitRec& h, const BlasStackT<OVF>& bstk, Tally& c,
                                               TraceExtra* x = nullptr, float sxMaxDist = 0.0f, int* sxOut = nullptr) {
     // the lane's shortcut state, one float: > 0 it may still take the shortcut (inside an instance: k = |M^-1 d|, the scale of its
@@ -747,13 +761,23 @@ __device__ __forceinline__ bool trace_closest(const KParams& K, v3 o, v3 d, HitR
     int bestTri = -1, bestInst = -1;
     v3 bestP = mk3(0.0f, 0.0f, 0.0f);
     if (COUNT) c.traversals += 1;
-    const v3 inv = rcp3(d);
+    bool allMid = false;                            // wave-uniform: every direction component of every active lane lies in [2^-126, 2^126]
+    const v3 inv = (ENTRY && tlas_entry<COUNT>) ? rcp3(d, allMid) : rcp3(d);
     int idx = 0;                                    // the position this lane visits next
     const int nDfs = K.nTlasDfs;
     // (pos strictly grows -- a skip position lies behind its node, by construction on the host and on the device -- so the
     //  list is walked in at most nDfs steps; `step` is the backstop against a list that says otherwise: a wave that never
     //  leaves this loop takes the device with it)
     int pos = 0;
+    if constexpr (ENTRY && tlas_entry<COUNT>) {
+        // At the root tHit is 1e30 and only the box test can fail; the root's box holds both children's, so a ray that fails it
+        // fails theirs too, and they are tested as ever: the root's step says nothing its next two do not.
+        // Wave-uniform, or a lane left at 0 would stand IN FRONT of the cursor.
+        // (the guard is the wave test rcp3 has made already: such reciprocals are finite, normal and not zero.  As a ballot of its
+        //  own in here -- |inv| < inf, as first built -- it cost 14 spilled SGPRs and 5 % of the frame: profiles/r08_tlas_front/)
+        const int start = (tlas_entry_of(K) != 0 && allMid) ? 1 : 0;
+        idx = start; pos = start;
+    }
     for (int step = 0; pos < nDfs && step < nDfs; ++step) {
         const f32x16 q = sload16(K.tlasDfs + pos);
         const bool at = idx == pos;
