@@ -1313,6 +1313,83 @@ int rz_ambient_occlusion(rz_ctx* ctx, const rz_frame_params* frame, const rz_ao_
                          size_t rgba8_bytes, unsigned flags);
 int rz_ao_directions(float* out, size_t bytes);
 
+/* ------------------------------------------------------------------------ */
+/* Adaptive sampling (new)                                                  */
+/* ------------------------------------------------------------------------ */
+/* rz_render_adaptive renders the frame of rz_set_frame in batches of s = batch_spp samples per pixel and stops sampling the
+ * 8 x 8 tiles whose estimated error has fallen under a threshold.  The render kernels are rz_render's own, launched over
+ * contiguous runs of tiles (row-major tile index, tile (0, 0) at the bottom left); a path's arithmetic does not depend on the
+ * launch that runs it, so every pixel ends with exactly the bits rz_render gives at that pixel's own sample count.  The result
+ * is the ordinary accumulation: rgb the running sum, a the pixel's own sample count, which every presenting and off-frame call
+ * divides by per pixel.  Between batches a metering kernel (rz_adaptive_meter, rz_adaptive.hip) decides which tiles go on.
+ * Sequence.  Batch 1 is the whole frame from sample 0.  After batch B = 1, 2, ... the meter runs over the tiles batch B rendered,
+ * one byte of flags per tile comes back to the host, rz_adaptive_plan makes the runs of batch B + 1 from them, and batch B + 1
+ * is one launch per run from sample B * s.  The call ends when no tile is active or after max_batches; it returns when the
+ * frame is complete.  The frame's spp and sample_base are ignored and left as they are.
+ * The meter.  All arithmetic is binary32 with one rounding per operation, no fused multiply-add; `/` and sqrt are correctly
+ * rounded.  The context keeps per pixel prev (4 floats: the accumulation after the previous batch) and (S1, S2), all zero
+ * before batch 1.  Per pixel inside the frame, with I the accumulation after batch B and fs = (float)s, fB = (float)B:
+ *   d.c = (I.c - prev.c) / fs for c = r, g, b;  L = (0.2126f * d.r + 0.7152f * d.g) + 0.0722f * d.b;
+ *   S1 = S1 + L;  S2 = S2 + L * L;  prev = I;  m = S1 / fB;
+ *   B >= 2: x = (S2 - S1 * m) / (float)(B - 1);  v = x > 0 ? x : (x is a NaN ? x : 0);  e = sqrt(v / fB).   B = 1: e = 0.
+ * A lane outside the frame contributes e = 0 and |m| = 0.  Per tile, lane = x + 8 * y inside the tile: num = the sum of e and
+ * sm = the sum of |m| over the 64 lanes, each by the butterfly t[l] = t[l] + t[l ^ o] for o = 32, 16, 8, 4, 2, 1 in this order;
+ * den = sm + luminance_floor * (float)(pixels of the tile inside the frame);  E = num / den.
+ * A tile starts active and retires -- for good -- when B >= min_batches and E <= threshold; the comparison is false for a NaN,
+ * so a tile with non-finite samples stays active to the end.  A tile is current while it has received every batch so far.  A
+ * retired tile that a merged run covers is rendered and metered again (its E and its count follow) and stays retired.
+ * The luminance of a batch is the difference of two running sums, so E carries their rounding: about 1e-4 on a tile of constant
+ * colour.  Thresholds under about 1e-3 ask for more than the numbers hold.
+ * The plan.  rz_adaptive_plan needs no GPU.  active / current: one byte per tile, non-zero = set.  (1) The runs are the maximal
+ * intervals of active tiles.  (2) Two neighbouring runs merge when the gap between them is at most merge_gap tiles and every
+ * tile of the gap is current; merged runs merge on by the same rule.  (3) While there are more than max_runs runs and two
+ * neighbours with an all-current gap between them, whatever its length, the pair with the smallest such gap merges, the lowest
+ * tile index first among equals.  (4) If none is left the plan stands with more runs: max_runs is a target.  The runs are
+ * written in ascending order and *n_runs is set to their number, also when `cap` is too small for them (RZ_ERR_BUFFER_SIZE,
+ * nothing written).  RZ_ERR_INVALID_ARG: null active, current (with n_tiles > 0) or n_runs, null runs with cap > 0, merge_gap
+ * < 0, max_runs < 1, n_tiles > 2^30.  Here merge_gap and max_runs are taken as given: 0 merges nothing in step 2.
+ * rz_render_adaptive.  params NULL = defaults.  tile_batches / tile_error: one int32 / float per tile, the batches the tile
+ * received and its last E; each optional; DEVICE memory (4-byte aligned), or host memory with RZ_ADAPTIVE_HOST.  info, optional,
+ * is host memory.  Both backends, a bound accumulation (rz_bind_accum) and the backstop word (left to rz_sync) work as in
+ * rz_render; rz_last_kernel_name and rz_debug_last_plan describe the call's last render launch, and the timing ring of
+ * rz_last_render_ms is not advanced.  No temporal, display or other state is touched, and a following rz_render from sample 0
+ * gives what it gives on a fresh context.  Continuing an adaptive frame with rz_render at sample_base > 0 is not defined: the
+ * pixels are at different sample counts.  rz_group_* has no adaptive form.
+ * Errors, nothing launched.  RZ_ERR_INVALID_ARG: null context; unknown flags; batch_spp outside 1..1024; min_batches outside
+ * 2..64; max_batches outside min_batches..64; a NaN threshold; luminance_floor not finite or < 0; merge_gap < -1; max_runs < 0;
+ * a misaligned device pointer; a frame that is one of several tile ranks (tile_nranks > 1).  RZ_ERR_NOT_READY: no rz_set_frame,
+ * no scene.  RZ_ERR_BUFFER_SIZE: tile_batches or tile_error too small, or a bound accumulation smaller than the frame.
+ * Cost, where it pays and where it loses: profiles/adaptive/README.md.  (Additive: RZ_ABI_VERSION stays 5.) */
+typedef struct rz_adaptive_params {      /* a zero field = its default; 32 B; rz_sizeof(38) */
+    int32_t  batch_spp;                  /* s, 1..1024; default 8 */
+    int32_t  min_batches;                /* 2..64; default 4 */
+    int32_t  max_batches;                /* min_batches..64; default 8, or min_batches if that is more */
+    float    threshold;                  /* default 0.02; negative: no tile retires; +inf: every finite tile retires at min_batches */
+    float    luminance_floor;            /* finite, > 0; default 0.01 */
+    int32_t  merge_gap;                  /* tiles; default 8; -1: merge nothing in step 2 */
+    int32_t  max_runs;                   /* the target of step 3; default 1: one launch per batch, from the first active tile to the last */
+    uint32_t flags;                      /* RZ_ADAPTIVE_HOST */
+} rz_adaptive_params;
+#define RZ_ADAPTIVE_HOST 1u              /* tile_batches and tile_error are host memory */
+#define RZ_ADAPTIVE_MAX_BATCHES 64
+typedef struct rz_adaptive_info {        /* 800 B; rz_sizeof(39) */
+    int32_t  batches;                    /* batches run */
+    int32_t  n_tiles;                    /* tiles of the frame */
+    uint64_t samples_traced;             /* s x the pixels inside the frame of every tile rendered, over the batches */
+    uint64_t samples_uniform;            /* width x height x max_batches x s */
+    float    render_ms, meter_ms;        /* the render launches and the metering launches, from events on the stream */
+    int32_t  tiles_active[RZ_ADAPTIVE_MAX_BATCHES];      /* [B - 1]: tiles still active after batch B's metering */
+    int32_t  tiles_rendered[RZ_ADAPTIVE_MAX_BATCHES];    /* [B - 1]: tiles batch B rendered, and */
+    int32_t  runs[RZ_ADAPTIVE_MAX_BATCHES];              /* [B - 1]: the launches it took */
+} rz_adaptive_info;
+typedef struct rz_tile_run {             /* 8 B; rz_sizeof(40) */
+    int32_t first, len;
+} rz_tile_run;
+int rz_render_adaptive(rz_ctx* ctx, const rz_adaptive_params* params, rz_adaptive_info* info, int32_t* tile_batches,
+                       size_t tile_batches_bytes, float* tile_error, size_t tile_error_bytes);
+int rz_adaptive_plan(const uint8_t* active, const uint8_t* current, size_t n_tiles, int merge_gap, int max_runs,
+                     rz_tile_run* runs, size_t cap, size_t* n_runs);
+
 /* Number of HIP devices visible to the process (0 without a GPU). */
 int rz_device_count(void);
 
@@ -1338,7 +1415,8 @@ const char* rz_source_hash(void);
  * 9 visibility, 10 editor_params, 11 denoise_params, 12 temporal_params,
  * 14 display_params, 15 display_info, 17 skin_triangle, 18 morph_triangle, 20 mesh_quality,
  * 21 upscale_params, 23 seethrough_params, 24 chain, 26 antialias_params, 28 pixel_cost, 29 cost_params, 30 cost_view_params,
- * 31 cost_stats, 33 coverage_params, 34 instance_coverage, 35 outline_params, 37 ao_params (13, 16, 19, 22, 25, 27, 32 and 36 are unassigned and
+ * 31 cost_stats, 33 coverage_params, 34 instance_coverage, 35 outline_params, 37 ao_params, 38 adaptive_params, 39 adaptive_info,
+ * 40 tile_run (13, 16, 19, 22, 25, 27, 32 and 36 are unassigned and
  * return 0, as every unknown index does). */
 size_t rz_sizeof(int which);
 

@@ -33,6 +33,7 @@ HIP_SYMBOLS = (
     "rz_render_cost", "rz_cost_view", "rz_present_cost",
     "rz_coverage", "rz_outline",
     "rz_ambient_occlusion", "rz_ao_directions",
+    "rz_render_adaptive", "rz_adaptive_plan",
 )
 ABI_VERSION = 5         # RZ_ABI_VERSION of the include/rayzen_hip.h this file mirrors
 # the symbols include/rayzen_host.h declares
@@ -261,6 +262,28 @@ AO_DIRECTIONS = 256                     # points of rz_ao_directions' table
 SIZEOF_AO_PARAMS = 37                   # its rz_sizeof index (36 is unassigned)
 
 
+class AdaptiveParams(C.Structure):
+    """rz_adaptive_params of include/rayzen_hip.h (32 B); a zero field = its default."""
+    _fields_ = [("batch_spp", C.c_int32), ("min_batches", C.c_int32), ("max_batches", C.c_int32), ("threshold", C.c_float),
+                ("luminance_floor", C.c_float), ("merge_gap", C.c_int32), ("max_runs", C.c_int32), ("flags", C.c_uint32)]
+
+
+ADAPTIVE_MAX_BATCHES = 64               # RZ_ADAPTIVE_MAX_BATCHES
+
+
+class AdaptiveInfo(C.Structure):
+    """rz_adaptive_info of include/rayzen_hip.h (800 B)."""
+    _fields_ = [("batches", C.c_int32), ("n_tiles", C.c_int32), ("samples_traced", C.c_uint64), ("samples_uniform", C.c_uint64),
+                ("render_ms", C.c_float), ("meter_ms", C.c_float), ("tiles_active", C.c_int32 * ADAPTIVE_MAX_BATCHES),
+                ("tiles_rendered", C.c_int32 * ADAPTIVE_MAX_BATCHES), ("runs", C.c_int32 * ADAPTIVE_MAX_BATCHES)]
+
+
+TILE_RUN_DTYPE = np.dtype([("first", np.int32), ("len", np.int32)])     # rz_tile_run (8 B)
+ADAPTIVE_HOST = 1                       # RZ_ADAPTIVE_HOST
+ADAPTIVE_DEFAULTS = dict(batch_spp=8, min_batches=4, max_batches=8, threshold=0.02, luminance_floor=0.01, merge_gap=8, max_runs=1)
+SIZEOF_ADAPTIVE_PARAMS, SIZEOF_ADAPTIVE_INFO, SIZEOF_TILE_RUN = 38, 39, 40      # their rz_sizeof indices
+
+
 class SkinTriangle(C.Structure):
     """rz_skin_triangle of include/rayzen_hip.h (64 B)."""
     _fields_ = [("bones", C.c_uint32 * 3), ("pad", C.c_uint32), ("weights", (C.c_float * 4) * 3)]
@@ -392,7 +415,9 @@ def hip():
                                 ("rz_coverage", i, [vp, C.POINTER(FrameParams), vp, vp, sz, vp, sz, C.c_uint]),
                                 ("rz_outline", i, [vp, vp, vp, sz, vp, sz, vp, sz, vp, sz, C.c_uint]),
                                 ("rz_ambient_occlusion", i, [vp, C.POINTER(FrameParams), vp, vp, sz, vp, sz, vp, sz, vp, sz, C.c_uint]),
-                                ("rz_ao_directions", i, [vp, sz])):
+                                ("rz_ao_directions", i, [vp, sz]),
+                                ("rz_render_adaptive", i, [vp, C.POINTER(AdaptiveParams), C.POINTER(AdaptiveInfo), vp, sz, vp, sz]),
+                                ("rz_adaptive_plan", i, [vp, vp, sz, i, i, vp, sz, C.POINTER(sz)])):
             try:
                 fn = getattr(L, name)
                 fn.restype, fn.argtypes = res, args

@@ -231,6 +231,14 @@ struct rz_ctx {
     // its waves claim tiles from (zeroed by every call); the guide it casts goes to dDnGuide, which every pass that casts one
     // rewrites before it reads it
     DevBuf dAoDirs, dAoRaw, dAoClaim;
+    // rz_render_adaptive (rz_adaptive.hip): per pixel, tile by tile, the accumulation after the tile's previous batch and the
+    // luminance moments; per tile its error, the batches it has received and its flags; the list of the tiles a batch rendered;
+    // the pinned block the flags come back to and the list goes up from; the events around a batch's render launches and its
+    // metering launch.  Allocated by the first call and kept; every call starts them afresh
+    DevBuf dAdPrev, dAdMoments, dAdError, dAdBatches, dAdFlags, dAdList;
+    uint8_t* adPinned = nullptr;
+    size_t adPinnedCap = 0;
+    hipEvent_t evAdaptive[3] = {nullptr, nullptr, nullptr};
 };
 
 namespace {
@@ -938,6 +946,7 @@ struct HostStage {
     }
 };
 
+// (evSlot: the pair of the ring that brackets the launch; negative: none -- rz_render_adaptive brackets its batches itself)
 int render_samples(rz_ctx* c, KParams K, bool counted, int evSlot) {
     K.nSlots = K.nLocalTiles * 64;
     int rc = ensure_group_counter(c);
@@ -1026,9 +1035,9 @@ int render_samples(rz_ctx* c, KParams K, bool counted, int evSlot) {
             K.snapStride = (uint32_t)stride;
         }
     }
-    RZ_HIP(c, hipEventRecord(c->evStart[evSlot], c->stream));
+    if (evSlot >= 0) RZ_HIP(c, hipEventRecord(c->evStart[evSlot], c->stream));
     if (K.nSlots > 0) launch_render_samples(K, counted, c->sceneHasTransparency, c->stream);
-    RZ_HIP(c, hipEventRecord(c->evStop[evSlot], c->stream));
+    if (evSlot >= 0) RZ_HIP(c, hipEventRecord(c->evStop[evSlot], c->stream));
     c->lastLaunches = K.nSlots > 0 ? 1 : 0;
     c->lastGrid = plan.grid;
     c->lastPlan = rz_launch_plan{plan.groups, plan.grid, plan.perClaim, (plan.compact && K.wpool) ? plan.claimUnits : 0,
@@ -1158,6 +1167,202 @@ int do_render(rz_ctx* c, bool counted, rz_counters* out) {
     return RZ_OK;
 }
 
+// ---- rz_render_adaptive / rz_adaptive_plan (rz_adaptive.hip; include/rayzen_hip.h states the rule) -----------------------------
+// The runs of the next batch.  A merge changes no other gap, so step 3's "smallest all-current gap first, lowest index among
+// equals" is a stable sort of the gaps step 2 left open.
+void adaptive_plan(const uint8_t* active, const uint8_t* current, size_t n, int mergeGap, int maxRuns, std::vector<rz_tile_run>& out) {
+    out.clear();
+    for (size_t i = 0; i < n;) {
+        if (!active[i]) { ++i; continue; }
+        size_t j = i;
+        while (j < n && active[j]) ++j;
+        out.push_back(rz_tile_run{(int32_t)i, (int32_t)(j - i)});
+        i = j;
+    }
+    if (out.size() < 2) return;
+    std::vector<char> join(out.size() - 1, 0);
+    std::vector<std::pair<int32_t, int32_t>> open;          // (length, the run in front) of the all-current gaps step 2 leaves
+    size_t runs = out.size();
+    for (size_t k = 0; k + 1 < out.size(); ++k) {
+        const int32_t g0 = out[k].first + out[k].len, g1 = out[k + 1].first;
+        bool allCurrent = true;
+        for (int32_t t = g0; t < g1 && allCurrent; ++t) allCurrent = current[t] != 0;
+        if (!allCurrent) continue;
+        if (g1 - g0 <= mergeGap) { join[k] = 1; --runs; }
+        else open.emplace_back(g1 - g0, (int32_t)k);
+    }
+    if (runs > (size_t)maxRuns) {
+        std::stable_sort(open.begin(), open.end(), [](const auto& a, const auto& b) { return a.first < b.first; });
+        for (size_t k = 0; k < open.size() && runs > (size_t)maxRuns; ++k, --runs) join[open[k].second] = 1;
+    }
+    size_t w = 0;
+    for (size_t k = 1; k < out.size(); ++k) {
+        if (join[k - 1]) out[w].len = out[k].first + out[k].len - out[w].first;
+        else out[++w] = out[k];
+    }
+    out.resize(w + 1);
+}
+
+// The frame of rz_set_frame in batches of s samples over runs of tiles.  Every launch is a launch of do_render's kernels with
+// three fields of its KParams overridden -- tileNRanks 1, tileRank the run's first tile, nLocalTiles its length -- which
+// render_samples and launch_render_pixels size everything else from; sampleBase continues the pixels from the accumulation and
+// currentIor.  The launches record no event pair of the ring, which therefore keeps the renders' history.
+int render_adaptive(rz_ctx* c, const rz_adaptive_params* pp, rz_adaptive_info* info, int32_t* tileBatches, size_t tileBatchesBytes,
+                    float* tileError, size_t tileErrorBytes) {
+    const char* what = "rz_render_adaptive";
+    if (!c) return fail(nullptr, RZ_ERR_INVALID_ARG, "%s: null context", what);
+    rz_adaptive_params P{};
+    if (pp) P = *pp;
+    if (P.flags & ~RZ_ADAPTIVE_HOST) return fail(c, RZ_ERR_INVALID_ARG, "%s: unknown flags 0x%x", what, P.flags);
+    if (P.batch_spp == 0) P.batch_spp = 8;
+    if (P.min_batches == 0) P.min_batches = 4;
+    if (P.max_batches == 0) P.max_batches = std::max(8, P.min_batches);
+    if (P.threshold == 0.0f) P.threshold = 0.02f;
+    if (P.luminance_floor == 0.0f) P.luminance_floor = 0.01f;
+    if (P.merge_gap == 0) P.merge_gap = 8;
+    if (P.max_runs == 0) P.max_runs = 1;         // (every further launch of a batch cost more than it saved: profiles/adaptive/README.md)
+    if (P.batch_spp < 1 || P.batch_spp > 1024) return fail(c, RZ_ERR_INVALID_ARG, "%s: batch_spp %d outside 1..1024", what, P.batch_spp);
+    if (P.min_batches < 2 || P.min_batches > RZ_ADAPTIVE_MAX_BATCHES)
+        return fail(c, RZ_ERR_INVALID_ARG, "%s: min_batches %d outside 2..%d", what, P.min_batches, RZ_ADAPTIVE_MAX_BATCHES);
+    if (P.max_batches < P.min_batches || P.max_batches > RZ_ADAPTIVE_MAX_BATCHES)
+        return fail(c, RZ_ERR_INVALID_ARG, "%s: max_batches %d outside %d..%d", what, P.max_batches, P.min_batches, RZ_ADAPTIVE_MAX_BATCHES);
+    if (P.threshold != P.threshold) return fail(c, RZ_ERR_INVALID_ARG, "%s: threshold is not a number", what);
+    if (!(P.luminance_floor > 0.0f && P.luminance_floor < INFINITY))
+        return fail(c, RZ_ERR_INVALID_ARG, "%s: luminance_floor %g (finite, > 0)", what, (double)P.luminance_floor);
+    if (P.merge_gap < -1) return fail(c, RZ_ERR_INVALID_ARG, "%s: merge_gap %d (-1: none, 0: the default, or a number of tiles)", what, P.merge_gap);
+    if (P.max_runs < 0) return fail(c, RZ_ERR_INVALID_ARG, "%s: max_runs %d", what, P.max_runs);
+    const int mergeGap = std::max(0, P.merge_gap);
+    const bool host = (P.flags & RZ_ADAPTIVE_HOST) != 0;
+    if (!host && ((reinterpret_cast<uintptr_t>(tileBatches) | reinterpret_cast<uintptr_t>(tileError)) & 3u))
+        return fail(c, RZ_ERR_INVALID_ARG, "%s: device pointers must be 4-byte aligned", what);
+    if (!c->haveFrame) return fail(c, RZ_ERR_NOT_READY, "%s: rz_set_frame has not been called", what);
+    const rz_frame_params& f = c->frame;
+    if (f.tile_nranks > 1)
+        return fail(c, RZ_ERR_INVALID_ARG, "%s: the frame is tile %d of %d; an adaptive frame is rendered whole", what, f.tile_rank, f.tile_nranks);
+    const int tilesX = (f.width + RZ_TILE_W - 1) / RZ_TILE_W, tilesY = (f.height + RZ_TILE_H - 1) / RZ_TILE_H;
+    const int nTiles = tilesX * tilesY;
+    const size_t nPix = (size_t)f.width * f.height;
+    if (tileBatches && tileBatchesBytes < (size_t)nTiles * 4)
+        return fail(c, RZ_ERR_BUFFER_SIZE, "%s: tile_batches needs %zu bytes, got %zu", what, (size_t)nTiles * 4, tileBatchesBytes);
+    if (tileError && tileErrorBytes < (size_t)nTiles * 4)
+        return fail(c, RZ_ERR_BUFFER_SIZE, "%s: tile_error needs %zu bytes, got %zu", what, (size_t)nTiles * 4, tileErrorBytes);
+    if (c->extAccum && c->extAccumBytes < nPix * 16)
+        return fail(c, RZ_ERR_BUFFER_SIZE, "%s: bound accumulation buffer holds %zu bytes, frame needs %zu", what, c->extAccumBytes, nPix * 16);
+    RZ_HIP(c, hipSetDevice(c->device));
+    int rc = finalize(c);
+    if (rc != RZ_OK) return rc;
+    KParams K{};
+    K.accum = static_cast<float4*>(c->extAccum ? c->extAccum : c->ownAccum.p);
+    K.ior = static_cast<float*>(c->dIor.p);
+    rc = frame_kparams(c, K, P.batch_spp, 0);
+    if (rc == RZ_OK) rc = ensure(c, c->dAdPrev, (size_t)nTiles * 64 * sizeof(float4));
+    if (rc == RZ_OK) rc = ensure(c, c->dAdMoments, (size_t)nTiles * 64 * sizeof(float2));
+    if (rc == RZ_OK) rc = ensure(c, c->dAdError, (size_t)nTiles * sizeof(float));
+    if (rc == RZ_OK) rc = ensure(c, c->dAdBatches, (size_t)nTiles * sizeof(int32_t));
+    if (rc == RZ_OK) rc = ensure(c, c->dAdFlags, (size_t)nTiles);
+    if (rc == RZ_OK) rc = ensure(c, c->dAdList, (size_t)nTiles * sizeof(int32_t));
+    if (rc != RZ_OK) return rc;
+    // pinned: the tiles' flags as they come back, then the list of the tiles a batch rendered as it goes up
+    const size_t listOff = ((size_t)nTiles + 15) & ~size_t(15), pinnedBytes = listOff + (size_t)nTiles * sizeof(int32_t);
+    if (c->adPinnedCap < pinnedBytes) {
+        if (c->adPinned) (void)hipHostFree(c->adPinned);
+        c->adPinned = nullptr; c->adPinnedCap = 0;
+        RZ_HIP(c, hipHostMalloc(reinterpret_cast<void**>(&c->adPinned), pinnedBytes, hipHostMallocDefault));
+        c->adPinnedCap = pinnedBytes;
+    }
+    for (hipEvent_t* e : {&c->evAdaptive[0], &c->evAdaptive[1], &c->evAdaptive[2]})
+        if (!*e) RZ_HIP(c, hipEventCreate(e));
+    const uint8_t* hFlags = c->adPinned;
+    int32_t* hList = reinterpret_cast<int32_t*>(c->adPinned + listOff);
+
+    AdaptiveMeterLaunch M{};
+    M.accum = K.accum;
+    M.prev = static_cast<float4*>(c->dAdPrev.p);
+    M.moments = static_cast<float2*>(c->dAdMoments.p);
+    M.width = f.width; M.height = f.height; M.tilesX = tilesX;
+    M.spp = P.batch_spp;
+    M.minBatches = P.min_batches;
+    M.threshold = P.threshold; M.floor = P.luminance_floor;
+    M.tileError = static_cast<float*>(c->dAdError.p);
+    M.tileBatches = static_cast<int32_t*>(c->dAdBatches.p);
+    M.tileFlags = static_cast<uint8_t*>(c->dAdFlags.p);
+
+    auto tilePixels = [&](int t) {
+        const int tx = t % tilesX, ty = t / tilesX;
+        return (uint64_t)(std::min<int>(RZ_TILE_W, f.width - tx * RZ_TILE_W) * std::min<int>(RZ_TILE_H, f.height - ty * RZ_TILE_H));
+    };
+    rz_adaptive_info I{};
+    I.n_tiles = nTiles;
+    I.samples_uniform = (uint64_t)nPix * (uint64_t)P.max_batches * (uint64_t)P.batch_spp;
+    alloc_point(c);
+    std::vector<uint8_t> active((size_t)nTiles, 1), current((size_t)nTiles, 1), rendered((size_t)nTiles, 1);
+    std::vector<rz_tile_run> runs(1, rz_tile_run{0, nTiles});
+    for (int B = 1;; ++B) {
+        RZ_HIP(c, hipEventRecord(c->evAdaptive[0], c->stream));
+        int nRendered = 0;
+        for (const rz_tile_run& r : runs) {
+            KParams KR = K;
+            KR.sampleBase = (B - 1) * P.batch_spp;
+            KR.tileNRanks = 1; KR.tileRank = r.first; KR.nLocalTiles = r.len;
+            if (use_samples(c)) {
+                rc = render_samples(c, KR, false, -1);
+                if (rc != RZ_OK) return rc;
+            } else {
+                launch_render_pixels(KR, false, c->stream);
+                c->lastLaunches = 1;
+                c->lastPlan = rz_launch_plan{KR.nLocalTiles, KR.nLocalTiles, 0, 0, (KR.spp + 63) / 64, 64, KR.blasStackCap, 0, c->sceneHasTransparency ? 1 : 0, 0};
+            }
+            RZ_HIP(c, hipGetLastError());
+            if (B > 1) for (int t = r.first; t < r.first + r.len; ++t) { hList[nRendered++] = t; rendered[t] = 1; }
+            else nRendered += r.len;
+        }
+        RZ_HIP(c, hipEventRecord(c->evAdaptive[1], c->stream));
+        M.batch = B;
+        M.nSlots = nRendered;
+        M.tiles = nullptr;
+        if (nRendered < nTiles) {       // (a batch of the whole frame needs no list: tile k is slot k)
+            RZ_HIP(c, hipMemcpyAsync(c->dAdList.p, hList, (size_t)nRendered * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+            M.tiles = static_cast<const int32_t*>(c->dAdList.p);
+        }
+        launch_adaptive_meter(M, c->stream);
+        RZ_HIP(c, hipGetLastError());
+        RZ_HIP(c, hipEventRecord(c->evAdaptive[2], c->stream));
+        RZ_HIP(c, hipMemcpyAsync(c->adPinned, c->dAdFlags.p, (size_t)nTiles, hipMemcpyDeviceToHost, c->stream));
+        RZ_HIP(c, hipStreamSynchronize(c->stream));
+        float msRender = 0.0f, msMeter = 0.0f;
+        RZ_HIP(c, hipEventElapsedTime(&msRender, c->evAdaptive[0], c->evAdaptive[1]));
+        RZ_HIP(c, hipEventElapsedTime(&msMeter, c->evAdaptive[1], c->evAdaptive[2]));
+        I.render_ms += msRender; I.meter_ms += msMeter;
+        int nActive = 0;
+        for (int t = 0; t < nTiles; ++t) {
+            if (rendered[t]) {
+                active[t] = (hFlags[t] & RZ_ADAPTIVE_ACTIVE) != 0;
+                current[t] = (hFlags[t] & RZ_ADAPTIVE_CURRENT) != 0;
+                I.samples_traced += tilePixels(t) * (uint64_t)P.batch_spp;
+            } else {
+                current[t] = 0;
+            }
+            nActive += active[t];
+            rendered[t] = 0;
+        }
+        I.batches = B;
+        I.tiles_active[B - 1] = nActive;
+        I.tiles_rendered[B - 1] = nRendered;
+        I.runs[B - 1] = (int32_t)runs.size();
+        if (nActive == 0 || B == P.max_batches) break;
+        adaptive_plan(active.data(), current.data(), (size_t)nTiles, mergeGap, P.max_runs, runs);
+    }
+    c->lastKernel = !use_samples(c) ? "rz_render_pixels"
+                  : c->sceneHasTransparency ? (c->lastCompact ? "rz_render_samples<glass>+pool" : "rz_render_samples<glass>")
+                                            : (c->lastGlobalPool ? "rz_render_samples+pool" : "rz_render_samples");
+    const hipMemcpyKind kind = host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+    if (tileBatches) RZ_HIP(c, hipMemcpyAsync(tileBatches, c->dAdBatches.p, (size_t)nTiles * 4, kind, c->stream));
+    if (tileError) RZ_HIP(c, hipMemcpyAsync(tileError, c->dAdError.p, (size_t)nTiles * 4, kind, c->stream));
+    RZ_HIP(c, hipStreamSynchronize(c->stream));
+    if (info) *info = I;
+    return RZ_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1210,6 +1415,9 @@ size_t rz_sizeof(int which) {
         case 34: return sizeof(rz_instance_coverage);
         case 35: return sizeof(rz_outline_params);
         case 37: return sizeof(rz_ao_params);            // (36 stays unassigned: probed as an unknown index)
+        case 38: return sizeof(rz_adaptive_params);
+        case 39: return sizeof(rz_adaptive_info);
+        case 40: return sizeof(rz_tile_run);
         default: return 0;
     }
 }
@@ -1257,10 +1465,13 @@ void rz_destroy(rz_ctx* c) {
                       &c->dQualViews, &c->dQualPartials, &c->dQualCost, &c->dUpGuideLo, &c->dUpGuideHi, &c->dUpOut,
                       &c->dStGuideLo, &c->dStGuideHi, &c->dAasList, &c->dAasCounts,
                       &c->dCost, &c->dCostCounters, &c->dCostPartials, &c->dCostStats, &c->dCostOut, &c->dCovSets,
-                      &c->dAoDirs, &c->dAoRaw, &c->dAoClaim})
+                      &c->dAoDirs, &c->dAoRaw, &c->dAoClaim,
+                      &c->dAdPrev, &c->dAdMoments, &c->dAdError, &c->dAdBatches, &c->dAdFlags, &c->dAdList})
         b->release();
     for (auto& kv : c->rigs) kv.second.release();
     for (hipEvent_t e : c->evSkin) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : c->evAdaptive) if (e) (void)hipEventDestroy(e);
+    if (c->adPinned) (void)hipHostFree(c->adPinned);
     if (c->refitPinned) (void)hipHostFree(c->refitPinned);
     if (c->tlasHostCounts) (void)hipHostFree(c->tlasHostCounts);
     if (c->relayoutPinned) (void)hipHostFree(c->relayoutPinned);
@@ -2380,6 +2591,29 @@ int rz_render(rz_ctx* c) {
 }
 int rz_render_counted(rz_ctx* c, rz_counters* out) {
     return guarded(c, "rz_render_counted", [&] { return do_render(c, true, out); });
+}
+int rz_render_adaptive(rz_ctx* c, const rz_adaptive_params* params, rz_adaptive_info* info, int32_t* tile_batches,
+                       size_t tile_batches_bytes, float* tile_error, size_t tile_error_bytes) {
+    return guarded(c, "rz_render_adaptive", [&] {
+        return render_adaptive(c, params, info, tile_batches, tile_batches_bytes, tile_error, tile_error_bytes);
+    });
+}
+int rz_adaptive_plan(const uint8_t* active, const uint8_t* current, size_t n_tiles, int merge_gap, int max_runs, rz_tile_run* runs,
+                     size_t cap, size_t* n_runs) {
+    const char* what = "rz_adaptive_plan";
+    if (!n_runs) return fail(nullptr, RZ_ERR_INVALID_ARG, "%s: null n_runs", what);
+    if ((!active || !current) && n_tiles > 0) return fail(nullptr, RZ_ERR_INVALID_ARG, "%s: null active or current", what);
+    if (!runs && cap > 0) return fail(nullptr, RZ_ERR_INVALID_ARG, "%s: null runs", what);
+    if (merge_gap < 0 || max_runs < 1) return fail(nullptr, RZ_ERR_INVALID_ARG, "%s: merge_gap %d, max_runs %d", what, merge_gap, max_runs);
+    if (n_tiles > ((size_t)1 << 30)) return fail(nullptr, RZ_ERR_INVALID_ARG, "%s: %zu tiles, at most 2^30", what, n_tiles);
+    return guarded(nullptr, what, [&]() -> int {
+        std::vector<rz_tile_run> out;
+        adaptive_plan(active, current, n_tiles, merge_gap, max_runs, out);
+        *n_runs = out.size();
+        if (out.size() > cap) return fail(nullptr, RZ_ERR_BUFFER_SIZE, "%s: %zu runs, room for %zu", what, out.size(), cap);
+        if (!out.empty()) std::memcpy(runs, out.data(), out.size() * sizeof(rz_tile_run));
+        return RZ_OK;
+    });
 }
 
 int rz_sync(rz_ctx* c) {

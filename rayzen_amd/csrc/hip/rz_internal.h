@@ -413,6 +413,25 @@ struct AoResolveLaunch {        // rz_ao_resolve
 void launch_ao_walks(const KParams& K, const AoWalkLaunch& A, hipStream_t stream);
 void launch_ao_resolve(const AoResolveLaunch& R, bool smooth, hipStream_t stream);
 
+// ---- rz_adaptive.hip
+constexpr unsigned RZ_ADAPTIVE_ACTIVE = 1u;     // a tile's flags: it still takes samples;
+constexpr unsigned RZ_ADAPTIVE_CURRENT = 2u;    // it has received every batch so far
+struct AdaptiveMeterLaunch {    // rz_adaptive_meter
+    const float4* accum;        // the accumulation after batch `batch`
+    float4* prev;               // tiles x 64, lane l of tile t at t * 64 + l: the accumulation after the tile's previous batch
+    float2* moments;            // tiles x 64: (S1, S2)
+    const int32_t* tiles;       // the nSlots tiles the batch rendered; null: tile k is slot k (batch 1)
+    int nSlots;
+    int width, height, tilesX;
+    int spp, batch;             // s and B (1-based)
+    int minBatches;
+    float threshold, floor;
+    float* tileError;           // per tile: E,
+    int32_t* tileBatches;       //   the batches it has received (read unless batch is 1),
+    uint8_t* tileFlags;         //   RZ_ADAPTIVE_ACTIVE | RZ_ADAPTIVE_CURRENT (read unless batch is 1)
+};
+void launch_adaptive_meter(const AdaptiveMeterLaunch& A, hipStream_t stream);
+
 // ---- rz_present.hip
 struct ProjBox;               // screen-space corners of one box (rz_present.hip)
 struct PresentParams {

@@ -112,6 +112,22 @@ def ao_directions():
     return out
 
 
+def adaptive_plan(active, current, merge_gap=8, max_runs=1):
+    """The runs of tiles rz_render_adaptive's next batch renders (rz_adaptive_plan), from one flag per tile in row-major tile
+    order: an (n, 2) int32 array of (first, len).  merge_gap and max_runs are taken as given.  Host-only, no GPU."""
+    a = np.ascontiguousarray(np.asarray(active) != 0, np.uint8).reshape(-1)
+    c = np.ascontiguousarray(np.asarray(current) != 0, np.uint8).reshape(-1)
+    if a.size != c.size:
+        raise ValueError("adaptive_plan: active and current differ in length")
+    runs = np.empty(a.size // 2 + 1, _lib.TILE_RUN_DTYPE)
+    n = C.c_size_t(0)
+    rc = _lib.hip().rz_adaptive_plan(a.ctypes.data, c.ctypes.data, a.size, int(merge_gap), int(max_runs), runs.ctypes.data, runs.size,
+                                     C.byref(n))
+    if rc != 0:
+        raise RayZenError("rz_adaptive_plan", rc, _lib.hip().rz_last_error(None).decode())
+    return runs[:n.value].view(np.int32).reshape(-1, 2).copy()
+
+
 class Renderer:
     def __init__(self, device=0, flags=0):
         self._L = _lib.hip()
@@ -1169,6 +1185,54 @@ class Renderer:
                                                  C.c_void_p(ao_ptr), n * 4 if ao_ptr else 0, C.c_void_p(rgb32f_ptr),
                                                  n * 12 if rgb32f_ptr else 0, C.c_void_p(rgba8_ptr), n * 4 if rgba8_ptr else 0, 0),
                     "rz_ambient_occlusion")
+
+    # -- adaptive sampling (rz_render_adaptive) -------------------------------------------
+    @staticmethod
+    def _adaptive_args(batch_spp, min_batches, max_batches, threshold, luminance_floor, merge_gap, max_runs, flags):
+        p = _lib.AdaptiveParams()
+        p.batch_spp, p.min_batches, p.max_batches = int(batch_spp or 0), int(min_batches or 0), int(max_batches or 0)
+        p.threshold, p.luminance_floor = float(threshold or 0.0), float(luminance_floor or 0.0)
+        # (0 tiles: the header's -1; None: the default)
+        p.merge_gap = 0 if merge_gap is None else (-1 if int(merge_gap) == 0 else int(merge_gap))
+        p.max_runs, p.flags = int(max_runs or 0), flags
+        return p
+
+    @staticmethod
+    def _adaptive_info(info):
+        n = info.batches
+        return dict(batches=n, n_tiles=info.n_tiles, samples_traced=int(info.samples_traced), samples_uniform=int(info.samples_uniform),
+                    render_ms=float(info.render_ms), meter_ms=float(info.meter_ms), tiles_active=list(info.tiles_active[:n]),
+                    tiles_rendered=list(info.tiles_rendered[:n]), runs=list(info.runs[:n]))
+
+    def render_adaptive(self, batch_spp=None, min_batches=None, max_batches=None, threshold=None, luminance_floor=None, merge_gap=None,
+                        max_runs=None):
+        """The frame of the last set_frame in batches of batch_spp samples, sampling on only the 8 x 8 tiles whose estimated error
+        is above `threshold` (include/rayzen_hip.h: rz_render_adaptive; None: the default).  The result is the accumulation
+        (read_accum, present, ...: a is each pixel's own sample count).  Returns (info, tile_batches, tile_error): a dict of
+        rz_adaptive_info's fields with the per-batch lists cut to the batches run, the batches every tile received ((tilesY,
+        tilesX) int32, row 0 = bottom) and its last error E (float32).  The frame's spp and sample_base are ignored.  Returns
+        when the frame is complete.  A zero stands for the default in every field of rz_adaptive_params, so threshold=0.0 is the
+        default 0.02, not "retire at E = 0" (pass a negative threshold to retire nothing); merge_gap is the exception here:
+        merge_gap=0 means what it says, no merging across gaps (the header's -1), and None the default."""
+        p = self._adaptive_args(batch_spp, min_batches, max_batches, threshold, luminance_floor, merge_gap, max_runs, _lib.ADAPTIVE_HOST)
+        ty, tx = (self.height + 7) // 8, (self.width + 7) // 8
+        batches, error = np.empty((ty, tx), np.int32), np.empty((ty, tx), np.float32)
+        info = _lib.AdaptiveInfo()
+        self._check(self._L.rz_render_adaptive(self._c, C.byref(p), C.byref(info), batches.ctypes.data, batches.nbytes,
+                                               error.ctypes.data, error.nbytes), "rz_render_adaptive")
+        return self._adaptive_info(info), batches, error
+
+    def render_adaptive_device(self, tile_batches_ptr=None, tile_error_ptr=None, batch_spp=None, min_batches=None, max_batches=None,
+                               threshold=None, luminance_floor=None, merge_gap=None, max_runs=None):
+        """rz_render_adaptive with the per-tile outputs in device memory (4-B aligned, tiles * 4 B each; each may be None).  The
+        call still returns when the frame is complete: the plan of every batch is made on the host.  Returns the info dict."""
+        p = self._adaptive_args(batch_spp, min_batches, max_batches, threshold, luminance_floor, merge_gap, max_runs, 0)
+        n = ((self.height + 7) // 8) * ((self.width + 7) // 8) * 4
+        info = _lib.AdaptiveInfo()
+        self._check(self._L.rz_render_adaptive(self._c, C.byref(p), C.byref(info), C.c_void_p(tile_batches_ptr),
+                                               n if tile_batches_ptr else 0, C.c_void_p(tile_error_ptr), n if tile_error_ptr else 0),
+                    "rz_render_adaptive")
+        return self._adaptive_info(info)
 
     # -- convenience -----------------------------------------------------------
     def render_scene(self, scene, width, height, spp, bounce_budget, num_lights=None, tile_rank=0, tile_nranks=1,
