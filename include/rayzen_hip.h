@@ -1390,6 +1390,74 @@ int rz_render_adaptive(rz_ctx* ctx, const rz_adaptive_params* params, rz_adaptiv
 int rz_adaptive_plan(const uint8_t* active, const uint8_t* current, size_t n_tiles, int merge_gap, int max_runs,
                      rz_tile_run* runs, size_t cap, size_t* n_runs);
 
+/* ------------------------------------------------------------------------ */
+/* Drawing into the scene: depth-tested 3D lines (new)                      */
+/* ------------------------------------------------------------------------ */
+/* rz_draw_lines blends n line segments given in world space, or in the space of an instance, over a presented image, in place,
+ * each tested per pixel against the depth of a hit image (rz_lines.hip): a ground grid, gizmo axes, the box of a selection, a
+ * camera frustum, the edges of a mesh.  All arithmetic is binary32 with one rounding per operation, no fused multiply-add; `/`
+ * and sqrt are correctly rounded.  m4v(M, x, y, z, w) is the column-major product with each row summed left to right,
+ * ((M[r] * x + M[4 + r] * y) + M[8 + r] * z) + M[12 + r] * w.  clamp(x, lo, hi) = min(max(x, lo), hi) with minNum / maxNum (a NaN
+ * x gives lo).  For line i, in this order:
+ *  1 World ends.  instance < 0: a and b, bit for bit.  Otherwise (x, y, z) of m4v(M, a, 1) and of m4v(M, b, 1) with M the
+ *    `transform` of that instance of binding 9 as it stands on the device after the last rz_update_transforms.  An instance >=
+ *    the instance count is RZ_ERR_INVALID_ARG on the host path; on the device path the line is dropped.
+ *  2 Clip space.  VP = proj * view, VP[4 c + r] = ((proj[r] * view[4 c] + proj[4 + r] * view[4 c + 1]) + proj[8 + r] *
+ *    view[4 c + 2]) + proj[12 + r] * view[4 c + 3] (rz_present's).  A = m4v(VP, a, 1), B = m4v(VP, b, 1).
+ *  3 Near clip on w, n = near_w.  If neither A.w >= n nor B.w >= n the line is dropped (a NaN fails the comparison).  If only A
+ *    fails: k = (n - A.w) / (B.w - A.w), A.x = A.x + k * (B.x - A.x), A.y likewise, A.w = n.  If only B fails, the same with the
+ *    roles swapped.  There is no far clip.
+ *  4 Screen ends.  sx = (x / w * 0.5f + 0.5f) * (float)width, sy likewise with height, for both ends: A_s and B_s.  A line with
+ *    a non-finite screen coordinate is dropped.  ia = 1.0f / A.w, ib = 1.0f / B.w.
+ *  5 Per pixel p = (px, py), centre (fx, fy) = ((float)px + 0.5f, (float)py + 0.5f), row 0 = the bottom row.  ab = B_s - A_s,
+ *    L = ab.x * ab.x + ab.y * ab.y, pa = (fx, fy) - A_s;  t = L == 0 ? 0 : clamp((pa.x * ab.x + pa.y * ab.y) / L, 0, 1);
+ *    dx = fx - (A_s.x + t * ab.x), dy likewise, d = sqrt(dx * dx + dy * dy): rz_present's distanceToSegment.  hw = width * 0.5f.
+ *    Hard edge (smooth = 0): covered iff d < hw, cov = 1.  Smooth: cov = clamp((hw + 0.5f) - d, 0, 1), covered iff cov > 0.
+ *  6 Depth, for a covered pixel.  w_s = 1.0f / (ia + t * (ib - ia)).  If hits is given and the pixel's record is a hit (instance
+ *    >= 0): w_h = ((VP[3] * X + VP[7] * Y) + VP[11] * Z) + VP[15] of its point (X, Y, Z), and the line is OCCLUDED at p iff
+ *    w_s * (1.0f - depth_bias) > w_h.  alpha = (float)alpha_byte / 255.0f, times hidden_alpha if occluded, then times cov.
+ *    alpha == 0: the line does not touch p.
+ *  7 Blend, over the lines that touch p in ascending index: o = in * (1.0f - alpha) + c * alpha per channel, c = (float)byte /
+ *    255.0f.  rgb32f is blended as it stands.  An rgba8 pixel is converted once, (float)byte / 255.0f, blended by all its lines in
+ *    float and quantised once as rz_present does, rint(clamp(o, 0, 1) * 255); its alpha byte is kept.  A pixel no line touches is
+ *    not written and keeps its bytes, non-finite floats included.
+ * `frame` is read as rz_render_editor reads it -- width, height, view and proj only; no rz_set_frame is needed and the tile
+ * fields are ignored.  width and height are at most 2^23 (a pixel centre is exact in binary32).  params NULL: the defaults.
+ * hits is optional: NULL means no depth test, every line counts as visible; else width * height rz_hit, rz_render_editor's hits
+ * or the guides of rz_denoise and its relatives.  Each image is optional, at least one must be given.  n = 0 is RZ_OK and writes
+ * nothing; n is at most 2^20.  A scene is needed only if some line has instance >= 0.
+ * Conventions are rz_outline's.  Pointers are DEVICE memory (lines and hits 16-byte, the images 4-byte aligned; rgba8 is read and
+ * written as 4-byte pixels) and the work is queued on the context's stream; with RZ_LINES_HOST they are host memory, staged, and
+ * the call returns when the images are written.  The lines are binned on the device into lists per 128 x 128 pixels, made with
+ * ballots and prefix sums in line order, in a workspace the context keeps and grows on demand: a device-path call whose lists
+ * might not fit what it holds (more than 4 MiB if every line met every cell) waits for the count of its entries before it
+ * queues the rest.  The bytes are the same on every run.  A failing call launches nothing that writes the images and leaves them
+ * untouched; that includes RZ_ERR_NO_MEMORY and RZ_ERR_HIP from growing the workspace.  No render, temporal or display state and
+ * not the frame of rz_set_frame is touched.
+ * Errors.  RZ_ERR_INVALID_ARG: null context or frame; unknown flags; a bad frame size; width outside [1, 16], near_w not > 0,
+ * depth_bias outside [0, 1), hidden_alpha outside [0, 1], any of them not finite, smooth not 0 or 1, a non-zero reserved word;
+ * NULL lines with n > 0; n > 2^20; both images NULL; a misaligned device pointer; on the host path a line whose instance is not
+ * below the instance count.  RZ_ERR_BUFFER_SIZE: hits or an image too small.  RZ_ERR_NOT_READY: on the host path a line names an
+ * instance and no scene has been uploaded (on the device path the lines are not read on the host: without a scene every line
+ * that names an instance is dropped).  Cost: profiles/lines/README.md.
+ * (Additive: RZ_ABI_VERSION stays 5; rz_sizeof(41) stays 0.) */
+typedef struct rz_line {                 /* 32 B; rz_sizeof(42) */
+    float    a[3];  uint32_t color;      /* bytes r, g, b, alpha in memory order */
+    float    b[3];  int32_t  instance;   /* < 0: a, b are world space; else local to that instance of binding 9 */
+} rz_line;
+typedef struct rz_lines_params {         /* NULL = defaults; 32 B; rz_sizeof(43) */
+    float   width;                       /* full line width in pixels, 1..16; default 1.5 */
+    float   near_w;                      /* clip threshold on clip-space w, > 0; default 0.01 */
+    float   depth_bias;                  /* relative, 0 <= bias < 1; default 0x1p-8 */
+    float   hidden_alpha;                /* 0..1: factor on alpha where the line is behind the hit; 0 = hidden; default 0 */
+    int32_t smooth;                      /* 0 hard edge, 1 one-pixel coverage ramp; default 0 */
+    int32_t reserved[3];                 /* must be 0 */
+} rz_lines_params;
+#define RZ_LINES_HOST 1u                 /* pointers are host memory, as RZ_DENOISE_HOST */
+int rz_draw_lines(rz_ctx* ctx, const rz_frame_params* frame, const rz_lines_params* params,
+                  const rz_line* lines, size_t n, const rz_hit* hits, size_t hits_bytes,
+                  uint8_t* rgba8, size_t rgba8_bytes, float* rgb32f, size_t rgb32f_bytes, unsigned flags);
+
 /* Number of HIP devices visible to the process (0 without a GPU). */
 int rz_device_count(void);
 
@@ -1416,7 +1484,7 @@ const char* rz_source_hash(void);
  * 14 display_params, 15 display_info, 17 skin_triangle, 18 morph_triangle, 20 mesh_quality,
  * 21 upscale_params, 23 seethrough_params, 24 chain, 26 antialias_params, 28 pixel_cost, 29 cost_params, 30 cost_view_params,
  * 31 cost_stats, 33 coverage_params, 34 instance_coverage, 35 outline_params, 37 ao_params, 38 adaptive_params, 39 adaptive_info,
- * 40 tile_run (13, 16, 19, 22, 25, 27, 32 and 36 are unassigned and
+ * 40 tile_run, 42 line, 43 lines_params (13, 16, 19, 22, 25, 27, 32, 36 and 41 are unassigned and
  * return 0, as every unknown index does). */
 size_t rz_sizeof(int which);
 

@@ -34,6 +34,7 @@ HIP_SYMBOLS = (
     "rz_coverage", "rz_outline",
     "rz_ambient_occlusion", "rz_ao_directions",
     "rz_render_adaptive", "rz_adaptive_plan",
+    "rz_draw_lines",
 )
 ABI_VERSION = 5         # RZ_ABI_VERSION of the include/rayzen_hip.h this file mirrors
 # the symbols include/rayzen_host.h declares
@@ -284,6 +285,20 @@ ADAPTIVE_DEFAULTS = dict(batch_spp=8, min_batches=4, max_batches=8, threshold=0.
 SIZEOF_ADAPTIVE_PARAMS, SIZEOF_ADAPTIVE_INFO, SIZEOF_TILE_RUN = 38, 39, 40      # their rz_sizeof indices
 
 
+class LinesParams(C.Structure):
+    """rz_lines_params of include/rayzen_hip.h (32 B)."""
+    _fields_ = [("width", C.c_float), ("near_w", C.c_float), ("depth_bias", C.c_float), ("hidden_alpha", C.c_float),
+                ("smooth", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+# rz_line as a numpy record: color = bytes r, g, b, alpha in memory order; instance < 0 = world space
+LINE_DTYPE = np.dtype([("a", "<f4", 3), ("color", "u1", 4), ("b", "<f4", 3), ("instance", "<i4")])
+LINES_DEFAULTS = dict(width=1.5, near_w=0.01, depth_bias=2.0 ** -8, hidden_alpha=0.0, smooth=0)
+LINES_HOST = 1                          # RZ_LINES_HOST
+LINES_MAX = 1 << 20                     # lines per call
+SIZEOF_LINE, SIZEOF_LINES_PARAMS = 42, 43       # their rz_sizeof indices (41 is unassigned)
+
+
 class SkinTriangle(C.Structure):
     """rz_skin_triangle of include/rayzen_hip.h (64 B)."""
     _fields_ = [("bones", C.c_uint32 * 3), ("pad", C.c_uint32), ("weights", (C.c_float * 4) * 3)]
@@ -417,7 +432,8 @@ def hip():
                                 ("rz_ambient_occlusion", i, [vp, C.POINTER(FrameParams), vp, vp, sz, vp, sz, vp, sz, vp, sz, C.c_uint]),
                                 ("rz_ao_directions", i, [vp, sz]),
                                 ("rz_render_adaptive", i, [vp, C.POINTER(AdaptiveParams), C.POINTER(AdaptiveInfo), vp, sz, vp, sz]),
-                                ("rz_adaptive_plan", i, [vp, vp, sz, i, i, vp, sz, C.POINTER(sz)])):
+                                ("rz_adaptive_plan", i, [vp, vp, sz, i, i, vp, sz, C.POINTER(sz)]),
+                                ("rz_draw_lines", i, [vp, C.POINTER(FrameParams), vp, vp, sz, vp, sz, vp, sz, vp, sz, C.c_uint])):
             try:
                 fn = getattr(L, name)
                 fn.restype, fn.argtypes = res, args

@@ -239,6 +239,9 @@ struct rz_ctx {
     uint8_t* adPinned = nullptr;
     size_t adPinnedCap = 0;
     hipEvent_t evAdaptive[3] = {nullptr, nullptr, nullptr};
+    // rz_draw_lines (rz_lines.hip): the projected records (52 B per line), the counts and offsets of the coarse lists (12 B per
+    // cell and segment, and the total) and the lists themselves; allocated by the first call, grown on demand and kept
+    DevBuf dLnRec, dLnCells, dLnList;
 };
 
 namespace {
@@ -1418,6 +1421,8 @@ size_t rz_sizeof(int which) {
         case 38: return sizeof(rz_adaptive_params);
         case 39: return sizeof(rz_adaptive_info);
         case 40: return sizeof(rz_tile_run);
+        case 42: return sizeof(rz_line);                 // (41 stays unassigned: probed as an unknown index)
+        case 43: return sizeof(rz_lines_params);
         default: return 0;
     }
 }
@@ -1466,7 +1471,8 @@ void rz_destroy(rz_ctx* c) {
                       &c->dStGuideLo, &c->dStGuideHi, &c->dAasList, &c->dAasCounts,
                       &c->dCost, &c->dCostCounters, &c->dCostPartials, &c->dCostStats, &c->dCostOut, &c->dCovSets,
                       &c->dAoDirs, &c->dAoRaw, &c->dAoClaim,
-                      &c->dAdPrev, &c->dAdMoments, &c->dAdError, &c->dAdBatches, &c->dAdFlags, &c->dAdList})
+                      &c->dAdPrev, &c->dAdMoments, &c->dAdError, &c->dAdBatches, &c->dAdFlags, &c->dAdList,
+                      &c->dLnRec, &c->dLnCells, &c->dLnList})
         b->release();
     for (auto& kv : c->rigs) kv.second.release();
     for (hipEvent_t e : c->evSkin) if (e) (void)hipEventDestroy(e);
@@ -3540,6 +3546,154 @@ static int outline_impl(rz_ctx* c, const rz_outline_params* P, const int32_t* id
     return host ? stage.fetch() : RZ_OK;
 }
 
+// rz_draw_lines (rz_lines.hip): no frame of rz_set_frame, and a scene only for the lines that name an instance; the images are
+// blended in place.  Everything that can fail without the counts is done before the first launch; in the one case where the
+// lists' size has to be waited for, the kernels queued by then have written the context's workspace only.
+static const rz_lines_params kLinesDefaults = {1.5f, 0.01f, 0x1p-8f, 0.0f, 0, {0, 0, 0}};
+
+static int lines_impl(rz_ctx* c, const rz_frame_params* f, const rz_lines_params* pp, const rz_line* lines, size_t n, const rz_hit* hits,
+                      size_t hits_bytes, uint8_t* rgba8, size_t rgba8_bytes, float* rgb32f, size_t rgb32f_bytes, unsigned flags) {
+    const char* what = "rz_draw_lines";
+    if (!c) return fail(nullptr, RZ_ERR_INVALID_ARG, "%s: null context", what);
+    if (!f) return fail(c, RZ_ERR_INVALID_ARG, "%s: null frame", what);
+    if (flags & ~RZ_LINES_HOST) return fail(c, RZ_ERR_INVALID_ARG, "%s: unknown flags 0x%x", what, flags);
+    if (f->width <= 0 || f->height <= 0 || f->width > (1 << 23) || f->height > (1 << 23))
+        return fail(c, RZ_ERR_INVALID_ARG, "%s: bad size %dx%d", what, f->width, f->height);
+    const size_t np = (size_t)f->width * (size_t)f->height;
+    if (np > (size_t)std::numeric_limits<int32_t>::max())
+        return fail(c, RZ_ERR_INVALID_ARG, "%s: %zu pixels, at most %d per frame", what, np, std::numeric_limits<int32_t>::max());
+    const rz_lines_params& P = pp ? *pp : kLinesDefaults;
+    if (!(P.width >= 1.0f && P.width <= 16.0f)) return fail(c, RZ_ERR_INVALID_ARG, "%s: width %g outside [1, 16]", what, (double)P.width);
+    if (!(P.near_w > 0.0f && P.near_w < INFINITY)) return fail(c, RZ_ERR_INVALID_ARG, "%s: near_w %g (finite, > 0)", what, (double)P.near_w);
+    if (!(P.depth_bias >= 0.0f && P.depth_bias < 1.0f)) return fail(c, RZ_ERR_INVALID_ARG, "%s: depth_bias %g outside [0, 1)", what, (double)P.depth_bias);
+    if (!(P.hidden_alpha >= 0.0f && P.hidden_alpha <= 1.0f))
+        return fail(c, RZ_ERR_INVALID_ARG, "%s: hidden_alpha %g outside [0, 1]", what, (double)P.hidden_alpha);
+    if (P.smooth != 0 && P.smooth != 1) return fail(c, RZ_ERR_INVALID_ARG, "%s: smooth %d (0 or 1)", what, P.smooth);
+    if (P.reserved[0] || P.reserved[1] || P.reserved[2]) return fail(c, RZ_ERR_INVALID_ARG, "%s: reserved words must be 0", what);
+    if (!lines && n) return fail(c, RZ_ERR_INVALID_ARG, "%s: null lines", what);
+    if (n > RZ_LINES_MAX) return fail(c, RZ_ERR_INVALID_ARG, "%s: %zu lines, at most %zu per call", what, n, RZ_LINES_MAX);
+    if (!rgba8 && !rgb32f) return fail(c, RZ_ERR_INVALID_ARG, "%s: neither rgba8 nor rgb32f given", what);
+    const bool host = (flags & RZ_LINES_HOST) != 0;
+    if (!host && (((reinterpret_cast<uintptr_t>(lines) | reinterpret_cast<uintptr_t>(hits)) & 15u) ||
+                  ((reinterpret_cast<uintptr_t>(rgba8) | reinterpret_cast<uintptr_t>(rgb32f)) & 3u)))
+        return fail(c, RZ_ERR_INVALID_ARG, "%s: device pointers must be 16-byte (lines, hits) or 4-byte (rgba8, rgb32f) aligned", what);
+    const size_t bLines = n * sizeof(rz_line), bHits = np * sizeof(rz_hit), bRgba = np * 4, bRgb = np * 3 * sizeof(float);
+    if (hits && hits_bytes < bHits) return fail(c, RZ_ERR_BUFFER_SIZE, "%s: hits needs %zu bytes, got %zu", what, bHits, hits_bytes);
+    if (rgba8 && rgba8_bytes < bRgba) return fail(c, RZ_ERR_BUFFER_SIZE, "%s: rgba8 needs %zu bytes, got %zu", what, bRgba, rgba8_bytes);
+    if (rgb32f && rgb32f_bytes < bRgb) return fail(c, RZ_ERR_BUFFER_SIZE, "%s: rgb32f needs %zu bytes, got %zu", what, bRgb, rgb32f_bytes);
+    // the instances a line may name: those of a complete scene.  Host lines are checked here; device lines in the kernel
+    bool scene = true;
+    for (int b : {RZ_BIND_TRIANGLES, RZ_BIND_MATERIALS, RZ_BIND_LIGHTS, RZ_BIND_TLAS_NODES, RZ_BIND_TLAS_INDICES, RZ_BIND_BLAS_NODES,
+                  RZ_BIND_BLAS_INDICES, RZ_BIND_INSTANCES})
+        scene = scene && c->present[b];
+    size_t nInst = scene ? hostCount<rz_bvh_instance>(c, RZ_BIND_INSTANCES) : 0;
+    bool named = !host;
+    if (host)
+        for (size_t i = 0; i < n; ++i) {
+            if (lines[i].instance < 0) continue;
+            if (!scene) return fail(c, RZ_ERR_NOT_READY, "%s: line %zu names instance %d and no scene has been uploaded", what, i, lines[i].instance);
+            if ((size_t)lines[i].instance >= nInst)
+                return fail(c, RZ_ERR_INVALID_ARG, "%s: line %zu names instance %d of %zu", what, i, lines[i].instance, nInst);
+            named = true;
+        }
+    if (n == 0) return RZ_OK;
+    int rc = RZ_OK;
+    if (scene && named) rc = finalize(c);           // the transforms as the last upload / rz_update_transforms left them
+    else nInst = 0;
+    if (rc != RZ_OK) return rc;
+    LinesLaunch V{};
+    V.n = (int)n;
+    V.instances = static_cast<const DevInstance*>(c->dInst.p);
+    V.nInst = (int)std::min<size_t>(nInst, (size_t)std::numeric_limits<int32_t>::max());
+    // proj * view as rz_present sums it
+    const float* A = f->proj; const float* B = f->view;
+    for (int col = 0; col < 4; ++col)
+        for (int row = 0; row < 4; ++row)
+            V.viewProj[col * 4 + row] = ((A[0 * 4 + row] * B[col * 4 + 0] + A[1 * 4 + row] * B[col * 4 + 1]) +
+                                         A[2 * 4 + row] * B[col * 4 + 2]) + A[3 * 4 + row] * B[col * 4 + 3];
+    V.width = f->width; V.height = f->height;
+    V.halfWidth = P.width * 0.5f;
+    V.nearW = P.near_w;
+    V.depthKeep = 1.0f - P.depth_bias;
+    V.hiddenAlpha = P.hidden_alpha;
+    V.smooth = P.smooth;
+    V.cellsX = (f->width + RZ_LINES_CELL - 1) / RZ_LINES_CELL;
+    V.cells = V.cellsX * ((f->height + RZ_LINES_CELL - 1) / RZ_LINES_CELL);
+    V.nSeg = (int)((n + RZ_LINES_SEG - 1) / RZ_LINES_SEG);
+    const size_t slots = (size_t)V.cells * V.nSeg, offOffsets = (slots * sizeof(unsigned) + 15) & ~size_t(15);
+    // the workspace: records, counts and offsets; and the lists at once if they fit whatever the counts will be -- the context
+    // holds that much already, or it is little (RZ_LINES_DIRECT_BYTES; the variable: a test aid, same bytes)
+    const char* unbinnedEnv = std::getenv("RZ_LINES_UNBINNED");     // A/B aid (profiles/lines/): no lists, same bytes
+    const bool binned = !(unbinnedEnv && std::atoi(unbinnedEnv) != 0);
+    size_t direct = RZ_LINES_DIRECT_BYTES;
+    if (const char* e = std::getenv("RZ_LINES_DIRECT_BYTES")) direct = (size_t)std::max<long long>(0, std::atoll(e));
+    const size_t worst = n * (size_t)V.cells * sizeof(int32_t);
+    const bool wait = binned && worst > direct && !(c->dLnList.p && worst <= c->dLnList.cap);
+    alloc_point(c);
+    rc = ensure(c, c->dLnRec, n * 52);
+    if (rc != RZ_OK) return rc;
+    alloc_point(c);
+    rc = ensure(c, c->dLnCells, offOffsets + (slots + 1) * sizeof(unsigned long long));
+    if (rc != RZ_OK) return rc;
+    if (binned && !wait) {
+        alloc_point(c);
+        if (ensure(c, c->dLnList, worst) != RZ_OK) {
+            (void)hipGetLastError();
+            return fail(c, RZ_ERR_NO_MEMORY, "%s: no device memory for the lists (%zu bytes)", what, worst);
+        }
+    }
+    char* rec = static_cast<char*>(c->dLnRec.p);
+    V.geo = reinterpret_cast<float4*>(rec);
+    V.misc = reinterpret_cast<float4*>(rec + n * 16);
+    V.rect = reinterpret_cast<float4*>(rec + n * 32);
+    V.reach = reinterpret_cast<float*>(rec + n * 48);
+    V.counts = static_cast<unsigned*>(c->dLnCells.p);
+    V.offsets = reinterpret_cast<unsigned long long*>(static_cast<char*>(c->dLnCells.p) + offOffsets);
+    // host buffers: the lines, then the hits in dRayIn; the images in dRayOut, copied in, blended there and copied back
+    HostStage stage(c, host);
+    const int sRgba = stage.add(rgba8, bRgba), sRgb = stage.add(rgb32f, bRgb);
+    rc = stage.place();
+    if (rc != RZ_OK) return rc;
+    V.rgba8 = stage.dev<uchar4>(sRgba);
+    V.rgb = stage.dev<float>(sRgb);
+    V.lines = lines;
+    V.hits = reinterpret_cast<const float4*>(hits);
+    if (host) {
+        const size_t offHits = (bLines + 15) & ~size_t(15);
+        rc = ensure(c, c->dRayIn, offHits + (hits ? bHits : 0));
+        if (rc != RZ_OK) return rc;
+        char* in = static_cast<char*>(c->dRayIn.p);
+        RZ_HIP(c, hipMemcpyAsync(in, lines, bLines, hipMemcpyHostToDevice, c->stream));
+        if (hits) RZ_HIP(c, hipMemcpyAsync(in + offHits, hits, bHits, hipMemcpyHostToDevice, c->stream));
+        if (rgba8) RZ_HIP(c, hipMemcpyAsync(V.rgba8, rgba8, bRgba, hipMemcpyHostToDevice, c->stream));
+        if (rgb32f) RZ_HIP(c, hipMemcpyAsync(V.rgb, rgb32f, bRgb, hipMemcpyHostToDevice, c->stream));
+        V.lines = in;
+        V.hits = hits ? reinterpret_cast<const float4*>(in + offHits) : nullptr;
+    }
+    launch_lines_project(V, c->stream);
+    RZ_HIP(c, hipGetLastError());
+    if (binned) {
+        launch_lines_count(V, c->stream);
+        RZ_HIP(c, hipGetLastError());
+        if (wait) {
+            unsigned long long total = 0;
+            RZ_HIP(c, hipMemcpyAsync(&total, V.offsets + slots, sizeof total, hipMemcpyDeviceToHost, c->stream));
+            RZ_HIP(c, hipStreamSynchronize(c->stream));
+            alloc_point(c);
+            if (ensure(c, c->dLnList, (size_t)total * sizeof(int32_t)) != RZ_OK) {
+                (void)hipGetLastError();
+                return fail(c, RZ_ERR_NO_MEMORY, "%s: no device memory for the lists (%llu entries)", what, total);
+            }
+        }
+        V.list = static_cast<int*>(c->dLnList.p);
+        launch_lines_fill(V, c->stream);
+        RZ_HIP(c, hipGetLastError());
+    }
+    launch_lines_draw(V, c->stream);
+    RZ_HIP(c, hipGetLastError());
+    return host ? stage.fetch() : RZ_OK;
+}
+
 // rz_denoise_temporal / rz_present_temporal (rz_temporal.hip).  They read what rz_denoise reads and touch no render state; the
 // history they keep is the context's own (rz_ctx: dTmp*).
 static const rz_temporal_params kTemporalDefaults = {0.2f, 0.2f, 32, 0.9f, 2.0f, 5, 0.5f, 128.0f, 1.0f, 1, {0, 0, 0, 0, 0, 0}};
@@ -4563,6 +4717,13 @@ int rz_outline(rz_ctx* c, const rz_outline_params* params, const int32_t* ids, s
                size_t n_instances, uint8_t* rgba8, size_t rgba8_bytes, float* rgb32f, size_t rgb32f_bytes, unsigned flags) {
     return guarded(c, "rz_outline", [&] {
         return outline_impl(c, params, ids, ids_bytes, selected, n_instances, rgba8, rgba8_bytes, rgb32f, rgb32f_bytes, flags);
+    });
+}
+int rz_draw_lines(rz_ctx* c, const rz_frame_params* frame, const rz_lines_params* params, const rz_line* lines, size_t n,
+                  const rz_hit* hits, size_t hits_bytes, uint8_t* rgba8, size_t rgba8_bytes, float* rgb32f, size_t rgb32f_bytes,
+                  unsigned flags) {
+    return guarded(c, "rz_draw_lines", [&] {
+        return lines_impl(c, frame, params, lines, n, hits, hits_bytes, rgba8, rgba8_bytes, rgb32f, rgb32f_bytes, flags);
     });
 }
 int rz_display_reset(rz_ctx* c) {

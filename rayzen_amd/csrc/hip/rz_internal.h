@@ -380,6 +380,43 @@ struct OutlineLaunch {          // rz_outline_kernel
 };
 void launch_outline(OutlineLaunch O, hipStream_t stream);
 
+// ---- rz_lines.hip
+constexpr int RZ_LINES_CELL = 128;              // pixels per side of a cell of the coarse lists
+constexpr int RZ_LINES_SEG = 4096;              // lines a workgroup of the coarse pass scans: a cell's list is made by ceil(n / SEG) of them
+constexpr size_t RZ_LINES_MAX = (size_t)1 << 20;        // lines per call
+constexpr size_t RZ_LINES_DIRECT_BYTES = (size_t)4 << 20;   // a list workspace that is no larger even if every line meets every cell is
+                                                            // taken whole, and the call never waits for the counts
+struct LinesLaunch {            // rz_lines_project, rz_lines_bin, rz_lines_draw
+    const void* lines;          // n x rz_line
+    int n;
+    const DevInstance* instances;   // step 1 reads fwd; nInst 0: no scene
+    int nInst;
+    float viewProj[16];         // proj * view, summed as rz_present's
+    int width, height;
+    float halfWidth;            // hw = width * 0.5f
+    float nearW;
+    float depthKeep;            // 1.0f - depth_bias
+    float hiddenAlpha;
+    int smooth;
+    float4* geo;                // the projected records, n each: (A_s.x, A_s.y, ab.x, ab.y),
+    float4* misc;               //   (ia, ib - ia, colour bits, L),
+    float4* rect;               //   the cull rectangle (lox, loy, hix, hiy), empty for a dropped line,
+    float* reach;               //   and what a cell or a tile adds to its own radius (rz_lines.hip: LINE CULL)
+    int cellsX, cells;          // cells of RZ_LINES_CELL^2 pixels, row by row
+    int nSeg;                   // ceil(n / RZ_LINES_SEG)
+    unsigned* counts;           // cells x nSeg: lines of segment s that meet cell c at [c * nSeg + s]
+    unsigned long long* offsets;    // their exclusive scan, cells * nSeg + 1 entries
+    int* list;                  // the lists, offsets[cells * nSeg] indices; null: no lists, every tile walks all n lines
+    const float4* hits;         // width x height rz_hit (3 float4), optional
+    uchar4* rgba8;              // images blended in place, each optional
+    float* rgb;
+    int tilesX;                 // (set by launch_lines_draw)
+};
+void launch_lines_project(const LinesLaunch& V, hipStream_t stream);
+void launch_lines_count(const LinesLaunch& V, hipStream_t stream);      // the counts and their scan
+void launch_lines_fill(const LinesLaunch& V, hipStream_t stream);
+void launch_lines_draw(LinesLaunch V, hipStream_t stream);
+
 // ---- rz_ao.hip
 constexpr int RZ_AO_DIRS = 256;                 // points of the direction table (rz_ao_directions)
 constexpr int RZ_AO_COUNTERS = 256;              // the most counters rz_ao_walks' waves claim units from (128 B apart)

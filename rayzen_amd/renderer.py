@@ -44,6 +44,7 @@ MESH_QUALITY = np.dtype([("node_offset", "<i4"), ("index_offset", "<i4"), ("tri_
 PIXEL_COST_DTYPE = _lib.PIXEL_COST_DTYPE # rz_pixel_cost (32 B): what render_cost returns
 INSTANCE_COVERAGE_DTYPE = _lib.INSTANCE_COVERAGE_DTYPE   # rz_instance_coverage (32 B): what coverage returns
 CHAIN_DTYPE = _lib.CHAIN_DTYPE           # rz_chain (16 B): what upscale(see_through=..., chains=True) returns
+LINE_DTYPE = _lib.LINE_DTYPE             # rz_line (32 B): what draw_lines takes (rayzen_amd.lines makes them)
 
 
 def make_rays(origins, dirs, max_dist=1e30):
@@ -1144,6 +1145,45 @@ class Renderer:
         self._check(self._L.rz_outline(self._c, C.byref(p), C.c_void_p(ids_ptr), n * 4, C.c_void_p(selected_ptr), int(n_instances),
                                        C.c_void_p(rgba8_ptr), n * 4 if rgba8_ptr else 0, C.c_void_p(rgb32f_ptr),
                                        n * 12 if rgb32f_ptr else 0, 0), "rz_outline")
+
+    # -- drawing into the scene (rz_draw_lines) -------------------------------------------
+    def _lines_args(self, frame, width, near_w, depth_bias, hidden_alpha, smooth):
+        fp = self._frame if frame is None else frame
+        if fp is None:
+            raise ValueError("draw_lines: no frame given and set_frame has not been called")
+        p = _lib.LinesParams()
+        p.width, p.near_w, p.depth_bias, p.hidden_alpha, p.smooth = float(width), float(near_w), float(depth_bias), float(hidden_alpha), int(smooth)
+        return fp, p
+
+    def draw_lines(self, lines, rgba8=None, rgb32f=None, hits=None, frame=None, width=1.5, near_w=0.01, depth_bias=2.0 ** -8,
+                   hidden_alpha=0.0, smooth=False):
+        """Blends `lines` (LINE_DTYPE records: rayzen_amd.lines makes them) over an image as seen through `frame`
+        (frame_params(...); None: the frame of the last set_frame), include/rayzen_hip.h: rz_draw_lines.  hits: (H, W) HIT_DTYPE,
+        render_editor's hits or a denoiser's guides, the depth the lines are tested against; None: no depth test.  rgba8
+        (H, W, 4) uint8 and rgb32f (H, W, 3) float32, each optional, are not modified: returns (rgba8, rgb32f) as blended
+        copies, None for the one not given.  A scene is needed only if a line names an instance."""
+        fp, p = self._lines_args(frame, width, near_w, depth_bias, hidden_alpha, smooth)
+        h, w = fp.height, fp.width
+        ln = np.ascontiguousarray(lines, _lib.LINE_DTYPE).reshape(-1)
+        ht = None if hits is None else np.ascontiguousarray(hits, HIT_DTYPE).reshape(h, w)
+        out8 = None if rgba8 is None else np.array(rgba8, np.uint8, order="C").reshape(h, w, 4)
+        out32 = None if rgb32f is None else np.array(rgb32f, np.float32, order="C").reshape(h, w, 3)
+        self._check(self._L.rz_draw_lines(self._c, C.byref(fp), C.byref(p), ln.ctypes.data if len(ln) else None, len(ln),
+                                          None if ht is None else ht.ctypes.data, 0 if ht is None else ht.nbytes,
+                                          None if out8 is None else out8.ctypes.data, 0 if out8 is None else out8.nbytes,
+                                          None if out32 is None else out32.ctypes.data, 0 if out32 is None else out32.nbytes,
+                                          _lib.LINES_HOST), "rz_draw_lines")
+        return out8, out32
+
+    def draw_lines_device(self, lines_ptr, n, rgba8_ptr=None, rgb32f_ptr=None, hits_ptr=None, frame=None, width=1.5, near_w=0.01,
+                          depth_bias=2.0 ** -8, hidden_alpha=0.0, smooth=False):
+        """rz_draw_lines on device memory, in place (lines n * 32 B and hits W*H*48 B, 16-B aligned; rgba8 W*H*4 B and rgb32f
+        W*H*12 B, 4-B aligned): enqueued on the context's stream."""
+        fp, p = self._lines_args(frame, width, near_w, depth_bias, hidden_alpha, smooth)
+        npx = fp.width * fp.height
+        self._check(self._L.rz_draw_lines(self._c, C.byref(fp), C.byref(p), C.c_void_p(lines_ptr), int(n), C.c_void_p(hits_ptr),
+                                          npx * 48 if hits_ptr else 0, C.c_void_p(rgba8_ptr), npx * 4 if rgba8_ptr else 0,
+                                          C.c_void_p(rgb32f_ptr), npx * 12 if rgb32f_ptr else 0, 0), "rz_draw_lines")
 
     # -- ambient occlusion for previews (rz_ambient_occlusion) ---------------------------
     def _ao_args(self, frame, samples, radius, smooth, strength, normal_cos, plane_tol):
