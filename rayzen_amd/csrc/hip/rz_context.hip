@@ -1,6 +1,8 @@
 // rz_context.hip -- the C-ABI of include/rayzen_hip.h: context, uploads, the
 // one-time re-layout of RayZen's SSBO arrays into the device structures of
 // rz_scene_dev.h, launches and read-back.  Host code, compiled by hipcc.
+// struct rz_ctx and what this file shares are declared in rz_ctx.h; the render calls (rz_render, rz_render_counted,
+// rz_render_adaptive and the timing ring) are in rz_ctx_render.hip.
 //
 // Replaces, call for call, what RayZen/src/main.cpp does with OpenGL:
 //   rz_upload     <- glGenBuffers+glBufferData+glBindBufferBase (main.cpp:1072-1119)
@@ -8,25 +10,8 @@
 //   rz_set_frame  <- glUniform* in sendSceneDataToShader        (main.cpp:1356-1379)
 //   rz_render     <- glDrawArrays(GL_TRIANGLE_FAN,0,4)          (main.cpp:637)
 //   rz_sync       <- glFinish                                   (main.cpp:1347)
-#include <hip/hip_runtime.h>
-
-#include <algorithm>
-#include <cmath>
-#include <cstdarg>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <map>
-#include <new>
-#include <string>
-#include <tuple>
-#include <limits>
-#include <vector>
-
-#include "rayzen_hip.h"
-#include "rz_internal.h"
+#include "rz_ctx.h"
 #include "rz_device_math.h"      // RZ_MATH_FLAVOUR (rz_math_flavour())
-
 
 using namespace rz;
 
@@ -34,51 +19,6 @@ namespace {
 
 thread_local std::string g_last_error = "";
 
-struct DevBuf {
-    void* p = nullptr;
-    size_t cap = 0;
-    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
-};
-
-// Where a group of the caller's arrays is current (DESIGN.md 4.3 has the table).  The context keeps a host copy and a device
-// copy of each group, several calls write only one of the two, and at least one of them always holds the bytes in force.
-//   kTris: host[0] | dRawTris.   kBlas: host[7], [8] | dRawNodes, dRawIdx, described by devNodes, devIdx, devRoots.
-//   kTlas: host[9], [5], [6] | dInstRef, dTlasNodes, dTlasIdx, described by tlasHostCounts, devTlasNodes; dXforms holds the transforms in force.
-struct Residency { bool host = true, dev = false; };
-enum Group { kTris, kBlas, kTlas, kNumGroups, kNoGroup = -1 };
-
-// One BLAS as seen from an instance: RayZen lets every instance name its own
-// node / index / triangle offsets (include/BVH.h:14-21); distinct triples are
-// laid out once each.
-struct BlasView {
-    int pairBase = 0, triBase = 0;
-    int rootEnc = 0;
-    float rootMin[3] = {0, 0, 0}, rootMax[3] = {0, 0, 0};
-    int depth = 1;
-    bool empty = false;
-    bool mayGlass = true;       // a triangle of the view may use a transparent material (a scheduling hint for the kernels: DevInstance.flags bit 1)
-    bool irregular = false;     // device re-layout: one of its child boxes has min > max or a NaN plane
-    int nPairs = 0, nSlots = 0; // what the view occupies behind pairBase / triBase
-};
-
-// What rz_refit_geometry needs of a laid-out view beyond the arrays (refit_topology): the breadth-first ranks of its
-// internal nodes, level by level.  Derived once per layout, kept until the views are laid out again.
-struct RefitView {
-    std::tuple<int, int, int> key;
-    int rankBase = 0;               // where its rankToNode entries start in dRefitRank
-    std::vector<int> levelStart;    // ranks of tree level d: [levelStart[d], levelStart[d + 1]); empty: the root is a leaf
-    int maxNode = 0;                // the largest node index (relative to the view) its root reaches
-};
-
-// One rig of rz_skin_create: the device copies rz_skin_pose's kernel reads (rz_skin.hip)
-struct SkinRig {
-    size_t first = 0, n = 0;        // its triangle range of binding 0
-    int nBones = 0, nMorphs = 0;    // nBones == 0: a morph-only rig (dSkin is empty)
-    DevBuf dRest, dSkin, dMorphs;
-    void release() { dRest.release(); dSkin.release(); dMorphs.release(); }
-};
-
-constexpr int kNumBindings = 10;
 size_t elem_size(int b) {
     switch (b) {
         case RZ_BIND_TRIANGLES: return sizeof(rz_triangle);
@@ -104,147 +44,8 @@ int group_of(int b) {
 
 }  // namespace
 
-struct rz_ctx {
-    int device = 0;
-    unsigned flags = 0;
-    hipStream_t ownStream = nullptr;
-    hipStream_t stream = nullptr;
-    // a ring of event pairs: every render launch is bracketed on its stream, and the durations can be
-    // collected later without synchronising inside a timed loop
-    static constexpr int kRing = 64;
-    hipEvent_t evStart[kRing] = {}, evStop[kRing] = {};
-    int ringHead = 0;       // next slot to record into
-    int ringCount = 0;      // launches recorded since the history was last drained (<= kRing)
-    bool timed = false;
-    int lastLaunches = 0;
-    float hemi0[3] = {0.0f, 0.0f, 0.0f};   // KParams::hemi0, computed at rz_create
-    long long triNValid = -1;       // triangles dTriN holds normals for (-1: none; reset with the geometry)
-    long long lastGrid = 0;         // workgroups of the last render launch (RZ_PROF: how many wave-log entries are valid)
-    rz_launch_plan lastPlan{};      // rz_debug_last_plan
-    bool lastCompact = false;       // the last launch took compacting claims (rz_kernels.hip: render_claim_compact)
-    bool lastGlobalPool = false;    // the last launch's waves kept their pools of parked paths across claims (rz_kernels.hip: pool_process)
-    std::string err;
-
-    // host copies of the caller's arrays (the re-layout needs them; rz_update patches them)
-    std::vector<unsigned char> host[kNumBindings];
-    bool present[kNumBindings] = {};
-    Residency where[kNumGroups];    // triangles, BLAS nodes + indices, instances + TLAS: which copy is current
-    bool geomDirty = true, instDirty = true, tlasDirty = true, matDirty = true, lightDirty = true;
-
-    // device scene
-    DevBuf dPairs, dTris, dInst, dTlasNodes, dTlasIdx, dMat, dLight, dCounters, dResolve, dGroupCtr, dBlasOvf;
-    std::map<std::tuple<int, int, int>, BlasView> views;
-    std::vector<DevPair> hPairs;
-    std::vector<DevTri> hTris;
-    int maxBlasDepth = 1, tlasDepth = 1;
-
-    // frame
-    bool haveFrame = false;
-    rz_frame_params frame{};
-    DevBuf ownAccum, dIor;
-    // device-side dynamic update (rz_update_transforms)
-    DevBuf dXforms, dInstRef, dTlasScratch, dProjBoxes, dBuildWs, dTlasDfs, dTriN;
-    int nTlasDfs = 0;               // pop positions of the TLAS (rz_trace.h: trace_closest)
-    int tlasEntry = 0;              // the verdict of whoever made dTlasDfs: queries may enter the list behind its root (rz_scene_dev.h: tlas_entry_verdict)
-    int* tlasHostCounts = nullptr;      // pinned: node count, index count, depth, entry verdict
-    int devTlasNodes = 0;
-    bool sceneHasTransparency = true;   // some triangle uses a material with transparency > 0
-    const char* lastKernel = "";
-    void* extAccum = nullptr;
-    size_t extAccumBytes = 0;
-    int failAllocCountdown = 0;         // rz_debug_fail_alloc (test hook)
-    // device re-layout (rz_relayout.hip): the caller's raw arrays on the device, the fill of dPairs / dTris, scratch
-    DevBuf dRawNodes, dRawIdx, dRawTris, dRelayoutWs, dClaimScratch;
-    DevBuf dSnap;                                  // transparent scenes: the resident waves' sample prefixes (rz_path.h: snapshot_store)
-    DevBuf dWavePools, dWaitMeta;     // the resident waves' pools of parked paths and the bookkeeping of their wait slots (rz_kernels.hip: pool_process; the slots themselves: behind the claim scratch in dClaimScratch)
-    size_t lastScratchBytes = 0;                   // what the last compacting launch's waves had in scratch (pools + wait slots + bookkeeping)
-    int* relayoutPinned = nullptr;
-    bool layoutOnDevice = false;        // dPairs / dTris were produced on the device (hPairs / hTris are empty)
-    long long devPairsUsed = 0, devTrisUsed = 0;
-    bool matChangedSinceLayout = false; // materials were uploaded after the BLAS views were laid out: their per-view transparency hints are stale
-    unsigned devTransparent = 0;       // device re-layout: bit 0 a transparent material is in use, bit 1 an irregular child box
-    bool irregularBoxes = false;       // some BLAS child box has min > max or a NaN plane: the traversal keeps the generic slab test
-    // what describes dRawNodes / dRawIdx while only they are current (rz_build_geometry, a device refit, rz_rebuild_geometry)
-    size_t devNodes = 0, devIdx = 0;
-    std::map<int, rz_bvh_node> devRoots;    // node offset of a mesh -> its root node
-    // ray queries (rz_trace_rays / rz_shadow_rays, rz_rays.hip): their own BLAS overflow columns, the staging buffers of
-    // RZ_RAYS_HOST calls and the globalTriOffset of every instance (re-uploaded after the instances change)
-    DevBuf dRayOvf, dRayIn, dRayOut, dRayInstOff;
-    bool rayInstOffStale = true;
-    // the denoiser (rz_denoise / rz_present_denoised, rz_denoise.hip): the guide (2 float4 per pixel), the two float4 buffers
-    // its passes ping-pong between, and the (colour, 1) buffer rz_present_denoised presents
-    DevBuf dDnGuide, dDnPing, dDnPong, dDnOut;
-    // rz_denoise_temporal (rz_temporal.hip): two sets of history buffers (colour | N, moments, guide, instance transforms) that
-    // swap roles at every committing call -- set tmpCur is the stored history, the other one is written -- the per-instance
-    // "transform unchanged" flags, and the frame the history was made for
-    DevBuf dTmpCol[2], dTmpMom[2], dTmpHits[2], dTmpInst[2], dTmpSame;
-    int tmpCur = 0;
-    bool tmpValid = false;
-    int tmpW = 0, tmpH = 0;
-    size_t tmpInst = 0;
-    float tmpView[16] = {}, tmpProj[16] = {}, tmpInvProj[16] = {}, tmpCam[3] = {};
-    // the display stage (rz_display / rz_present_display, rz_display.hip): one DisplayState -- the exposure last applied, the
-    // rz_display_info record and the working histogram -- allocated and zeroed by the first call that needs it
-    DevBuf dDisplay;
-    // rz_upscale / rz_present_upscaled (rz_upscale.hip): the guides cast at the low and at the high size (2 float4 per pixel
-    // each) and the high-size (colour, 1) buffer rz_present_upscaled presents; allocated on first use and kept
-    DevBuf dUpGuideLo, dUpGuideHi, dUpOut;
-    // rz_upscale_seethrough / rz_present_upscaled_seethrough (rz_seethrough.hip): the chain guides at both sizes (3 float4 per
-    // pixel each); allocated on first use and kept.  The first-hit buffers above are not touched by those calls.
-    DevBuf dStGuideLo, dStGuideHi;
-    // rz_antialias_seethrough (rz_antialias_seethrough.hip): the edge pixels its classifying waves found, a segment per wave,
-    // and the segments' counts; allocated on first use and kept
-    DevBuf dAasList, dAasCounts;
-    // rz_refit_geometry (rz_refit.hip)
-    unsigned long long layoutGen = 0;   // counts the times the views / instances were laid out
-    unsigned long long refitGen = ~0ull; // the layout the refit topology below was derived from
-    std::vector<RefitView> refitViews;  // in the order of `views`
-    DevBuf dRefitRank, dRefitInstView, dRefitViewOff, dRefitFlags, dRefitRoots;
-    unsigned char* refitPinned = nullptr;   // per view: 4 flag words, then per view: its root node
-    size_t refitPinnedCap = 0;
-    // rz_skin_create / rz_skin_pose (rz_skin.hip): the rigs by id, the posed triangles the refit is given, the bones and morph
-    // weights of a host-argument pose, and the events around the last pose's kernel
-    std::map<int, SkinRig> rigs;
-    int nextRig = 0;
-    DevBuf dSkinOut, dSkinBones, dSkinWeights;
-    hipEvent_t evSkin[2] = {nullptr, nullptr};
-    bool skinTimed = false;
-    // rz_geometry_quality (rz_quality.hip): the views as its kernels see them (derived with the refit topology), the
-    // per-workgroup partial sums and the costs; and the cost of every laid-out mesh's tree as it was when it was last handed
-    // over or built -- measured at the library's first look at it (note_built_costs), dropped with the tree
-    DevBuf dQualViews, dQualPartials, dQualCost;
-    int qualBlocks = 0;
-    std::map<std::tuple<int, int, int>, double> costBuilt;
-    unsigned long long costGen = ~0ull;  // the layout whose views all have their entry in costBuilt
-    // rz_render_cost / rz_cost_view / rz_present_cost (rz_cost.hip): the last cost buffer (rz_pixel_cost per pixel) with the size
-    // and spp it was measured at, the call's own counters, the reduction's partial records and its rz_cost_stats, and the
-    // (colour, 1) buffer rz_present_cost presents; allocated on first use and kept
-    DevBuf dCost, dCostCounters, dCostPartials, dCostStats, dCostOut;
-    bool costValid = false;
-    int costW = 0, costH = 0, costSpp = 0;
-    // rz_coverage (rz_coverage.hip): the private sets of records its workgroups merge into, and the layout (sets, stride in
-    // bytes, records per set) at which they are all empty -- rz_coverage_merge leaves them so; 0 sets: not known to be
-    DevBuf dCovSets;
-    long long covSets = 0;
-    size_t covStride = 0, covCount = 0;
-    // rz_ambient_occlusion (rz_ao.hip): the direction table (uploaded by the first call), raw_p of every pixel and the counter
-    // its waves claim tiles from (zeroed by every call); the guide it casts goes to dDnGuide, which every pass that casts one
-    // rewrites before it reads it
-    DevBuf dAoDirs, dAoRaw, dAoClaim;
-    // rz_render_adaptive (rz_adaptive.hip): per pixel, tile by tile, the accumulation after the tile's previous batch and the
-    // luminance moments; per tile its error, the batches it has received and its flags; the list of the tiles a batch rendered;
-    // the pinned block the flags come back to and the list goes up from; the events around a batch's render launches and its
-    // metering launch.  Allocated by the first call and kept; every call starts them afresh
-    DevBuf dAdPrev, dAdMoments, dAdError, dAdBatches, dAdFlags, dAdList;
-    uint8_t* adPinned = nullptr;
-    size_t adPinnedCap = 0;
-    hipEvent_t evAdaptive[3] = {nullptr, nullptr, nullptr};
-    // rz_draw_lines (rz_lines.hip): the projected records (52 B per line), the counts and offsets of the coarse lists (12 B per
-    // cell and segment, and the total) and the lists themselves; allocated by the first call, grown on demand and kept
-    DevBuf dLnRec, dLnCells, dLnList;
-};
-
-namespace {
+// ---- declared in rz_ctx.h: rz_ctx_render.hip calls these too ----
+namespace rz {
 
 int fail(rz_ctx* c, int code, const char* fmt, ...) {
     char buf[512];
@@ -259,38 +60,9 @@ int fail(rz_ctx* c, int code, const char* fmt, ...) {
     return code;
 }
 
-// No C++ exception crosses the C-ABI: every exported entry point that can reach a std::vector / std::map /
-// std::string growth runs its body through guarded(), which turns std::bad_alloc into RZ_ERR_NO_MEMORY and anything
-// else into RZ_ERR_HIP.  (rz_debug_fail_alloc arms a countdown that makes alloc_point() throw std::bad_alloc at the
-// n-th host allocation site reached -- the test hook that proves the conversion.)
-// It also makes the context's device the calling thread's current one: a context may be driven while another device is
-// current (a group of several devices in one process, rz_group.hip: a member reached through rz_group_ctx), and every
-// hipMalloc, kernel launch and event below would otherwise land on THAT device.
-template <class F>
-int guarded(rz_ctx* c, const char* what, F&& body) {
-    try {
-        if (c) {
-            const hipError_t e = hipSetDevice(c->device);
-            if (e != hipSuccess) return fail(c, RZ_ERR_HIP, "%s: hipSetDevice(%d): %s", what, c->device, hipGetErrorString(e));
-        }
-        return body();
-    } catch (const std::bad_alloc&) {
-        return fail(c, RZ_ERR_NO_MEMORY, "%s: out of host memory", what);
-    } catch (const std::exception& e) {
-        return fail(c, RZ_ERR_HIP, "%s: %s", what, e.what());
-    } catch (...) {
-        return fail(c, RZ_ERR_HIP, "%s: unknown C++ exception", what);
-    }
-}
 void alloc_point(rz_ctx* c) {
     if (c->failAllocCountdown > 0 && --c->failAllocCountdown == 0) throw std::bad_alloc();
 }
-
-#define RZ_HIP(c, call)                                                                            \
-    do {                                                                                           \
-        hipError_t e_ = (call);                                                                    \
-        if (e_ != hipSuccess) return fail((c), RZ_ERR_HIP, "%s: %s", #call, hipGetErrorString(e_)); \
-    } while (0)
 
 int ensure(rz_ctx* c, DevBuf& b, size_t bytes) {
     if (bytes <= b.cap && b.p) return RZ_OK;
@@ -313,6 +85,10 @@ bool ensure_optional(DevBuf& b, size_t bytes) {
     b.cap = std::max<size_t>(bytes, 256);
     return true;
 }
+
+}  // namespace rz
+
+namespace {
 
 int upload_vec(rz_ctx* c, DevBuf& b, const void* src, size_t bytes) {
     int rc = ensure(c, b, bytes);
@@ -777,44 +553,8 @@ int finalize_body(rz_ctx* c) {
     return RZ_OK;
 }
 
-// A failure half-way through the re-layout (an exception from a growing vector) must not leave a half-built scene
-// behind: drop the derived state, keep the caller's arrays, and let the next call redo it.
-int finalize(rz_ctx* c) {
-    try {
-        return finalize_body(c);
-    } catch (...) {
-        drop_layout(c);
-        c->geomDirty = true;
-        throw;
-    }
-}
-
-#ifndef RZ_SPREAD_MIN_INSTANCES
-#define RZ_SPREAD_MIN_INSTANCES 3
-#endif
-#ifndef RZ_WPOOL_CHUNK
-#define RZ_WPOOL_CHUNK 256         // paths a wave collects across claims before it traces them together
-#endif
-#ifndef RZ_CLAIM_STRIDE_PAD
-#define RZ_CLAIM_STRIDE_PAD 0      // extra dwords between the scratch regions of neighbouring resident waves
-#endif
-
 long long tlas_index_count(const rz_ctx* c) {
     return c->where[kTlas].host ? (long long)hostCount<int32_t>(c, RZ_BIND_TLAS_INDICES) : (long long)c->tlasHostCounts[1];
-}
-
-// One lane per sample: independent samples when no triangle is transparent, speculated currentIor otherwise
-// (rz_kernels.hip).  The one-lane-per-pixel kernel remains as RZ_FLAG_MEGAKERNEL (the literal, sequential form).
-bool use_samples(const rz_ctx* c) { return (c->flags & RZ_FLAG_MEGAKERNEL) == 0; }
-
-// The claim counter (word 0, zeroed per launch) and the backstop word (word RZ_ERRWORD, zeroed when made and when reported).
-int ensure_group_counter(rz_ctx* c) {
-    if (c->dGroupCtr.p) return RZ_OK;
-    // (+ a row of 64 zeros at byte 512, read by every wave's ordered sums in place of a dark unit's light rows: rz_kernels.hip, zero_row)
-    int rc = ensure(c, c->dGroupCtr, 1024);
-    if (rc != RZ_OK) return rc;
-    RZ_HIP(c, hipMemsetAsync(c->dGroupCtr.p, 0, 1024, c->stream));
-    return RZ_OK;
 }
 
 unsigned* backstop_word(const rz_ctx* c) { return static_cast<unsigned*>(c->dGroupCtr.p) + RZ_ERRWORD; }
@@ -836,27 +576,6 @@ int report_backstop(rz_ctx* c, const char* what, const char* consequence) {
     const int rc = take_backstop(c, bits);
     if (rc != RZ_OK) return rc;
     if (bits != 0u) return fail(c, RZ_ERR_INTERNAL, "%s: a kernel reached a backstop (bits 0x%x): %s", what, bits, consequence);
-    return RZ_OK;
-}
-
-// The BLAS stack of a launch of one-wave workgroups (K.blasStackCap entries per lane needed).  LDS budget: the stack's LDS
-// window is cut to what keeps `wavesPerCu` waves on a CU beside `fixedLds` bytes of other LDS per wave; deeper entries go to
-// global overflow columns in `ovf`, which are indexed by resident workgroup and therefore only exist for persistent launches
-// (`residentWaves` > 0: the grid).  Sets K.blasStackCap (the window, when one is cut), K.blasOvfCap and K.blasOvf.
-int size_blas_stack(rz_ctx* c, KParams& K, size_t fixedLds, int wavesPerCu, long long residentWaves, DevBuf& ovf) {
-    const int need = K.blasStackCap;
-    const size_t budget = (size_t)160 * 1024 / wavesPerCu;
-    int window = budget > fixedLds ? (int)((budget - fixedLds) / 512) : 0;
-    if (const char* e = std::getenv("RZ_BLAS_STACK_WINDOW")) window = std::atoi(e);        // test aid: force a small window
-    window = std::max(window, 2);
-    K.blasOvfCap = 0; K.blasOvf = nullptr;
-    if (residentWaves > 0 && need > window) {
-        K.blasStackCap = window;
-        K.blasOvfCap = need - window;
-        const int rc = ensure(c, ovf, (size_t)residentWaves * K.blasOvfCap * 64 * sizeof(uint2));
-        if (rc != RZ_OK) return rc;
-        K.blasOvf = static_cast<uint2*>(ovf.p);
-    }
     return RZ_OK;
 }
 
@@ -949,105 +668,57 @@ struct HostStage {
     }
 };
 
-// (evSlot: the pair of the ring that brackets the launch; negative: none -- rz_render_adaptive brackets its batches itself)
-int render_samples(rz_ctx* c, KParams K, bool counted, int evSlot) {
-    K.nSlots = K.nLocalTiles * 64;
-    int rc = ensure_group_counter(c);
-    if (rc != RZ_OK) return rc;
-    K.groupCounter = static_cast<unsigned*>(c->dGroupCtr.p);
-    // (16 waves per CU for the opaque variant = its VGPR limit, and for the transparent one too: 5.4 KB of versions leave it a
-    // 9-entry window -- measured 40.2 -> 34.3 ms on the glass+mirror scene against 12 waves with the whole stack in LDS)
-    const SamplesPlan plan = plan_render_samples(K.spp, K.nSlots, c->sceneHasTransparency);
-#ifndef RZ_GLASS_WAVES_PER_CU
-#define RZ_GLASS_WAVES_PER_CU 16
-#endif
-#ifndef RZ_OPAQUE_WAVES_PER_CU
-#define RZ_OPAQUE_WAVES_PER_CU 16
-#endif
-    rc = size_blas_stack(c, K, samples_lds_extra(c->sceneHasTransparency, plan.compact) + (size_t)K.tlasStackCap * 256,
-                         c->sceneHasTransparency ? RZ_GLASS_WAVES_PER_CU : RZ_OPAQUE_WAVES_PER_CU,
-                         plan.perClaim > 0 ? plan.grid : 0, c->dBlasOvf);
-    if (rc != RZ_OK) return rc;
-    // Compacting launches: every resident wave's scratch (rz_kernels.hip: WAIT SLOTS, pool_process) --
-    //   * its pool of parked paths: room for the chunk it collects before it traces them + the most one more claim can park;
-    //   * its claim scratch (the addends of the claim it is running, 1.5 KB per unit) and behind it its wait slots, one waiting
-    //     group's addends (batches x 1.5 KB) each: twice the groups of a claim by default (a claim that
-    //     finds fewer free ones than it has groups makes the wave trace its pool first; RZ_WAIT_SLOTS overrides);
-    //   * 2 ints of bookkeeping per slot.
-    // C2: 80 + 12 + 24 KB per wave, 470 MiB for the grid (round 3: 3.7 GB, of which 3.2 GB an array of 1.5 KB per unit of the launch).
-    // The scratch is optional: a launch that cannot have it (or is told so: RZ_DEBUG_NO_POOL_MEMORY=1, a test aid) runs the
-    // plain persistent loop instead, same image.
-    K.wslots = nullptr; K.wslotStride = 0; K.slotFloats = 0; K.nWaitSlots = 0; K.wmeta = nullptr; K.drainEachClaim = 0; K.claimUnits = 0; K.claimScratchFloats = 0;
-    K.wpool = nullptr; K.wpoolStride = 0; K.wpoolChunk = 0;
-    if (plan.compact && K.maxBounces < 32768) {     // (a pool entry keeps its path's bounce in 15 bits: rz_kernels.hip, BACK)
-        long long chunk = RZ_WPOOL_CHUNK;
-        if (const char* e = std::getenv("RZ_WPOOL_CHUNK")) chunk = std::max<long long>(1, std::atoll(e));      // tuning / test aid
-        const int nBatches = (K.spp + 63) / 64;
-        const int groupsPerClaim = std::max(1, plan.perClaim);
-        // (twice a claim's groups: measured on the final build against 24 and 32 slots, C2 / C3 / C4 / C5 / glass all within
-        //  0.4 % -- profiles/r04_wait_slots/slots_chunk_final.log -- and 24 KB per wave less to keep: C2's scratch 553 -> 470 MiB)
-        int nSlots = std::max(2 * groupsPerClaim, 16 / nBatches);
-        if (const char* e = std::getenv("RZ_WAIT_SLOTS")) nSlots = std::max(2 * groupsPerClaim, std::atoi(e));  // tuning / test aid
-        nSlots = std::min(nSlots, 64);
-        // a pool's capacity: what a wave may hold when it starts a pass -- fewer than `chunk` paths plus a whole claim's -- and what a
-        // pass can ADD to that: nothing in an opaque scene (a path survives in place or ends); in a transparent one every sample on the
-        // wave's late list (at most RZ_GLATE_CAP, listed in this pass or earlier ones) can be released into the pool behind the survivors
-        const size_t stride = (size_t)chunk + (size_t)plan.claimUnits * 64 + 64 + (c->sceneHasTransparency ? (size_t)RZ_GLATE_CAP : 0);
-        // (a group's addends; transparent scenes: + one row, the currentIor each pixel ends with)
-        const size_t slotFloats = (size_t)nBatches * 384 + (c->sceneHasTransparency ? 64 : 0);
-        const size_t claimScratchFloats = (size_t)groupsPerClaim * slotFloats;
-        bool snapOn = true;                 // transparent scenes resolve currentIor from the samples' snapshots: no snapshots, no claims
-        if (const char* e = std::getenv("RZ_GLASS_SNAPSHOT")) snapOn = std::atoi(e) != 0;
-        size_t slotPad = 0;                                                                                      // floats between neighbouring waves' slot regions
-        if (const char* e = std::getenv("RZ_SLOT_STRIDE_PAD")) slotPad = (size_t)std::max(0, std::atoi(e));     // tuning aid
-        const char* forceNo = std::getenv("RZ_DEBUG_NO_POOL_MEMORY");      // test aid: as if the device had no room for it
-        if (nSlots >= groupsPerClaim && !(forceNo && std::atoi(forceNo) != 0) && (!c->sceneHasTransparency || snapOn) &&
-            ensure_optional(c->dWavePools, (size_t)plan.grid * stride * RZ_GPOOL_FIELDS * sizeof(unsigned)) &&
-            ensure_optional(c->dClaimScratch, (size_t)plan.grid * (claimScratchFloats + nSlots * slotFloats + slotPad) * sizeof(float)) &&
-            ensure_optional(c->dWaitMeta, (size_t)plan.grid * 4 * nSlots * sizeof(int32_t))) {
-            K.wpool = static_cast<unsigned*>(c->dWavePools.p);
-            K.wpoolStride = (uint32_t)stride;
-            K.wpoolChunk = (uint32_t)chunk;
-            K.wslots = static_cast<float*>(c->dClaimScratch.p);
-            K.wslotStride = (uint32_t)(claimScratchFloats + nSlots * slotFloats + slotPad);
-            K.claimUnits = plan.claimUnits;
-            K.claimScratchFloats = (uint32_t)claimScratchFloats;
-            K.glassBoxHint = 1;
-            if (const char* e = std::getenv("RZ_GLASS_BOX_HINT")) K.glassBoxHint = std::atoi(e) != 0 ? 1 : 0;      // A/B and test aid
-            K.slotFloats = (uint32_t)slotFloats;
-            K.nWaitSlots = nSlots;
-            K.wmeta = static_cast<int32_t*>(c->dWaitMeta.p);
-            K.drainEachClaim = plan.drainEachClaim ? 1 : 0;
-        }
+}  // namespace
+
+// ---- declared in rz_ctx.h, as above ----
+namespace rz {
+
+// A failure half-way through the re-layout (an exception from a growing vector) must not leave a half-built scene
+// behind: drop the derived state, keep the caller's arrays, and let the next call redo it.
+int finalize(rz_ctx* c) {
+    try {
+        return finalize_body(c);
+    } catch (...) {
+        drop_layout(c);
+        c->geomDirty = true;
+        throw;
     }
-    c->lastGlobalPool = K.wpool != nullptr && K.drainEachClaim == 0;
-    c->lastCompact = K.wpool != nullptr;
-    c->lastScratchBytes = K.wpool ? (size_t)plan.grid * ((size_t)K.wpoolStride * RZ_GPOOL_FIELDS * 4 + (size_t)K.wslotStride * 4 + (size_t)16 * K.nWaitSlots) : 0;
-    // transparent scenes, persistent launches: room for every resident wave's sample prefixes (19 + 14 dwords per lane, 34 MB for
-    // the grid), so that a sample's second version starts at its first transparent scatter instead of at the camera.
-    // RZ_GLASS_SNAPSHOT=0 switches it off (A/B aid: same image either way).
-    K.snap = nullptr; K.snapStride = 0;
-    if (c->sceneHasTransparency && plan.perClaim > 0) {
-        bool on = true;
-        if (const char* e = std::getenv("RZ_GLASS_SNAPSHOT")) on = std::atoi(e) != 0;
-        const size_t stride = (size_t)(RZ_SNAP_FIELDS + RZ_SNAP_TALLY + RZ_GVER_ROWS) * 64 + (size_t)RZ_GLATE_FIELDS * RZ_GLATE_CAP;
-        if (on) {
-            rc = ensure(c, c->dSnap, (size_t)plan.grid * stride * sizeof(float));
-            if (rc != RZ_OK) return rc;
-            K.snap = static_cast<float*>(c->dSnap.p);
-            K.snapStride = (uint32_t)stride;
-        }
-    }
-    if (evSlot >= 0) RZ_HIP(c, hipEventRecord(c->evStart[evSlot], c->stream));
-    if (K.nSlots > 0) launch_render_samples(K, counted, c->sceneHasTransparency, c->stream);
-    if (evSlot >= 0) RZ_HIP(c, hipEventRecord(c->evStop[evSlot], c->stream));
-    c->lastLaunches = K.nSlots > 0 ? 1 : 0;
-    c->lastGrid = plan.grid;
-    c->lastPlan = rz_launch_plan{plan.groups, plan.grid, plan.perClaim, (plan.compact && K.wpool) ? plan.claimUnits : 0,
-                                 (K.spp + 63) / 64, K.spp >= 64 ? 1 : 64 / K.spp, K.blasStackCap, K.blasOvfCap,
-                                 c->sceneHasTransparency ? 1 : 0, (int32_t)((c->lastScratchBytes + (1u << 20) - 1) >> 20)};
+}
+
+// The claim counter (word 0, zeroed per launch) and the backstop word (word RZ_ERRWORD, zeroed when made and when reported).
+int ensure_group_counter(rz_ctx* c) {
+    if (c->dGroupCtr.p) return RZ_OK;
+    // (+ a row of 64 zeros at byte 512, read by every wave's ordered sums in place of a dark unit's light rows: rz_kernels.hip, zero_row)
+    int rc = ensure(c, c->dGroupCtr, 1024);
+    if (rc != RZ_OK) return rc;
+    RZ_HIP(c, hipMemsetAsync(c->dGroupCtr.p, 0, 1024, c->stream));
     return RZ_OK;
 }
+
+// The BLAS stack of a launch of one-wave workgroups (K.blasStackCap entries per lane needed).  LDS budget: the stack's LDS
+// window is cut to what keeps `wavesPerCu` waves on a CU beside `fixedLds` bytes of other LDS per wave; deeper entries go to
+// global overflow columns in `ovf`, which are indexed by resident workgroup and therefore only exist for persistent launches
+// (`residentWaves` > 0: the grid).  Sets K.blasStackCap (the window, when one is cut), K.blasOvfCap and K.blasOvf.
+int size_blas_stack(rz_ctx* c, KParams& K, size_t fixedLds, int wavesPerCu, long long residentWaves, DevBuf& ovf) {
+    const int need = K.blasStackCap;
+    const size_t budget = (size_t)160 * 1024 / wavesPerCu;
+    int window = budget > fixedLds ? (int)((budget - fixedLds) / 512) : 0;
+    if (const char* e = std::getenv("RZ_BLAS_STACK_WINDOW")) window = std::atoi(e);        // test aid: force a small window
+    window = std::max(window, 2);
+    K.blasOvfCap = 0; K.blasOvf = nullptr;
+    if (residentWaves > 0 && need > window) {
+        K.blasStackCap = window;
+        K.blasOvfCap = need - window;
+        const int rc = ensure(c, ovf, (size_t)residentWaves * K.blasOvfCap * 64 * sizeof(uint2));
+        if (rc != RZ_OK) return rc;
+        K.blasOvf = static_cast<uint2*>(ovf.p);
+    }
+    return RZ_OK;
+}
+
+#ifndef RZ_SPREAD_MIN_INSTANCES
+#define RZ_SPREAD_MIN_INSTANCES 3
+#endif
 
 // What a render launch reads of the scene and of the frame of rz_set_frame -- its tiles, camera, lights and bounce budget --
 // for `spp` samples per pixel from sample `sampleBase` (do_render: the frame's own; rz_render_cost: its own spp from sample 0),
@@ -1083,290 +754,7 @@ int frame_kparams(rz_ctx* c, KParams& K, int spp, int sampleBase) {
     return RZ_OK;
 }
 
-int do_render(rz_ctx* c, bool counted, rz_counters* out) {
-    if (!c) return fail(nullptr, RZ_ERR_INVALID_ARG, "null context");
-    if (!c->haveFrame) return fail(c, RZ_ERR_NOT_READY, "rz_set_frame has not been called");
-    RZ_HIP(c, hipSetDevice(c->device));
-    int rc = finalize(c);
-    if (rc != RZ_OK) return rc;
-    const rz_frame_params& f = c->frame;
-    const size_t nPix = (size_t)f.width * f.height;
-    float4* accum = nullptr;
-    if (c->extAccum) {
-        if (c->extAccumBytes < nPix * 16) return fail(c, RZ_ERR_BUFFER_SIZE, "bound accumulation buffer holds %zu bytes, frame needs %zu", c->extAccumBytes, nPix * 16);
-        accum = static_cast<float4*>(c->extAccum);
-    } else {
-        accum = static_cast<float4*>(c->ownAccum.p);
-    }
-    KParams K{};
-    K.accum = accum;
-    K.ior = static_cast<float*>(c->dIor.p);
-    rc = frame_kparams(c, K, f.spp, f.sample_base);
-    if (rc != RZ_OK) return rc;
-    if (counted) {
-        rc = ensure(c, c->dCounters, sizeof(DevCounters) + 160 * sizeof(unsigned long long));
-        if (rc != RZ_OK) return rc;
-        RZ_HIP(c, hipMemsetAsync(c->dCounters.p, 0, sizeof(DevCounters) + 160 * sizeof(unsigned long long), c->stream));
-        K.counters = static_cast<DevCounters*>(c->dCounters.p);
-    }
-    // The event pair brackets the render kernels of this call (for the one-lane-per-sample path: the
-    // rz_render_samples launches; its small ordered-sum kernel runs after the stop event when unchunked).
-    const int slot = c->ringHead;
-    if (use_samples(c)) {
-        rc = render_samples(c, K, counted, slot);
-        if (rc != RZ_OK) return rc;
-        c->lastKernel = c->sceneHasTransparency ? (c->lastCompact ? "rz_render_samples<glass>+pool" : "rz_render_samples<glass>")
-                                                : (c->lastGlobalPool ? "rz_render_samples+pool" : "rz_render_samples");
-    } else {
-        RZ_HIP(c, hipEventRecord(c->evStart[slot], c->stream));
-        launch_render_pixels(K, counted, c->stream);
-        RZ_HIP(c, hipEventRecord(c->evStop[slot], c->stream));
-        c->lastLaunches = 1;
-        c->lastKernel = "rz_render_pixels";
-        c->lastPlan = rz_launch_plan{K.nLocalTiles, K.nLocalTiles, 0, 0, (K.spp + 63) / 64, 64, K.blasStackCap, 0, c->sceneHasTransparency ? 1 : 0, 0};
-    }
-    RZ_HIP(c, hipGetLastError());
-    c->ringHead = (slot + 1) % rz_ctx::kRing;
-    c->ringCount = std::min(c->ringCount + 1, (int)rz_ctx::kRing);
-    c->timed = true;
-    if (counted && out) {
-        DevCounters h{};
-        RZ_HIP(c, hipMemcpyAsync(&h, c->dCounters.p, sizeof h, hipMemcpyDeviceToHost, c->stream));
-        RZ_HIP(c, hipStreamSynchronize(c->stream));
-        out->samples = h.samples; out->traversals = h.traversals; out->tlas_nodes = h.tlas_nodes;
-        out->tlas_leaf_indices = h.tlas_leaf_indices; out->instances = h.instances; out->blas_nodes = h.blas_nodes;
-        out->triangles = h.triangles; out->materials = h.materials; out->light_fetches = h.light_fetches;
-        out->pixels = h.pixels;
-        out->scatters = h.scatters; out->diffuse_scatters = h.diffuse_scatters; out->hemi_draws = h.hemi_draws; out->lit_lights = h.lit_lights; out->triangles_past_u = h.triangles_past_u;
-#ifdef RZ_PROF
-        unsigned long long pr[160];
-        RZ_HIP(c, hipMemcpy(pr, static_cast<char*>(c->dCounters.p) + sizeof(DevCounters), sizeof pr, hipMemcpyDeviceToHost));
-        for (int r = 0; r < 8; ++r) {       // per query round of a path: 0 primary, 1-2 shadow, 3 first bounce, ...
-            const unsigned long long* q = pr + 32 + 11 * r;
-            auto avg = [](unsigned long long l, unsigned long long e) { return e ? (double)l / (double)e : 0.0; };
-            fprintf(stderr, "[rz_prof] round %d: queries %10llu x %4.1f lanes | descend steps %11llu x %4.1f (uniform %11llu) | triangle tests %11llu x %4.1f | instance entries %10llu x %4.1f | trace wave-cycles %llu\n",
-                    r, q[8], avg(q[9], q[8]), q[0], avg(q[1], q[0]), q[6], q[2], avg(q[3], q[2]), q[4], avg(q[5], q[4]), q[10]);
-        }
-        dump_wave_log(use_samples(c) ? (int)std::min<long long>(c->lastGrid, 1 << 17) : K.nLocalTiles);
-        static const char* namesPx[] = {"blas loop iter", "leaf branch", "triangle test", "internal branch", "tlas pop", "instance enter", "outer iter", "uniform pair"};
-        const char** names = namesPx;
-        for (int k = 0; k < 8; ++k)
-            fprintf(stderr, "[rz_prof] %-16s wave-execs %12llu  lanes %14llu  avg active lanes %.1f\n", names[k], pr[2 * k], pr[2 * k + 1], pr[2 * k] ? (double)pr[2 * k + 1] / (double)pr[2 * k] : 0.0);
-        fprintf(stderr, "[rz_prof] wave cycles: begin %llu  trace %llu  advance %llu | inside trace: descend loops %llu  leaf phases %llu  whole BLAS walks %llu\n", pr[16], pr[17], pr[18], pr[19], pr[20], pr[21]);
-        fprintf(stderr, "[rz_prof] compacting claims: phase 1 (units) %llu  pool rounds %llu wave cycles; %llu rounds with %llu paths = %.1f lanes per round\n", pr[23], pr[28], pr[29], pr[30], pr[29] ? (double)pr[30] / (double)pr[29] : 0.0);
-        fprintf(stderr, "[rz_prof] cross-claim pools: %llu traced, %llu queries in them, shade rounds %llu wave cycles\n", pr[29], pr[30], pr[28]);
-        fprintf(stderr, "[rz_prof] pool_trace (a claim's pooled queries traced together): %llu wave cycles = T phases %llu + B phases %llu (of which refills %llu); round 7 above = its steps\n", pr[120], pr[121], pr[122], pr[123]);
-        fprintf(stderr, "[rz_prof] descend steps of the general (per-lane) walk by children entered: none %llu  one %llu  both %llu (lane-level; the scalar-unit steps are not in here); in the pools' walks: none %llu  one %llu  both %llu\n", pr[132], pr[133], pr[134], pr[136], pr[137], pr[138]);
-        fprintf(stderr, "[rz_prof] wait slots: end-of-claim sections %llu wave cycles (of which the claim-end sums %llu); slot_sums inside pool_process %llu\n", pr[124], pr[126], pr[125]);
-        // (this build's counted frame takes the shortcut, as the product's uncounted one does: rz_path.h, shadow_exit)
-        for (int r = 0; r < 3; ++r) {
-            const unsigned long long* q = pr + 140 + 6 * r;
-            fprintf(stderr, "[rz_prof] shadow exit, round %d%s: eligible queries %llu | walks cut short %llu | refused: hit within 2 EPS %llu, not clearly nearer than the light %llu | held %llu | traced again %llu\n",
-                    r + 1, r == 2 ? " and later" : "", q[0], q[1], q[2], q[3], q[4], q[5]);
-        }
-        fprintf(stderr, "[rz_prof] inside advance: sky %llu  hit %llu  start_light %llu  shade_light %llu  scatter %llu (hemisphere %llu)  shadow step %llu\n", pr[22], pr[23], pr[24], pr[25], pr[26], pr[27], pr[28]);
-#endif
-    }
-    return RZ_OK;
-}
-
-// ---- rz_render_adaptive / rz_adaptive_plan (rz_adaptive.hip; include/rayzen_hip.h states the rule) -----------------------------
-// The runs of the next batch.  A merge changes no other gap, so step 3's "smallest all-current gap first, lowest index among
-// equals" is a stable sort of the gaps step 2 left open.
-void adaptive_plan(const uint8_t* active, const uint8_t* current, size_t n, int mergeGap, int maxRuns, std::vector<rz_tile_run>& out) {
-    out.clear();
-    for (size_t i = 0; i < n;) {
-        if (!active[i]) { ++i; continue; }
-        size_t j = i;
-        while (j < n && active[j]) ++j;
-        out.push_back(rz_tile_run{(int32_t)i, (int32_t)(j - i)});
-        i = j;
-    }
-    if (out.size() < 2) return;
-    std::vector<char> join(out.size() - 1, 0);
-    std::vector<std::pair<int32_t, int32_t>> open;          // (length, the run in front) of the all-current gaps step 2 leaves
-    size_t runs = out.size();
-    for (size_t k = 0; k + 1 < out.size(); ++k) {
-        const int32_t g0 = out[k].first + out[k].len, g1 = out[k + 1].first;
-        bool allCurrent = true;
-        for (int32_t t = g0; t < g1 && allCurrent; ++t) allCurrent = current[t] != 0;
-        if (!allCurrent) continue;
-        if (g1 - g0 <= mergeGap) { join[k] = 1; --runs; }
-        else open.emplace_back(g1 - g0, (int32_t)k);
-    }
-    if (runs > (size_t)maxRuns) {
-        std::stable_sort(open.begin(), open.end(), [](const auto& a, const auto& b) { return a.first < b.first; });
-        for (size_t k = 0; k < open.size() && runs > (size_t)maxRuns; ++k, --runs) join[open[k].second] = 1;
-    }
-    size_t w = 0;
-    for (size_t k = 1; k < out.size(); ++k) {
-        if (join[k - 1]) out[w].len = out[k].first + out[k].len - out[w].first;
-        else out[++w] = out[k];
-    }
-    out.resize(w + 1);
-}
-
-// The frame of rz_set_frame in batches of s samples over runs of tiles.  Every launch is a launch of do_render's kernels with
-// three fields of its KParams overridden -- tileNRanks 1, tileRank the run's first tile, nLocalTiles its length -- which
-// render_samples and launch_render_pixels size everything else from; sampleBase continues the pixels from the accumulation and
-// currentIor.  The launches record no event pair of the ring, which therefore keeps the renders' history.
-int render_adaptive(rz_ctx* c, const rz_adaptive_params* pp, rz_adaptive_info* info, int32_t* tileBatches, size_t tileBatchesBytes,
-                    float* tileError, size_t tileErrorBytes) {
-    const char* what = "rz_render_adaptive";
-    if (!c) return fail(nullptr, RZ_ERR_INVALID_ARG, "%s: null context", what);
-    rz_adaptive_params P{};
-    if (pp) P = *pp;
-    if (P.flags & ~RZ_ADAPTIVE_HOST) return fail(c, RZ_ERR_INVALID_ARG, "%s: unknown flags 0x%x", what, P.flags);
-    if (P.batch_spp == 0) P.batch_spp = 8;
-    if (P.min_batches == 0) P.min_batches = 4;
-    if (P.max_batches == 0) P.max_batches = std::max(8, P.min_batches);
-    if (P.threshold == 0.0f) P.threshold = 0.02f;
-    if (P.luminance_floor == 0.0f) P.luminance_floor = 0.01f;
-    if (P.merge_gap == 0) P.merge_gap = 8;
-    if (P.max_runs == 0) P.max_runs = 1;         // (every further launch of a batch cost more than it saved: profiles/adaptive/README.md)
-    if (P.batch_spp < 1 || P.batch_spp > 1024) return fail(c, RZ_ERR_INVALID_ARG, "%s: batch_spp %d outside 1..1024", what, P.batch_spp);
-    if (P.min_batches < 2 || P.min_batches > RZ_ADAPTIVE_MAX_BATCHES)
-        return fail(c, RZ_ERR_INVALID_ARG, "%s: min_batches %d outside 2..%d", what, P.min_batches, RZ_ADAPTIVE_MAX_BATCHES);
-    if (P.max_batches < P.min_batches || P.max_batches > RZ_ADAPTIVE_MAX_BATCHES)
-        return fail(c, RZ_ERR_INVALID_ARG, "%s: max_batches %d outside %d..%d", what, P.max_batches, P.min_batches, RZ_ADAPTIVE_MAX_BATCHES);
-    if (P.threshold != P.threshold) return fail(c, RZ_ERR_INVALID_ARG, "%s: threshold is not a number", what);
-    if (!(P.luminance_floor > 0.0f && P.luminance_floor < INFINITY))
-        return fail(c, RZ_ERR_INVALID_ARG, "%s: luminance_floor %g (finite, > 0)", what, (double)P.luminance_floor);
-    if (P.merge_gap < -1) return fail(c, RZ_ERR_INVALID_ARG, "%s: merge_gap %d (-1: none, 0: the default, or a number of tiles)", what, P.merge_gap);
-    if (P.max_runs < 0) return fail(c, RZ_ERR_INVALID_ARG, "%s: max_runs %d", what, P.max_runs);
-    const int mergeGap = std::max(0, P.merge_gap);
-    const bool host = (P.flags & RZ_ADAPTIVE_HOST) != 0;
-    if (!host && ((reinterpret_cast<uintptr_t>(tileBatches) | reinterpret_cast<uintptr_t>(tileError)) & 3u))
-        return fail(c, RZ_ERR_INVALID_ARG, "%s: device pointers must be 4-byte aligned", what);
-    if (!c->haveFrame) return fail(c, RZ_ERR_NOT_READY, "%s: rz_set_frame has not been called", what);
-    const rz_frame_params& f = c->frame;
-    if (f.tile_nranks > 1)
-        return fail(c, RZ_ERR_INVALID_ARG, "%s: the frame is tile %d of %d; an adaptive frame is rendered whole", what, f.tile_rank, f.tile_nranks);
-    const int tilesX = (f.width + RZ_TILE_W - 1) / RZ_TILE_W, tilesY = (f.height + RZ_TILE_H - 1) / RZ_TILE_H;
-    const int nTiles = tilesX * tilesY;
-    const size_t nPix = (size_t)f.width * f.height;
-    if (tileBatches && tileBatchesBytes < (size_t)nTiles * 4)
-        return fail(c, RZ_ERR_BUFFER_SIZE, "%s: tile_batches needs %zu bytes, got %zu", what, (size_t)nTiles * 4, tileBatchesBytes);
-    if (tileError && tileErrorBytes < (size_t)nTiles * 4)
-        return fail(c, RZ_ERR_BUFFER_SIZE, "%s: tile_error needs %zu bytes, got %zu", what, (size_t)nTiles * 4, tileErrorBytes);
-    if (c->extAccum && c->extAccumBytes < nPix * 16)
-        return fail(c, RZ_ERR_BUFFER_SIZE, "%s: bound accumulation buffer holds %zu bytes, frame needs %zu", what, c->extAccumBytes, nPix * 16);
-    RZ_HIP(c, hipSetDevice(c->device));
-    int rc = finalize(c);
-    if (rc != RZ_OK) return rc;
-    KParams K{};
-    K.accum = static_cast<float4*>(c->extAccum ? c->extAccum : c->ownAccum.p);
-    K.ior = static_cast<float*>(c->dIor.p);
-    rc = frame_kparams(c, K, P.batch_spp, 0);
-    if (rc == RZ_OK) rc = ensure(c, c->dAdPrev, (size_t)nTiles * 64 * sizeof(float4));
-    if (rc == RZ_OK) rc = ensure(c, c->dAdMoments, (size_t)nTiles * 64 * sizeof(float2));
-    if (rc == RZ_OK) rc = ensure(c, c->dAdError, (size_t)nTiles * sizeof(float));
-    if (rc == RZ_OK) rc = ensure(c, c->dAdBatches, (size_t)nTiles * sizeof(int32_t));
-    if (rc == RZ_OK) rc = ensure(c, c->dAdFlags, (size_t)nTiles);
-    if (rc == RZ_OK) rc = ensure(c, c->dAdList, (size_t)nTiles * sizeof(int32_t));
-    if (rc != RZ_OK) return rc;
-    // pinned: the tiles' flags as they come back, then the list of the tiles a batch rendered as it goes up
-    const size_t listOff = ((size_t)nTiles + 15) & ~size_t(15), pinnedBytes = listOff + (size_t)nTiles * sizeof(int32_t);
-    if (c->adPinnedCap < pinnedBytes) {
-        if (c->adPinned) (void)hipHostFree(c->adPinned);
-        c->adPinned = nullptr; c->adPinnedCap = 0;
-        RZ_HIP(c, hipHostMalloc(reinterpret_cast<void**>(&c->adPinned), pinnedBytes, hipHostMallocDefault));
-        c->adPinnedCap = pinnedBytes;
-    }
-    for (hipEvent_t* e : {&c->evAdaptive[0], &c->evAdaptive[1], &c->evAdaptive[2]})
-        if (!*e) RZ_HIP(c, hipEventCreate(e));
-    const uint8_t* hFlags = c->adPinned;
-    int32_t* hList = reinterpret_cast<int32_t*>(c->adPinned + listOff);
-
-    AdaptiveMeterLaunch M{};
-    M.accum = K.accum;
-    M.prev = static_cast<float4*>(c->dAdPrev.p);
-    M.moments = static_cast<float2*>(c->dAdMoments.p);
-    M.width = f.width; M.height = f.height; M.tilesX = tilesX;
-    M.spp = P.batch_spp;
-    M.minBatches = P.min_batches;
-    M.threshold = P.threshold; M.floor = P.luminance_floor;
-    M.tileError = static_cast<float*>(c->dAdError.p);
-    M.tileBatches = static_cast<int32_t*>(c->dAdBatches.p);
-    M.tileFlags = static_cast<uint8_t*>(c->dAdFlags.p);
-
-    auto tilePixels = [&](int t) {
-        const int tx = t % tilesX, ty = t / tilesX;
-        return (uint64_t)(std::min<int>(RZ_TILE_W, f.width - tx * RZ_TILE_W) * std::min<int>(RZ_TILE_H, f.height - ty * RZ_TILE_H));
-    };
-    rz_adaptive_info I{};
-    I.n_tiles = nTiles;
-    I.samples_uniform = (uint64_t)nPix * (uint64_t)P.max_batches * (uint64_t)P.batch_spp;
-    alloc_point(c);
-    std::vector<uint8_t> active((size_t)nTiles, 1), current((size_t)nTiles, 1), rendered((size_t)nTiles, 1);
-    std::vector<rz_tile_run> runs(1, rz_tile_run{0, nTiles});
-    for (int B = 1;; ++B) {
-        RZ_HIP(c, hipEventRecord(c->evAdaptive[0], c->stream));
-        int nRendered = 0;
-        for (const rz_tile_run& r : runs) {
-            KParams KR = K;
-            KR.sampleBase = (B - 1) * P.batch_spp;
-            KR.tileNRanks = 1; KR.tileRank = r.first; KR.nLocalTiles = r.len;
-            if (use_samples(c)) {
-                rc = render_samples(c, KR, false, -1);
-                if (rc != RZ_OK) return rc;
-            } else {
-                launch_render_pixels(KR, false, c->stream);
-                c->lastLaunches = 1;
-                c->lastPlan = rz_launch_plan{KR.nLocalTiles, KR.nLocalTiles, 0, 0, (KR.spp + 63) / 64, 64, KR.blasStackCap, 0, c->sceneHasTransparency ? 1 : 0, 0};
-            }
-            RZ_HIP(c, hipGetLastError());
-            if (B > 1) for (int t = r.first; t < r.first + r.len; ++t) { hList[nRendered++] = t; rendered[t] = 1; }
-            else nRendered += r.len;
-        }
-        RZ_HIP(c, hipEventRecord(c->evAdaptive[1], c->stream));
-        M.batch = B;
-        M.nSlots = nRendered;
-        M.tiles = nullptr;
-        if (nRendered < nTiles) {       // (a batch of the whole frame needs no list: tile k is slot k)
-            RZ_HIP(c, hipMemcpyAsync(c->dAdList.p, hList, (size_t)nRendered * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-            M.tiles = static_cast<const int32_t*>(c->dAdList.p);
-        }
-        launch_adaptive_meter(M, c->stream);
-        RZ_HIP(c, hipGetLastError());
-        RZ_HIP(c, hipEventRecord(c->evAdaptive[2], c->stream));
-        RZ_HIP(c, hipMemcpyAsync(c->adPinned, c->dAdFlags.p, (size_t)nTiles, hipMemcpyDeviceToHost, c->stream));
-        RZ_HIP(c, hipStreamSynchronize(c->stream));
-        float msRender = 0.0f, msMeter = 0.0f;
-        RZ_HIP(c, hipEventElapsedTime(&msRender, c->evAdaptive[0], c->evAdaptive[1]));
-        RZ_HIP(c, hipEventElapsedTime(&msMeter, c->evAdaptive[1], c->evAdaptive[2]));
-        I.render_ms += msRender; I.meter_ms += msMeter;
-        int nActive = 0;
-        for (int t = 0; t < nTiles; ++t) {
-            if (rendered[t]) {
-                active[t] = (hFlags[t] & RZ_ADAPTIVE_ACTIVE) != 0;
-                current[t] = (hFlags[t] & RZ_ADAPTIVE_CURRENT) != 0;
-                I.samples_traced += tilePixels(t) * (uint64_t)P.batch_spp;
-            } else {
-                current[t] = 0;
-            }
-            nActive += active[t];
-            rendered[t] = 0;
-        }
-        I.batches = B;
-        I.tiles_active[B - 1] = nActive;
-        I.tiles_rendered[B - 1] = nRendered;
-        I.runs[B - 1] = (int32_t)runs.size();
-        if (nActive == 0 || B == P.max_batches) break;
-        adaptive_plan(active.data(), current.data(), (size_t)nTiles, mergeGap, P.max_runs, runs);
-    }
-    c->lastKernel = !use_samples(c) ? "rz_render_pixels"
-                  : c->sceneHasTransparency ? (c->lastCompact ? "rz_render_samples<glass>+pool" : "rz_render_samples<glass>")
-                                            : (c->lastGlobalPool ? "rz_render_samples+pool" : "rz_render_samples");
-    const hipMemcpyKind kind = host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
-    if (tileBatches) RZ_HIP(c, hipMemcpyAsync(tileBatches, c->dAdBatches.p, (size_t)nTiles * 4, kind, c->stream));
-    if (tileError) RZ_HIP(c, hipMemcpyAsync(tileError, c->dAdError.p, (size_t)nTiles * 4, kind, c->stream));
-    RZ_HIP(c, hipStreamSynchronize(c->stream));
-    if (info) *info = I;
-    return RZ_OK;
-}
-
-}  // namespace
+}  // namespace rz
 
 extern "C" {
 
@@ -1461,32 +849,24 @@ void rz_destroy(rz_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    for (DevBuf* b : {&c->dPairs, &c->dTris, &c->dInst, &c->dTlasNodes, &c->dTlasIdx, &c->dMat, &c->dLight,
-                      &c->dCounters, &c->dResolve, &c->dGroupCtr, &c->dBlasOvf, &c->ownAccum, &c->dIor, &c->dXforms, &c->dInstRef, &c->dTlasScratch, &c->dProjBoxes, &c->dBuildWs, &c->dTlasDfs, &c->dTriN, &c->dRawNodes, &c->dRawIdx, &c->dRawTris, &c->dRelayoutWs, &c->dClaimScratch, &c->dWavePools, &c->dWaitMeta, &c->dSnap,
-                      &c->dRayOvf, &c->dRayIn, &c->dRayOut, &c->dRayInstOff, &c->dDnGuide, &c->dDnPing, &c->dDnPong, &c->dDnOut,
-                      &c->dRefitRank, &c->dRefitInstView, &c->dRefitViewOff, &c->dRefitFlags, &c->dRefitRoots,
-                      &c->dTmpCol[0], &c->dTmpCol[1], &c->dTmpMom[0], &c->dTmpMom[1], &c->dTmpHits[0], &c->dTmpHits[1],
-                      &c->dTmpInst[0], &c->dTmpInst[1], &c->dTmpSame, &c->dDisplay, &c->dSkinOut, &c->dSkinBones, &c->dSkinWeights,
-                      &c->dQualViews, &c->dQualPartials, &c->dQualCost, &c->dUpGuideLo, &c->dUpGuideHi, &c->dUpOut,
-                      &c->dStGuideLo, &c->dStGuideHi, &c->dAasList, &c->dAasCounts,
-                      &c->dCost, &c->dCostCounters, &c->dCostPartials, &c->dCostStats, &c->dCostOut, &c->dCovSets,
-                      &c->dAoDirs, &c->dAoRaw, &c->dAoClaim,
-                      &c->dAdPrev, &c->dAdMoments, &c->dAdError, &c->dAdBatches, &c->dAdFlags, &c->dAdList,
-                      &c->dLnRec, &c->dLnCells, &c->dLnList})
-        b->release();
-    for (auto& kv : c->rigs) kv.second.release();
-    for (hipEvent_t e : c->evSkin) if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : c->evAdaptive) if (e) (void)hipEventDestroy(e);
-    if (c->adPinned) (void)hipHostFree(c->adPinned);
-    if (c->refitPinned) (void)hipHostFree(c->refitPinned);
-    if (c->tlasHostCounts) (void)hipHostFree(c->tlasHostCounts);
-    if (c->relayoutPinned) (void)hipHostFree(c->relayoutPinned);
-    for (int i = 0; i < rz_ctx::kRing; ++i) {
-        if (c->evStart[i]) (void)hipEventDestroy(c->evStart[i]);
-        if (c->evStop[i]) (void)hipEventDestroy(c->evStop[i]);
+    const hipStream_t own = c->ownStream;
+    delete c;                                   // events, pinned blocks, then every device buffer
+    if (own) (void)hipStreamDestroy(own);       // the stream goes last
+}
+
+// On the context's device, its stream idle (rz_destroy).  The events and the pinned blocks are few and go by hand; every
+// device buffer -- the members once this body has run, the rigs' with their map -- is freed by its DevBuf.
+rz_ctx::~rz_ctx() {
+    for (hipEvent_t e : evSkin) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : evAdaptive) if (e) (void)hipEventDestroy(e);
+    if (adPinned) (void)hipHostFree(adPinned);
+    if (refitPinned) (void)hipHostFree(refitPinned);
+    if (tlasHostCounts) (void)hipHostFree(tlasHostCounts);
+    if (relayoutPinned) (void)hipHostFree(relayoutPinned);
+    for (int i = 0; i < kRing; ++i) {
+        if (evStart[i]) (void)hipEventDestroy(evStart[i]);
+        if (evStop[i]) (void)hipEventDestroy(evStop[i]);
     }
-    if (c->ownStream) (void)hipStreamDestroy(c->ownStream);
-    delete c;
 }
 
 // What rz_upload, rz_update and rz_read_binding share.  Before the call touches a binding's host copy: its group's, current
@@ -2072,18 +1452,17 @@ static int skin_create_impl(rz_ctx* c, size_t first, size_t n, const rz_triangle
     const Part parts[3] = {{&R.dRest, rest, n * sizeof(rz_triangle)},
                            {&R.dSkin, skin, skin ? n * sizeof(rz_skin_triangle) : 0},
                            {&R.dMorphs, morphs, (size_t)nMorphs * n * sizeof(rz_morph_triangle)}};
-    for (const Part& P : parts) {
+    for (const Part& P : parts) {      // (exact sizes and synchronous copies, not ensure(): R frees what it holds on every return)
         if (!P.bytes) continue;
         hipError_t e = hipMalloc(&P.buf->p, P.bytes);
         if (e == hipSuccess) { P.buf->cap = P.bytes; e = hipMemcpy(P.buf->p, P.src, P.bytes, hipMemcpyHostToDevice); }
         if (e != hipSuccess) {
             (void)hipGetLastError();
-            R.release();
             return fail(c, RZ_ERR_HIP, "%s: %zu bytes of device memory: %s", what, P.bytes, hipGetErrorString(e));
         }
     }
     const int id = c->nextRig;
-    try { c->rigs.emplace(id, R); } catch (...) { R.release(); throw; }
+    c->rigs.emplace(id, std::move(R));
     ++c->nextRig;
     *rigOut = id;
     return RZ_OK;
@@ -2157,7 +1536,6 @@ static int skin_destroy_impl(rz_ctx* c, int rig) {
     if (it == c->rigs.end()) return fail(c, RZ_ERR_INVALID_ARG, "rz_skin_destroy: no rig %d", rig);
     RZ_HIP(c, hipSetDevice(c->device));
     RZ_HIP(c, hipStreamSynchronize(c->stream));     // (a pose in flight reads the rig's buffers)
-    it->second.release();
     c->rigs.erase(it);
     return RZ_OK;
 }
@@ -2257,7 +1635,6 @@ struct RebuildSaved {
     Residency blas, tlas;           // of the arrays above (instances and TLAS: on the host, on either side of the swap)
     bool tmpValid = false;
     size_t devNodes = 0, devIdx = 0;
-    ~RebuildSaved() { nodes.release(); idx.release(); }
 };
 
 static void rebuild_swap(rz_ctx* c, RebuildSaved& S) {
@@ -2433,7 +1810,7 @@ static int build_geometry_impl(rz_ctx* c, const rz_triangle* triangles, size_t n
     // The build goes into FRESH buffers that replace the context's node / index arrays only when every mesh has been built:
     // a call that fails half-way (HIP error, internal limit, out of host memory) leaves the context exactly as it was -- the
     // arrays of an earlier rz_build_geometry, which devRoots / devNodes / the BLAS group's record still describe, are never written to.
-    struct Fresh { DevBuf nodes, idx; ~Fresh() { nodes.release(); idx.release(); } } fresh;
+    struct Fresh { DevBuf nodes, idx; } fresh;
     int rc = ensure(c, fresh.nodes, std::max<size_t>(capNodes, 1) * sizeof(rz_bvh_node));
     if (rc != RZ_OK) return rc;
     rc = ensure(c, fresh.idx, std::max<size_t>(capIdx, 1) * sizeof(int32_t));
@@ -2590,36 +1967,6 @@ static int bind_accum_impl(rz_ctx* c, void* device_rgba, size_t bytes) {
         RZ_HIP(c, hipMemsetAsync(c->ownAccum.p, 0, nPix * 16, c->stream));
     }
     return RZ_OK;
-}
-
-int rz_render(rz_ctx* c) {
-    return guarded(c, "rz_render", [&] { return do_render(c, false, nullptr); });
-}
-int rz_render_counted(rz_ctx* c, rz_counters* out) {
-    return guarded(c, "rz_render_counted", [&] { return do_render(c, true, out); });
-}
-int rz_render_adaptive(rz_ctx* c, const rz_adaptive_params* params, rz_adaptive_info* info, int32_t* tile_batches,
-                       size_t tile_batches_bytes, float* tile_error, size_t tile_error_bytes) {
-    return guarded(c, "rz_render_adaptive", [&] {
-        return render_adaptive(c, params, info, tile_batches, tile_batches_bytes, tile_error, tile_error_bytes);
-    });
-}
-int rz_adaptive_plan(const uint8_t* active, const uint8_t* current, size_t n_tiles, int merge_gap, int max_runs, rz_tile_run* runs,
-                     size_t cap, size_t* n_runs) {
-    const char* what = "rz_adaptive_plan";
-    if (!n_runs) return fail(nullptr, RZ_ERR_INVALID_ARG, "%s: null n_runs", what);
-    if ((!active || !current) && n_tiles > 0) return fail(nullptr, RZ_ERR_INVALID_ARG, "%s: null active or current", what);
-    if (!runs && cap > 0) return fail(nullptr, RZ_ERR_INVALID_ARG, "%s: null runs", what);
-    if (merge_gap < 0 || max_runs < 1) return fail(nullptr, RZ_ERR_INVALID_ARG, "%s: merge_gap %d, max_runs %d", what, merge_gap, max_runs);
-    if (n_tiles > ((size_t)1 << 30)) return fail(nullptr, RZ_ERR_INVALID_ARG, "%s: %zu tiles, at most 2^30", what, n_tiles);
-    return guarded(nullptr, what, [&]() -> int {
-        std::vector<rz_tile_run> out;
-        adaptive_plan(active, current, n_tiles, merge_gap, max_runs, out);
-        *n_runs = out.size();
-        if (out.size() > cap) return fail(nullptr, RZ_ERR_BUFFER_SIZE, "%s: %zu runs, room for %zu", what, out.size(), cap);
-        if (!out.empty()) std::memcpy(runs, out.data(), out.size() * sizeof(rz_tile_run));
-        return RZ_OK;
-    });
 }
 
 int rz_sync(rz_ctx* c) {
@@ -4477,37 +3824,6 @@ static int debug_read_temporal_impl(rz_ctx* c, int which, void* out, size_t byte
     RZ_HIP(c, hipStreamSynchronize(c->stream));
     RZ_HIP(c, hipMemcpy(out, src, have, hipMemcpyDeviceToHost));
     return RZ_OK;
-}
-
-int rz_last_render_ms(rz_ctx* c, float* ms, int* launches) {
-    if (!c) return fail(nullptr, RZ_ERR_INVALID_ARG, "null context");
-    if (!c->timed) return fail(c, RZ_ERR_NOT_READY, "nothing rendered yet");
-    return guarded(c, "rz_last_render_ms", [&]() -> int {
-        const int slot = (c->ringHead + rz_ctx::kRing - 1) % rz_ctx::kRing;
-        RZ_HIP(c, hipEventSynchronize(c->evStop[slot]));
-        float t = 0.0f;
-        RZ_HIP(c, hipEventElapsedTime(&t, c->evStart[slot], c->evStop[slot]));
-        if (ms) *ms = t;
-        if (launches) *launches = c->lastLaunches;
-        return RZ_OK;
-    });
-}
-
-const char* rz_last_kernel_name(const rz_ctx* c) { return c ? c->lastKernel : ""; }
-
-int rz_render_history_ms(rz_ctx* c, float* ms, int cap) {
-    if (!c) return fail(nullptr, RZ_ERR_INVALID_ARG, "null context");
-    if (cap < 0 || (cap > 0 && !ms)) return fail(c, RZ_ERR_INVALID_ARG, "bad history buffer");
-    return guarded(c, "rz_render_history_ms", [&]() -> int {
-        const int n = std::min(c->ringCount, cap);
-        for (int i = 0; i < n; ++i) {     // oldest of the last n first
-            const int slot = (c->ringHead + 2 * rz_ctx::kRing - n + i) % rz_ctx::kRing;
-            RZ_HIP(c, hipEventSynchronize(c->evStop[slot]));
-            RZ_HIP(c, hipEventElapsedTime(&ms[i], c->evStart[slot], c->evStop[slot]));
-        }
-        c->ringCount = 0;
-        return n;
-    });
 }
 
 // ---- exported wrappers: no exception leaves the library (guarded(), above) ----

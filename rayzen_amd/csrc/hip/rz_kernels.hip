@@ -157,7 +157,7 @@ __global__ __launch_bounds__(WAVES_PER_BLOCK * 64, RZ_MIN_WAVES_PER_SIMD) void r
 // off (build.py: it paired f32 ops into 64-bit register tuples and cost 25 VGPRs): 142 VGPRs -> 128 with 13 spilled,
 // 18.65 -> 17.65 ms.  The transparent variant first stayed at 3 (its LDS capped occupancy at 11 waves per CU, so the
 // 28 registers spilled at 128 VGPRs bought nothing: 49.4 -> 54.3 ms); with the BLAS stack cut to an LDS window
-// (rz_context.hip: render_samples) 16 waves fit and 4 wins: 40.2 -> 34.3 ms.
+// (rz_ctx_render.hip: render_samples) 16 waves fit and 4 wins: 40.2 -> 34.3 ms.
 #ifndef RZ_SAMPLES_MIN_WAVES
 #define RZ_SAMPLES_MIN_WAVES 4
 #endif
@@ -1595,7 +1595,7 @@ void launch_render_samples(const KParams& K, bool counted, bool glass, hipStream
     const dim3 g((unsigned)grid), b(64);
     const unsigned nGroups = (unsigned)blocks;
     if (perClaim && hipMemsetAsync(K.groupCounter, 0, sizeof(unsigned), stream) != hipSuccess) return;
-    const bool ovf = K.blasOvfCap > 0;           // only set for persistent launches (rz_context.hip: render_samples)
+    const bool ovf = K.blasOvfCap > 0;           // only set for persistent launches (rz_ctx_render.hip: render_samples)
 #define RZ_LAUNCH_SAMPLES(C, G, O, M) hipLaunchKernelGGL((rz_render_samples<C, G, O, M>), g, b, lds, stream, K, nGroups, (unsigned)perClaim, (unsigned)plan.nClaims, (unsigned)plan.runShift)
     // (trace_spread for the third and later segments: launches of several pixels per wave over scenes of several instances)
     const bool spread = K.spreadTrace != 0 && K.spp < 64;

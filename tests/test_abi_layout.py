@@ -28,6 +28,36 @@ def test_hip_library_exports_every_declared_symbol():
     assert set(names) == set(_lib.HIP_SYMBOLS)
 
 
+def _dynamic_symbols(so_path):
+    """The names a 64-bit little-endian ELF shared library defines in .dynsym (read from the file: the library is not loaded)."""
+    import struct
+    blob = open(so_path, "rb").read()
+    assert blob[:6] == b"\x7fELF\x02\x01", "not a 64-bit little-endian ELF file"
+    shoff, = struct.unpack_from("<Q", blob, 0x28)
+    shentsize, shnum = struct.unpack_from("<HH", blob, 0x3A)
+    sections = [struct.unpack_from("<IIQQQQIIQQ", blob, shoff + k * shentsize) for k in range(shnum)]
+    names = set()
+    for (_, kind, _, _, off, size, link, _, _, entsize) in sections:
+        if kind != 11:                          # SHT_DYNSYM
+            continue
+        stroff = sections[link][4]
+        for k in range(size // entsize):
+            st_name, _, _, st_shndx = struct.unpack_from("<IBBH", blob, off + k * entsize)
+            if st_shndx != 0:                   # (0: SHN_UNDEF, a symbol the library imports)
+                names.add(blob[stroff + st_name:blob.index(b"\0", stroff + st_name)].decode())
+    return names
+
+
+def test_hip_library_exports_exactly_the_declared_symbols():
+    """The C-ABI is the header, no more and no less: the unmangled rz_* names librayzen_hip.so defines are the rz_* functions
+    include/rayzen_hip.h declares.  (Helpers the host files share live in namespace rz and are therefore mangled.)  Neither set
+    has a known exception."""
+    declared = set(_declared("rayzen_hip.h", "rz_"))
+    exported = {n for n in _dynamic_symbols(_lib.HIP_SO) if n.startswith("rz_")}
+    undeclared, missing = sorted(exported - declared), sorted(declared - exported)
+    assert not undeclared and not missing, f"exported but not declared: {undeclared}; declared but not exported: {missing}"
+
+
 def test_host_library_exports_every_declared_symbol():
     names = _declared("rayzen_host.h", "rzh_")
     lib = C.CDLL(_lib.HOST_SO)

@@ -98,7 +98,7 @@ def test_cpp_group_example_is_bit_identical_to_a_single_context(tmp_path):
 @pytest.mark.gpu
 def test_two_contexts_on_two_devices_interleaved():
     """a context may be driven while ANOTHER device is current (the members of a one-process group).  Every exported
-    entry point binds its context's device first (guarded(), rz_context.hip); without that, resolve / present / counters of a
+    entry point binds its context's device first (guarded(), rz_ctx.h); without that, resolve / present / counters of a
     member allocate and launch on the wrong GPU.  Needs two devices: skipped on the one-GPU test box, run by whoever has a node."""
     L = _lib.hip()
     if L.rz_device_count() < 2:
