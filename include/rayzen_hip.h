@@ -1458,6 +1458,69 @@ int rz_draw_lines(rz_ctx* ctx, const rz_frame_params* frame, const rz_lines_para
                   const rz_line* lines, size_t n, const rz_hit* hits, size_t hits_bytes,
                   uint8_t* rgba8, size_t rgba8_bytes, float* rgb32f, size_t rgb32f_bytes, unsigned flags);
 
+/* ------------------------------------------------------------------------ */
+/* Glare: light that spills from over-bright pixels (new)                   */
+/* ------------------------------------------------------------------------ */
+/* The display stage tones every pixel on its own, so a pixel 50 times over white looks like one barely over it.  rz_bloom adds
+ * the glare of the over-bright pixels to their neighbours, in linear HDR colour, in front of that stage (rz_bloom.hip): the
+ * bright part of the frame is taken down an image pyramid and back up.  All arithmetic is binary32 with one rounding per
+ * operation, no fused multiply-add; `/` is correctly rounded; min / max are minNum / maxNum.  Row 0 = the bottom row; the frame
+ * is W x H.
+ *  1 Level sizes.  (w_0, h_0) = (ceil(W / 2), ceil(H / 2)), (w_{k+1}, h_{k+1}) = (ceil(w_k / 2), ceil(h_k / 2)); levels are
+ *    appended until one is 1 x 1 or there are `levels` of them; L is their number (a 1 x 1 frame: L = 1; 1920 x 1080 with 6
+ *    levels ends at 30 x 17).
+ *  2 Prefilter, per pixel of colour c.  A pixel with a NaN or +-Inf channel (decided on the bit pattern, as rz_denoise decides
+ *    it) contributes p = (0, 0, 0).  Otherwise c' = max(c, 0) per channel (+0 for every c <= 0), b = max(max(c'.r, c'.g), c'.b),
+ *    d = b - threshold, s = min(max(d + knee, 0), 2 * knee), q = knee > 0 ? (s * s) / (4 * knee) : 0, m = min(max(q, d), limit),
+ *    f = m > 0 ? m / max(b, 1e-4f) : 0, p = c' * f: nothing below threshold - knee, m = b - threshold above threshold + knee, a
+ *    quadratic onset between them, and no pixel glares with more than `limit`.
+ *  3 Down.  D_0 is made from p, D_{k+1} from D_k, by the 4 x 4 filter (1, 3, 3, 1) x (1, 3, 3, 1) / 64 with its taps at 2X - 1 ..
+ *    2X + 2 and 2Y - 1 .. 2Y + 2, each index clamped to the source.  Rows first, r_j = ((t_{-1} + 3 * t_0) + 3 * t_1) + t_2; the
+ *    four row results are combined the same way in ascending y; the result is multiplied by 0.015625f.
+ *  4 Up(S, w, h) resamples a coarse image S to w x h.  For output x: near = x / 2, far = x even ? x / 2 - 1 : x / 2 + 1, both
+ *    clamped to S; the same for y.  r = 3 * S[near_x] + S[far_x] on a row, then (3 * r[near_y] + r[far_y]) * 0.0625f.
+ *  5 Merge.  U_{L-1} = D_{L-1}; for k = L - 2 down to 0, U_k = D_k + spread * Up(U_{k+1}, w_k, h_k).
+ *  6 Combine.  N = the sum of spread^k over k < L in binary64 on the host, ascending k, the powers by repeated multiplication
+ *    from (double)spread; n = (float)(1 / N); glare = Up(U_0, W, H) * n; out = c + intensity * glare.  A bad pixel's out is
+ *    whatever that expression gives; its neighbours stay finite.  With intensity == 0 out is c bit for bit (a copy, or nothing
+ *    when in place) and the pyramid is made only if `glare` is asked for.
+ * rz_bloom has rz_display's conventions: device pointers by default (4-byte aligned), the work is queued on the context's stream
+ * and the call returns at once; width and height come from the last rz_set_frame (no scene is needed).  rgb_in is W*H*3 floats
+ * of linear colour; rgb_in NULL reads the accumulation as c = rgb / n, n = a > 0 ? a : 1 (refused for a frame with tile_nranks
+ * > 1, as rz_display refuses it).  Outputs, each optional, at least one:
+ *   rgb32f   W*H*3 floats: the frame with glare, linear and unclamped (may be rgb_in itself: in place)
+ *   glare    W*H*3 floats: the normalised glare alone (must not alias rgb_in or rgb32f)
+ * With RZ_BLOOM_HOST the pointers are host memory, staged through buffers of the context, and the call returns when the outputs
+ * are written.  The pyramid (a float4 per texel, 4 / 3 of a quarter frame) lives in a workspace of the context, allocated on
+ * first use, kept, and freed with the context.  2 L kernels run, the same bytes on every run.  The call touches no render
+ * state, temporal history, display state or frame.
+ * rz_present_bloomed is rz_present_display with the pass between the source's colour and the display stage: source and
+ * filter_params are rz_present_display's (source 2 advances the temporal history as rz_present_temporal does); the display
+ * stage, metering included, runs unchanged on the bloomed colour and commits its exposure as rz_present_display does; the
+ * overlays are drawn on top.  bloom NULL: the defaults.  With intensity == 0 the bytes are rz_present_display's exactly.  With
+ * source 0 and intensity > 0 it needs the whole frame (tile_nranks == 1), as metering does.
+ * Errors.  RZ_ERR_INVALID_ARG: null context; a field outside its range or not finite where it must be; non-zero reserved words;
+ * unknown flags; a misaligned device pointer; both outputs NULL; glare aliasing rgb_in or rgb32f; a frame of more than 262140
+ * rows (rz_present_bloomed: also what rz_present_display says).  RZ_ERR_BUFFER_SIZE: a buffer that is too small.
+ * RZ_ERR_NOT_READY: no rz_set_frame.  RZ_ERR_NO_MEMORY, RZ_ERR_HIP: the workspace could not be allocated.  A failing call
+ * launches nothing and writes nothing.  Cost: profiles/bloom/README.md.
+ * (Additive: RZ_ABI_VERSION stays 5; rz_sizeof(44) stays 0.) */
+typedef struct rz_bloom_params {         /* NULL = defaults; 32 B; rz_sizeof(45) */
+    float   threshold;                   /* brightness above which a pixel glares; finite, >= 0; default 1 */
+    float   knee;                        /* half-width of the soft onset below / above the threshold; finite, >= 0; default 0.5 */
+    float   limit;                       /* cap on a pixel's glaring brightness (fireflies); > 0, +Inf allowed; default 64 */
+    float   intensity;                   /* weight of the glare added to the frame; finite, >= 0; default 0.25 */
+    float   spread;                      /* weight of each coarser level relative to the finer; finite, 0 < spread <= 4; default 1 */
+    int32_t levels;                      /* most pyramid levels, 1..8; default 6 */
+    int32_t reserved[2];                 /* must be 0 */
+} rz_bloom_params;
+#define RZ_BLOOM_HOST 1u                 /* pointers are host memory, as RZ_DISPLAY_HOST */
+int rz_bloom(rz_ctx* ctx, const rz_bloom_params* params, const float* rgb_in, size_t rgb_in_bytes,
+             float* rgb32f, size_t rgb32f_bytes, float* glare, size_t glare_bytes, unsigned flags);
+int rz_present_bloomed(rz_ctx* ctx, const rz_present_params* present, const rz_display_params* display,
+                       const rz_bloom_params* bloom, int source, const void* filter_params,
+                       uint8_t* rgba8, size_t rgba8_bytes, float* rgb32f, size_t rgb32f_bytes);
+
 /* Number of HIP devices visible to the process (0 without a GPU). */
 int rz_device_count(void);
 
@@ -1484,7 +1547,7 @@ const char* rz_source_hash(void);
  * 14 display_params, 15 display_info, 17 skin_triangle, 18 morph_triangle, 20 mesh_quality,
  * 21 upscale_params, 23 seethrough_params, 24 chain, 26 antialias_params, 28 pixel_cost, 29 cost_params, 30 cost_view_params,
  * 31 cost_stats, 33 coverage_params, 34 instance_coverage, 35 outline_params, 37 ao_params, 38 adaptive_params, 39 adaptive_info,
- * 40 tile_run, 42 line, 43 lines_params (13, 16, 19, 22, 25, 27, 32, 36 and 41 are unassigned and
+ * 40 tile_run, 42 line, 43 lines_params, 45 bloom_params (13, 16, 19, 22, 25, 27, 32, 36, 41 and 44 are unassigned and
  * return 0, as every unknown index does). */
 size_t rz_sizeof(int which);
 

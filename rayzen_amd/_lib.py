@@ -35,6 +35,7 @@ HIP_SYMBOLS = (
     "rz_ambient_occlusion", "rz_ao_directions",
     "rz_render_adaptive", "rz_adaptive_plan",
     "rz_draw_lines",
+    "rz_bloom", "rz_present_bloomed",
 )
 ABI_VERSION = 5         # RZ_ABI_VERSION of the include/rayzen_hip.h this file mirrors
 # the symbols include/rayzen_host.h declares
@@ -299,6 +300,18 @@ LINES_MAX = 1 << 20                     # lines per call
 SIZEOF_LINE, SIZEOF_LINES_PARAMS = 42, 43       # their rz_sizeof indices (41 is unassigned)
 
 
+class BloomParams(C.Structure):
+    """rz_bloom_params of include/rayzen_hip.h (32 B)."""
+    _fields_ = [("threshold", C.c_float), ("knee", C.c_float), ("limit", C.c_float), ("intensity", C.c_float),
+                ("spread", C.c_float), ("levels", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+BLOOM_DEFAULTS = dict(threshold=1.0, knee=0.5, limit=64.0, intensity=0.25, spread=1.0, levels=6)
+BLOOM_HOST = 1                          # RZ_BLOOM_HOST
+BLOOM_MAX_LEVELS = 8
+SIZEOF_BLOOM_PARAMS = 45                # its rz_sizeof index (44 is unassigned)
+
+
 class SkinTriangle(C.Structure):
     """rz_skin_triangle of include/rayzen_hip.h (64 B)."""
     _fields_ = [("bones", C.c_uint32 * 3), ("pad", C.c_uint32), ("weights", (C.c_float * 4) * 3)]
@@ -433,7 +446,9 @@ def hip():
                                 ("rz_ao_directions", i, [vp, sz]),
                                 ("rz_render_adaptive", i, [vp, C.POINTER(AdaptiveParams), C.POINTER(AdaptiveInfo), vp, sz, vp, sz]),
                                 ("rz_adaptive_plan", i, [vp, vp, sz, i, i, vp, sz, C.POINTER(sz)]),
-                                ("rz_draw_lines", i, [vp, C.POINTER(FrameParams), vp, vp, sz, vp, sz, vp, sz, vp, sz, C.c_uint])):
+                                ("rz_draw_lines", i, [vp, C.POINTER(FrameParams), vp, vp, sz, vp, sz, vp, sz, vp, sz, C.c_uint]),
+                                ("rz_bloom", i, [vp, vp, vp, sz, vp, sz, vp, sz, C.c_uint]),
+                                ("rz_present_bloomed", i, [vp, C.POINTER(PresentParams), vp, vp, i, vp, vp, sz, vp, sz])):
             try:
                 fn = getattr(L, name)
                 fn.restype, fn.argtypes = res, args

@@ -811,6 +811,7 @@ size_t rz_sizeof(int which) {
         case 40: return sizeof(rz_tile_run);
         case 42: return sizeof(rz_line);                 // (41 stays unassigned: probed as an unknown index)
         case 43: return sizeof(rz_lines_params);
+        case 45: return sizeof(rz_bloom_params);         // (44 stays unassigned: probed as an unknown index)
         default: return 0;
     }
 }
@@ -3394,6 +3395,195 @@ static int present_display_impl(rz_ctx* c, const rz_present_params* pp, const rz
     return source == 0 ? RZ_OK : report_backstop(c, what, "the guide may be wrong");
 }
 
+// rz_bloom / rz_present_bloomed (rz_bloom.hip).  Of the frame they read the size only; rz_bloom needs no scene.  They touch no
+// render, temporal or display state of their own; what they keep is the pyramid.
+static const rz_bloom_params kBloomDefaults = {1.0f, 0.5f, 64.0f, 0.25f, 1.0f, 6, {0, 0}};
+
+static int bloom_check(rz_ctx* c, const char* what, const rz_bloom_params& P) {
+    auto finite0 = [](float v) { return v >= 0.0f && v < INFINITY; };
+    if (!finite0(P.threshold)) return fail(c, RZ_ERR_INVALID_ARG, "%s: threshold %g (finite, >= 0)", what, (double)P.threshold);
+    if (!finite0(P.knee)) return fail(c, RZ_ERR_INVALID_ARG, "%s: knee %g (finite, >= 0)", what, (double)P.knee);
+    if (!(P.limit > 0.0f)) return fail(c, RZ_ERR_INVALID_ARG, "%s: limit %g (> 0; +Inf: none)", what, (double)P.limit);
+    if (!finite0(P.intensity)) return fail(c, RZ_ERR_INVALID_ARG, "%s: intensity %g (finite, >= 0)", what, (double)P.intensity);
+    if (!(P.spread > 0.0f && P.spread <= 4.0f)) return fail(c, RZ_ERR_INVALID_ARG, "%s: spread %g outside (0, 4]", what, (double)P.spread);
+    if (P.levels < 1 || P.levels > RZ_BLOOM_MAX_LEVELS) return fail(c, RZ_ERR_INVALID_ARG, "%s: levels %d outside 1..%d", what, P.levels, RZ_BLOOM_MAX_LEVELS);
+    if (P.reserved[0] || P.reserved[1]) return fail(c, RZ_ERR_INVALID_ARG, "%s: reserved words must be 0", what);
+    if (!c->haveFrame) return fail(c, RZ_ERR_NOT_READY, "%s: rz_set_frame has not been called", what);
+    if (((long long)c->frame.height + 3) / 4 > 65535) return fail(c, RZ_ERR_INVALID_ARG, "%s: a frame of %d rows is more than 262140", what, c->frame.height);
+    return RZ_OK;
+}
+
+// step 1 of the definition: the sizes of the levels, and where each starts in the workspace (in texels)
+struct BloomLevels {
+    int n = 0;
+    int w[RZ_BLOOM_MAX_LEVELS] = {}, h[RZ_BLOOM_MAX_LEVELS] = {};
+    size_t off[RZ_BLOOM_MAX_LEVELS] = {}, texels = 0;
+};
+
+static BloomLevels bloom_levels(int W, int H, int levels) {
+    BloomLevels L;
+    int w = W, h = H;
+    do {
+        w = (w + 1) / 2; h = (h + 1) / 2;
+        L.w[L.n] = w; L.h[L.n] = h; L.off[L.n] = L.texels;
+        L.texels += (size_t)w * h;
+        ++L.n;
+    } while (L.n < levels && !(w == 1 && h == 1));
+    return L;
+}
+
+// Whether a call with these parameters and outputs builds the pyramid at all (step 6: with intensity 0 only `glare` needs it).
+static bool bloom_needs_pyramid(const rz_bloom_params& P, bool glare) { return glare || P.intensity != 0.0f; }
+
+// The workspace of a call, before anything is queued: a failure here leaves nothing launched and nothing written.
+static int bloom_workspace(rz_ctx* c, const char* what, const rz_bloom_params& P) {
+    const BloomLevels L = bloom_levels(c->frame.width, c->frame.height, P.levels);
+    alloc_point(c);
+    if (ensure(c, c->dBloom, L.texels * sizeof(float4)) != RZ_OK) {
+        (void)hipGetLastError();
+        return fail(c, RZ_ERR_NO_MEMORY, "%s: no device memory for the pyramid (%zu bytes)", what, L.texels * sizeof(float4));
+    }
+    return RZ_OK;
+}
+
+// The pass on the stream, bloom_workspace done.  The input (device) is `in` (3 floats per pixel) or in4 (RGBA32F sum and count);
+// outputs (device, each optional): rgb (may be `in`), glare, out4 ((out, 1); may be in4).
+static int bloom_run(rz_ctx* c, const rz_bloom_params& P, const float* in, const float4* in4, float* rgb, float* glare, float4* out4) {
+    const int W = c->frame.width, H = c->frame.height;
+    BloomCombine C{};
+    C.in = in; C.in4 = in4;
+    C.w = W; C.h = H;
+    C.intensity = P.intensity;
+    C.copy = P.intensity == 0.0f ? 1 : 0;
+    C.rgb = rgb; C.glare = glare; C.out4 = out4;
+    if (!bloom_needs_pyramid(P, glare != nullptr)) {        // out = c: nothing in place, a copy of the rgb frame, or the resolve
+        if (in && !out4) {
+            if (rgb != in) RZ_HIP(c, hipMemcpyAsync(rgb, in, (size_t)W * H * 3 * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+            return RZ_OK;
+        }
+        launch_bloom_combine(C, c->stream);
+        RZ_HIP(c, hipGetLastError());
+        return RZ_OK;
+    }
+    const BloomLevels L = bloom_levels(W, H, P.levels);
+    float4* ws = static_cast<float4*>(c->dBloom.p);
+    for (int k = 0; k < L.n; ++k) {
+        BloomDown K{};
+        if (k == 0) { K.rgb = in; K.src4 = in4; K.prefilter = 1; K.sw = W; K.sh = H; }
+        else { K.src4 = ws + L.off[k - 1]; K.sw = L.w[k - 1]; K.sh = L.h[k - 1]; }
+        K.dst = ws + L.off[k];
+        K.dw = L.w[k]; K.dh = L.h[k];
+        K.threshold = P.threshold; K.knee = P.knee; K.limit = P.limit;
+        launch_bloom_down(K, c->stream);
+        RZ_HIP(c, hipGetLastError());
+    }
+    for (int k = L.n - 2; k >= 0; --k) {
+        BloomUp U{};
+        U.coarse = ws + L.off[k + 1]; U.cw = L.w[k + 1]; U.ch = L.h[k + 1];
+        U.fine = ws + L.off[k]; U.w = L.w[k]; U.h = L.h[k];
+        U.spread = P.spread;
+        launch_bloom_up(U, c->stream);
+        RZ_HIP(c, hipGetLastError());
+    }
+    double N = 0.0, pw = 1.0;       // N = sum of spread^k, the powers by repeated multiplication, ascending k
+    for (int k = 0; k < L.n; ++k) { N += pw; pw *= (double)P.spread; }
+    C.u0 = ws; C.cw = L.w[0]; C.ch = L.h[0];
+    C.n = (float)(1.0 / N);
+    launch_bloom_combine(C, c->stream);
+    RZ_HIP(c, hipGetLastError());
+    return RZ_OK;
+}
+
+static bool ranges_overlap(const void* a, const void* b, size_t bytes) {
+    const uintptr_t p = reinterpret_cast<uintptr_t>(a), q = reinterpret_cast<uintptr_t>(b);
+    return a && b && p < q + bytes && q < p + bytes;
+}
+
+static int bloom_impl(rz_ctx* c, const rz_bloom_params* pp, const float* rgb_in, size_t rgb_in_bytes, float* rgb32f, size_t rgb32f_bytes,
+                      float* glare, size_t glare_bytes, unsigned flags) {
+    const char* what = "rz_bloom";
+    if (!c) return fail(nullptr, RZ_ERR_INVALID_ARG, "%s: null context", what);
+    if (flags & ~RZ_BLOOM_HOST) return fail(c, RZ_ERR_INVALID_ARG, "%s: unknown flags 0x%x", what, flags);
+    const rz_bloom_params& P = pp ? *pp : kBloomDefaults;
+    int rc = bloom_check(c, what, P);
+    if (rc != RZ_OK) return rc;
+    if (!rgb_in && c->frame.tile_nranks > 1)
+        return fail(c, RZ_ERR_INVALID_ARG, "%s: the frame is tile %d of %d; the accumulation is not the whole frame", what, c->frame.tile_rank, c->frame.tile_nranks);
+    const bool host = (flags & RZ_BLOOM_HOST) != 0;
+    if (!host && ((reinterpret_cast<uintptr_t>(rgb_in) | reinterpret_cast<uintptr_t>(rgb32f) | reinterpret_cast<uintptr_t>(glare)) & 3u))
+        return fail(c, RZ_ERR_INVALID_ARG, "%s: device pointers must be 4-byte aligned", what);
+    if (!rgb32f && !glare) return fail(c, RZ_ERR_INVALID_ARG, "%s: neither rgb32f nor glare is given", what);
+    const size_t np = (size_t)c->frame.width * c->frame.height;
+    const size_t bRgb = np * 3 * sizeof(float);
+    if (ranges_overlap(glare, rgb_in, bRgb) || ranges_overlap(glare, rgb32f, bRgb))
+        return fail(c, RZ_ERR_INVALID_ARG, "%s: glare must not alias rgb_in or rgb32f", what);
+    if (rgb_in && rgb_in_bytes < bRgb) return fail(c, RZ_ERR_BUFFER_SIZE, "%s: rgb_in needs %zu bytes, got %zu", what, bRgb, rgb_in_bytes);
+    if (!rgb_in) {
+        rc = accum_fits(c, what);
+        if (rc != RZ_OK) return rc;
+    }
+    if (rgb32f && rgb32f_bytes < bRgb) return fail(c, RZ_ERR_BUFFER_SIZE, "%s: rgb32f needs %zu bytes, got %zu", what, bRgb, rgb32f_bytes);
+    if (glare && glare_bytes < bRgb) return fail(c, RZ_ERR_BUFFER_SIZE, "%s: glare needs %zu bytes, got %zu", what, bRgb, glare_bytes);
+    if (bloom_needs_pyramid(P, glare != nullptr)) {
+        rc = bloom_workspace(c, what, P);
+        if (rc != RZ_OK) return rc;
+    }
+    const float* in = rgb_in;
+    const float4* in4 = rgb_in ? nullptr : static_cast<const float4*>(rz_accum_device_ptr(c));
+    // host buffers are staged as rz_display stages them: the input in dRayIn; rgb32f, then glare in dRayOut
+    HostStage stage(c, host);
+    const int sRgb = stage.add(rgb32f, bRgb), sGlare = stage.add(glare, bRgb);
+    rc = stage.input(rgb_in, bRgb, in);
+    if (rc == RZ_OK) rc = stage.place();
+    if (rc != RZ_OK) return rc;
+    rc = bloom_run(c, P, in, in4, stage.dev<float>(sRgb), stage.dev<float>(sGlare), nullptr);
+    if (rc != RZ_OK) return rc;
+    if (!host) return RZ_OK;
+    return stage.fetch();
+}
+
+static int present_bloomed_impl(rz_ctx* c, const rz_present_params* pp, const rz_display_params* dp, const rz_bloom_params* bp,
+                                int source, const void* filter_params, uint8_t* rgba8, size_t rgba8_bytes, float* rgb32f,
+                                size_t rgb32f_bytes) {
+    const char* what = "rz_present_bloomed";
+    if (!c) return fail(nullptr, RZ_ERR_INVALID_ARG, "%s: null context", what);
+    if (!pp) return fail(c, RZ_ERR_INVALID_ARG, "%s: null present params", what);
+    const rz_display_params& D = dp ? *dp : kDisplayDefaults;
+    const rz_bloom_params& B = bp ? *bp : kBloomDefaults;
+    FilterSource F;
+    int rc = source_check(c, what, source, filter_params, D, F);
+    if (rc != RZ_OK) return rc;
+    rc = bloom_check(c, what, B);
+    if (rc != RZ_OK) return rc;
+    const bool bloomed = B.intensity != 0.0f;       // intensity 0: out = c, the call IS rz_present_display
+    if (source == 0 && (D.exposure_mode == 1 || bloomed) && c->frame.tile_nranks > 1)
+        return fail(c, RZ_ERR_INVALID_ARG, "%s: the frame is tile %d of %d; %s needs the whole frame", what, c->frame.tile_rank,
+                    c->frame.tile_nranks, D.exposure_mode == 1 ? "metering" : "the glare");
+    const size_t np = (size_t)c->frame.width * c->frame.height;
+    rc = present_sizes(c, what, np, rgba8, rgba8_bytes, rgb32f, rgb32f_bytes);
+    if (rc != RZ_OK) return rc;
+    rc = ensure(c, c->dDnOut, np * 16);
+    if (rc == RZ_OK && bloomed) rc = bloom_workspace(c, what, B);
+    if (rc != RZ_OK) return rc;
+    float4* out4 = static_cast<float4*>(c->dDnOut.p);
+    const float4* accum = static_cast<const float4*>(rz_accum_device_ptr(c));
+    rc = source_run(c, F, accum, out4);
+    if (rc != RZ_OK) return rc;
+    // the source's colour -- the accumulation, or the (colour, 1) a denoiser left in out4 -- becomes (bloomed colour, 1) in out4,
+    // which the tone kernel then rewrites in place
+    const float4* colour = source == 0 ? accum : out4;
+    if (bloomed) {
+        rc = bloom_run(c, B, nullptr, colour, nullptr, nullptr, out4);
+        if (rc != RZ_OK) return rc;
+        colour = out4;
+    }
+    rc = display_run(c, D, nullptr, colour, nullptr, nullptr, out4, false);
+    if (rc != RZ_OK) return rc;
+    rc = present_impl(c, pp, rgba8, rgba8_bytes, rgb32f, rgb32f_bytes, out4);
+    if (rc != RZ_OK) return rc;
+    return source == 0 ? RZ_OK : report_backstop(c, what, "the guide may be wrong");
+}
+
 // rz_upscale / rz_present_upscaled (rz_upscale.hip).  The frame rz_set_frame set is the LOW one; they read its size and camera,
 // the device scene as finalize left it, and touch no render state.  What they keep is buffers of the high size.
 static const rz_upscale_params kUpscaleDefaults = {2, 128.0f, 1.0f, 1, {0, 0, 0, 0}};
@@ -3942,6 +4132,18 @@ int rz_present_display(rz_ctx* c, const rz_present_params* present, const rz_dis
                        const void* filter_params, uint8_t* rgba8, size_t rgba8_bytes, float* rgb32f, size_t rgb32f_bytes) {
     return guarded(c, "rz_present_display", [&] {
         return present_display_impl(c, present, display, source, filter_params, rgba8, rgba8_bytes, rgb32f, rgb32f_bytes);
+    });
+}
+int rz_bloom(rz_ctx* c, const rz_bloom_params* params, const float* rgb_in, size_t rgb_in_bytes, float* rgb32f, size_t rgb32f_bytes,
+             float* glare, size_t glare_bytes, unsigned flags) {
+    return guarded(c, "rz_bloom", [&] {
+        return bloom_impl(c, params, rgb_in, rgb_in_bytes, rgb32f, rgb32f_bytes, glare, glare_bytes, flags);
+    });
+}
+int rz_present_bloomed(rz_ctx* c, const rz_present_params* present, const rz_display_params* display, const rz_bloom_params* bloom,
+                       int source, const void* filter_params, uint8_t* rgba8, size_t rgba8_bytes, float* rgb32f, size_t rgb32f_bytes) {
+    return guarded(c, "rz_present_bloomed", [&] {
+        return present_bloomed_impl(c, present, display, bloom, source, filter_params, rgba8, rgba8_bytes, rgb32f, rgb32f_bytes);
     });
 }
 int rz_upscale(rz_ctx* c, const rz_upscale_params* params, const float* rgb_in, size_t rgb_in_bytes, float* rgb32f,

@@ -221,6 +221,9 @@ struct rz_ctx {
     // rz_draw_lines (rz_lines.hip): the projected records (52 B per line), the counts and offsets of the coarse lists (12 B per
     // cell and segment, and the total) and the lists themselves; allocated by the first call, grown on demand and kept
     DevBuf dLnRec, dLnCells, dLnList;
+    // rz_bloom / rz_present_bloomed (rz_bloom.hip): the pyramid, level after level, a float4 per texel; allocated by the first
+    // call that needs one, grown on demand and kept
+    DevBuf dBloom;
 
     ~rz_ctx();      // the events and the pinned blocks (rz_context.hip, with rz_destroy); the DevBufs and the rigs free themselves
 };

@@ -248,6 +248,37 @@ void launch_display_meter(const float* rgb, const float4* rgba, long long n, Dis
 void launch_display_expose(DisplayState* S, const DisplayExpose& X, hipStream_t s);
 void launch_display_tone(const DisplayTone& T, hipStream_t s);
 
+// ---- rz_bloom.hip
+constexpr int RZ_BLOOM_MAX_LEVELS = 8;  // rz_bloom_params::levels
+struct BloomDown {              // rz_bloom_down: dst (dw x dh) from a source of sw x sh, dw = ceil(sw / 2), dh = ceil(sh / 2)
+    const float* rgb;           // the frame as 3 floats per pixel (prefiltered at staging), or
+    const float4* src4;         // prefilter: the RGBA32F sum and count (resolved, prefiltered); else a pyramid level
+    int prefilter;
+    float4* dst;
+    int sw, sh, dw, dh;
+    float threshold, knee, limit;
+};
+struct BloomUp {                // rz_bloom_up: fine (w x h) += spread * Up(coarse (cw x ch))
+    const float4* coarse;
+    float4* fine;
+    int cw, ch, w, h;
+    float spread;
+};
+struct BloomCombine {           // rz_bloom_combine, w x h pixels
+    const float* in;            // 3 floats per pixel, or
+    const float4* in4;          // RGBA32F sum and count (then `in` is unused)
+    const float4* u0;           // U_0 (cw x ch); null: no glare is computed (copy, nothing asks for the glare)
+    int cw, ch, w, h;
+    float n, intensity;         // 1 / N; the weight
+    int copy;                   // intensity == 0: out = c, bit for bit
+    float* rgb;                 // outputs, each optional: out as 3 floats per pixel (may be `in`),
+    float* glare;               //   the normalised glare as 3 floats per pixel,
+    float4* out4;               //   (out, 1) per pixel (may be in4)
+};
+void launch_bloom_down(const BloomDown& K, hipStream_t s);
+void launch_bloom_up(const BloomUp& U, hipStream_t s);
+void launch_bloom_combine(const BloomCombine& C, hipStream_t s);
+
 // ---- rz_tlas_device.hip
 void launch_tlas_refit(const TlasWork& W, hipStream_t s);
 

@@ -749,6 +749,82 @@ class Renderer:
         """Drops the adapted exposure: the next metered call jumps to its target."""
         self._check(self._L.rz_display_reset(self._c), "rz_display_reset")
 
+    # -- glare (rz_bloom / rz_present_bloomed) -------------------------
+    @staticmethod
+    def _bloom_params(threshold=1.0, knee=0.5, limit=64.0, intensity=0.25, spread=1.0, levels=6):
+        """rz_bloom_params from the keyword arguments of bloom() / present_bloomed(), every field checked here (ValueError);
+        None (params NULL) when nothing departs from the defaults."""
+        def finite0(name, v):
+            v = float(v)
+            if not (0.0 <= v < float("inf")):
+                raise ValueError(f"{name} = {v!r}: must be finite and >= 0")
+            return v
+
+        p = _lib.BloomParams()
+        p.threshold, p.knee, p.intensity = finite0("threshold", threshold), finite0("knee", knee), finite0("intensity", intensity)
+        if not float(limit) > 0.0:
+            raise ValueError(f"limit = {limit!r}: must be > 0 (inf: none)")
+        p.limit = float(limit)
+        if not 0.0 < float(spread) <= 4.0:
+            raise ValueError(f"spread = {spread!r}: outside (0, 4]")
+        p.spread = float(spread)
+        if not 1 <= int(levels) <= _lib.BLOOM_MAX_LEVELS:
+            raise ValueError(f"levels = {levels!r}: outside 1..{_lib.BLOOM_MAX_LEVELS}")
+        p.levels = int(levels)
+        return None if bytes(p) == bytes(_lib.BloomParams(**_lib.BLOOM_DEFAULTS)) else p
+
+    def bloom(self, rgb=None, glare=False, **params):
+        """HDR glare (include/rayzen_hip.h: rz_bloom) on rgb ((H, W, 3) float32 linear colour) or, with rgb None, on the
+        accumulation; host memory, returns when done.  params: threshold=1.0, knee=0.5, limit=64.0, intensity=0.25, spread=1.0,
+        levels=6.  Returns the frame with glare ((H, W, 3) float32, linear, unclamped: what display() takes), or with glare=True
+        (frame, the normalised glare alone); row 0 = bottom row."""
+        bp = self._bloom_params(**params)
+        src = None if rgb is None else np.ascontiguousarray(rgb, np.float32)
+        out = np.empty((self.height, self.width, 3), np.float32)
+        gl = np.empty((self.height, self.width, 3), np.float32) if glare else None
+        self._check(self._L.rz_bloom(self._c, None if bp is None else C.byref(bp), None if src is None else src.ctypes.data,
+                                     0 if src is None else src.nbytes, out.ctypes.data, out.nbytes,
+                                     None if gl is None else gl.ctypes.data, 0 if gl is None else gl.nbytes, _lib.BLOOM_HOST),
+                    "rz_bloom")
+        return (out, gl) if glare else out
+
+    def bloom_device(self, rgb_in_ptr=None, rgb32f_ptr=None, glare_ptr=None, **params):
+        """rz_bloom on device memory (4-byte aligned; rgb_in None: the accumulation; each output optional, at least one; rgb32f
+        may be rgb_in): enqueued on the context's stream, asynchronous.  Sizes: W*H*12 B each."""
+        bp = self._bloom_params(**params)
+        n = self.width * self.height * 12
+        self._check(self._L.rz_bloom(self._c, None if bp is None else C.byref(bp), C.c_void_p(rgb_in_ptr), n if rgb_in_ptr else 0,
+                                     C.c_void_p(rgb32f_ptr), n if rgb32f_ptr else 0, C.c_void_p(glare_ptr), n if glare_ptr else 0, 0),
+                    "rz_bloom")
+
+    def present_bloomed(self, source="accum", bloom=None, filter=None, fps=0.0, show_fps=True, show_lights=False, show_bvh=False,
+                        bvh_mode=0, selected_blas=0, selected_tri=0, **params):
+        """present_display() with the glare between the source's colour and the display stage, which runs -- metering included --
+        on the bloomed colour.  bloom: a dict of bloom()'s parameters (None: the defaults); filter and params: present_display()'s.
+        Returns (rgb float32 (H,W,3), rgba8 uint8 (H,W,4)); with bloom=dict(intensity=0), present_display()'s bytes."""
+        if source not in _lib.DISPLAY_SOURCES:
+            raise ValueError(f"source = {source!r}: one of {sorted(_lib.DISPLAY_SOURCES)}")
+        if source == "accum" and filter:
+            raise ValueError("filter parameters need source 'denoise' or 'temporal'")
+        p = _lib.PresentParams(float(fps), int(bool(show_fps)), int(bool(show_lights)), int(bool(show_bvh)),
+                               int(bvh_mode), int(selected_blas), int(selected_tri))
+        dp = self._display_params(**params)
+        bp = self._bloom_params(**dict(bloom or {}))
+        fp = None
+        if source == "denoise":
+            f = dict(filter or {})
+            fp = self._denoise_params(*(f.pop(k, None) for k in ("iterations", "sigma_color", "sigma_normal", "sigma_plane", "demodulate")))
+            if f:
+                raise TypeError(f"unknown denoise parameter(s): {sorted(f)}")
+        elif source == "temporal":
+            fp = self._temporal_params(dict(filter or {}))
+        rgb = np.empty((self.height, self.width, 3), np.float32)
+        rgba8 = np.empty((self.height, self.width, 4), np.uint8)
+        self._check(self._L.rz_present_bloomed(self._c, C.byref(p), None if dp is None else C.byref(dp),
+                                               None if bp is None else C.byref(bp), _lib.DISPLAY_SOURCES[source], fp,
+                                               rgba8.ctypes.data, rgba8.nbytes, rgb.ctypes.data, rgb.nbytes), "rz_present_bloomed")
+        return rgb, rgba8
+
     # -- guided upsampling (rz_upscale / rz_present_upscaled) -------------------------
     @staticmethod
     def _upscale_params(factor, sigma_normal, sigma_plane, demodulate):
