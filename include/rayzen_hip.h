@@ -191,7 +191,14 @@ int rz_update_transforms(rz_ctx* ctx, const float* transforms, size_t n);
 /* BVH::buildBLAS (RayZen/src/BVH.cpp:99-175 with the full-sweep SAH of :22-97; called per mesh from main.cpp:954-958)
  * on the device.  Output is byte-identical to the reference builder's `nodes` / `triIndices`: nodes_out receives
  * *n_nodes <= 2n-1 nodes (nodes_cap >= 2n-1, or 1 for n == 0), indices_out n triangle indices.  depth and device_ms
- * (device time, host<->device copies excluded) may be NULL.  tris / outputs are host pointers. */
+ * (device time, host<->device copies excluded) may be NULL.  tris / outputs are host pointers.
+ * Supported: n up to 2^30 (more: RZ_ERR_INVALID_ARG) and finite coordinates only -- no NaN and no infinity: the reference's
+ * std::sort is undefined on a NaN centroid; magnitudes whose box areas overflow binary32 are fine and take the reference's
+ * midpoint fallback.  The tree may be of ANY depth: the builder has no level bound of its own, so n identical triangles
+ * build to the n - 3 levels the reference gives them (one level costs one small round trip to the device: 4200
+ * zero-area triangles, 4197 levels, take half a second).  rz_build_geometry and rz_rebuild_geometry run the same builder
+ * under the same terms; rz_render rejects a scene whose BLAS is too deep for its stack (RZ_ERR_BAD_SCENE), which is
+ * a limit of the traversal, not of the build. */
 int rz_build_blas(rz_ctx* ctx, const rz_triangle* tris, size_t n, rz_bvh_node* nodes_out, size_t nodes_cap,
                   int32_t* indices_out, size_t* n_nodes, int* depth, float* device_ms);
 

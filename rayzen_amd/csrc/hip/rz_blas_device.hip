@@ -886,13 +886,21 @@ size_t blas_build_workspace_bytes(size_t n) {
     return b;
 }
 
-#define BB_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { if (temp) (void)hipFree(temp); return (int)e_; } } while (0)
+#define BB_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { release(); return (int)e_; } } while (0)
 
-// Returns 0, a hipError_t (> 0), or -1 (bad arguments / internal limit).  hostTris, nodes_out (capacity 2n+1) and
+// Returns 0, a hipError_t (> 0), or -1 (bad arguments / a level loop that does not end).  The tree may be as deep as the
+// reference makes it: every internal node splits off at least one triangle, so a mesh of n triangles has at most n levels
+// (n identical triangles reach n - 3), and that is the only bound on the loop.  hostTris, nodes_out (capacity 2n+1) and
 // idx_out (n) may be HOST or DEVICE pointers (copies use hipMemcpyDefault).  ms (optional): device time from the first kernel to the last, copies excluded.
 int blas_build_device(const rz_triangle* hostTris, size_t n, void* workspace, size_t workspaceBytes, rz_bvh_node* nodes_out,
                       int32_t* idx_out, int* nNodesOut, int* depthOut, float* ms, hipStream_t s) {
     void* temp = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    auto release = [&]() {
+        if (temp) (void)hipFree(temp);
+        if (ev0) (void)hipEventDestroy(ev0);
+        if (ev1) (void)hipEventDestroy(ev1);
+    };
     if (n == 0 || n > ((size_t)1 << 30) || !workspace || workspaceBytes < blas_build_workspace_bytes(n)) return -1;
     const size_t N = n, M = 2 * N + 2;
     char* w = static_cast<char*>(workspace);
@@ -927,7 +935,6 @@ int blas_build_device(const rz_triangle* hostTris, size_t n, void* workspace, si
     B.outNodes = reinterpret_cast<rz_bvh_node*>(carve(M * sizeof(rz_bvh_node)));
     B.counters = reinterpret_cast<int*>(carve(64));
 
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
     if (ms) { BB_HIP(hipEventCreate(&ev0)); BB_HIP(hipEventCreate(&ev1)); }
     BB_HIP(hipMemcpyAsync(devTris, hostTris, N * sizeof(rz_triangle), hipMemcpyDefault, s));
     if (ms) BB_HIP(hipEventRecord(ev0, s));
@@ -943,9 +950,10 @@ int blas_build_device(const rz_triangle* hostTris, size_t n, void* workspace, si
     }
     hipLaunchKernelGGL(bb_init_root, dim3(1), dim3(1), 0, s, B);
     int largeCount = n > (size_t)BB_LARGE ? 1 : 0, smallCount = n <= (size_t)BB_SMALL ? 1 : 0, bigCount = 1 - largeCount - smallCount;
-    int buf = 0, hostCounters[8] = {0}, levels = 0;
+    int buf = 0, hostCounters[8] = {0};
+    size_t levels = 0;
     while (largeCount > 0 || bigCount > 0 || smallCount > 0) {
-        if (++levels > 4096) { (void)hipFree(temp); return -1; }
+        if (++levels > N) { release(); return -1; }      // (never: a backstop against a loop that does not end)
         if (largeCount > 0) {
             const unsigned g = (unsigned)(N / BB_CHUNK) + (unsigned)largeCount;       // >= sum of ceil(N_j / chunk)
             const dim3 T(BB_THREADS);
@@ -968,7 +976,7 @@ int blas_build_device(const rz_triangle* hostTris, size_t n, void* workspace, si
         BB_HIP(hipMemsetAsync(B.counters + 1, 0, 16, s));
         buf ^= 1;
     }
-    const int nNodes = hostCounters[0], depth = levels;      // every level of the loop produced nodes of that depth
+    const int nNodes = hostCounters[0], depth = (int)levels;      // every level of the loop produced nodes of that depth
     const int nb = (nNodes + 255) / 256;
     for (int d = depth; d >= 1; --d) hipLaunchKernelGGL(bb_count_internals, dim3(nb), dim3(256), 0, s, B, nNodes, d);
     for (int d = 1; d <= depth; ++d) hipLaunchKernelGGL(bb_rank_level, dim3(nb), dim3(256), 0, s, B, rank, refIdx, nNodes, d);
@@ -978,8 +986,8 @@ int blas_build_device(const rz_triangle* hostTris, size_t n, void* workspace, si
     BB_HIP(hipMemcpyAsync(nodes_out, B.outNodes, (size_t)nNodes * sizeof(rz_bvh_node), hipMemcpyDefault, s));
     BB_HIP(hipMemcpyAsync(idx_out, B.idx, N * 4, hipMemcpyDefault, s));
     BB_HIP(hipStreamSynchronize(s));
-    if (ms) { BB_HIP(hipEventElapsedTime(ms, ev0, ev1)); (void)hipEventDestroy(ev0); (void)hipEventDestroy(ev1); }
-    (void)hipFree(temp);
+    if (ms) BB_HIP(hipEventElapsedTime(ms, ev0, ev1));
+    release();
     if (nNodesOut) *nNodesOut = nNodes;
     if (depthOut) *depthOut = depth;
     return 0;

@@ -212,6 +212,101 @@ LARGE = [("blob76_r2.8", lambda: S.make_blob(76, 2.8, 0), False),           # te
          ("blob150_r1", lambda: S.make_blob(150, 1.0, 0), False),            # 270 000
          ("blob289_r10", lambda: S.make_blob(289, 10.0, 0), True)]           # 1 002 252 (slow)
 
+# ---- adversarial meshes of more than 4096 triangles: the device builder's large-node path (rz_blas_device.hip, bbL_*) -------
+# What each is for is asserted, on the host's nodes, by tests/test_blas_large_cases.py.
+
+def _cluster(n, seed, x):
+    """A soup of extent ~2 whose every vertex is moved by x along the x axis."""
+    t = _rand(n, seed, 1.0, 0.05)
+    for k in ("v0", "v1", "v2"):
+        v = t[k]
+        v[:, 0] += F32(x)
+        t[k] = v
+    return t
+
+
+def _huge(n, seed, widest=None):
+    """Boxes whose area overflows binary32: no SAH cost is finite, the midpoint fallback splits (along `widest`, stretched 8 x)."""
+    t = _rand(n, seed, 1e19, 1e18)
+    for k in ("v0", "v1", "v2"):
+        v = t[k]
+        if widest is not None:
+            v[:, widest] *= F32(8.0)
+        t[k] = v
+    return t
+
+
+def _floor(n, y_of):
+    """A soup flattened into the plane y = 0; y_of(n) gives each vertex' zero, (n, 3 vertices) float32 of +0 / -0."""
+    t = _rand(n, 5, 4.0, 0.3)
+    y = np.asarray(y_of(n), F32)
+    for j, k in enumerate(("v0", "v1", "v2")):
+        v = t[k]
+        v[:, 1] = y[:, j]
+        t[k] = v
+    return t
+
+
+def _floor_pm0(n):
+    return np.where(np.random.default_rng(6).random((n, 3)) < 0.5, F32(0.0), F32(-0.0))
+
+
+def _floor_planted(n, everywhere, planted, at):
+    y = np.full((n, 3), everywhere, F32)
+    y[at] = planted
+    return y
+
+
+LARGE_ADVERSARIAL = [
+    ("adv_lattice_20000", lambda: _lattice(20000, 1, 12), False),             # cost ties in droves, across chunks and axes
+    ("adv_lattice_tight_9000", lambda: _lattice(9000, 2, 2), False),          # 125 distinct vertices: a tree ~1000 levels deep
+    ("adv_huge_6000", lambda: _huge(6000, 3), False),                         # the fallback on a large node (y the widest)
+    ("adv_huge_widest_z_6000", lambda: _huge(6000, 3, 2), False),             # the fallback along z
+    ("adv_huge_widest_x_6000", lambda: _huge(6000, 3, 0), False),             # ... and with axis == -1
+    ("adv_clusters_4096_2000", lambda: np.concatenate([_cluster(4096, 1, -100), _cluster(2000, 2, 100)]), False),
+    ("adv_clusters_2048_4049", lambda: np.concatenate([_cluster(4049, 3, 100), _cluster(2048, 4, -100)]), False),
+    ("adv_three_clusters", lambda: np.concatenate([_cluster(2048, 5, -300), _cluster(4096, 6, 0), _cluster(4097, 7, 300)]), False),
+    ("adv_outlier_first", lambda: np.concatenate([_cluster(1, 8, -1e4), _cluster(6000, 9, 0)]), False),      # a split at i == 1
+    ("adv_outlier_last", lambda: np.concatenate([_cluster(6000, 9, 0), _cluster(1, 8, 1e4)]), False),        # at i == N - 1
+    ("adv_floor_pm0_10000", lambda: _floor(10000, _floor_pm0), False),        # the sign of a zero in a large node's box
+    ("adv_floor_one_minus_zero_last", lambda: _floor(10000, lambda n: _floor_planted(n, 0.0, -0.0, n - 1)), False),
+    ("adv_floor_plus_zero_first", lambda: _floor(10000, lambda n: _floor_planted(n, -0.0, 0.0, 0)), False),
+    ("adv_dup_4200", lambda: np.repeat(_rand(1, 7, 1.0, 0.3), 4200), False),  # one triangle 4200 times
+    ("adv_zero_4200", lambda: np.zeros(4200, S.TRIANGLE), False),             # a chain 4197 levels deep: every node splits 1 | N-1
+    ("adv_soup_2300000", lambda: _rand(2300000, 8, 4.0, 0.05), True),         # more than 256 large nodes on one level (slow)
+    ("adv_soup_4200000", lambda: _rand(4200000, 8, 4.0, 0.05), True),         # a root of more than 2048 chunks (slow)
+]
+LARGE += LARGE_ADVERSARIAL
+
+_HOST_BUILDS = {}
+
+
+def host_build(name, tris):
+    """S.build_blas of a LARGE case, built once per session for the modules that share it (up to 2.3 M triangles are kept)."""
+    if name in _HOST_BUILDS:
+        return _HOST_BUILDS[name]
+    out = S.build_blas(tris)
+    if len(tris) <= 2300000:
+        _HOST_BUILDS[name] = out
+    return out
+
+
+def node_counts_and_levels(nodes):
+    """Per node: the triangles below it and its level (the root: 1)."""
+    left = nodes["leftFirst"].astype(np.int64)
+    count, level = nodes["count"].astype(np.int64), np.zeros(len(nodes), np.int64)
+    internal_by_level, front = [], np.zeros(1, np.int64)
+    while len(front):                                # level by level: a deep chain is thousands of short steps, not of nodes
+        level[front] = len(internal_by_level) + 1
+        internal = front[count[front] < 0]
+        internal_by_level.append(internal)
+        front = np.concatenate([left[internal], left[internal] + 1])
+    for internal in internal_by_level[::-1]:
+        count[internal] = count[left[internal]] + count[left[internal] + 1]
+    assert (level > 0).all()
+    return count, level
+
+
 BLAS_GROUPS = {"suite": suite_cases, "adversarial": adversarial_cases, "sizes": size_cases}
 
 

@@ -4,7 +4,7 @@ inputs of tests/cppref_cases.py.  Needs the reference checkout (oracle/cppref/RE
     python tests/golden/make_cppref.py [--skip-slow] [--only-tlas]
 
 Files: cppref_suite / cppref_adversarial / cppref_sizes (BLAS: input, nodes, indices, count of axis == -1 reads), cppref_large
-(digests of the big blobs), cppref_tlas (root boxes, nodes, indices), cppref_obj (texts, the reader's output, which components
+(digests of the big blobs and of the large adversarial meshes), cppref_tlas (root boxes, nodes, indices), cppref_obj (texts, the reader's output, which components
 may be asserted).  Each file stays under 1 MB.  --skip-slow keeps the 1 M-triangle entry of an existing cppref_large.npz;
 --only-tlas rewrites cppref_tlas.npz alone (a new TLAS case leaves the other files as they are).
 """

@@ -110,10 +110,20 @@ def _large(name, ctor, builders):
 @pytest.mark.parametrize("name", [n for n, _, slow in K.LARGE if not slow])
 def test_large_blas_by_digest(name):
     ctor = dict((n, c) for n, c, _ in K.LARGE)[name]
-    builders = [("host", S.build_blas)]
+    builders = [("host", lambda tris: K.host_build(name, tris))]     # (shared with tests/test_blas_large_cases.py)
     if int(LARGE[f"{name}__digest"][3]) <= 20000:           # the oracle's O(N log^2 N) restatement: the bigger ones are slow
         builders.append(("oracle", rzo.build_blas))
     _large(name, ctor, builders)
+
+
+SLOW_ADVERSARIAL = [n for n, _, slow in K.LARGE_ADVERSARIAL if slow]
+
+
+@pytest.mark.slow
+@pytest.mark.parametrize("name", SLOW_ADVERSARIAL)
+def test_large_adversarial_soups_by_digest_host(name):
+    """2.3 M and 4.2 M triangles: 9 s and 19 s of host build on the build machine (the oracle's restatement would take minutes)."""
+    _large(name, dict((n, c) for n, c, _ in K.LARGE)[name], [("host", lambda tris: K.host_build(name, tris))])
 
 
 @pytest.mark.slow
@@ -236,6 +246,14 @@ def test_live_large_fixtures_are_current(name):
 def test_live_one_million_triangles():
     """The reference's buildBLAS takes 7.3 s on 1 002 252 triangles on the build machine (the fixture records the time)."""
     _large("blob289_r10", dict((n, c) for n, c, _ in K.LARGE)["blob289_r10"], [("RayZen's BVH.cpp", cppref.build_blas)])
+
+
+@live
+@pytest.mark.slow
+@pytest.mark.parametrize("name", SLOW_ADVERSARIAL)
+def test_live_large_adversarial_soups(name):
+    """The reference's buildBLAS takes 26 s on the 2.3 M soup and 41 s on the 4.2 M one on the build machine."""
+    _large(name, dict((n, c) for n, c, _ in K.LARGE)[name], [("RayZen's BVH.cpp", cppref.build_blas)])
 
 
 def _random_soup(seed):

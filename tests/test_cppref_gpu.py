@@ -10,6 +10,7 @@ import pytest
 import cppref_cases as K
 from rayzen_amd import scene as S
 from rayzen_amd.renderer import Renderer
+from test_blas_device_gpu import check
 
 pytestmark = pytest.mark.gpu
 
@@ -46,28 +47,68 @@ def test_build_blas_equals_rayzens_build(r, group, name):
 
 @pytest.mark.parametrize("name", [n for n, _, _ in K.LARGE])
 def test_build_blas_large_by_digest(r, name):
+    """The blobs, and the adversarial meshes of the large-node path (cppref_cases.LARGE_ADVERSARIAL; what each is there for:
+    tests/test_blas_large_cases.py).  Only where a digest differs is the host library asked for its build, to name the first
+    record that differs: 9 s and 19 s of host build for the two soups of millions are not on the passing path.
+    Measured on an MI355X, generator and hashing included (device time of the build alone in brackets): adv_soup_2300000
+    0.43 s (34 ms), adv_soup_4200000 0.76 s (48 ms), adv_zero_4200 -- 4197 levels, one round trip each, and 8394 launches of
+    the two numbering kernels -- 0.46 s (462 ms); adv_lattice_tight_9000, 1042 levels, 0.11 s."""
     tin, tnodes, tidx, n, nn, depth = [str(x) for x in LARGE[f"{name}__digest"]]
     tris = dict((k, c) for k, c, _ in K.LARGE)[name]()
     assert (len(tris), K.sha(tris)) == (int(n), tin), f"{name}: the generator no longer makes the mesh the fixture was recorded for"
     dn, di, ddepth, ms = r.build_blas(tris)
+    print(f"[cppref] {name}: {len(tris)} triangles, {len(dn)} nodes, depth {ddepth}, device {ms:.1f} ms")
+    same = (len(dn), K.sha(dn), K.sha(di)) == (int(nn), tnodes, tidx)
+    if not same and name in [k for k, _, _ in K.LARGE_ADVERSARIAL]:
+        hn, hi, _ = S.build_blas(tris)
+        assert (K.sha(hn), K.sha(hi)) == (tnodes, tidx), f"{name}: the HOST library differs from RayZen's build"
+        _same(dn, hn, f"{name}: device nodes")
+        _same(di, hi, f"{name}: device indices")
     assert (len(dn), ddepth) == (int(nn), int(depth))
     assert K.sha(dn) == tnodes, f"device nodes differ from RayZen's build of {name}"
     assert K.sha(di) == tidx, f"device indices differ from RayZen's build of {name}"
+
+
+@pytest.mark.parametrize("name", [n for n, _, slow in K.LARGE_ADVERSARIAL if not slow])
+def test_build_blas_large_adversarial_equals_the_host_library(r, name):
+    """Byte for byte, so that a failure names the record (the digests above only say that one differs)."""
+    check(r, dict((k, c) for k, c, _ in K.LARGE_ADVERSARIAL)[name](), oracle=False)
+
+
+def test_a_tree_deeper_than_4096_levels_leaves_the_context_usable(r):
+    """adv_zero_4200 builds (4197 levels: the builder has no depth bound), and the build workspace serves the next mesh."""
+    cases = dict((k, c) for k, c, _ in K.LARGE_ADVERSARIAL)
+    nodes, idx, depth, _ = r.build_blas(cases["adv_zero_4200"]())
+    assert depth == 4197 and len(nodes) == 8393
+    tris, want, widx, _ = _by_name("size_4097")
+    dn, di, _, _ = r.build_blas(tris)
+    _same(dn, want, "size_4097 after the deep chain: nodes")
+    _same(di, widx, "size_4097 after the deep chain: indices")
 
 
 GEOMETRY_SETS = [
     ["bvh_monkey", "bvh_empty", "dev_signed_zeros300", "dev_big50", "size_5", "lattice_tight_700", "bvh_cube"],
     ["huge_widest_x_120", "dev_soup2049", "zeros_pm_513", "size_1", "huge_3e38_260", "denormal_wide_300", "bvh_empty",
      "points_lines_and_triangles_300", "flat_y_huge_extent_90", "size_4097", "dev_mixed250"],
+    # large, small, large: the context's build workspace is used again after a bigger build
+    ["adv_lattice_20000", "size_5", "adv_huge_6000", "adv_floor_pm0_10000", "bvh_empty", "adv_clusters_4096_2000", "adv_outlier_last"],
 ]
 
 
 def _by_name(name):
+    """(triangles, nodes, indices, ...): RayZen's build from the whole fixtures; of a large adversarial case the host library's,
+    which test_build_blas_large_by_digest's digests and tests/test_cppref.py hold to RayZen's."""
+    large = dict((k, c) for k, c, _ in K.LARGE_ADVERSARIAL)
+    if name in large:
+        tris = large[name]()
+        nodes, idx, _ = K.host_build(name, tris)
+        assert (K.sha(nodes), K.sha(idx)) == tuple(str(x) for x in LARGE[f"{name}__digest"][1:3]), name
+        return tris, nodes, idx, 0
     group = [g for g, n in BLAS if n == name][0]
     return K.load_blas(group, name)
 
 
-@pytest.mark.parametrize("names", GEOMETRY_SETS, ids=["seven_meshes", "eleven_meshes"])
+@pytest.mark.parametrize("names", GEOMETRY_SETS, ids=["seven_meshes", "eleven_meshes", "large_small_large"])
 def test_build_geometry_slices_equal_rayzens_per_mesh_builds(r, names):
     """Bindings 7 / 8 hold the meshes' BLAS back to back, unmodified (main.cpp:1030-1035): mesh i is nodes[node_offset ..
     + n_nodes) and indices[index_offset .. + n_triangles)."""
@@ -172,4 +213,44 @@ def test_refit_with_unchanged_vertices_keeps_rayzens_build_device_built_scene():
     _check_refit(rr, cases, offsets)
     rr.refit_geometry()
     _check_refit(rr, cases, offsets)
+    rr.close()
+
+
+def test_rebuild_geometry_builds_a_large_node_from_the_device_triangles():
+    """rz_rebuild_geometry hands the builder binding 0 where it is current -- on the device, after a refit -- and the mesh is
+    adv_floor_pm0_10000, moved in x only (every y stays the +0 or -0 it was): three nodes of more than 4096 triangles whose y
+    bounds carry the sign of a zero.  Bindings 0 and 5 to 9 equal the host partner's (Scene.refit_mesh, Scene.rebuild_mesh),
+    and the mesh's slice is the host builder's BLAS of the moved triangles."""
+    mesh = dict((k, c) for k, c, _ in K.LARGE_ADVERSARIAL)["adv_floor_pm0_10000"]()
+    s = S.Scene()
+    floor, big = s.add_mesh(S.make_cube(4)), s.add_mesh(mesh)
+    s.add_object(floor, S.translate(S.scale(S.identity(), (8.0, 0.5, 8.0)), (0.0, -3.0, 0.0)))
+    s.add_object(big, S.identity())
+    sc = s.build()
+    inst = sc.arrays[S.BIND_INSTANCES]
+    first = int(inst[1]["globalTriOffset"])
+    assert first == 12 and len(sc.arrays[S.BIND_TRIANGLES]) == 12 + len(mesh)
+    moved = mesh.copy()
+    for k in ("v0", "v1", "v2"):
+        v = moved[k]
+        v[:, 0] += np.float32(0.5) * np.sin(np.float32(2.0) * v[:, 2]).astype(np.float32)
+        moved[k] = v
+    y = np.stack([moved[k][:, 1] for k in ("v0", "v1", "v2")])
+    assert (y == 0).all() and np.signbit(y).any() and not np.signbit(y).all()
+    rr = Renderer(0)
+    rr.upload_scene(sc)
+    rr.refit_geometry(moved, first)
+    sc.refit_mesh(big, moved)
+    rec = rr.rebuild_geometry(0.0)
+    assert (rec["flags"] == 1).all() and len(rec) == 2          # RZ_QUALITY_REBUILT, both meshes
+    sc.rebuild_mesh(floor)
+    sc.rebuild_mesh(big)
+    for b in (S.BIND_BLAS_NODES, S.BIND_BLAS_INDICES, S.BIND_TRIANGLES, S.BIND_INSTANCES, S.BIND_TLAS_NODES, S.BIND_TLAS_INDICES):
+        _same(rr.read_binding(b), sc.arrays[b], f"binding {b} after the rebuild")
+    nodes, idx, _ = S.build_blas(moved)
+    count, _ = K.node_counts_and_levels(nodes)
+    assert int((count > 4096).sum()) >= 2
+    o, t = int(rec["node_offset"][1]), int(rec["index_offset"][1])
+    _same(rr.read_binding(S.BIND_BLAS_NODES)[o:o + len(nodes)], nodes, "the mesh's nodes")
+    _same(rr.read_binding(S.BIND_BLAS_INDICES)[t:t + len(idx)], idx, "the mesh's indices")
     rr.close()
